@@ -16,6 +16,14 @@ Scaling is STRONG: the batch is fixed and sharded by reference scan across ranks
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by torch.distributed.run
 (one rank per GPU).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, pre-warm, W warm-up steps, the K timed steps and the
+result line.  `--full` adds everything else this file measures (association timings, the per-rank projection,
+materialise / pcie / panorama / features / pose_solve / mvs blocks, the all-reduce timing and image-space block
+at N > 1, the CPU baseline); `--no-cpu-baseline`, `--no-mvs` and `--no-projection` trim a `--full` run.
+`--dump-outputs DIR` writes what the last timed step computed (the normal equations of NormalEq.unpack) as
+DIR/<name>.npy; the timed steps start from the same parameter point in every run, so two runs (or two builds)
+of one command can be compared output for output.
 """
 import argparse
 import glob
@@ -195,7 +203,15 @@ def main():
     ap.add_argument("--no-projection", action="store_true", help="skip the per-rank projection block (scans/2, /4, /8 on this GPU)")
     ap.add_argument("--collective-timeout", type=float, default=float(os.environ.get("PVLM_BENCH_COLLECTIVE_TIMEOUT", "240")),
                     help="N > 1: seconds any phase that waits for other ranks may take before the watchdog aborts the run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (association timings, projection, materialise, pcie, panorama, features, pose_solve, mvs, "
+                         "all-reduce timing and image-space block at N > 1, CPU baseline); a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the normal equations of the last timed step (H_diag, H_offdiag, gradient, robust_cost) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
+        sys.exit(2)
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -258,7 +274,8 @@ def main():
     # (tools/micro/alloc_cost.hip), the association's output alone is 56 B x accepted rows.  Upper bound: every query
     # accepted + the two pipeline slots of scratch + the scans.
     t_res = time.perf_counter()
-    shards_extra = 0.9 if (world == 1 and not args.no_projection and args.scans >= 64) else 0.0     # rank-0 shards of N = 2, 4, 8 live beside the batch
+    run_projection = args.full and world == 1 and not args.no_projection and args.scans >= 64
+    shards_extra = 0.9 if run_projection else 0.0     # rank-0 shards of N = 2, 4, 8 live beside the batch
     reserve_bytes = int(n_queries * 56 * (1.02 + shards_extra)) + 2 * min(n_queries, 16 << 20) * 100 + sum(
         (len(s["flat_xyz"]) * 16 + len(s["less_xyz"]) * 48 + (4 << 20)) for s in scans.values()) + (1 << 30)
     info = ctx.device_info()
@@ -287,11 +304,15 @@ def main():
         ctx.profile_enable(False)
         return r_, wall, ms, launches, ctx.mem_info()["device_allocs"] - m0["device_allocs"]
 
-    rs, t_assoc_first, assoc_ms_first, _, allocs_first = timed_assoc(ref, nei, args.tolerance)
-    # the reference re-associates at every outer iteration (lidar_mapping/LidarOdometry.cpp:38-110): the steady state
-    # of the call is the SECOND and later ones, with the previous residual set given back first
-    rs.close()
-    rs, t_assoc, assoc_ms, assoc_n, allocs_steady = timed_assoc(ref, nei, args.tolerance)
+    if args.full:
+        rs, t_assoc_first, assoc_ms_first, _, allocs_first = timed_assoc(ref, nei, args.tolerance)
+        # the reference re-associates at every outer iteration (lidar_mapping/LidarOdometry.cpp:38-110): the steady state
+        # of the call is the SECOND and later ones, with the previous residual set given back first
+        rs.close()
+        rs, t_assoc, assoc_ms, assoc_n, allocs_steady = timed_assoc(ref, nei, args.tolerance)
+    else:
+        rs = associate(ref, nei, args.tolerance)
+        ctx.synchronize()
     n_local = rs.n
 
     poses = [sy.pose_params(*sy.estimated_pose(k)) for k in range(F)]
@@ -301,6 +322,7 @@ def main():
     packed = torch.zeros(neq.size, dtype=torch.float64, device=dev)
     d_aa = torch.from_numpy(np.ascontiguousarray(aa0)).to(dev)
     d_t = torch.from_numpy(np.ascontiguousarray(t0)).to(dev)
+    d_t_init = d_t.clone()
     tot = torch.tensor([n_local, n_queries], dtype=torch.int64, device=dev)
     if world > 1:
         # the first collective of the run: set-up times differ between ranks (scan generation, association), so the deadline is generous
@@ -409,6 +431,9 @@ def main():
         for _ in range(8):
             local_step()
         torch.cuda.synchronize()
+    # the pre-warm ran a clock-dependent number of steps: the warm-up and timed steps start again from the initial point, so that the last timed
+    # step (--dump-outputs) sees the same parameters in every run of the same command
+    d_t.copy_(d_t_init)
     if world > 1:
         dog.arm("warm-up + timed steps (all-reduce of %d doubles per step)" % neq.size, max(args.collective_timeout, 60.0 + 2.0 * (args.steps + args.warmup)))
     for _ in range(max(args.warmup, 1) if world > 1 else args.warmup):
@@ -424,6 +449,7 @@ def main():
         step()
     fence()
     dt = time.perf_counter() - t_wall
+    last_packed = packed.cpu().numpy().copy() if (args.dump_outputs and rank == 0) else None     # the last timed step's system, before anything else writes the buffer
     if graph is not None:
         ctx.profile_enable(True)
         for _ in range(args.steps):
@@ -454,7 +480,7 @@ def main():
     dog.disarm()
     # N > 1: the all-reduce of the packed blocks alone (barrier-bracketed, max over ranks) and the per-rank load table
     allreduce_us, rank_table = None, None
-    if world > 1:
+    if world > 1 and args.full:
         dog.arm("all-reduce timing", args.collective_timeout)
         scratch = torch.zeros_like(packed)
         reps = 50
@@ -482,7 +508,7 @@ def main():
 
     # ---- what one rank of an N-GPU run has to do, measured on this one GPU (no 8-GPU node is mine to launch) ----
     projection = None
-    if rank == 0 and world == 1 and not args.no_projection and args.scans >= 64:
+    if rank == 0 and run_projection:
         try:
             projection = per_rank_projection(ctx, pv, torch, sharding, args, associate, make_step, ref_all, nei_all, F, ui, uj, dev,
                                              dt / args.steps * 1e3, kern_ms / max(kern_n, 1), neq.size)
@@ -490,7 +516,7 @@ def main():
             projection = {"error": str(e)[:200]}
 
     extra_assoc = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             extra_assoc = association_points(ctx, pv, torch, args, scans, dscans, ref, nei, associate, timed_assoc, make_step, F, ui, uj, dev)
         except Exception as e:  # reporting extra only
@@ -498,7 +524,7 @@ def main():
 
     # materialise mode (r + 1x12 J written to HBM: the Ceres-feeding path) — reported, never `value`
     mat = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             d_r = torch.empty(max(n_local, 1), dtype=torch.float64, device=dev)
             d_J = torch.empty((max(n_local, 1), 12), dtype=torch.float64, device=dev)
@@ -518,7 +544,7 @@ def main():
 
     # the Ceres-feeding boundary: r + J made HOST-visible (pinned memory, asynchronous copies) — PCIe-bound, reported, never `value`
     pcie = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             pcie = pcie_block(ctx, pv, associate, ref, nei, args)
         except Exception as e:  # reporting extra only
@@ -527,7 +553,7 @@ def main():
     # 5.7K equirectangular panorama (5760 x 2880): whole-image CamToImage / ImageToCam maps (K7) and the
     # camera<->LiDAR line-association voting loop (K8) for a Room-sized batch — reported beside the headline, never `value`
     pano = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             pano = panorama_block(ctx, pv, torch, dev)
         except Exception as e:  # reporting extra only
@@ -536,7 +562,7 @@ def main():
     # 5.7K panorama (K7) and runs the PatchMatch kernels on its own 5.7K view (K11, one K13 iteration); the job's rate is
     # the sum of the ranks' rates.  Every rank takes part in the one all-reduce whatever happened to its measurement.
     image_space = None
-    if world > 1:
+    if world > 1 and args.full:
         dog.arm("image-space block (per-view shards, one all-reduce of the rates)", max(args.collective_timeout, 600.0))
         local = [0.0, 0.0, 0.0, 0.0, 0.0]
         try:
@@ -561,7 +587,7 @@ def main():
 
     # the stage in front of the path: ReOrderVLP + Segmentation + adaptive curvature of a Room-sized batch of raw scans
     features = None
-    if rank == 0 and world == 1 and not args.no_mvs:
+    if args.full and rank == 0 and world == 1 and not args.no_mvs:
         try:
             features = features_block(ctx, pv)
         except Exception as e:  # reporting extra only
@@ -575,13 +601,13 @@ def main():
         except Exception as e:
             features["extract_features_batch"] = {"error": str(e)[:200]}
     pose_solve = None
-    if rank == 0 and world == 1 and not args.no_mvs:
+    if args.full and rank == 0 and world == 1 and not args.no_mvs:
         try:
             pose_solve = pose_solve_block(ctx)
         except Exception as e:  # reporting extra only
             pose_solve = {"error": str(e)[:200]}
     mvs = None
-    if rank == 0 and world == 1 and not args.no_mvs:
+    if args.full and rank == 0 and world == 1 and not args.no_mvs:
         try:
             mvs = mvs_block(ctx, pv)
         except Exception as e:  # reporting extra only
@@ -628,9 +654,6 @@ def main():
                 "mode": "fused-normal-equations", "functor": args.functor, "targets": args.targets, "scans": F, "pairs": int(len(ref_all)),
                 "points_per_scan": 16 * args.cols, "residual_blocks": n_total, "robust_cost": cost},
             "roofline": {"bound": "hbm", "frac": achieved / HBM_PEAK_GBPS,
-                         # the same kernel on SURVEY.md §8(d)'s LITERAL workload (every one of the 65 536 points a target: 94 % of the queries are
-                         # rejected by the reference's collinearity test, the surviving segments are short) — measured below in this same run
-                         "frac_literal_workload": (((extra_assoc or {}).get("raw_targets") or {}).get("fused") or {}).get("frac_of_hbm_peak"),
                          "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src, "traffic_provenance": traffic_stamp,
                          "algorithmic_bytes_per_launch": n_local * bytes_per_eval,
                          "kernel": "k_eval_fused", "kernel_avg_ms": kern_ms / max(kern_n, 1), "launches": kern_n,
@@ -638,10 +661,7 @@ def main():
                          "M_evals_per_s_kernel": n_local / k_avg_s / 1e6,
                          "frac_of_64B_ceiling": (n_local / k_avg_s) / (HBM_PEAK_GBPS * 1e9 / 64),
                          "ceiling_M_evals_per_s_64B": HBM_PEAK_GBPS * 1e9 / 64 / 1e6,
-                         "ceiling_M_evals_per_s_56B": HBM_PEAK_GBPS * 1e9 / 56 / 1e6,
-                         "literal_workload": "association.raw_targets.fused: %s" % ((((extra_assoc or {}).get("raw_targets") or {}).get("fused") or {}).get("what"))},
-            "association": association_block(n_queries, n_targets, n_local, int(len(ref)), assoc_ms, assoc_n, t_assoc, t_assoc_first, assoc_ms_first,
-                                             allocs_first, allocs_steady, t_res, reserve_bytes, ctx.mem_info(), extra_assoc),
+                         "ceiling_M_evals_per_s_56B": HBM_PEAK_GBPS * 1e9 / 56 / 1e6},
             "step": {"graph": graph is not None, "comm": comm_mode, "packed_sum": packed_sum, "packed_l1": packed_l1, "allreduce_doubles": int(neq.size) if world > 1 else 0,
                      "comm_backend": None if world == 1 else ("gloo (PVLM_BENCH_SHARED_GPU: all ranks on one GPU, functional check, not a measurement)" if shared_gpu
                                                              else ("RCCL through torch.distributed (backend nccl)" if comm is None else "RCCL through pvlm_comm_*")),
@@ -649,18 +669,23 @@ def main():
                      "allreduce_us_note": None if world == 1 else "all-reduce of the packed blocks alone, %d doubles, 50 repetitions, barrier-bracketed, max over ranks" % neq.size,
                      "per_rank": rank_table, "collective_timeout_s": args.collective_timeout if world > 1 else None,
                      "kernels_per_step": 5, "ms_per_step_minus_fused_kernel": dt / args.steps * 1e3 - kern_ms / max(kern_n, 1)},
-            "per_rank_projection": projection,
-            "materialise": mat,
-            "pcie": pcie,
-            "panorama": pano,
-            "mvs": mvs,
-            "features": features,
-            "pose_solve": pose_solve,
-            "image_space_all_ranks": image_space,
             "setup": {"scan_generation_s": t_gen, "scans_generated": len(needed)},
+            "full": bool(args.full),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(ctx, pv, dscans, ref, nei, aa0, t0, kind, args)
+        if args.full:
+            # the same kernel on SURVEY.md §8(d)'s LITERAL workload (every one of the 65 536 points a target: 94 % of the queries are
+            # rejected by the reference's collinearity test, the surviving segments are short) — measured above in this same run
+            lit = ((extra_assoc or {}).get("raw_targets") or {}).get("fused") or {}
+            out["roofline"]["frac_literal_workload"] = lit.get("frac_of_hbm_peak")
+            out["roofline"]["literal_workload"] = "association.raw_targets.fused: %s" % lit.get("what")
+            out["association"] = association_block(n_queries, n_targets, n_local, int(len(ref)), assoc_ms, assoc_n, t_assoc, t_assoc_first, assoc_ms_first,
+                                                   allocs_first, allocs_steady, t_res, reserve_bytes, ctx.mem_info(), extra_assoc)
+            out.update({"per_rank_projection": projection, "materialise": mat, "pcie": pcie, "panorama": pano, "mvs": mvs, "features": features,
+                        "pose_solve": pose_solve, "image_space_all_ranks": image_space})
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(ctx, pv, dscans, ref, nei, aa0, t0, kind, args)
+        if last_packed is not None:
+            dump_outputs(args.dump_outputs, neq, last_packed)
         # RCCL prints a version banner through C stdio; on a pipe that buffer is flushed at exit, i.e. AFTER Python's own
         # output — push it out first so that the JSON line is the last line of stdout
         try:
@@ -674,6 +699,15 @@ def main():
         dist.barrier()
         dog.disarm()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, neq, packed):
+    """What the caller of the timed step receives — the summed normal equations of its last step, as NormalEq.unpack splits them — one
+    float64 .npy per array (a few MB at the default size)."""
+    os.makedirs(d, exist_ok=True)
+    Hd, Ho, g, cost = neq.unpack(packed)
+    for name, a in (("H_diag", Hd), ("H_offdiag", Ho), ("gradient", g), ("robust_cost", np.array([cost]))):
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def association_block(n_queries, n_targets, accepted, pairs, kernel_ms, launches, wall, wall_first, kernel_ms_first, allocs_first, allocs_steady,

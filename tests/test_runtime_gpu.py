@@ -315,7 +315,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_multi_rank_branch_of_bench_py():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--scans", "64", "--cols", "512", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-mvs", "--no-projection"]
+    common = ["--full", "--scans", "64", "--cols", "512", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-mvs", "--no-projection"]
 
     def run(gpus, env_extra):
         env = dict(os.environ, **env_extra)

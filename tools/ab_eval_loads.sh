@@ -6,7 +6,7 @@
 mkdir -p gpurun_out/r2
 for v in ${VARIANTS:-base nost base nost}; do
   lib=panovlm_amd/libpvlm.so; [ $v != base ] && lib=build/var/libpvlm_$v.so
-  PVLM_LIB=$PWD/$lib timeout 170 python bench.py --no-mvs --no-projection --no-cpu-baseline --steps 30 2>/dev/null | tail -1 | \
+  PVLM_LIB=$PWD/$lib timeout 170 python bench.py --full --no-mvs --no-projection --no-cpu-baseline --steps 30 2>/dev/null | tail -1 | \
     python -c "
 import sys, json
 o = json.loads(sys.stdin.read()); p = o.get('panorama') or {}; m = o.get('materialise') or {}; pc = o.get('pcie') or {}

@@ -9,7 +9,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/
 tail -1 $O/assoc_trace.log > $O/assoc_workload.json
 cd $R && python tools/pmc_assoc.py $O/assoc_workload.json $O/r2_pmc_assoc_scans256.json $O/assoc_trace $O/assoc_pmc_sq $O/assoc_pmc_fetch $O/assoc_pmc_write
 # the default bench under the kernel trace (roofline cross-check)
-cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
+cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
 tail -1 $O/bench_under_rocprof.log | head -c 400
 find $O/bench_trace -name "*kernel_stats.csv" | head
 # drop the big per-dispatch traces before the merge (64 MiB cap)

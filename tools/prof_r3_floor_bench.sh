@@ -7,7 +7,7 @@ timeout 900 python tools/floor_like_odometry.py --scans 1593 --ranks 2,8 --iters
 tail -40 $O/r3_floor_like_1593.txt
 timeout 1500 python -m pytest tests -x -q -m gpu --deselect tests/test_floor_scale_gpu.py > $O/r3_gpu_tests.txt 2>&1
 tail -5 $O/r3_gpu_tests.txt
-timeout 900 python bench.py > $O/r3_bench_default.log 2>$O/r3_bench_default.err
+timeout 900 python bench.py --full > $O/r3_bench_default.log 2>$O/r3_bench_default.err
 tail -1 $O/r3_bench_default.log > $O/r3_bench_default.json
 python - <<'PY'
 import json,os

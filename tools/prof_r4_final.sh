@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|erro
 cd /tmp && export TMPDIR=/tmp
 SQ="SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_INSTS_VMEM_RD"
 # HBM read traffic of the fused kernel: FETCH_SIZE in its own pass (the WRITE_SIZE pass hung on this pool in round 2 and is skipped)
-timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
+timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --full --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
 grep '^{' $O/bench_fetch.log | tail -1 > $O/bench_fetch.json
 cd $R && python tools/pmc_traffic.py $O/bench_fetch - $O/bench_fetch.json $O/r4_pmc_traffic_default.json > /dev/null && cp $O/r4_pmc_traffic_default.json $R/profiles/r4_pmc_traffic_default.json   # bench.py quotes it
 # association counters: voxel targets (256 scans) and the literal raw targets (32 scans)
@@ -34,9 +34,9 @@ python tools/ring_bench.py --reps 4 --json $O/r4_ring_bench_454x1800.json > /dev
 python tools/ring_bench.py --scans 256 --cols 4096 --cpu 2 --json $O/r4_ring_bench_256x4096.json > /dev/null 2>&1
 python tools/feature_batch_bench.py 454 > $O/r4_feature_batch_454.txt 2>&1
 # the default bench, then the same command under the kernel trace
-timeout 900 python bench.py > $O/r4_bench_default.json 2> $O/r4_bench_default.err; tail -c 300 $O/r4_bench_default.err
+timeout 900 python bench.py --full > $O/r4_bench_default.json 2> $O/r4_bench_default.err; tail -c 300 $O/r4_bench_default.err
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --full --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
 grep '^{' $O/bench_under_rocprof.log | tail -1 > $O/r4_bench_under_rocprof.json
 cd $R && python tools/trace_groups.py $(find $O/bench_trace -name "*kernel_trace.csv" | head -1) $O/r4_kernel_groups_default.csv > /dev/null
 cp $(find $O/bench_trace -name "*kernel_stats.csv" | head -1) $O/r4_kernel_stats_default.csv

@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|erro
 cd /tmp && export TMPDIR=/tmp
 SQ="SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_INSTS_VMEM_RD"
 # HBM read traffic of the fused kernel: FETCH_SIZE in its own pass (the WRITE_SIZE pass hung on this pool in round 2 and is skipped)
-timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
+timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --full --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
 grep '^{' $O/bench_fetch.log | tail -1 > $O/bench_fetch.json
 cd $R && python tools/pmc_traffic.py $O/bench_fetch - $O/bench_fetch.json $O/r5_pmc_traffic_default.json > /dev/null && cp $O/r5_pmc_traffic_default.json $R/profiles/   # bench.py quotes it
 # association counters: voxel targets (256 scans) and the literal raw targets (32 scans)
@@ -47,9 +47,9 @@ cd $R && python tools/pmc_kernels.py $O/r5_pmc_mvs.json '{"k_mvs_propagate_flow"
 cp $O/r5_pmc_mvs.json $R/profiles/
 find $O -name "*kernel_trace.csv" -size +8M -delete; find $O -name "*counter_collection.csv" -size +8M -delete
 # the default bench, then the same command under the kernel trace
-timeout 900 python bench.py > $O/r5_bench_default.json 2> $O/r5_bench_default.err; tail -c 300 $O/r5_bench_default.err
+timeout 900 python bench.py --full > $O/r5_bench_default.json 2> $O/r5_bench_default.err; tail -c 300 $O/r5_bench_default.err
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --full --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
 grep '^{' $O/bench_under_rocprof.log | tail -1 > $O/r5_bench_under_rocprof.json
 cd $R && python tools/trace_groups.py $(find $O/bench_trace -name "*kernel_trace.csv" | head -1) $O/r5_kernel_groups_default.csv > /dev/null
 cp $(find $O/bench_trace -name "*kernel_stats.csv" | head -1) $O/r5_kernel_stats_default.csv

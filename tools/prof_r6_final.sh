@@ -12,7 +12,7 @@ if [ "${PART:-a}" = a ]; then
   timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" > $O/r6_gpu_tests.txt; cat $O/r6_gpu_tests.txt
   cd /tmp && export TMPDIR=/tmp
   # HBM read traffic of the fused kernel: FETCH_SIZE in its own pass (the WRITE_SIZE pass hung on this pool in round 2 and is skipped)
-  timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
+  timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/bench_fetch -- python $R/bench.py --full --no-cpu-baseline --no-mvs --no-projection --steps 10 > $O/bench_fetch.log 2>&1
   grep '^{' $O/bench_fetch.log | tail -1 > $O/bench_fetch.json
   cd $R && python tools/pmc_traffic.py $O/bench_fetch - $O/bench_fetch.json $O/r6_pmc_traffic_default.json > /dev/null && cp $O/r6_pmc_traffic_default.json $R/profiles/   # bench.py quotes it
   # association counters: voxel targets (256 scans) and the literal raw targets (32 scans)
@@ -30,15 +30,15 @@ if [ "${PART:-a}" = a ]; then
   find $O -name "*kernel_trace.csv" -size +8M -delete; find $O -name "*counter_collection.csv" -size +8M -delete
   # the default bench, then the same command under the kernel trace
   cd $R
-  timeout 900 python bench.py > $O/r6_bench_default.json 2> $O/r6_bench_default.err; tail -c 300 $O/r6_bench_default.err
+  timeout 900 python bench.py --full > $O/r6_bench_default.json 2> $O/r6_bench_default.err; tail -c 300 $O/r6_bench_default.err
   cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python $R/bench.py --full --no-cpu-baseline --no-mvs > $O/bench_under_rocprof.log 2>&1
   grep '^{' $O/bench_under_rocprof.log | tail -1 > $O/r6_bench_under_rocprof.json
   cd $R && python tools/trace_groups.py $(find $O/bench_trace -name "*kernel_trace.csv" | head -1) $O/r6_kernel_groups_default.csv > /dev/null
   cp $(find $O/bench_trace -name "*kernel_stats.csv" | head -1) $O/r6_kernel_stats_default.csv
   # the N > 1 branch of bench.py as ranks sharing this GPU (gloo; a functional check, not a measurement)
   for N in 2 8; do
-    PVLM_BENCH_SHARED_GPU=1 timeout 900 python bench.py --gpus $N --scans 256 --steps 5 --warmup 2 --no-cpu-baseline --no-mvs --no-projection 2> $O/bench_shared_$N.err | grep '^{' | tail -1 > $O/r6_bench_shared_gpu_${N}ranks.json
+    PVLM_BENCH_SHARED_GPU=1 timeout 900 python bench.py --full --gpus $N --scans 256 --steps 5 --warmup 2 --no-cpu-baseline --no-mvs --no-projection 2> $O/bench_shared_$N.err | grep '^{' | tail -1 > $O/r6_bench_shared_gpu_${N}ranks.json
     tail -c 200 $O/bench_shared_$N.err
   done
   find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -size +4M -delete
