@@ -767,6 +767,32 @@ typedef struct pvlm_undistort_scan {
 } pvlm_undistort_scan;
 pvlm_status pvlm_undistort_batch(pvlm_ctx* ctx, int n_scans, const pvlm_undistort_scan* scans);
 
+/* ---- the fused LiDAR map (K29) -----------------------------------------------------------------------------------------------------------
+ * The body of LidarOdometry::FuseLidar (lidar_mapping/LidarOdometry.cpp:323-348; CameraLidarOptimizer::FuseLidar has the same) for the scans the caller
+ * selected: a point is kept unless range > max_range^2 or range < min_range^2, range = (double)((x*x + y*z) + z*z) in float (upstream's y*z kept;
+ * NaN ranges are kept), and moved to the world frame, float(((m00 x + m01 y) + m02 z) + m03) in double per coordinate; intensity unchanged.
+ * The result is the kept points in scan order, then point order, as 4 floats (x, y, z, intensity) each.  The selection of the scans (stride, valid
+ * flags, reloads) is the caller's (host mirror: LidarOdometry::FuseLidar).
+ * pvlm_fuse_scan: n points; x, y, z at xyz[i * stride_floats + 0..2], intensity at intensity[i * stride_floats] (pcl::PointXYZI: stride 8, intensity =
+ * xyz + 4; a packed x y z i record: stride 4, intensity = xyz + 3); T_wl: 16 doubles, row-major world <- sensor (the last row is not read). */
+typedef struct pvlm_fuse_scan {
+  const float* xyz;
+  const float* intensity;
+  int n;
+  int stride_floats;
+  const double* T_wl;
+} pvlm_fuse_scan;
+/* Host clouds in, the caller's host buffer out (capacity points of 4 floats).  *n_out = points kept; per_scan_or_null[s] = those of scan s.  A capacity below
+ * *n_out returns PVLM_ERR_ARG with *n_out (and the per-scan counts) set; points past capacity are not written.  Works through a bounded pinned window in pieces of
+ * whole scans (the upload of one piece beside the kernels and the download of the one before); synchronous; PVLM_ERR_STATE inside a graph capture. */
+pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fuse_scan* scans, double min_range, double max_range, float* out_xyzi, long long capacity,
+                            long long* n_out, long long* per_scan_or_null);
+/* The same on device clouds: the descriptor array and the poses are host memory, xyz / intensity, d_out, d_n_out and d_per_scan_or_null (n_scans counts) device
+ * memory; d_out must be 16-byte aligned (the points are written as float4; PVLM_ERR_ARG otherwise).  Queued on the context's stream without a host synchronisation: *d_n_out is the full kept count even when it exceeds capacity (points past capacity are
+ * not written).  PVLM_ERR_STATE inside a graph capture. */
+pvlm_status pvlm_fuse_scans_dev(pvlm_ctx* ctx, int n_scans, const pvlm_fuse_scan* device_clouds, double min_range, double max_range, float* d_out,
+                                long long capacity, long long* d_n_out, long long* d_per_scan_or_null);
+
 #ifdef __cplusplus
 }
 #endif

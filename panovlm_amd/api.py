@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "pvlm_reserve", "pvlm_reserve_staging", "pvlm_preload", "pvlm_trim", "pvlm_mem_info", "pvlm_graph_begin", "pvlm_graph_end", "pvlm_graph_launch", "pvlm_graph_destroy",
     "pvlm_allreduce_sum_f64_host", "pvlm_host_alloc", "pvlm_host_free", "pvlm_eval_host_async", "pvlm_eval_wrench_host_async", "pvlm_eval_force_host_async", "pvlm_line2line_residuals", "pvlm_mvs_init_depth_normal", "pvlm_mvs_remove_small_segments", "pvlm_mvs_depth_to_cloud", "pvlm_mvs_views_depth_to_cloud",
     "pvlm_spd_plan_info", "pvlm_spd_plan_schedule", "pvlm_spd_plan_tail", "pvlm_spd_one_launch", "pvlm_spd_plan_prefetch", "pvlm_spd_plan_prefetch_hits", "pvlm_line_grow_batch", "pvlm_line_grow_begin", "pvlm_line_grow_finish", "pvlm_line_grow_scan", "pvlm_line_grow_destroy", "pvlm_ring_extract_batch", "pvlm_ring_extract_batch_picks", "pvlm_ring_debug_sort", "pvlm_undistort_batch", "pvlm_assoc_point2plane_stats", "pvlm_assoc_point2plane_stats2", "pvlm_scan_transform_batch", "pvlm_scan_set_pose", "pvlm_scan_cloud_info", "pvlm_scan_cloud_fetch", "pvlm_ring_batch_scan", "pvlm_ring_batch_fetch", "pvlm_ring_batch_timing", "pvlm_ring_batch_destroy",
+    "pvlm_fuse_scans", "pvlm_fuse_scans_dev",
 ]
 
 
@@ -125,6 +126,7 @@ class Context:
             raise PvlmError("pvlm_create(device=%d) failed with status %d: no usable HIP device "
                             "(this package has no CPU path)" % (device, rc))
         self.device = device
+        self._bound_stream = None      # the hipStream_t handle set_stream bound last; None = the context's own stream
 
     def _check(self, rc, what):
         if rc != 0:
@@ -144,9 +146,11 @@ class Context:
     def set_stream(self, stream_handle):
         """Issue all kernels on this hipStream_t (0 / None = HIP's default stream, e.g. torch's default stream)."""
         self._check(self.lib.pvlm_set_stream(self._h, C.c_void_p(stream_handle or 0)), "pvlm_set_stream")
+        self._bound_stream = int(stream_handle or 0)
 
     def use_own_stream(self):
         self._check(self.lib.pvlm_use_own_stream(self._h), "pvlm_use_own_stream")
+        self._bound_stream = None
 
     def synchronize(self):
         self._check(self.lib.pvlm_synchronize(self._h), "pvlm_synchronize")
@@ -1072,6 +1076,83 @@ def undistort_batch(ctx, clouds, start_poses, end_poses, inplace=False):
         descs[k].R_wl, descs[k].t_wl, descs[k].R_we, descs[k].t_we = (_p(a, C.c_double) for a in arrs)
     ctx._check(ctx.lib.pvlm_undistort_batch(ctx._h, C.c_int(len(out)), descs), "pvlm_undistort_batch")
     return out
+
+
+class FuseScanDesc(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("intensity", C.c_void_p), ("n", C.c_int), ("stride_floats", C.c_int), ("T_wl", C.POINTER(C.c_double))]
+
+
+def _pose16(pose):
+    """A 4x4 world <- sensor matrix or an (R 3x3, t 3) pair -> 16 contiguous doubles, row-major."""
+    if isinstance(pose, (tuple, list)) and len(pose) == 2:
+        T = np.eye(4)
+        T[:3, :3] = np.asarray(pose[0], np.float64).reshape(3, 3); T[:3, 3] = np.asarray(pose[1], np.float64).reshape(3)
+        return _f64(T).reshape(16)
+    return _f64(pose).reshape(16).copy()
+
+
+def _fuse_descs(clouds, poses, intensity_at, addr_of):
+    if len(clouds) != len(poses):
+        raise ValueError("fuse: one pose per cloud")
+    cols = [intensity_at] * len(clouds) if np.isscalar(intensity_at) else list(intensity_at)
+    keep = [_pose16(p) for p in poses]
+    descs = (FuseScanDesc * max(len(clouds), 1))()
+    for k, c in enumerate(clouds):
+        n, stride = int(c.shape[0]), int(c.shape[1])
+        if stride < 3 or not (0 <= cols[k] < stride):
+            raise ValueError("fuse: cloud %d has %d columns, intensity at %d" % (k, stride, cols[k]))
+        base = addr_of(c)
+        descs[k].xyz = base; descs[k].intensity = base + 4 * int(cols[k]); descs[k].n = n; descs[k].stride_floats = stride
+        descs[k].T_wl = _p(keep[k], C.c_double)
+    return descs, keep
+
+
+def fuse_scans(ctx, clouds, poses, min_range, max_range, intensity_at=3, capacity=None):
+    """pvlm_fuse_scans (K29, the body of LidarOdometry::FuseLidar over the given scans): clouds — list of n x stride float32 arrays (x, y, z in columns 0..2,
+    intensity in column `intensity_at`: 3 for packed x y z i, 4 for pcl::PointXYZI's 8-float layout; an int or one per cloud); poses — 4x4 world <- sensor
+    matrices or (R, t) pairs.  Returns (kept points, m x 4 float32 in scan order then point order; per-scan counts, int64).  capacity (points, default: every
+    input point) below the kept count raises PvlmError."""
+    clouds = [np.ascontiguousarray(c, np.float32) for c in clouds]
+    if any(c.ndim != 2 for c in clouds):
+        raise ValueError("fuse_scans: n x stride arrays")
+    descs, keep = _fuse_descs(clouds, poses, intensity_at, lambda c: c.ctypes.data)
+    total = int(sum(len(c) for c in clouds))
+    cap = total if capacity is None else int(capacity)
+    out = np.zeros((max(cap, 1), 4), np.float32)
+    n_out = C.c_longlong(0)
+    per = np.zeros(max(len(clouds), 1), np.int64)
+    rc = ctx.lib.pvlm_fuse_scans(ctx._h, C.c_int(len(clouds)), descs, C.c_double(min_range), C.c_double(max_range), _p(out, C.c_float), C.c_longlong(cap),
+                                 C.byref(n_out), _p(per, C.c_longlong))
+    ctx._check(rc, "pvlm_fuse_scans (%d points kept)" % n_out.value)
+    return out[:n_out.value], per[:len(clouds)]
+
+
+def fuse_scans_dev(ctx, tensors, poses, min_range, max_range, intensity_at=3, out=None, capacity=None):
+    """pvlm_fuse_scans_dev on torch tensors (float32, C-contiguous n x stride on the context's device), queued on torch's current stream without a host
+    synchronisation.  The context is bound to that stream (Context.set_stream) only when it is not bound to it already: that first binding waits for what the
+    context had queued on the stream it was bound to before, and it lasts — later calls on this context run on torch's stream until Context.use_own_stream.
+    out: a float32 (capacity x 4) device tensor, 16-byte aligned (default: room for every input point).  Returns (out, per-scan counts (int64 device tensor),
+    kept count (int64 device tensor of one element, the full count even past capacity)): out[:min(count, capacity)] holds the points."""
+    import torch
+    dev = tensors[0].device if len(tensors) else torch.device("cuda", ctx.device)
+    for t in tensors:
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("fuse_scans_dev: float32, 2-D, C-contiguous tensors on one device")
+    descs, keep = _fuse_descs(tensors, poses, intensity_at, lambda t: t.data_ptr())
+    total = int(sum(int(t.shape[0]) for t in tensors))
+    if out is None:
+        out = torch.empty((max(total if capacity is None else int(capacity), 1), 4), dtype=torch.float32, device=dev)
+    cap = int(out.shape[0]) if capacity is None else int(capacity)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or cap < 0 or out.numel() < 4 * cap or out.data_ptr() % 16:
+        raise ValueError("fuse_scans_dev: out must be a contiguous, 16-byte aligned float32 tensor of at least capacity x 4 on the clouds' device")
+    per = torch.zeros(max(len(tensors), 1), dtype=torch.int64, device=dev)
+    n = torch.zeros(1, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if ctx._bound_stream != int(stream or 0):
+        ctx.set_stream(stream)
+    ctx._check(ctx.lib.pvlm_fuse_scans_dev(ctx._h, C.c_int(len(tensors)), descs, C.c_double(min_range), C.c_double(max_range), C.c_void_p(out.data_ptr()),
+                                           C.c_longlong(cap), C.c_void_p(n.data_ptr()), C.c_void_p(per.data_ptr())), "pvlm_fuse_scans_dev")
+    return out, per[:len(tensors)], n
 
 
 def device_sort(ctx, keys):

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
-NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip")
+NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip")
 
 
 def _hipcc():
@@ -109,6 +109,7 @@ def build_variant(tag, defines):
 
 HOST_LIB = os.path.join(HERE, "libpvlm_host.so")
 HOST_DRIVER = os.path.join(HERE, "build", "pvlm_host_driver")
+FUSE_DRIVER = os.path.join(HERE, "build", "pvlm_fuse_driver")
 
 
 def build_host(force=False):
@@ -143,6 +144,12 @@ def build_host(force=False):
         # for the handful of Ceres classes the adapter touches (this image has no Ceres)
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "tests", "cpp", "ceres_double"),
                                drv, "-o", HOST_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm", "-Wl,-rpath," + HERE])
+    # the fused map's driver (FuseLidar, SavePCDFileBinary, the timing of the device call against the host loop)
+    fdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_fuse_driver.cpp")
+    if os.path.exists(fdrv) and (force or not os.path.exists(FUSE_DRIVER) or
+                                 os.path.getmtime(FUSE_DRIVER) < max(os.path.getmtime(fdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", fdrv, "-o", FUSE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
     return HOST_LIB
 
 

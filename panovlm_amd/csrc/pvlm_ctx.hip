@@ -384,6 +384,7 @@ pvlm_status pvlm_preload(pvlm_ctx* ctx) {
   pvlm_i_preload_assoc(ctx->stream);
   pvlm_i_preload_ba(ctx->stream);
   pvlm_i_preload_eval(ctx->stream);
+  pvlm_i_preload_fuse(ctx->stream);
   pvlm_i_preload_linalg(ctx->stream);
   pvlm_i_preload_linegrow(ctx->stream);
   pvlm_i_preload_lines(ctx->stream);

@@ -276,6 +276,7 @@ void pvlm_i_spd_plan_release(pvlm_ctx* ctx);
 void pvlm_i_preload_assoc(hipStream_t s);
 void pvlm_i_preload_ba(hipStream_t s);
 void pvlm_i_preload_eval(hipStream_t s);
+void pvlm_i_preload_fuse(hipStream_t s);
 void pvlm_i_preload_linalg(hipStream_t s);
 void pvlm_i_preload_linegrow(hipStream_t s);
 void pvlm_i_preload_lines(hipStream_t s);

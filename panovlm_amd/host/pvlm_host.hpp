@@ -472,6 +472,8 @@ class LidarOdometry {
   // world frame and back in float, and may have dropped them); the in-memory form of that reload: scan k gets clouds[k] again
   void ReloadClouds(const std::vector<PointCloud>& clouds);
   void ResetAllLidars();                          // lidar_mapping/LidarOdometry.cpp:295-304 (the reload of an empty cloud is LoadLidar's business)
+  // lidar_mapping/LidarOdometry.cpp:323-348: the fused map of every (skip + 1)-th scan in the world frame (FuseLidarScans below; one device call)
+  PointCloud FuseLidar(int skip = 2, double min_range = 0, double max_range = 100);
   const std::vector<Velodyne>& GetLidarData() const { return lidars; }
   std::vector<Matrix3d> GetGlobalRotation() const;
   std::vector<Vector3d> GetGlobalTranslation() const;
@@ -491,6 +493,17 @@ class LidarOdometry {
   Config config;
   Exchange exchange_;
 };
+
+// The body of LidarOdometry::FuseLidar / CameraLidarOptimizer::FuseLidar (lidar_mapping/LidarOdometry.cpp:323-348): scans i = 0, skip + 1, 2 (skip + 1), ... that
+// are valid with a valid pose (the stride does not re-sync after a skipped scan); an empty `cloud` is reloaded from `name` (LoadLidar: cloud_scan untouched, and a
+// reload that leaves the scan invalid still contributes, as upstream's check came before it); the points of cloud_scan when it is non-empty, of cloud otherwise.
+// Point selection and transform: pvlm_fuse_scans (K29), one call for all scans.  The one deliberate divergence: skip < 0, which never ends upstream, throws
+// std::invalid_argument.
+PointCloud FuseLidarScans(std::vector<Velodyne>& lidars, int skip, double min_range, double max_range);
+// pcl::io::savePCDFileBinary<pcl::PointXYZI>(path, cloud): header lines "# .PCD v0.7 - Point Cloud Data file format", VERSION 0.7, FIELDS x y z intensity,
+// SIZE 4 4 4 4, TYPE F F F F, COUNT 1 1 1 1, WIDTH n, HEIGHT 1, VIEWPOINT 0 0 0 1 0 0 0, POINTS n, DATA binary, then n packed 16-byte records.  An empty
+// cloud writes nothing and returns false (PCL refuses it).  The layout is recalled from PCL 1.x, not pinned against a PCL build.
+bool SavePCDFileBinary(const std::string& file_path, const PointCloud& cloud);
 
 // base/Geometry.hpp:572-583: the pose a fraction `ratio` of the way from pose_w1 to pose_w2 (rotation by slerp, translation of T_21 scaled)
 Matrix4d SlerpPose(const Matrix4d& pose_w1, const Matrix4d& pose_w2, double ratio);
@@ -603,6 +616,8 @@ class CameraLidarOptimizer {
   const Matrix4d& GetOptimizedTcl() const { return T_cl_optimized; }
   const std::vector<Velodyne>& GetLidars() const { return lidars; }
   const std::vector<Frame>& GetFrames() const { return frames; }
+  // joint_optimization/CameraLidarOptimizer.cpp:777-802: the same body as LidarOdometry::FuseLidar (FuseLidarScans)
+  PointCloud FuseLidar(int skip, double min_range, double max_range);
   struct IterLog { double cost; int steps; int residual_blocks; size_t line_pairs; std::vector<double> cost_history; };
   std::vector<IterLog> log;
  private:

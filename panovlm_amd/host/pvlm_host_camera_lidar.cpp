@@ -532,6 +532,10 @@ bool CameraLidarOptimizer::JointOptimize() {
   return true;
 }
 
+PointCloud CameraLidarOptimizer::FuseLidar(int skip, double min_range, double max_range) {
+  return FuseLidarScans(lidars, skip, min_range, max_range);
+}
+
 // ================================================================================================
 // MVS::FuseDepthImages — mvs/MVS.cpp:2168-2334 (ConfToWeight :2337-2340, BGR2HSV util/Visualization.cpp:57-77)
 // ================================================================================================

@@ -50,6 +50,19 @@ void ExportPoseT(const std::string file_path, const std::vector<Matrix3d>& rotat
   }
 }
 
+// pcl::io::savePCDFileBinary<pcl::PointXYZI> (main.cpp:408, :441, :508, :516): the header PCL 1.x writes for the type (recalled, not pinned against a PCL build),
+// then the points as packed x y z intensity records — PCL drops the padding of the in-memory point.  PCL refuses an empty cloud; so does this.
+bool SavePCDFileBinary(const std::string& file_path, const PointCloud& cloud) {
+  if (cloud.empty()) { fprintf(stderr, "[pcl::PCDWriter::writeBinary] Input point cloud has no data!\n"); return false; }
+  std::ofstream out(file_path, std::ios::binary);
+  if (!out.is_open()) { fprintf(stderr, "Fail to write %s\n", file_path.c_str()); return false; }
+  out << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\nWIDTH " << cloud.size()
+      << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << cloud.size() << "\nDATA binary\n";
+  static_assert(sizeof(PointXYZI) == 16, "PointXYZI is the packed record");
+  out.write(reinterpret_cast<const char*>(cloud.data()), (std::streamsize)(cloud.size() * sizeof(PointXYZI)));
+  return (bool)out;
+}
+
 // ================================================================================================
 // LoadLidar — sensors/Velodyne.cpp:92-172 (+ the part of pcl::io::loadPCDFile a PointXYZI cloud needs)
 // ================================================================================================

@@ -233,4 +233,39 @@ bool LidarOdometry::UndistortLidars(const float gap_time) {
   return true;
 }
 
+// ---- lidar_mapping/LidarOdometry.cpp:323-348 (joint_optimization/CameraLidarOptimizer.cpp:777-802 has the same body) ----------------------------------------
+PointCloud FuseLidarScans(std::vector<Velodyne>& lidars, int skip, double min_range, double max_range) {
+  if (skip < 0) throw std::invalid_argument("FuseLidar: skip < 0 (upstream's loop would not end)");
+  std::vector<const PointCloud*> src;
+  std::vector<Matrix4d> poses;
+  for (size_t i = 0; i < lidars.size(); i += (size_t)skip + 1) {
+    Velodyne& v = lidars[i];
+    if (!v.valid || !v.IsPoseValid()) continue;
+    if (v.cloud.empty()) v.LoadLidar(v.name);
+    const PointCloud& c = v.cloud_scan.empty() ? v.cloud : v.cloud_scan;
+    if (c.empty()) continue;
+    src.push_back(&c);
+    poses.push_back(v.GetPose());
+  }
+  long long total = 0;
+  std::vector<pvlm_fuse_scan> descs(src.size());
+  for (size_t k = 0; k < src.size(); ++k) {
+    const float* p = &(*src[k])[0].x;
+    descs[k] = pvlm_fuse_scan{p, p + 3, (int)src[k]->size(), (int)(sizeof(PointXYZI) / sizeof(float)), poses[k].data()};
+    total += (long long)src[k]->size();
+  }
+  PointCloud fused((size_t)total);
+  if (total == 0) return fused;
+  long long kept = 0;
+  Engine& e = Engine::Default();
+  e.Check(pvlm_fuse_scans(e.ctx(), (int)descs.size(), descs.data(), min_range, max_range, &fused[0].x, total, &kept, nullptr), "pvlm_fuse_scans");
+  fused.resize((size_t)kept);
+  return fused;
+}
+
+PointCloud LidarOdometry::FuseLidar(int skip, double min_range, double max_range) {
+  StageTimer stage_timer_("fused map (FuseLidar)");
+  return FuseLidarScans(lidars, skip, min_range, max_range);
+}
+
 }  // namespace pvlm
