@@ -793,6 +793,41 @@ pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fuse_scan* sc
 pvlm_status pvlm_fuse_scans_dev(pvlm_ctx* ctx, int n_scans, const pvlm_fuse_scan* device_clouds, double min_range, double max_range, float* d_out,
                                 long long capacity, long long* d_n_out, long long* d_per_scan_or_null);
 
+/* ---- the coloured LiDAR map (K30) --------------------------------------------------------------------------------------------------------
+ * The colour stage of Texture::ColorizeLidarPointCloud (mvs/Texture.cpp:14-80) for the (scan, frame) pairs the caller selected (both poses valid): a point of the
+ * scan (cloud_scan, LiDAR frame) is kept when distance = (double)((x*x + y*y) + z*z) in float is neither < min_dist^2 nor > max_dist^2 (NaN passes), its camera
+ * point p = (T_cl (x, y, z, 1)).hnormalized() in double ((m0 x + m1 y) + m2 z) + m3 per row) projects through the double Equirectangular::CamToImage to
+ * (round(u), round(v)) inside the image (std::round, then x86-64's conversion: NaN never lands on a pixel), and the pixel's OpenCV 8-bit HSV is not sky
+ * (h 100..124, s 43..200, v 150..255).  The record is (x, y, z of the LiDAR-frame point, colour word): 4 x 4 bytes, the fourth the bits of
+ * b | g << 8 | r << 16 | 255 << 24 (pcl::PointXYZRGB's rgb and the PCD data record).  Kept points in pair order, then point order.
+ * pvlm_colorize_pair: n points, x y z at xyz[i * stride_floats + 0..2] (pcl::PointXYZI: stride 8); T_cl: 12 doubles, rows 0..2 of the rigid camera <- LiDAR
+ * transform T_wc^-1 T_wl (its last row is taken as 0 0 0 1); bgr: rows x cols BGR8 pixels, row r at bgr + r * row_bytes (row_bytes >= 3 cols,
+ * rows * row_bytes < 2^31). */
+typedef struct pvlm_colorize_pair {
+  const float* xyz;
+  int n;
+  int stride_floats;
+  const double* T_cl;
+  const unsigned char* bgr;
+  int rows;
+  int cols;
+  long long row_bytes;
+} pvlm_colorize_pair;
+/* Host clouds and images in, the caller's host buffer out (capacity records).  *n_out = points kept; per_pair_or_null[s] = those of pair s.  A capacity below
+ * *n_out returns PVLM_ERR_ARG with *n_out (and the per-pair counts) set; records past capacity are not written.  The images stay on the host: pieces of whole pairs
+ * go through a bounded pinned window (clouds up, the pixel of every point projected on the device and brought down, the pixels' BGR gathered by host threads
+ * and sent up, the HSV test and the compaction on the device); the next piece's upload and projection overlap this one's gather.  Synchronous;
+ * PVLM_ERR_STATE inside a graph capture. */
+pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvlm_colorize_pair* pairs, double min_dist, double max_dist, float* out_records,
+                                long long capacity, long long* n_out, long long* per_pair_or_null);
+/* The same on device clouds and images: the descriptor array and T_cl are host memory, xyz, bgr, d_out, d_n_out and d_per_pair_or_null (n_pairs counts) device
+ * memory; d_out must be 16-byte aligned (PVLM_ERR_ARG otherwise).  Queued on the context's stream without a host synchronisation: *d_n_out is the full kept count
+ * even when it exceeds capacity (records past capacity are not written).  PVLM_ERR_STATE inside a graph capture. */
+pvlm_status pvlm_colorize_scans_dev(pvlm_ctx* ctx, int n_pairs, const pvlm_colorize_pair* device_pairs, double min_dist, double max_dist, float* d_out,
+                                    long long capacity, long long* d_n_out, long long* d_per_pair_or_null);
+/* Tests: the device's OpenCV 8-bit BGR -> HSV (hrange 180) of n host pixels, bgr and hsv_out n x 3 bytes. */
+pvlm_status pvlm_colorize_debug_hsv(pvlm_ctx* ctx, long long n, const unsigned char* bgr, unsigned char* hsv_out);
+
 #ifdef __cplusplus
 }
 #endif

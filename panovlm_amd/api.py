@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "pvlm_allreduce_sum_f64_host", "pvlm_host_alloc", "pvlm_host_free", "pvlm_eval_host_async", "pvlm_eval_wrench_host_async", "pvlm_eval_force_host_async", "pvlm_line2line_residuals", "pvlm_mvs_init_depth_normal", "pvlm_mvs_remove_small_segments", "pvlm_mvs_depth_to_cloud", "pvlm_mvs_views_depth_to_cloud",
     "pvlm_spd_plan_info", "pvlm_spd_plan_schedule", "pvlm_spd_plan_tail", "pvlm_spd_one_launch", "pvlm_spd_plan_prefetch", "pvlm_spd_plan_prefetch_hits", "pvlm_line_grow_batch", "pvlm_line_grow_begin", "pvlm_line_grow_finish", "pvlm_line_grow_scan", "pvlm_line_grow_destroy", "pvlm_ring_extract_batch", "pvlm_ring_extract_batch_picks", "pvlm_ring_debug_sort", "pvlm_undistort_batch", "pvlm_assoc_point2plane_stats", "pvlm_assoc_point2plane_stats2", "pvlm_scan_transform_batch", "pvlm_scan_set_pose", "pvlm_scan_cloud_info", "pvlm_scan_cloud_fetch", "pvlm_ring_batch_scan", "pvlm_ring_batch_fetch", "pvlm_ring_batch_timing", "pvlm_ring_batch_destroy",
     "pvlm_fuse_scans", "pvlm_fuse_scans_dev",
+    "pvlm_colorize_scans", "pvlm_colorize_scans_dev", "pvlm_colorize_debug_hsv",
 ]
 
 
@@ -1153,6 +1154,93 @@ def fuse_scans_dev(ctx, tensors, poses, min_range, max_range, intensity_at=3, ou
     ctx._check(ctx.lib.pvlm_fuse_scans_dev(ctx._h, C.c_int(len(tensors)), descs, C.c_double(min_range), C.c_double(max_range), C.c_void_p(out.data_ptr()),
                                            C.c_longlong(cap), C.c_void_p(n.data_ptr()), C.c_void_p(per.data_ptr())), "pvlm_fuse_scans_dev")
     return out, per[:len(tensors)], n
+
+
+class ColorizePairDesc(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_int), ("stride_floats", C.c_int), ("T_cl", C.POINTER(C.c_double)), ("bgr", C.c_void_p), ("rows", C.c_int),
+                ("cols", C.c_int), ("row_bytes", C.c_longlong)]
+
+
+def _colorize_descs(clouds, T_cl, images, addr_of, shape_of):
+    """T_cl[k] None: pair k is left out (a pose is invalid; it gets no points).  Otherwise 12 (rows 0..2) or 16 doubles, or a 3x4 / 4x4 matrix."""
+    if not (len(clouds) == len(T_cl) == len(images)):
+        raise ValueError("colorize: one T_cl and one image per cloud")
+    keep, descs = [], (ColorizePairDesc * max(len(clouds), 1))()
+    for k, (c, T, im) in enumerate(zip(clouds, T_cl, images)):
+        n, stride = int(c.shape[0]), int(c.shape[1])
+        if stride < 3:
+            raise ValueError("colorize: cloud %d has %d columns" % (k, stride))
+        if T is None or n == 0:
+            continue
+        t = _f64(T).reshape(-1)[:12].copy()
+        if t.size != 12:
+            raise ValueError("colorize: T_cl %d needs rows 0..2 of a 4x4 transform" % k)
+        rows, cols, ch = shape_of(im)
+        if ch != 3:
+            raise ValueError("colorize: image %d is not rows x cols x 3 BGR" % k)
+        keep.append(t)
+        descs[k].xyz = addr_of(c); descs[k].n = n; descs[k].stride_floats = stride; descs[k].T_cl = _p(t, C.c_double)
+        descs[k].bgr = addr_of(im); descs[k].rows = rows; descs[k].cols = cols; descs[k].row_bytes = 3 * cols
+    return descs, keep
+
+
+def colorize_scans(ctx, clouds, T_cl, images, min_dist, max_dist, capacity=None):
+    """pvlm_colorize_scans (K30, the colour stage of Texture::ColorizeLidarPointCloud): clouds — list of n x stride float32 arrays (x, y, z in columns 0..2;
+    pcl::PointXYZI's layout is stride 8); T_cl — camera <- LiDAR transforms (rows 0..2 used; None = the pair is skipped); images — rows x cols x 3 uint8 BGR
+    arrays (host memory; they never go to the device).  Returns (records, m x 4 float32: x y z of the LiDAR-frame point and the bits of the colour word
+    b | g << 8 | r << 16 | 255 << 24, in pair order then point order; per-pair counts, int64)."""
+    clouds = [np.ascontiguousarray(c, np.float32) for c in clouds]
+    images = [np.ascontiguousarray(im, np.uint8) for im in images]
+    if any(c.ndim != 2 for c in clouds) or any(im.ndim != 3 for im in images):
+        raise ValueError("colorize_scans: n x stride clouds and rows x cols x 3 images")
+    descs, keep = _colorize_descs(clouds, T_cl, images, lambda a: a.ctypes.data, lambda im: im.shape)
+    total = int(sum(len(c) for c, T in zip(clouds, T_cl) if T is not None))
+    cap = total if capacity is None else int(capacity)
+    out = np.zeros((max(cap, 1), 4), np.float32)
+    n_out = C.c_longlong(0)
+    per = np.zeros(max(len(clouds), 1), np.int64)
+    rc = ctx.lib.pvlm_colorize_scans(ctx._h, C.c_int(len(clouds)), descs, C.c_double(min_dist), C.c_double(max_dist), _p(out, C.c_float), C.c_longlong(cap),
+                                     C.byref(n_out), _p(per, C.c_longlong))
+    ctx._check(rc, "pvlm_colorize_scans (%d points kept)" % n_out.value)
+    return out[:n_out.value], per[:len(clouds)]
+
+
+def colorize_scans_dev(ctx, clouds, T_cl, images, min_dist, max_dist, out=None, capacity=None):
+    """pvlm_colorize_scans_dev on torch tensors: clouds float32 n x stride, images uint8 rows x cols x 3 (BGR), all C-contiguous on the context's device; queued
+    on torch's current stream without a host synchronisation.  The context is bound to that stream only when it is not bound to it already (as fuse_scans_dev).
+    Returns (out (capacity x 4 float32, 16-byte aligned; out[:min(count, capacity)] holds the records), per-pair counts (int64 device tensor), kept count
+    (int64 device tensor of one element, the full count even past capacity))."""
+    import torch
+    dev = clouds[0].device if len(clouds) else torch.device("cuda", ctx.device)
+    for t in clouds:
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("colorize_scans_dev: float32, 2-D, C-contiguous clouds on one device")
+    for im in images:
+        if im.dtype != torch.uint8 or im.dim() != 3 or not im.is_contiguous() or im.device != dev:
+            raise ValueError("colorize_scans_dev: uint8 rows x cols x 3, C-contiguous images on the clouds' device")
+    descs, keep = _colorize_descs(clouds, T_cl, images, lambda t: t.data_ptr(), lambda im: tuple(int(v) for v in im.shape))
+    total = int(sum(int(c.shape[0]) for c, T in zip(clouds, T_cl) if T is not None))
+    if out is None:
+        out = torch.empty((max(total if capacity is None else int(capacity), 1), 4), dtype=torch.float32, device=dev)
+    cap = int(out.shape[0]) if capacity is None else int(capacity)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or cap < 0 or out.numel() < 4 * cap or out.data_ptr() % 16:
+        raise ValueError("colorize_scans_dev: out must be a contiguous, 16-byte aligned float32 tensor of at least capacity x 4 on the clouds' device")
+    per = torch.zeros(max(len(clouds), 1), dtype=torch.int64, device=dev)
+    n = torch.zeros(1, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if ctx._bound_stream != int(stream or 0):
+        ctx.set_stream(stream)
+    ctx._check(ctx.lib.pvlm_colorize_scans_dev(ctx._h, C.c_int(len(clouds)), descs, C.c_double(min_dist), C.c_double(max_dist), C.c_void_p(out.data_ptr()),
+                                               C.c_longlong(cap), C.c_void_p(n.data_ptr()), C.c_void_p(per.data_ptr())), "pvlm_colorize_scans_dev")
+    return out, per[:len(clouds)], n
+
+
+def colorize_debug_hsv(ctx, bgr):
+    """pvlm_colorize_debug_hsv: the device's OpenCV 8-bit BGR -> HSV of n x 3 uint8 pixels (tests)."""
+    bgr = np.ascontiguousarray(bgr, np.uint8).reshape(-1, 3)
+    hsv = np.zeros_like(bgr)
+    ctx._check(ctx.lib.pvlm_colorize_debug_hsv(ctx._h, C.c_longlong(len(bgr)), _p(bgr, C.c_ubyte), _p(hsv, C.c_ubyte)), "pvlm_colorize_debug_hsv")
+    return hsv
 
 
 def device_sort(ctx, keys):

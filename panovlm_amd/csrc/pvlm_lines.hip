@@ -15,6 +15,7 @@
 #include "pvlm_internal.h"
 #include "pvlm_workers.h"
 #include "pvlm_exact_math.h"
+#include "pvlm_equirect_core.h"
 
 // ---- K4 -----------------------------------------------------------------------------------------
 // PointToLineDistance3D (base/Geometry.hpp:198-211), fp64, line = (point, direction).
@@ -169,18 +170,7 @@ static inline hipError_t ln_up(pvlm_ctx* ctx, void* d, const void* h, size_t byt
 static inline hipError_t ln_down(pvlm_ctx* ctx, void* h, const void* d, size_t bytes) { return pvlm_i_d2h_q(ctx, h, d, bytes) == PVLM_OK ? hipSuccess : hipErrorUnknown; }
 static inline hipError_t ln_sync(pvlm_ctx* ctx) { return pvlm_i_sync(ctx) == PVLM_OK ? hipSuccess : hipErrorUnknown; }
 
-template <typename T>
-__device__ __forceinline__ T fast_atan2(T y, T x) {
-  const T ax = x < 0 ? -x : x, ay = y < 0 ? -y : y;  // std::abs
-  const T mn = ay < ax ? ay : ax, mxv = ax < ay ? ay : ax;  // std::min(ax, ay), std::max(ax, ay)
-  const T a = mn / (mxv + (T)DBL_EPSILON);
-  const T s = a * a;
-  T r = ((-0.04432655554792128 * s + 0.1555786518463281) * s - 0.3258083974640975) * s * a + 0.9997878412794807 * a;
-  if (ay > ax) r = 1.57079632679489661923 - r;
-  if (x < 0) r = 3.14159265358979323846 - r;
-  if (y < 0) r = -r;
-  return r;
-}
+using pvlm_equirect::fast_atan2;   // csrc/pvlm_equirect_core.h (shared with K30)
 
 template <typename T>
 __global__ void k_cam_to_image(int rows, int cols, long long n, const T* __restrict__ cam, T* __restrict__ px) {
@@ -195,10 +185,7 @@ __global__ void k_cam_to_image(int rows, int cols, long long n, const T* __restr
     px[2 * i] = (float)(cols * (0.5 + pvlm_exact::div_two_pi(lon)));
     px[2 * i + 1] = (float)(rows * (0.5 - pvlm_exact::div_pi(lat)));
   } else {
-    const T lon = fast_atan2<T>(x, z);
-    const T lat = -fast_atan2<T>(y, (T)sqrt((double)(x * x + z * z)));
-    px[2 * i] = (T)(cols * (0.5 + lon / (2.0 * 3.14159265358979323846)));
-    px[2 * i + 1] = (T)(rows * (0.5 - lat / 3.14159265358979323846));
+    pvlm_equirect::cam_to_image_f64(rows, cols, x, y, z, &px[2 * i], &px[2 * i + 1]);
   }
 }
 

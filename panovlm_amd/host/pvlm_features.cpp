@@ -213,7 +213,7 @@ void Velodyne::ReOrderVLP() {
   for (int r = 0; r < N_SCANS; ++r) { L.scanStartInd[r] = ring_begin[r] + 5; L.scanEndInd[r] = ring_begin[r + 1] - 6; }
 }
 
-void Velodyne::Segmentation() {
+int Velodyne::Segmentation() {
   RingLayout& L = layout_;
   const int rows = N_SCANS, cols = horizon_scans;
   const size_t cells = (size_t)rows * cols;
@@ -267,6 +267,7 @@ void Velodyne::Segmentation() {
   L.image_to_point_idx.swap(cell_to_point);
   int begin = 0;
   for (int r = 0; r < rows; ++r) { L.scanStartInd[r] = begin + 5; begin += ring_count[r]; L.scanEndInd[r] = begin - 6; }
+  return 1;
 }
 
 void Velodyne::ExtractFeatures(float max_curvature, float intersect_angle_threshold, int method, bool segment, ExtractionTrace* trace, bool edge_to_line) {

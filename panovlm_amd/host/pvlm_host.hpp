@@ -180,6 +180,17 @@ class Velodyne {
   // horizon_scans of the first.  Call from the thread that owns the engine.
   static void ExtractFeaturesBatch(const std::vector<Velodyne*>& scans, float max_curvature = 50, float intersect_angle_threshold = 5, int method = ADAPTIVE,
                                    bool segment = true, bool edge_to_line = true, int num_threads = 1, std::vector<ExtractionTrace>* traces = nullptr);
+  // Segmentation (sensors/Velodyne.cpp:1438-1586): the points of small range-image components dropped from cloud_scan; returns 1 like upstream
+  // (sensors/Velodyne.h:184).  Needs the range image ReOrderVLP built.
+  int Segmentation();
+  // ReOrderVLP() + Segmentation() for MANY scans (the first loop of Texture::ColorizeLidarPointCloud, mvs/Texture.cpp:29-37): one
+  // pvlm_ring_extract_batch(segment = 1) per part of the list, cloud_scan / point_idx_to_image / scanStartInd / scanEndInd assembled from its source, ring_col
+  // and ring_count as ExtractFeaturesBatch does, on `num_threads` host threads; Layout().range_image and .image_to_point_idx are not filled (nothing
+  // downstream reads them).  Scans already re-ordered (cloud_scan not empty), scans with no points, scans whose range-image shape differs from the first
+  // batched one and every scan of a part the device refused (a non-finite coordinate) take the per-scan host path, ReOrderVLP() then Segmentation(), so
+  // each ends up as those two calls leave it.  The deliberate divergence: an invalid scan is left untouched (an empty cloud_scan after LoadLidar) —
+  // upstream runs Segmentation() on it without a range image, which is undefined behaviour.  Call from the thread that owns the engine.
+  static void SegmentBatch(const std::vector<Velodyne*>& scans, int num_threads = 1);
   const RingLayout& Layout() const { return layout_; }
   void Transform2LidarWorld();                    // :1773-1808  (float clouds, in place)
   void Transform2Local();                         // :1810-1848
@@ -204,7 +215,6 @@ class Velodyne {
   Vector3d t_wl_;
   bool world_ = false;
   RingLayout layout_;
-  void Segmentation();                            // sensors/Velodyne.cpp:1438-1586
   // the second half of ExtractFeatures (:707-753, ExtractEdgeFeatures2, EdgeToLine, ExtractPlaneFeatures2) from the per-point arrays
   // per-point arrays the picks read (cloud_scan.size() entries each; the caller keeps them alive).  Window ends: left / right, or — when both are
   // null — index -+ half_window (-1 = no window).  sorted / sector_host: the sector orders of pvlm_ring_result, or null = sort every sector here.
@@ -586,6 +596,50 @@ struct DepthFrame {
 struct PointXYZRGB { float x, y, z; unsigned char r, g, b; };
 std::vector<PointXYZRGB> FuseDepthImages(int rows, int cols, std::vector<DepthFrame>& frames, const std::vector<std::vector<NeighborInfo>>& neighbors, float max_depth,
                                          float depth_diff_threshold);
+
+// ---- mvs/Texture.h, mvs/Texture.cpp — the coloured LiDAR map (main.cpp:524-552) ---------------------------------------------------------------
+// A frame's colour image as the caller decoded it (no JPEG decoding here): rows x cols BGR8 pixels, row-major, 3 cols bytes per row — the size of
+// frames[i] (GetImageRows / GetImageCols), i.e. already scaled as Frame::GetImageColor would return it.
+struct ColorImage {
+  int rows = 0, cols = 0;
+  std::vector<unsigned char> bgr;
+};
+// Fills `image` with the colour image of frame `frame`; false = no image (ColorizeLidarPointCloud throws std::runtime_error).
+using ColorImageProvider = std::function<bool(size_t frame, ColorImage& image)>;
+
+// PointXYZRGB{x, y, z, r, g, b} as the 16-byte PCD record pcl::PointXYZRGB writes: x y z, then the colour word b | g << 8 | r << 16 | 255 << 24
+inline unsigned ColourWord(const PointXYZRGB& p) { return (unsigned)p.b | ((unsigned)p.g << 8) | ((unsigned)p.r << 16) | (255u << 24); }
+
+class Texture {
+ public:
+  // mvs/Texture.cpp:10-12.  images: where ColorizeLidarPointCloud gets frame i's colour image; it asks for the images of `images_per_call` pairs, colours
+  // them in one device call and drops them before it asks for the next ones, so the images held at any time are those of one call.
+  Texture(const std::vector<Velodyne>& lidars, const std::vector<Frame>& frames, const Config& config, ColorImageProvider images = nullptr)
+      : lidars(lidars), frames(frames), config(config), images_(std::move(images)) {}
+  void SetImageProvider(ColorImageProvider images) { images_ = std::move(images); }
+  int images_per_call = 16;
+  // mvs/Texture.cpp:14-80: every scan with a valid pose is loaded again (LoadLidar(name)) and segmented (Velodyne::SegmentBatch); then for every pair i whose
+  // scan and frame poses are valid, the points of cloud_scan in range whose pixel of frame i is not sky are kept with that pixel's colour, in the LiDAR frame
+  // (pvlm_colorize_scans, K30; T_cl = T_wc^-1 T_wl with the rigid inverse, the project's convention — see SelectNeighborKNN).  Deliberate divergences:
+  // lidars and frames of different sizes throw std::invalid_argument (upstream asserts); an invalid scan (Velodyne::valid false) contributes no points
+  // (upstream's Segmentation of it is undefined behaviour).
+  bool ColorizeLidarPointCloud(const double min_dist = 0, const double max_dist = 1000);
+  // mvs/Texture.cpp:82-97: the coloured clouds of pairs i = 0, skip + 1, ... whose scan pose is valid, moved to the world frame (pcl::transformPointCloud in
+  // double, pvlm_fuse::transform_point; the colour copied) and concatenated, on host threads.  skip < 0 throws std::invalid_argument (upstream asserts).
+  std::vector<PointXYZRGB> FuseCloud(int skip = 1);
+  const std::vector<std::vector<PointXYZRGB>>& GetColoredLidar() const { return lidar_colored; }
+  const std::vector<Velodyne>& GetLidars() const { return lidars; }
+
+ private:
+  std::vector<Velodyne> lidars;
+  std::vector<Frame> frames;
+  std::vector<std::vector<PointXYZRGB>> lidar_colored;   // LiDAR frame
+  const Config config;
+  ColorImageProvider images_;
+};
+// pcl::io::savePCDFileBinary<pcl::PointXYZRGB>: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F, COUNT 1 1 1 1, then n 16-byte records x y z and the bytes
+// b g r 255.  Recalled from PCL 1.x, not pinned against a PCL build.  An empty cloud writes nothing and returns false, as for PointXYZI.
+bool SavePCDFileBinary(const std::string& file_path, const std::vector<PointXYZRGB>& cloud);
 
 class CameraLidarOptimizer {
  public:

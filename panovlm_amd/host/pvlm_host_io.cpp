@@ -63,6 +63,23 @@ bool SavePCDFileBinary(const std::string& file_path, const PointCloud& cloud) {
   return (bool)out;
 }
 
+// pcl::io::savePCDFileBinary<pcl::PointXYZRGB> (main.cpp:548): the header PCL 1.x writes for the type (recalled, not pinned against a PCL build), then the
+// points as x y z records followed by the colour float whose bytes are b g r 255 (PCL's rgb word).  An empty cloud writes nothing.
+bool SavePCDFileBinary(const std::string& file_path, const std::vector<PointXYZRGB>& cloud) {
+  if (cloud.empty()) { fprintf(stderr, "[pcl::PCDWriter::writeBinary] Input point cloud has no data!\n"); return false; }
+  std::ofstream out(file_path, std::ios::binary);
+  if (!out.is_open()) { fprintf(stderr, "Fail to write %s\n", file_path.c_str()); return false; }
+  out << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\nWIDTH " << cloud.size()
+      << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << cloud.size() << "\nDATA binary\n";
+  std::vector<uint32_t> rec(cloud.size() * 4);
+  for (size_t i = 0; i < cloud.size(); ++i) {
+    std::memcpy(&rec[4 * i], &cloud[i].x, 12);
+    rec[4 * i + 3] = ColourWord(cloud[i]);
+  }
+  out.write(reinterpret_cast<const char*>(rec.data()), (std::streamsize)(rec.size() * 4));
+  return (bool)out;
+}
+
 // ================================================================================================
 // LoadLidar — sensors/Velodyne.cpp:92-172 (+ the part of pcl::io::loadPCDFile a PointXYZI cloud needs)
 // ================================================================================================
