@@ -229,8 +229,9 @@ pvlm_status pvlm_neq_accumulate_sets(pvlm_ctx* ctx, int n, pvlm_neq* const* neq,
  * U_diag / g_cam = diagonal and gradient of the camera blocks BEFORE elimination (for the caller's scaling,
  * damping and gradient test);
  * gmax_points = max |gradient| over the point blocks; cost = sum rho(r^2)/2.
- * pvlm_ba_step back-substitutes the points for the camera steps dcam (F x 6, zeros for constant blocks)
- * into the candidate points and returns out3 = [model cost decrease of these blocks, |dX|^2, |X|^2];
+ * pvlm_ba_step back-substitutes the points for the camera steps dcam (F x 6, zeros for constant blocks; it needs a
+ * pvlm_ba_reduce at the current poses: no pvlm_set_poses since, or one that set the same values from host memory again, so that a
+ * caller with several sets can reload each set's poses before its step) into the candidate points and returns out3 = [model cost decrease of these blocks, |dX|^2, |X|^2];
  * pvlm_ba_cost evaluates the cost at the current (candidate = 0) or candidate points with the poses of the
  * last pvlm_set_poses; pvlm_ba_accept makes the candidate current.  pvlm_ba_eval materialises r and the
  * 1x9 Jacobian rows [d/daa_cw | d/dt_cw | d/dX] (Ceres-feeding / parity mode).  pvlm_ba_set_constant marks
@@ -252,6 +253,53 @@ pvlm_status pvlm_ba_reduce(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, doubl
 pvlm_status pvlm_ba_step(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, double loss_a, const double* dcam, double* out3);
 pvlm_status pvlm_ba_cost(pvlm_ctx* ctx, const pvlm_baset* set, pvlm_loss loss, double loss_a, int candidate, double* cost);
 pvlm_status pvlm_ba_accept(pvlm_ctx* ctx, pvlm_baset* set);
+
+/* ---- K31: the two-row reprojection kinds (SfMGlobalBA / MVS::RefineCameraPose) ----------------------------------- *
+ * AddCameraResidual (util/Optimization.cpp:172-222) adds, per (track, observation) of a frame with a valid pose:
+ *   PVLM_BA_ANGLE1  PanoramaReprojResidual_1Angle (base/CostFunction.h:218-247): obs = n_obs x 3 bearings, exactly
+ *                   pvlm_ba_create; pvlm_ba_create(...) == pvlm_ba_create_kind(PVLM_BA_ANGLE1, 0, 0, ...).
+ *   PVLM_BA_ANGLE2  PanoramaReprojResidual_2Angle (:178-214): obs = n_obs x 2 sphere angles (lon, lat) as
+ *                   eq.ImageToSphere(kp.pt) gives them (float template, Equirectangular.h:99-105, widened to double); the
+ *                   constructor's "x += 2 pi if x < 0" is applied here, in double.
+ *                   r = w (lon' - x, lat - y), lon' = atan2(p0, p2) + (2 pi if < 0), lat = -asin(p1 / |p|).
+ *   PVLM_BA_PIXEL   PanoramaReprojResidual_Pixel (:249-288): obs = n_obs x 2 keypoint pixels kp.pt (float widened to
+ *                   double, no rounding); rows, cols > 0 = image size.
+ *                   r = w (cols (0.5 + lon / 2pi) - x, rows (0.5 - lat / pi) - y).
+ * p = R(aa_cw) X + t_cw with the exact atan2 / asin (not FastAtan2).  Parity traps kept from upstream, not fixed:
+ *   - no seam wrap: the pixel residual jumps by cols across lon = +-pi, the 2Angle one by 2 pi across lon = 0;
+ *   - the loss acts on the block's squared norm s = r0^2 + r1^2 (Huber's outer region scales r and J by sqrt(rho'),
+ *     no rank-one term), as for the one-row kind;
+ *   - at the poles (p0 = p2 = 0) upstream's Jets give inf / NaN derivatives; here both rows' derivatives are 0.
+ * The Jacobian is closed form (dlon/dp = (p2, 0, -p0) / (p0^2 + p2^2), dlat/dp = -(e1 - p1 p / |p|^2) / sqrt(p0^2 + p2^2)).
+ * Every other entry point takes a set of any kind with the same meaning and the same packed layout; for a two-row set
+ * pvlm_ba_eval writes n_obs x 2 residuals (row 0 then row 1 of each observation) and n_obs x 2 x 9 Jacobian rows.
+ * The reduce of every kind is the gather form: no atomics, the same bits on every run. */
+typedef enum { PVLM_BA_ANGLE1 = 0, PVLM_BA_ANGLE2 = 1, PVLM_BA_PIXEL = 2 } pvlm_ba_kind;
+pvlm_status pvlm_ba_create_kind(pvlm_ctx* ctx, pvlm_ba_kind kind, int rows, int cols, int n_points, int64_t n_obs, const int64_t* point_offsets,
+                                const int* cam_ids, const double* obs, const double* points, double weight, pvlm_baset** out);
+/* kind, image size and residual rows per observation (1 or 2) of a set; null outputs are skipped */
+pvlm_status pvlm_ba_info(const pvlm_baset* set, pvlm_ba_kind* kind, int* rows, int* cols, int* rows_per_obs);
+
+/* ---- K31: track filters after a global BA (SfM::GlobalBundleAdjustment, sfm/SfM.cpp:1362-1383) ------------------- *
+ * One thread per track, all-of over its observations; keep[t] = 1 when the track survives.  The caller compacts.
+ *   track t owns the observations [point_offsets[t], point_offsets[t+1]); frame_ids[i] indexes T_cw (n_frames x 12, row-major
+ *   3 x 4 [R | t]); keypoints_f32: n_obs x 2 keypoint pixels (cv::Point2f); points: n_points x 3 (double).
+ *   T_cw = GetPose().inverse() for valid frames, all zero for invalid ones (upstream does not skip them).  The host mirror
+ *   inverts rigidly (R^T, -R^T t), as elsewhere; upstream's general Eigen 4x4 inverse differs by about 1e-16.
+ *   p = ((T0 X0 + T1 X1) + T2 X2) + T3 per row, in double.
+ * PVLM_FILTER_PIXEL  FilterTracksPixelResidual (sfm/Structure.cpp:121-156): threshold < 0 keeps everything.  Rejects when
+ *   (kp.x - u)^2 + (kp.y - v)^2 > threshold^2 in double, (u, v) = the double eq.CamToImage with FastAtan2
+ *   (USE_FAST_ATAN2).  An invalid frame projects (0, 0, 0) to the image centre, so its observation can reject.
+ * PVLM_FILTER_ANGLE  FilterTracksAngleResidual (:158-193): rejects when (p . ray) / |p| / |ray| < cos(threshold pi / 180)
+ *   (the cosine is taken on the host).  ray = eq.ImageToCam(kp.pt), which binds to the cv::Point2i overload: the keypoint
+ *   is rounded half-to-even and un-projected in float with r = 1.  |ray| = cv::norm(Point3f) is taken as
+ *   sqrt((double)x*x + (double)y*y + (double)z*z), recalled from OpenCV, not pinned.  An invalid frame gives a NaN cosine:
+ *   its observations never reject.
+ * Threshold tests in double without FMA contraction: the same decisions as a non-FMA x86-64 build. */
+typedef enum { PVLM_FILTER_PIXEL = 0, PVLM_FILTER_ANGLE = 1 } pvlm_filter_mode;
+pvlm_status pvlm_filter_tracks(pvlm_ctx* ctx, pvlm_filter_mode mode, int rows, int cols, int n_points, const int64_t* point_offsets, const int* frame_ids,
+                               const float* keypoints_f32, const double* points, int n_frames, const double* T_cw_3x4, double threshold,
+                               unsigned char* keep);
 
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled

@@ -12,6 +12,8 @@ FLAG_NORMALIZE_DISTANCE = 1
 FLAG_ASSOC_KEEP_INDICES = 0x100   # pvlm_assoc_point2plane: keep query / neighbour indices for pvlm_assoc_point2plane_debug
 FLAG_ASSOC_EXACT_FIT = 0x200      # pvlm_assoc_point2plane: the reference's QR for every query (bit-identical records)
 LOSS_NONE, LOSS_HUBER = 0, 1
+BA_KINDS = {"angle1": 0, "angle2": 1, "pixel": 2}    # pvlm_ba_kind (K31)
+FILTER_MODES = {"pixel": 0, "angle": 1}              # pvlm_filter_mode (K31)
 PAIR_BLOCK = 121
 STRIDE = {0: 7, 1: 7, 2: 9, 3: 9, 4: 10, 5: 12}
 
@@ -35,6 +37,7 @@ ABI_SYMBOLS = [
     "pvlm_spd_plan_info", "pvlm_spd_plan_schedule", "pvlm_spd_plan_tail", "pvlm_spd_one_launch", "pvlm_spd_plan_prefetch", "pvlm_spd_plan_prefetch_hits", "pvlm_line_grow_batch", "pvlm_line_grow_begin", "pvlm_line_grow_finish", "pvlm_line_grow_scan", "pvlm_line_grow_destroy", "pvlm_ring_extract_batch", "pvlm_ring_extract_batch_picks", "pvlm_ring_debug_sort", "pvlm_undistort_batch", "pvlm_assoc_point2plane_stats", "pvlm_assoc_point2plane_stats2", "pvlm_scan_transform_batch", "pvlm_scan_set_pose", "pvlm_scan_cloud_info", "pvlm_scan_cloud_fetch", "pvlm_ring_batch_scan", "pvlm_ring_batch_fetch", "pvlm_ring_batch_timing", "pvlm_ring_batch_destroy",
     "pvlm_fuse_scans", "pvlm_fuse_scans_dev",
     "pvlm_colorize_scans", "pvlm_colorize_scans_dev", "pvlm_colorize_debug_hsv",
+    "pvlm_ba_create_kind", "pvlm_ba_info", "pvlm_filter_tracks",
 ]
 
 
@@ -809,15 +812,28 @@ class NormalEq:
 
 
 class BundleSet:
-    """Reprojection blocks (PanoramaReprojResidual_1Angle) with the 3-D points resident on the GPU and eliminated
-    there (pvlm_ba_* of include/pvlm.h).  Camera poses come from Context.set_poses (angleAxis_cw, t_cw)."""
+    """Reprojection blocks with the 3-D points resident on the GPU and eliminated there (pvlm_ba_* of include/pvlm.h).
+    Camera poses come from Context.set_poses (angleAxis_cw, t_cw).  kind = "angle1" (PanoramaReprojResidual_1Angle: bearings
+    n x 3), "angle2" (_2Angle: n x 2 sphere angles) or "pixel" (_Pixel: n x 2 keypoint pixels, rows / cols = image size);
+    the two-row kinds give 2 residual rows per observation (pvlm_ba_create_kind, K31)."""
 
-    def __init__(self, ctx, point_offsets, cam_ids, bearings, points, weight=1.0):
+    def __init__(self, ctx, point_offsets, cam_ids, bearings, points, weight=1.0, kind="angle1", rows=0, cols=0):
         self.ctx = ctx
+        if kind not in BA_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(BA_KINDS))
+        self.kind = kind
+        self.rows_per_obs = 1 if kind == "angle1" else 2
         off = _i64(point_offsets); cam = _i32(cam_ids); b = _f64(bearings); X = _f64(points)
+        if len(cam) and b.reshape(len(cam), -1).shape[1] != (3 if kind == "angle1" else 2):
+            raise ValueError("observations must be n x %d for kind %r" % (3 if kind == "angle1" else 2, kind))
         self._h = C.c_void_p()
-        ctx._check(ctx.lib.pvlm_ba_create(ctx._h, C.c_int(len(off) - 1), C.c_int64(len(cam)), _p(off, C.c_int64), _p(cam, C.c_int),
-                                          _p(b, C.c_double), _p(X, C.c_double), C.c_double(weight), C.byref(self._h)), "pvlm_ba_create")
+        if kind == "angle1":
+            ctx._check(ctx.lib.pvlm_ba_create(ctx._h, C.c_int(len(off) - 1), C.c_int64(len(cam)), _p(off, C.c_int64), _p(cam, C.c_int),
+                                              _p(b, C.c_double), _p(X, C.c_double), C.c_double(weight), C.byref(self._h)), "pvlm_ba_create")
+        else:
+            ctx._check(ctx.lib.pvlm_ba_create_kind(ctx._h, C.c_int(BA_KINDS[kind]), C.c_int(rows), C.c_int(cols), C.c_int(len(off) - 1), C.c_int64(len(cam)),
+                                                   _p(off, C.c_int64), _p(cam, C.c_int), _p(b, C.c_double), _p(X, C.c_double), C.c_double(weight),
+                                                   C.byref(self._h)), "pvlm_ba_create_kind")
         npts = C.c_int(); nobs = C.c_int64(); ncam = C.c_int(); nup = C.c_int()
         ctx.lib.pvlm_ba_structure(self._h, C.byref(npts), C.byref(nobs), C.byref(ncam), C.byref(nup), None, None)
         self.n_points, self.n_obs, self.n_cams, self.n_upairs = npts.value, nobs.value, ncam.value, nup.value
@@ -852,8 +868,9 @@ class BundleSet:
         self.ctx._check(self.ctx.lib.pvlm_ba_set_constant(self.ctx._h, self._h, _p(m, C.c_ubyte)), "pvlm_ba_set_constant")
 
     def evaluate(self, jac=True):
-        r = np.zeros(self.n_obs, np.float64)
-        J = np.zeros((self.n_obs, 9), np.float64) if jac else None
+        """r: n_obs x rows_per_obs residual rows (flat), J: (n_obs x rows_per_obs) x 9 rows [aa_cw | t_cw | X]."""
+        r = np.zeros(self.n_obs * self.rows_per_obs, np.float64)
+        J = np.zeros((self.n_obs * self.rows_per_obs, 9), np.float64) if jac else None
         self.ctx._check(self.ctx.lib.pvlm_ba_eval(self.ctx._h, self._h, _p(r, C.c_double), _p(J, C.c_double)), "pvlm_ba_eval")
         return r, J
 
@@ -1241,6 +1258,19 @@ def colorize_debug_hsv(ctx, bgr):
     hsv = np.zeros_like(bgr)
     ctx._check(ctx.lib.pvlm_colorize_debug_hsv(ctx._h, C.c_longlong(len(bgr)), _p(bgr, C.c_ubyte), _p(hsv, C.c_ubyte)), "pvlm_colorize_debug_hsv")
     return hsv
+
+
+def filter_tracks(ctx, mode, rows, cols, point_offsets, frame_ids, keypoints, points, T_cw, threshold):
+    """pvlm_filter_tracks (K31): FilterTracksPixelResidual (mode "pixel") / FilterTracksAngleResidual (mode "angle") as a keep mask.
+    point_offsets: tracks + 1 (int64), frame_ids / keypoints (float32 n x 2): one per observation, points: tracks x 3, T_cw: frames x 3 x 4
+    (zeros for frames without a valid pose).  Returns a uint8 mask, 1 = the track survives."""
+    off = _i64(point_offsets); fid = _i32(frame_ids); kp = _f32(keypoints); X = _f64(points); T = _f64(T_cw)
+    n = len(off) - 1
+    keep = np.zeros(n, np.uint8)
+    ctx._check(ctx.lib.pvlm_filter_tracks(ctx._h, C.c_int(FILTER_MODES[mode]), C.c_int(rows), C.c_int(cols), C.c_int(n), _p(off, C.c_int64), _p(fid, C.c_int),
+                                          _p(kp, C.c_float), _p(X, C.c_double), C.c_int(T.reshape(-1, 12).shape[0]), _p(T, C.c_double), C.c_double(threshold),
+                                          _p(keep, C.c_ubyte)), "pvlm_filter_tracks")
+    return keep
 
 
 def device_sort(ctx, keys):

@@ -12,7 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
-NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip")
+NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
+               "pvlm_sfm_filter.hip")
 
 
 def _hipcc():
@@ -111,6 +112,7 @@ HOST_LIB = os.path.join(HERE, "libpvlm_host.so")
 HOST_DRIVER = os.path.join(HERE, "build", "pvlm_host_driver")
 FUSE_DRIVER = os.path.join(HERE, "build", "pvlm_fuse_driver")
 TEXTURE_DRIVER = os.path.join(HERE, "build", "pvlm_texture_driver")
+SFM_DRIVER = os.path.join(HERE, "build", "pvlm_sfm_driver")
 
 
 def build_host(force=False):
@@ -156,6 +158,12 @@ def build_host(force=False):
     if os.path.exists(tdrv) and (force or not os.path.exists(TEXTURE_DRIVER) or
                                  os.path.getmtime(TEXTURE_DRIVER) < max(os.path.getmtime(tdrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", tdrv, "-o", TEXTURE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    # the SfM global BA's driver (SfMGlobalBA, GlobalBundleAdjustment, RefineCameraPose: K31)
+    sdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_sfm_driver.cpp")
+    if os.path.exists(sdrv) and (force or not os.path.exists(SFM_DRIVER) or
+                                 os.path.getmtime(SFM_DRIVER) < max(os.path.getmtime(sdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", sdrv, "-o", SFM_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     return HOST_LIB
 

@@ -22,12 +22,14 @@ struct pvlm_baset {
   int n_points = 0, n_cams = 0, n_upairs = 0;
   int64_t n_obs = 0;
   double weight = 1.0;
+  int kind = 0;                     // pvlm_ba_kind: 0 PanoramaReprojResidual_1Angle, 1 _2Angle, 2 _Pixel (K31)
+  pvlm_ba::Geo geo{0.0, 0.0};       // image rows / cols of the pixel kind
   std::vector<int> ui, uj;
   std::vector<int2> h_cpl;          // staging of the couple lists during pvlm_ba_create
   long long* d_pt_off = nullptr;
   int* d_cam = nullptr;
   int* d_obs_pt = nullptr;
-  double* d_s = nullptr;
+  double* d_s = nullptr;            // n_obs x 3 unit bearings (kind 0) or n_obs x 2 observations
   double* d_X = nullptr;
   double* d_Xc = nullptr;
   double* d_scale = nullptr;
@@ -47,6 +49,8 @@ struct pvlm_baset {
   bool scaled = false;          // Jacobi scaling of the point columns initialised
   bool reduced = false;         // Vinv / gp valid for the current points
   uint64_t reduced_epoch = ~0ull;
+  std::vector<double> reduced_poses;   // the host poses of the reduce (ctx->host_poses), when they were set from host memory
+  bool reduced_poses_known = false;
   bool have_candidate = false;
 };
 
@@ -90,8 +94,10 @@ __global__ void __launch_bounds__(128) k_ba_obs(pvlm_ba::View v, const double* _
 
 // Pass B, gather form: wave s sums the couples of block s (s < n_cams: diagonal block of camera s + its g / Udiag / gcam /
 // cost share; otherwise pair s - n_cams) — lane-strided partial sums, then a fixed shuffle tree: no atomics, bit-reproducible.
-__global__ void __launch_bounds__(256) k_ba_blocks(pvlm_ba::View v, const double* __restrict__ pose_tab, const long long* __restrict__ cpl_off,
-                                                   const int2* __restrict__ cpl, double* __restrict__ packed, double* __restrict__ cost_cam) {
+// couple(i, j, acc, vec) adds one couple (pvlm_ba::couple_pass, or couple_pass2 of a two-row kind).
+template <typename Couple>
+__device__ __forceinline__ void blocks_body(const pvlm_ba::View& v, const long long* __restrict__ cpl_off, const int2* __restrict__ cpl,
+                                            double* __restrict__ packed, double* __restrict__ cost_cam, Couple couple) {
   const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (s >= v.n_cams + v.n_upairs) return;
   double acc[36], vec[19];
@@ -101,7 +107,7 @@ __global__ void __launch_bounds__(256) k_ba_blocks(pvlm_ba::View v, const double
   for (int k = 0; k < 19; ++k) vec[k] = 0.0;
   for (long long q = cpl_off[s] + lane; q < cpl_off[s + 1]; q += 64) {
     const int2 c = cpl[q];
-    pvlm_ba::couple_pass(v, pose_tab, c.x, c.y, acc, vec);
+    couple(c.x, c.y, acc, vec);
   }
 #pragma unroll
   for (int k = 0; k < 36; ++k)
@@ -126,6 +132,12 @@ __global__ void __launch_bounds__(256) k_ba_blocks(pvlm_ba::View v, const double
     for (int k = 0; k < 6; ++k) { g[k] = vec[k]; Ud[k] = vec[6 + k]; gc[k] = vec[12 + k]; }
     cost_cam[s] = vec[18];
   }
+}
+
+__global__ void __launch_bounds__(256) k_ba_blocks(pvlm_ba::View v, const double* __restrict__ pose_tab, const long long* __restrict__ cpl_off,
+                                                   const int2* __restrict__ cpl, double* __restrict__ packed, double* __restrict__ cost_cam) {
+  blocks_body(v, cpl_off, cpl, packed, cost_cam,
+              [&](long long i, long long j, double* acc, double* vec) { pvlm_ba::couple_pass(v, pose_tab, i, j, acc, vec); });
 }
 __global__ void k_ba_cost_sum(int n_cams, const double* __restrict__ cost_cam, double* __restrict__ cost) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { double c = 0.0; for (int k = 0; k < n_cams; ++k) c += cost_cam[k]; *cost = c; }
@@ -179,6 +191,66 @@ __global__ void __launch_bounds__(256) k_ba_eval(pvlm_ba::View v, const double* 
   }
 }
 
+// ---- K31: the two-row kinds (PanoramaReprojResidual_2Angle / _Pixel).  Same launch shapes, same gather order and the same reproducible
+// sums as the 1Angle kernels above; the image size rides along as an extra argument so that the 1Angle kernels' arguments do not change.
+template <int KIND>
+__global__ void __launch_bounds__(128) k_ba2_points(pvlm_ba::View v, pvlm_ba::Geo geo, const double* __restrict__ pose_tab, int init_scale, double radius,
+                                                    double min_diag, double max_diag, double* gmax) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < v.n_points) pvlm_ba::point_pass2<KIND>(v, geo, pose_tab, p, init_scale, radius, min_diag, max_diag, gmax);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) k_ba2_blocks(pvlm_ba::View v, pvlm_ba::Geo geo, const double* __restrict__ pose_tab, const long long* __restrict__ cpl_off,
+                                                    const int2* __restrict__ cpl, double* __restrict__ packed, double* __restrict__ cost_cam) {
+  blocks_body(v, cpl_off, cpl, packed, cost_cam,
+              [&](long long i, long long j, double* acc, double* vec) { pvlm_ba::couple_pass2<KIND>(v, geo, pose_tab, i, j, acc, vec); });
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(128) k_ba2_step(pvlm_ba::View v, pvlm_ba::Geo geo, const double* __restrict__ pose_tab, const double* __restrict__ dcam,
+                                                  double* __restrict__ partials) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  double o[3] = {0.0, 0.0, 0.0};
+  if (p < v.n_points) pvlm_ba::step_point2<KIND>(v, geo, pose_tab, p, dcam, o);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) block_partial(o[k], &partials[(size_t)k * gridDim.x + blockIdx.x]);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) k_ba2_cost(pvlm_ba::View v, pvlm_ba::Geo geo, const double* __restrict__ pose_tab, int candidate, double* __restrict__ partials) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  double c = 0.0;
+  if (i < v.n_obs) c = pvlm_ba::cost_obs2<KIND>(v, geo, pose_tab, i, candidate);
+  block_partial(c, &partials[blockIdx.x]);
+}
+
+// materialise the two rows r (2 per observation) and their 1 x 9 Jacobian rows [aa_cw | t_cw | X]
+template <int KIND>
+__global__ void __launch_bounds__(256) k_ba2_eval(pvlm_ba::View v, pvlm_ba::Geo geo, const double* __restrict__ pose_tab, double* __restrict__ r, double* __restrict__ J) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v.n_obs) return;
+  double rr[2], Jc[12], Jp[6];
+  pvlm_reproj::eval_obs2<KIND>(pose_tab + (size_t)v.cam[i] * PVLM_BA_POSE_TAB, v.X + 3 * (size_t)v.obs_pt[i], v.s + 2 * i, v.w, geo.rows, geo.cols, rr, Jc, Jp);
+  r[2 * i] = rr[0]; r[2 * i + 1] = rr[1];
+  if (J) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      double* o = J + 9 * (2 * i + k);
+#pragma unroll
+      for (int c = 0; c < 6; ++c) o[c] = Jc[6 * k + c];
+      o[6] = Jp[3 * k]; o[7] = Jp[3 * k + 1]; o[8] = Jp[3 * k + 2];
+    }
+  }
+}
+
+// launches the kind's instance of a two-row kernel: BA2_LAUNCH(set, k_ba2_x, grid, block, args...)
+#define BA2_LAUNCH(set, kern, grid, block, ...)                                                                        \
+  do {                                                                                                                 \
+    if ((set)->kind == pvlm_reproj::kPixel) hipLaunchKernelGGL(kern<pvlm_reproj::kPixel>, grid, block, 0, ctx->stream, __VA_ARGS__);   \
+    else hipLaunchKernelGGL(kern<pvlm_reproj::kAngle2>, grid, block, 0, ctx->stream, __VA_ARGS__);                     \
+  } while (0)
+
 static pvlm_status ba_free(pvlm_ctx* ctx, pvlm_baset* s) {
   pvlm_i_free(ctx, s->d_pt_off); pvlm_i_free(ctx, s->d_cam); pvlm_i_free(ctx, s->d_obs_pt); pvlm_i_free(ctx, s->d_s); pvlm_i_free(ctx, s->d_X); pvlm_i_free(ctx, s->d_Xc); pvlm_i_free(ctx, s->d_scale);
   pvlm_i_free(ctx, s->d_Vinv); pvlm_i_free(ctx, s->d_gp); pvlm_i_free(ctx, s->d_adj_off); pvlm_i_free(ctx, s->d_adj_cam); pvlm_i_free(ctx, s->d_adj_slot); pvlm_i_free(ctx, s->d_packed);
@@ -201,10 +273,12 @@ static pvlm_status h2d(pvlm_ctx* ctx, T* dst, const T* src, size_t n) {
 
 extern "C" {
 
-pvlm_status pvlm_ba_create(pvlm_ctx* ctx, int n_points, int64_t n_obs, const int64_t* point_offsets, const int* cam_ids, const double* bearings,
-                           const double* points, double weight, pvlm_baset** out) {
-  if (!ctx || !out || n_points < 0 || n_obs < 0 || (n_points > 0 && (!point_offsets || !points)) || (n_obs > 0 && (!cam_ids || !bearings)))
+pvlm_status pvlm_ba_create_kind(pvlm_ctx* ctx, pvlm_ba_kind kind, int rows, int cols, int n_points, int64_t n_obs, const int64_t* point_offsets,
+                                const int* cam_ids, const double* obs, const double* points, double weight, pvlm_baset** out) {
+  if (!ctx || !out || n_points < 0 || n_obs < 0 || (n_points > 0 && (!point_offsets || !points)) || (n_obs > 0 && (!cam_ids || !obs)))
     return PVLM_ERR_ARG;
+  if (kind != PVLM_BA_ANGLE1 && kind != PVLM_BA_ANGLE2 && kind != PVLM_BA_PIXEL) return PVLM_ERR_ARG;
+  if (kind == PVLM_BA_PIXEL && (rows <= 0 || cols <= 0)) return PVLM_ERR_ARG;
   *out = nullptr;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   if (n_points > 0 && (point_offsets[0] != 0 || point_offsets[n_points] != n_obs)) { PVLM_SET_ERR(ctx, "point_offsets must run from 0 to n_obs"); return PVLM_ERR_ARG; }
@@ -243,15 +317,25 @@ pvlm_status pvlm_ba_create(pvlm_ctx* ctx, int n_points, int64_t n_obs, const int
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
   }
-  // unit bearings: point_sphere.normalize() of the functor's constructor (CostFunction.h:227-230)
-  std::vector<double> s((size_t)n_obs * 3);
-  for (int64_t i = 0; i < n_obs; ++i) {
-    const double* b = bearings + 3 * i;
-    const double n = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-    for (int k = 0; k < 3; ++k) s[(size_t)i * 3 + k] = n > 0.0 ? b[k] / n : b[k];
+  const int od = kind == PVLM_BA_ANGLE1 ? 3 : 2;     // doubles per observation
+  std::vector<double> s((size_t)n_obs * od);
+  if (kind == PVLM_BA_ANGLE1) {
+    // unit bearings: point_sphere.normalize() of the functor's constructor (CostFunction.h:227-230)
+    for (int64_t i = 0; i < n_obs; ++i) {
+      const double* b = obs + 3 * i;
+      const double n = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+      for (int k = 0; k < 3; ++k) s[(size_t)i * 3 + k] = n > 0.0 ? b[k] / n : b[k];
+    }
+  } else {
+    for (int64_t i = 0; i < n_obs; ++i) {
+      s[(size_t)i * 2] = obs[2 * i]; s[(size_t)i * 2 + 1] = obs[2 * i + 1];
+      // PanoramaReprojResidual_2Angle's constructor (CostFunction.h:185-189): x += 2 pi if x < 0, in double
+      if (kind == PVLM_BA_ANGLE2 && s[(size_t)i * 2] < 0) s[(size_t)i * 2] += 2 * M_PI;
+    }
   }
   pvlm_baset* bs = new pvlm_baset();
   bs->n_points = n_points; bs->n_obs = n_obs; bs->n_cams = n_cams; bs->weight = weight;
+  bs->kind = (int)kind; bs->geo = pvlm_ba::Geo{(double)rows, (double)cols};
   std::vector<int> adj_off((size_t)n_cams + 1, 0), adj_cam, adj_slot;
   for (unsigned long long k : keys) { bs->ui.push_back((int)(k >> 32)); bs->uj.push_back((int)(k & 0xFFFFFFFFu)); }   // sorted by (ui, uj): CSR order
   bs->n_upairs = (int)bs->ui.size();
@@ -291,7 +375,7 @@ pvlm_status pvlm_ba_create(pvlm_ctx* ctx, int n_points, int64_t n_obs, const int
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_pt_off, (size_t)n_points + 1);
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_cam, (size_t)n_obs);
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_obs_pt, (size_t)n_obs);
-  if (!st) st = pvlm_i_alloc(ctx, &bs->d_s, (size_t)n_obs * 3);
+  if (!st) st = pvlm_i_alloc(ctx, &bs->d_s, (size_t)n_obs * od);
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_X, (size_t)n_points * 3);
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_Xc, (size_t)n_points * 3);
   if (!st) st = pvlm_i_alloc(ctx, &bs->d_scale, (size_t)n_points * 3);
@@ -322,6 +406,20 @@ pvlm_status pvlm_ba_create(pvlm_ctx* ctx, int n_points, int64_t n_obs, const int
   bs->h_cpl.clear(); bs->h_cpl.shrink_to_fit();
   if (st) { ba_free(ctx, bs); return st; }
   *out = bs;
+  return PVLM_OK;
+}
+
+pvlm_status pvlm_ba_create(pvlm_ctx* ctx, int n_points, int64_t n_obs, const int64_t* point_offsets, const int* cam_ids, const double* bearings,
+                           const double* points, double weight, pvlm_baset** out) {
+  return pvlm_ba_create_kind(ctx, PVLM_BA_ANGLE1, 0, 0, n_points, n_obs, point_offsets, cam_ids, bearings, points, weight, out);
+}
+
+pvlm_status pvlm_ba_info(const pvlm_baset* set, pvlm_ba_kind* kind, int* rows, int* cols, int* rows_per_obs) {
+  if (!set) return PVLM_ERR_ARG;
+  if (kind) *kind = (pvlm_ba_kind)set->kind;
+  if (rows) *rows = (int)set->geo.rows;
+  if (cols) *cols = (int)set->geo.cols;
+  if (rows_per_obs) *rows_per_obs = set->kind == PVLM_BA_ANGLE1 ? 1 : 2;
   return PVLM_OK;
 }
 
@@ -383,15 +481,19 @@ pvlm_status pvlm_ba_eval(pvlm_ctx* ctx, const pvlm_baset* set, double* r, double
   pvlm_status st = ba_ready(ctx, set);
   if (st) return st;
   if (set->n_obs == 0) return PVLM_OK;
+  const size_t nr = (size_t)set->n_obs * (set->kind == PVLM_BA_ANGLE1 ? 1 : 2);    // residual rows
   double *d_r = nullptr, *d_J = nullptr;
-  if ((st = pvlm_i_alloc(ctx, &d_r, (size_t)set->n_obs))) return st;
-  if (J && (st = pvlm_i_alloc(ctx, &d_J, (size_t)set->n_obs * 9))) { pvlm_i_free(ctx, d_r); return st; }
+  if ((st = pvlm_i_alloc(ctx, &d_r, nr))) return st;
+  if (J && (st = pvlm_i_alloc(ctx, &d_J, nr * 9))) { pvlm_i_free(ctx, d_r); return st; }
   const pvlm_ba::View v = make_view(set, 0, 0.0);
-  hipLaunchKernelGGL(k_ba_eval, dim3((unsigned)((set->n_obs + 255) / 256)), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, d_r, d_J);
+  if (set->kind == PVLM_BA_ANGLE1)
+    hipLaunchKernelGGL(k_ba_eval, dim3((unsigned)((set->n_obs + 255) / 256)), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, d_r, d_J);
+  else
+    BA2_LAUNCH(set, k_ba2_eval, dim3((unsigned)((set->n_obs + 255) / 256)), dim3(256), v, set->geo, ctx->d_pose_tab, d_r, d_J);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_ba_eval: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  if (!st) st = pvlm_i_d2h_q(ctx, r, d_r, (size_t)set->n_obs * 8);
-  if (!st && J) st = pvlm_i_d2h_q(ctx, J, d_J, (size_t)set->n_obs * 72);
+  if (!st) st = pvlm_i_d2h_q(ctx, r, d_r, nr * 8);
+  if (!st && J) st = pvlm_i_d2h_q(ctx, J, d_J, nr * 72);
   { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
   pvlm_i_free(ctx, d_r); pvlm_i_free(ctx, d_J);
   return st;
@@ -409,21 +511,29 @@ pvlm_status pvlm_ba_reduce(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, doubl
   const pvlm_ba::View v = make_view(set, (int)loss, a);
   double* d_cost = set->d_packed + (size_t)set->n_cams * 42 + (size_t)set->n_upairs * 36;
   double* d_gmax = set->d_packed + psz - 1;
+  const bool two = set->kind != PVLM_BA_ANGLE1;
   if (set->n_points) {
-    hipLaunchKernelGGL(k_ba_points, dim3((unsigned)((set->n_points + 127) / 128)), dim3(128), 0, ctx->stream, v, ctx->d_pose_tab, init_scale, radius,
-                       min_diag, max_diag, d_gmax);
+    if (two)
+      BA2_LAUNCH(set, k_ba2_points, dim3((unsigned)((set->n_points + 127) / 128)), dim3(128), v, set->geo, ctx->d_pose_tab, init_scale, radius,
+                 min_diag, max_diag, d_gmax);
+    else
+      hipLaunchKernelGGL(k_ba_points, dim3((unsigned)((set->n_points + 127) / 128)), dim3(128), 0, ctx->stream, v, ctx->d_pose_tab, init_scale, radius,
+                         min_diag, max_diag, d_gmax);
     PVLM_HIP(ctx, hipGetLastError());
   }
   {
 #if PVLM_MEASURED_VARIANTS
     static const bool scatter = getenv("PVLM_BA_ATOMICS") != nullptr;   // round 1's scatter with fp64 atomics (k_ba_obs)
-    if (scatter) {
+    if (scatter && !two) {
       if (set->n_obs) hipLaunchKernelGGL(k_ba_obs, dim3((unsigned)((set->n_obs + 127) / 128)), dim3(128), 0, ctx->stream, v, ctx->d_pose_tab, set->d_packed, d_cost);
     } else
 #endif
     {
       const int n_slots = set->n_cams + set->n_upairs;
-      if (n_slots) hipLaunchKernelGGL(k_ba_blocks, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, set->d_cpl_off, set->d_cpl, set->d_packed,
+      if (n_slots && two)
+        BA2_LAUNCH(set, k_ba2_blocks, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), v, set->geo, ctx->d_pose_tab, set->d_cpl_off, set->d_cpl, set->d_packed,
+                   set->d_cost_cam);
+      else if (n_slots) hipLaunchKernelGGL(k_ba_blocks, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, set->d_cpl_off, set->d_cpl, set->d_packed,
                                       set->d_cost_cam);
       hipLaunchKernelGGL(k_ba_cost_sum, dim3(1), dim3(64), 0, ctx->stream, set->n_cams, set->d_cost_cam, d_cost);
     }
@@ -432,6 +542,8 @@ pvlm_status pvlm_ba_reduce(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, doubl
   if ((st = pvlm_i_d2h(ctx, packed, set->d_packed, psz * 8))) return st;      // 1.2 MB at Room scale, every LM step: pinned arena, not a pageable copy
   if (init_scale) set->scaled = true;
   set->reduced = true; set->reduced_epoch = ctx->pose_epoch;
+  set->reduced_poses_known = ctx->host_poses_known;
+  if (ctx->host_poses_known) set->reduced_poses = ctx->host_poses;
   return PVLM_OK;
 }
 
@@ -440,7 +552,11 @@ pvlm_status pvlm_ba_step(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, double 
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   pvlm_status st = ba_ready(ctx, set);
   if (st) return st;
-  if (!set->reduced || set->reduced_epoch != ctx->pose_epoch) {
+  // the same poses: no pvlm_set_poses since the reduce, or the same values set again from host memory (a caller with several sets
+  // reloads each set's poses before its step)
+  const bool same_poses = set->reduced_epoch == ctx->pose_epoch ||
+                          (set->reduced_poses_known && ctx->host_poses_known && set->reduced_poses == ctx->host_poses);
+  if (!set->reduced || !same_poses) {
     PVLM_SET_ERR(ctx, "pvlm_ba_step needs pvlm_ba_reduce at the same camera poses and points first");
     return PVLM_ERR_STATE;
   }
@@ -449,7 +565,8 @@ pvlm_status pvlm_ba_step(pvlm_ctx* ctx, pvlm_baset* set, pvlm_loss loss, double 
   const pvlm_ba::View v = make_view(set, (int)loss, a);
   if (set->n_points) {
     const int nb = (set->n_points + 127) / 128;
-    hipLaunchKernelGGL(k_ba_step, dim3((unsigned)nb), dim3(128), 0, ctx->stream, v, ctx->d_pose_tab, set->d_dcam, set->d_partials);
+    if (set->kind != PVLM_BA_ANGLE1) BA2_LAUNCH(set, k_ba2_step, dim3((unsigned)nb), dim3(128), v, set->geo, ctx->d_pose_tab, set->d_dcam, set->d_partials);
+    else hipLaunchKernelGGL(k_ba_step, dim3((unsigned)nb), dim3(128), 0, ctx->stream, v, ctx->d_pose_tab, set->d_dcam, set->d_partials);
     hipLaunchKernelGGL(k_ba_sum_partials, dim3(1), dim3(64), 0, ctx->stream, nb, 3, set->d_partials, set->d_small);
     PVLM_HIP(ctx, hipGetLastError());
   }
@@ -468,7 +585,8 @@ pvlm_status pvlm_ba_cost(pvlm_ctx* ctx, const pvlm_baset* set, pvlm_loss loss, d
   const pvlm_ba::View v = make_view(set, (int)loss, a);
   if (set->n_obs) {
     const int nb = (int)((set->n_obs + 255) / 256);
-    hipLaunchKernelGGL(k_ba_cost, dim3((unsigned)nb), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, candidate, set->d_partials);
+    if (set->kind != PVLM_BA_ANGLE1) BA2_LAUNCH(set, k_ba2_cost, dim3((unsigned)nb), dim3(256), v, set->geo, ctx->d_pose_tab, candidate, set->d_partials);
+    else hipLaunchKernelGGL(k_ba_cost, dim3((unsigned)nb), dim3(256), 0, ctx->stream, v, ctx->d_pose_tab, candidate, set->d_partials);
     hipLaunchKernelGGL(k_ba_sum_partials, dim3(1), dim3(64), 0, ctx->stream, nb, 1, set->d_partials, set->d_small);
     PVLM_HIP(ctx, hipGetLastError());
   }

@@ -28,7 +28,7 @@ struct View {
   const long long* pt_off;  // n_points + 1 : observations of point p are [pt_off[p], pt_off[p+1])
   const int* cam;           // n_obs : pose-table row of the observing camera
   const int* obs_pt;        // n_obs : point of each observation
-  const double* s;          // n_obs x 3 unit bearings
+  const double* s;          // n_obs x 3 unit bearings (two-row kinds: n_obs x 2 observations)
   const double* X;          // n_points x 3 current points
   double* Xc;               // n_points x 3 candidate points (written by step_point)
   double* scale;            // n_points x 3 Jacobi scaling of the point columns (set when init_scale)
@@ -199,6 +199,133 @@ PVLM_HD inline double cost_obs(const View& v, const double* pose_tab, long long 
   double r, rho, rho1;
   pvlm_reproj::eval_obs(pose_tab + (size_t)v.cam[i] * PVLM_BA_POSE_TAB, X, v.s + 3 * i, v.w, &r, nullptr, nullptr);
   pvlm_reproj::loss_eval(v.loss, v.a, r * r, &rho, &rho1);
+  return 0.5 * rho;
+}
+
+// ==== two-row kinds (K31): the same passes for PanoramaReprojResidual_2Angle / _Pixel (pvlm_reproj::eval_obs2) ==================
+// View.s holds n_obs x 2 observations (wrapped sphere angles or pixels); Huber acts on the block's squared norm r0^2 + r1^2 and scales
+// both rows by sqrt(rho').  Separate bodies rather than a row-count template over the ones above: the 1Angle kernels keep their ISA.
+struct Geo { double rows, cols; };    // image size of the pixel kind (unused by the 2Angle kind)
+
+struct Lin2 { double r[2], rho, rho1, Jc[12], Jp[6]; };
+
+template <int KIND>
+PVLM_HD inline void linearise2(const View& v, const Geo& geo, const double* pose_tab, long long i, const double* X, Lin2* o) {
+  pvlm_reproj::eval_obs2<KIND>(pose_tab + (size_t)v.cam[i] * PVLM_BA_POSE_TAB, X, v.s + 2 * i, v.w, geo.rows, geo.cols, o->r, o->Jc, o->Jp);
+  pvlm_reproj::loss_eval(v.loss, v.a, o->r[0] * o->r[0] + o->r[1] * o->r[1], &o->rho, &o->rho1);
+}
+
+// pass A: V = sum rho' Jp^T Jp over both rows, gp = sum rho' Jp^T r, damped inverse (as point_pass)
+template <int KIND>
+PVLM_HD inline void point_pass2(const View& v, const Geo& geo, const double* pose_tab, int p, int init_scale, double radius, double min_diag,
+                                double max_diag, double* gmax) {
+  const double* X = v.X + 3 * (size_t)p;
+  double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+  for (long long i = v.pt_off[p]; i < v.pt_off[p + 1]; ++i) {
+    Lin2 l; linearise2<KIND>(v, geo, pose_tab, i, X, &l);
+    for (int k = 0; k < 2; ++k) {
+      const double* jp = l.Jp + 3 * k;
+      const double a0 = l.rho1 * jp[0], a1 = l.rho1 * jp[1], a2 = l.rho1 * jp[2];
+      V[0] += a0 * jp[0]; V[1] += a0 * jp[1]; V[2] += a0 * jp[2];
+      V[3] += a1 * jp[1]; V[4] += a1 * jp[2]; V[5] += a2 * jp[2];
+      g[0] += a0 * l.r[k]; g[1] += a1 * l.r[k]; g[2] += a2 * l.r[k];
+    }
+  }
+  double* sc = v.scale + 3 * (size_t)p;
+  if (init_scale) { sc[0] = 1.0 / (1.0 + sqrt(V[0])); sc[1] = 1.0 / (1.0 + sqrt(V[3])); sc[2] = 1.0 / (1.0 + sqrt(V[5])); }
+  double Vd[6], inv[6];
+  pvlm_reproj::damp3(V, sc, radius, min_diag, max_diag, Vd);
+  const bool frozen = v.frozen && v.frozen[p];
+  if (frozen || !pvlm_reproj::spd3_inverse(Vd, inv)) { for (int k = 0; k < 6; ++k) inv[k] = 0.0; }
+  for (int k = 0; k < 6; ++k) v.Vinv[6 * (size_t)p + k] = inv[k];
+  for (int k = 0; k < 3; ++k) v.gp[3 * (size_t)p + k] = g[k];
+  const double m = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
+  if (m > 0.0 && !frozen) PVLM_ATOMIC_MAXPOS(gmax, m);
+}
+
+// pass B, gather form (as couple_pass): the couple (i, j) adds Jc_i^T M Jc_j to its block, with the 2 x 2
+//   M = -rho'_i rho'_j Jp_i Vinv Jp_j^T  (+ rho'_i I when j == i)
+// and, when j == i, g += rho' Jc^T (r - Jp Vinv gp), Udiag += rho' sum_rows Jc^2, gcam += rho' Jc^T r, cost += rho / 2.
+template <int KIND>
+PVLM_HD inline void couple_pass2(const View& v, const Geo& geo, const double* pose_tab, long long i, long long j, double* acc, double* vec) {
+  const int p = v.obs_pt[i];
+  const double* X = v.X + 3 * (size_t)p;
+  const double* Vi = v.Vinv + 6 * (size_t)p;
+  Lin2 li, lj;
+  linearise2<KIND>(v, geo, pose_tab, i, X, &li);
+  if (j == i) lj = li; else linearise2<KIND>(v, geo, pose_tab, j, X, &lj);
+  double y[2][3];
+  pvlm_reproj::sym3_mul(Vi, li.Jp, y[0]); pvlm_reproj::sym3_mul(Vi, li.Jp + 3, y[1]);
+  double M[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) {
+      const double* jp = lj.Jp + 3 * b;
+      M[a][b] = -li.rho1 * lj.rho1 * (y[a][0] * jp[0] + y[a][1] * jp[1] + y[a][2] * jp[2]);
+    }
+  if (j == i) { M[0][0] += li.rho1; M[1][1] += li.rho1; }
+  double T[2][6];      // M Jc_j
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 6; ++b) T[a][b] = M[a][0] * lj.Jc[b] + M[a][1] * lj.Jc[6 + b];
+  for (int a = 0; a < 6; ++a) {
+    const double c0 = li.Jc[a], c1 = li.Jc[6 + a];
+    for (int b = 0; b < 6; ++b) acc[a * 6 + b] += c0 * T[0][b] + c1 * T[1][b];
+  }
+  if (j == i) {
+    const double* gp = v.gp + 3 * (size_t)p;
+    const double e0 = li.r[0] - (y[0][0] * gp[0] + y[0][1] * gp[1] + y[0][2] * gp[2]);
+    const double e1 = li.r[1] - (y[1][0] * gp[0] + y[1][1] * gp[1] + y[1][2] * gp[2]);
+    for (int k = 0; k < 6; ++k) {
+      const double c0 = li.Jc[k], c1 = li.Jc[6 + k];
+      vec[k] += li.rho1 * (c0 * e0 + c1 * e1);
+      vec[6 + k] += li.rho1 * (c0 * c0 + c1 * c1);
+      vec[12 + k] += li.rho1 * (c0 * li.r[0] + c1 * li.r[1]);
+    }
+    vec[18] += 0.5 * li.rho;
+  }
+}
+
+// back-substitution (as step_point): d = Jc dc + Jp dp per row, model -= rho' (r . d + |d|^2 / 2)
+template <int KIND>
+PVLM_HD inline void step_point2(const View& v, const Geo& geo, const double* pose_tab, int p, const double* dcam, double* out3_local) {
+  const double* X = v.X + 3 * (size_t)p;
+  const double* Vi = v.Vinv + 6 * (size_t)p;
+  double b[3] = {v.gp[3 * (size_t)p], v.gp[3 * (size_t)p + 1], v.gp[3 * (size_t)p + 2]};
+  for (long long i = v.pt_off[p]; i < v.pt_off[p + 1]; ++i) {
+    Lin2 l; linearise2<KIND>(v, geo, pose_tab, i, X, &l);
+    const double* dc = dcam + 6 * (size_t)v.cam[i];
+    for (int r = 0; r < 2; ++r) {
+      double e = 0.0;
+      for (int k = 0; k < 6; ++k) e += l.Jc[6 * r + k] * dc[k];
+      e *= l.rho1;
+      b[0] += e * l.Jp[3 * r]; b[1] += e * l.Jp[3 * r + 1]; b[2] += e * l.Jp[3 * r + 2];
+    }
+  }
+  double dp[3]; pvlm_reproj::sym3_mul(Vi, b, dp);
+  dp[0] = -dp[0]; dp[1] = -dp[1]; dp[2] = -dp[2];
+  double model = 0.0;
+  for (long long i = v.pt_off[p]; i < v.pt_off[p + 1]; ++i) {
+    Lin2 l; linearise2<KIND>(v, geo, pose_tab, i, X, &l);
+    const double* dc = dcam + 6 * (size_t)v.cam[i];
+    double rd = 0.0, dd = 0.0;
+    for (int r = 0; r < 2; ++r) {
+      double d = l.Jp[3 * r] * dp[0] + l.Jp[3 * r + 1] * dp[1] + l.Jp[3 * r + 2] * dp[2];
+      for (int k = 0; k < 6; ++k) d += l.Jc[6 * r + k] * dc[k];
+      rd += l.r[r] * d; dd += d * d;
+    }
+    model -= l.rho1 * (rd + 0.5 * dd);
+  }
+  for (int k = 0; k < 3; ++k) v.Xc[3 * (size_t)p + k] = X[k] + dp[k];
+  out3_local[0] = model;
+  out3_local[1] = dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2];
+  out3_local[2] = (v.frozen && v.frozen[p]) ? 0.0 : X[0] * X[0] + X[1] * X[1] + X[2] * X[2];
+}
+
+template <int KIND>
+PVLM_HD inline double cost_obs2(const View& v, const Geo& geo, const double* pose_tab, long long i, int candidate) {
+  const double* X = (candidate ? v.Xc : v.X) + 3 * (size_t)v.obs_pt[i];
+  double r[2], rho, rho1;
+  pvlm_reproj::eval_obs2<KIND>(pose_tab + (size_t)v.cam[i] * PVLM_BA_POSE_TAB, X, v.s + 2 * i, v.w, geo.rows, geo.cols, r, nullptr, nullptr);
+  pvlm_reproj::loss_eval(v.loss, v.a, r[0] * r[0] + r[1] * r[1], &rho, &rho1);
   return 0.5 * rho;
 }
 

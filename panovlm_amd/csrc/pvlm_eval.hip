@@ -694,7 +694,12 @@ pvlm_status pvlm_set_poses(pvlm_ctx* ctx, int n, const double* aa, const double*
     if ((st = pvlm_i_h2d_q(ctx, ctx->d_aa, aa, (size_t)n * 3 * sizeof(double)))) return st;
     if ((st = pvlm_i_h2d_q(ctx, ctx->d_t, t, (size_t)n * 3 * sizeof(double)))) return st;
   }
-  return pose_table_launch(ctx, n, ctx->d_aa, ctx->d_t);
+  ctx->host_poses_known = false;
+  if ((st = pose_table_launch(ctx, n, ctx->d_aa, ctx->d_t))) return st;
+  ctx->host_poses.assign(aa, aa + 3 * (size_t)n);
+  ctx->host_poses.insert(ctx->host_poses.end(), t, t + 3 * (size_t)n);
+  ctx->host_poses_known = true;
+  return PVLM_OK;
 }
 
 pvlm_status pvlm_set_poses_dev(pvlm_ctx* ctx, int n, const double* d_aa, const double* d_t) {
@@ -702,6 +707,7 @@ pvlm_status pvlm_set_poses_dev(pvlm_ctx* ctx, int n, const double* d_aa, const d
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   pvlm_status st = ensure_pose_cap(ctx, n);
   if (st) return st;
+  ctx->host_poses_known = false;
   return pose_table_launch(ctx, n, d_aa, d_t);
 }
 

@@ -97,6 +97,8 @@ struct pvlm_ctx {
   int n_poses = 0, cap_poses = 0;
   bool poses_set = false;
   uint64_t pose_epoch = 0;  // bumps on every pvlm_set_poses
+  std::vector<double> host_poses;   // aa (3n) | t (3n) of the last pvlm_set_poses (host memory); host_poses_known = false after pvlm_set_poses_dev
+  bool host_poses_known = false;
   double* d_aa = nullptr;
   double* d_t = nullptr;
   double* d_pose_tab = nullptr;
@@ -283,6 +285,7 @@ void pvlm_i_preload_lines(hipStream_t s);
 void pvlm_i_preload_texture(hipStream_t s);
 void pvlm_i_preload_mvs(hipStream_t s);
 void pvlm_i_preload_ring(hipStream_t s);
+void pvlm_i_preload_sfm_filter(hipStream_t s);
 void pvlm_i_preload_undistort(hipStream_t s);
 // builds work list + scratch for a resset whose segment table is final (h_* mirrors filled)
 pvlm_status pvlm_i_resset_finalize(pvlm_ctx* ctx, pvlm_resset* rs);

@@ -49,7 +49,65 @@ PVLM_HD inline void eval_obs(const double* pose, const double* X, const double* 
   Jp[2] = g0 * R[2] + g1 * R[5] + g2 * R[8];
 }
 
-// ceres::HuberLoss(a) on s = r^2: rho (block cost = rho/2) and rho' (Ceres' corrector with rho'' <= 0
+// ---- two-row kinds (K31): PanoramaReprojResidual_2Angle (base/CostFunction.h:178-214) and PanoramaReprojResidual_Pixel (:249-288),
+// added by AddCameraResidual for ANGLE_RESIDUAL_2 / PIXEL_RESIDUAL.  Both project p = R(aa_cw) X + t_cw with the exact atan2 / asin:
+//   lon = atan2(p0, p2),  lat = -asin(p1 / |p|)
+//   kind 2 (pixel):  r = w (cols (0.5 + lon / 2pi) - x,  rows (0.5 - lat / pi) - y)        o = keypoint pixel (x, y)
+//   kind 1 (2Angle): lon += 2pi if lon < 0;  r = w (lon - x_s,  lat - y_s)                 o = sphere angles, x_s wrapped into [0, 2pi)
+// No seam wrap of the residual: the pixel row jumps by cols across lon = +-pi, the 2Angle row by 2pi across lon = 0 (upstream leaves
+// that to Huber).  With rho2 = p0^2 + p2^2:
+//   dlon/dp = (p2, 0, -p0) / rho2        dlat/dp = -(e1 - p1 p / |p|^2) / sqrt(rho2)
+// At the poles (rho2 == 0) Jet arithmetic gives inf / NaN; here both rows' dr/dp are 0 (the angle-0 convention of eval_obs).
+// Each row g = dr/dp maps to the parameters like eval_obs: dr/daa = ((R X) x g)^T J_l, dr/dt = g^T, dr/dX = g^T R.
+// r[2], Jc: 2 x 6 row-major, Jp: 2 x 3 row-major.
+constexpr int kAngle1 = 0, kAngle2 = 1, kPixel = 2;
+
+template <int KIND>
+PVLM_HD inline void eval_obs2(const double* pose, const double* X, const double* o, double w, double rows, double cols, double* r, double* Jc, double* Jp) {
+  const double* R = pose; const double* Jl = pose + 9; const double* t = pose + 18;
+  const double q0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
+  const double q1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
+  const double q2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+  const double p0 = q0 + t[0], p1 = q1 + t[1], p2 = q2 + t[2];
+  const double n2 = p0 * p0 + p1 * p1 + p2 * p2;
+  const double n = sqrt(n2);
+  double lon = atan2(p0, p2);
+  const double lat = -asin(p1 / n);
+  if (KIND == kPixel) {
+    r[0] = w * (cols * (0.5 + lon / (2.0 * 3.14159265358979323846)) - o[0]);
+    r[1] = w * (rows * (0.5 - lat / 3.14159265358979323846) - o[1]);
+  } else {
+    if (lon < 0.0) lon += 2.0 * 3.14159265358979323846;
+    r[0] = w * (lon - o[0]);
+    r[1] = w * (lat - o[1]);
+  }
+  if (!Jc) return;
+  const double rho2 = p0 * p0 + p2 * p2;
+  double g[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (rho2 > 0.0) {
+    const double rho = sqrt(rho2);
+    // row 0: k0 dlon/dp, row 1: k1 dlat/dp with dlat/dp = (p1 p / |p|^2 - e1) / rho
+    const double k0 = KIND == kPixel ? w * cols / (2.0 * 3.14159265358979323846) : w;
+    const double k1 = KIND == kPixel ? -w * rows / 3.14159265358979323846 : w;
+    g[0][0] = k0 * p2 / rho2; g[0][2] = -k0 * p0 / rho2;
+    const double c = p1 / n2;
+    g[1][0] = k1 * (c * p0) / rho; g[1][1] = k1 * (c * p1 - 1.0) / rho; g[1][2] = k1 * (c * p2) / rho;
+  }
+  for (int k = 0; k < 2; ++k) {
+    const double g0 = g[k][0], g1 = g[k][1], g2 = g[k][2];
+    const double m0 = q1 * g2 - q2 * g1, m1 = q2 * g0 - q0 * g2, m2 = q0 * g1 - q1 * g0;  // (R X) x g
+    double* jc = Jc + 6 * k; double* jp = Jp + 3 * k;
+    jc[0] = m0 * Jl[0] + m1 * Jl[3] + m2 * Jl[6];
+    jc[1] = m0 * Jl[1] + m1 * Jl[4] + m2 * Jl[7];
+    jc[2] = m0 * Jl[2] + m1 * Jl[5] + m2 * Jl[8];
+    jc[3] = g0; jc[4] = g1; jc[5] = g2;
+    jp[0] = g0 * R[0] + g1 * R[3] + g2 * R[6];
+    jp[1] = g0 * R[1] + g1 * R[4] + g2 * R[7];
+    jp[2] = g0 * R[2] + g1 * R[5] + g2 * R[8];
+  }
+}
+
+// ceres::HuberLoss(a) on s = r^2 (two-row kinds: s = r0^2 + r1^2, the block's squared norm): rho (block cost = rho/2) and rho' (Ceres' corrector with rho'' <= 0
 // scales r and J by sqrt(rho')).  loss: 0 none, 1 Huber.
 PVLM_HD inline void loss_eval(int loss, double a, double s, double* rho, double* rho1) {
   if (loss == 1 && s > a * a) {

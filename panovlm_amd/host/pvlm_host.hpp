@@ -34,6 +34,7 @@
 
 namespace pvlm {
 
+using Vector2d = std::array<double, 2>;
 using Vector3d = std::array<double, 3>;
 using Vector4d = std::array<double, 4>;
 using Vector6d = std::array<double, 6>;
@@ -405,6 +406,14 @@ struct PlaneIOUResidual { static ceres_like::CostFunction* Create(const Vector4d
 // base/CostFunction.h:218-247 — AutoDiffCostFunction<.,1,3,3,3> on (angleAxis_cw, t_cw, point_3d)
 struct PanoramaReprojResidual_1Angle { static ceres_like::CostFunction* Create(const Vector3d& pt, double weight = 1.0); };
 constexpr int kReprojKind = 100;   // CostFunction::kind of the three-block functor (not a pvlm_functor)
+// base/CostFunction.h:178-214 — AutoDiffCostFunction<.,2,3,3,3>: pt = sphere angles (lon, lat) of the keypoint (K31)
+struct PanoramaReprojResidual_2Angle { static ceres_like::CostFunction* Create(const Vector2d& pt, double weight = 1.0); };
+// base/CostFunction.h:249-288 — AutoDiffCostFunction<.,2,3,3,3>: pt = keypoint pixel (x, y), rows x cols image (K31)
+struct PanoramaReprojResidual_Pixel { static ceres_like::CostFunction* Create(const Vector2d& pt, const int rows, const int cols, double weight = 1.0); };
+constexpr int kReprojKind2Angle = 101, kReprojKindPixel = 102;
+inline pvlm_ba_kind ReprojBaKind(int cost_kind) {
+  return cost_kind == kReprojKindPixel ? PVLM_BA_PIXEL : (cost_kind == kReprojKind2Angle ? PVLM_BA_ANGLE2 : PVLM_BA_ANGLE1);
+}
 
 // ---- util/Optimization.h ---------------------------------------------------------------------------------
 size_t AddLidarPointToPlaneResidual(const std::vector<std::vector<int>>& neighbors, const std::vector<Velodyne>& lidars,
@@ -442,12 +451,36 @@ struct PointTrack {
 };
 enum RESIDUAL_TYPE { ANGLE_RESIDUAL_1 = 0, ANGLE_RESIDUAL_2 = 1, PIXEL_RESIDUAL = 2 };
 struct Frame;
-// AddCameraResidual (util/Optimization.cpp:172-222), ANGLE_RESIDUAL_1 branch (the one Optimize uses,
-// CameraLidarOptimizer.cpp:431-432): one PanoramaReprojResidual_1Angle per (track, observation) whose frame has a
-// valid pose; bearing = eq.ImageToCam(keypoint.pt) — which resolves to the cv::Point2i overload, i.e. the keypoint
-// is rounded to the nearest pixel (cvRound) and un-projected in float; HuberLoss(4 deg).
+// AddCameraResidual (util/Optimization.cpp:172-222): one block per (track, observation) whose frame has a valid pose.
+//   ANGLE_RESIDUAL_1 (the one Optimize uses, CameraLidarOptimizer.cpp:431-432): PanoramaReprojResidual_1Angle, bearing =
+//     eq.ImageToCam(keypoint.pt) — which resolves to the cv::Point2i overload, i.e. the keypoint is rounded to the nearest
+//     pixel (cvRound) and un-projected in float; HuberLoss(4 deg).
+//   ANGLE_RESIDUAL_2: PanoramaReprojResidual_2Angle on eq.ImageToSphere(keypoint.pt) (float template); HuberLoss(4 deg).
+//   PIXEL_RESIDUAL: PanoramaReprojResidual_Pixel on keypoint.pt widened to double; HuberLoss(4.0).
 size_t AddCameraResidual(const std::vector<Frame>& frames, std::vector<Vector3d>& angleAxis_cw_list, std::vector<Vector3d>& t_cw_list,
                          std::vector<PointTrack>& structure, ceres_like::Problem& problem, int residual_type, double weight);
+
+// ---- K31: global bundle adjustment of the SfM result and the track filters after it ---------------------------------
+// SfMGlobalBA (util/Optimization.cpp:10-82): T_cw = GetPose()^-1 (rigid inverse, the mirror's convention; upstream's general
+// Eigen inverse differs by ~1e-16) -> angle-axis, AddCameraResidual(residual_type, weight 1), constant blocks for
+// refine_rotation / translation / structure = false, the FIRST valid frame's aa and t constant, SetOptionsSfM, Solve.  Returns false
+// when all three refine flags are false or the solution is not usable; otherwise writes SetPose(T_cw^-1) back into the valid frames and
+// the refined points into the tracks.  The reprojection blocks are solved on the GPU (K9 / K31, points eliminated there).
+bool SfMGlobalBA(std::vector<Frame>& frames, std::vector<PointTrack>& tracks, int residual_type, int num_threads, bool refine_structure = true,
+                 bool refine_rotation = true, bool refine_translation = true, ceres_like::Solver::Summary* summary = nullptr);
+// FilterTracksPixelResidual / FilterTracksAngleResidual (sfm/Structure.cpp:121-193) on the GPU (pvlm_filter_tracks): the surviving tracks
+// keep their order; returns the number removed.  Invalid frames use T_cw = 0 and are not skipped (an observation there projects to the
+// image centre, pixel filter, or gives a NaN cosine that never rejects, angle filter).  threshold < 0: the pixel filter removes nothing.
+size_t FilterTracksPixelResidual(const std::vector<Frame>& frames, std::vector<PointTrack>& tracks, const double& threshold);
+size_t FilterTracksAngleResidual(const std::vector<Frame>& frames, std::vector<PointTrack>& tracks, const double& threshold);
+// SfM::GlobalBundleAdjustment (sfm/SfM.cpp:1362-1383): SfMGlobalBA then the filter of the residual type (pixel for PIXEL_RESIDUAL,
+// angle for the angle types).  False when the BA fails (the structure is then left unfiltered).
+bool GlobalBundleAdjustment(std::vector<Frame>& frames, std::vector<PointTrack>& structure, int residual_type, float residual_threshold,
+                            bool refine_structure = true, bool refine_rotation = true, bool refine_translation = true, int num_threads = 1);
+// MVS::RefineCameraPose (mvs/MVS.cpp:383-428): keeps T_cl = T_wc^-1 T_wl of every frame / scan pair valid on both sides, runs the pixel
+// BA with everything free, then re-poses the scans as T_wc T_cl.  The image scale of upstream's frames does not exist in the mirror: the
+// BA works on full-resolution keypoints, which is what upstream's SetImageScale(0) restores.  The PCD / pose-file exports are left out.
+bool RefineCameraPose(std::vector<Frame>& frames, std::vector<Velodyne>& lidars, std::vector<PointTrack>& structure, const Config& config);
 
 // util/FileIO.cpp:11-79, :168-191 — pose text files: one row per pose, optional name + 12 numbers
 // (R row-major interleaved with t: r00 r01 r02 tx r10 r11 r12 ty r20 r21 r22 tz); rows containing
@@ -670,6 +703,9 @@ class CameraLidarOptimizer {
   const Matrix4d& GetOptimizedTcl() const { return T_cl_optimized; }
   const std::vector<Velodyne>& GetLidars() const { return lidars; }
   const std::vector<Frame>& GetFrames() const { return frames; }
+  // CameraLidarOptimizer.cpp:732-740: SfMGlobalBA(frames, structure, ANGLE_RESIDUAL_1, num_threads, refine flags) on this optimizer's frames
+  // and the caller's structure, as upstream
+  bool GlobalBundleAdjustment(std::vector<PointTrack>& structure, bool refine_structure, bool refine_rotation, bool refine_translation);
   // joint_optimization/CameraLidarOptimizer.cpp:777-802: the same body as LidarOdometry::FuseLidar (FuseLidarScans)
   PointCloud FuseLidar(int skip, double min_range, double max_range);
   struct IterLog { double cost; int steps; int residual_blocks; size_t line_pairs; std::vector<double> cost_history; };

@@ -243,16 +243,17 @@ size_t AddCameraLidarResidual(int rows, int cols, const std::vector<bool>& frame
 }
 
 // ================================================================================================
-// AddCameraResidual — util/Optimization.cpp:172-222 (ANGLE_RESIDUAL_1)
+// AddCameraResidual — util/Optimization.cpp:172-222
 // ================================================================================================
 size_t AddCameraResidual(const std::vector<Frame>& frames, std::vector<Vector3d>& angleAxis_cw_list, std::vector<Vector3d>& t_cw_list,
                          std::vector<PointTrack>& structure, ceres_like::Problem& problem, int residual_type, double weight) {
   StageTimer stage_timer_("reprojection blocks");
-  if (residual_type != ANGLE_RESIDUAL_1)
-    throw std::runtime_error("AddCameraResidual: only ANGLE_RESIDUAL_1 (the variant CameraLidarOptimizer::Optimize uses) is mirrored");
+  if (residual_type != ANGLE_RESIDUAL_1 && residual_type != ANGLE_RESIDUAL_2 && residual_type != PIXEL_RESIDUAL)
+    throw std::runtime_error("AddCameraResidual: unknown residual type");
   if (frames.empty() || structure.empty()) return 0;
   const Equirect eq{frames[0].GetImageCols(), frames[0].GetImageRows()};           // :178
-  ceres_like::LossFunction* loss_function = new ceres_like::HuberLoss(4.0 * M_PI / 180.0);   // :180-181
+  // :180-185: HuberLoss(4 deg) for the angle residuals, HuberLoss(4.0) pixels for PIXEL_RESIDUAL
+  ceres_like::LossFunction* loss_function = new ceres_like::HuberLoss(residual_type == PIXEL_RESIDUAL ? 4.0 : 4.0 * M_PI / 180.0);
   size_t num_residual = 0;
   for (size_t i = 0; i < structure.size(); i++) {
     PointTrack& track = structure[i];
@@ -262,6 +263,21 @@ size_t AddCameraResidual(const std::vector<Frame>& frames, std::vector<Vector3d>
       // eq.ImageToCam(keypoint.pt) binds to ImageToCam(const cv::Point2i&): the float keypoint is converted with
       // saturate_cast<int> (= cvRound, round-half-even), then un-projected in float with r = 1 (Equirectangular.h:153-161)
       const std::array<float, 2>& kp = frames[frame_idx].keypoints[pair.second];
+      if (residual_type == PIXEL_RESIDUAL) {          // PanoramaReprojResidual_Pixel::Create(keypoint.pt, rows, cols): float widened to double
+        ceres_like::CostFunction* cost_function = PanoramaReprojResidual_Pixel::Create({(double)kp[0], (double)kp[1]}, frames[frame_idx].GetImageRows(),
+                                                                                               frames[frame_idx].GetImageCols(), weight);
+        problem.AddResidualBlock(cost_function, loss_function, angleAxis_cw_list[frame_idx].data(), t_cw_list[frame_idx].data(), track.point_3d.data());
+        num_residual++;
+        continue;
+      }
+      if (residual_type == ANGLE_RESIDUAL_2) {        // eq.ImageToSphere(keypoint.pt), float template (Equirectangular.h:99-105), widened
+        const float sx = (float)((2 * kp[0] / eq.cols - 1) * M_PI);
+        const float sy = (float)((0.5 - kp[1] / eq.rows) * M_PI);
+        ceres_like::CostFunction* cost_function = PanoramaReprojResidual_2Angle::Create({(double)sx, (double)sy}, weight);
+        problem.AddResidualBlock(cost_function, loss_function, angleAxis_cw_list[frame_idx].data(), t_cw_list[frame_idx].data(), track.point_3d.data());
+        num_residual++;
+        continue;
+      }
       const float px[2] = {(float)(int)std::lrintf(kp[0]), (float)(int)std::lrintf(kp[1])};
       float cam[3];
       eq.ImageToCam(px, 1.f, cam);

@@ -27,6 +27,21 @@ bool CostFunction::Evaluate(double const* const* parameters, double* residuals, 
         if (jacobians[b]) for (int k = 0; k < 3; ++k) jacobians[b][k] = J[3 * b + k];
     return ok && std::isfinite(residuals[0]);
   }
+  if (kind == kReprojKind2Angle || kind == kReprojKindPixel) {   // two residuals; jacobians[b] = 2 x 3 row-major (Ceres' layout)
+    const int64_t off[2] = {0, 1};
+    const int cam = 0;
+    pvlm_baset* bs = nullptr;
+    if (pvlm_ba_create_kind(e.ctx(), ReprojBaKind(kind), (int)row[2], (int)row[3], 1, 1, off, &cam, row.data(), parameters[2], weight, &bs) != PVLM_OK)
+      return false;
+    bool ok = pvlm_set_poses(e.ctx(), 1, parameters[0], parameters[1]) == PVLM_OK;
+    double J[18];
+    ok = ok && pvlm_ba_eval(e.ctx(), bs, residuals, jacobians ? J : nullptr) == PVLM_OK;
+    pvlm_ba_destroy(e.ctx(), bs);
+    if (ok && jacobians)
+      for (int b = 0; b < 3; ++b)
+        if (jacobians[b]) for (int r = 0; r < 2; ++r) for (int k = 0; k < 3; ++k) jacobians[b][3 * r + k] = J[9 * r + 3 * b + k];
+    return ok && std::isfinite(residuals[0]) && std::isfinite(residuals[1]);
+  }
   double aa[6] = {parameters[0][0], parameters[0][1], parameters[0][2], parameters[2][0], parameters[2][1], parameters[2][2]};
   double t[6] = {parameters[1][0], parameters[1][1], parameters[1][2], parameters[3][0], parameters[3][1], parameters[3][2]};
   const int64_t off[2] = {0, 1};
@@ -64,12 +79,13 @@ struct Problem::Impl {
     std::vector<int> dev_to_pose;       // dev id -> Problem pose id (-1 unused)
   };
   std::vector<Group> groups;
-  // Reprojection blocks (camera pose + free 3-D point), one group per (weight, loss).  At Solve the observations
+  // Reprojection blocks (camera pose + free 3-D point), one group per (kind, image size, weight, loss).  At Solve the observations
   // are sorted by point and handed to the GPU (pvlm_baset); the point blocks are eliminated there.
   struct Bundle {
     double weight = 1.0; LossFunction* loss = nullptr;
+    pvlm_ba_kind kind = PVLM_BA_ANGLE1; int rows = 0, cols = 0;   // functor of the group (K31: _2Angle / _Pixel)
     std::vector<int> obs_pose, obs_point;      // Problem pose id / parameter-block id of the point, insertion order
-    std::vector<double> obs_bearing;           // 3 per observation (as handed to Create, un-normalised)
+    std::vector<double> obs_bearing;           // 3 per observation (as handed to Create, un-normalised); 2 for the two-row kinds
     pvlm_baset* set = nullptr;
     std::vector<int> point_blocks;             // device point index -> parameter-block id
     std::vector<int> dev_to_pose;              // device camera id -> Problem pose id
@@ -163,7 +179,11 @@ void Problem::AddResidualRows(int kind, unsigned flags, double weight, LossFunct
 
 void Problem::AddResidualBlock(CostFunction* cost, LossFunction* loss, double* aa_c, double* t_c, double* point_3d) {
   Impl& I = *impl_;
-  if (cost->kind != kReprojKind) throw std::runtime_error("three-block AddResidualBlock expects PanoramaReprojResidual_1Angle");
+  if (cost->kind != kReprojKind && cost->kind != kReprojKind2Angle && cost->kind != kReprojKindPixel)
+    throw std::runtime_error("three-block AddResidualBlock expects a PanoramaReprojResidual_{1Angle,2Angle,Pixel}");
+  const pvlm_ba_kind bk = ReprojBaKind(cost->kind);
+  const int rows = bk == PVLM_BA_PIXEL ? (int)cost->row[2] : 0, cols = bk == PVLM_BA_PIXEL ? (int)cost->row[3] : 0;
+  const int od = bk == PVLM_BA_ANGLE1 ? 3 : 2;
   const int pose = I.Pose(aa_c, t_c);
   const int pb = I.Block(point_3d);
   I.is_point[pb] = true;
@@ -171,11 +191,15 @@ void Problem::AddResidualBlock(CostFunction* cost, LossFunction* loss, double* a
   I.owned_costs.push_back(cost);
   int bi = -1;
   for (int k = (int)I.bundles.size() - 1; k >= 0; --k)
-    if (!I.bundles[k].set && I.bundles[k].weight == cost->weight && I.bundles[k].loss == loss) { bi = k; break; }
-  if (bi < 0) { Impl::Bundle b; b.weight = cost->weight; b.loss = loss; I.bundles.push_back(b); bi = (int)I.bundles.size() - 1; }
+    if (!I.bundles[k].set && I.bundles[k].weight == cost->weight && I.bundles[k].loss == loss && I.bundles[k].kind == bk && I.bundles[k].rows == rows &&
+        I.bundles[k].cols == cols) { bi = k; break; }
+  if (bi < 0) {
+    Impl::Bundle b; b.weight = cost->weight; b.loss = loss; b.kind = bk; b.rows = rows; b.cols = cols;
+    I.bundles.push_back(b); bi = (int)I.bundles.size() - 1;
+  }
   Impl::Bundle& b = I.bundles[bi];
   b.obs_pose.push_back(pose); b.obs_point.push_back(pb);
-  b.obs_bearing.insert(b.obs_bearing.end(), cost->row.begin(), cost->row.begin() + 3);
+  b.obs_bearing.insert(b.obs_bearing.end(), cost->row.begin(), cost->row.begin() + od);
   I.num_blocks++;
 }
 
@@ -391,20 +415,22 @@ void Solve(const Solver::Options& opt, Problem* problem, Solver::Summary* summar
     for (size_t i = 0; i < n; ++i) off[(size_t)obs_dev_point[i] + 1]++;
     for (int p = 0; p < M; ++p) off[(size_t)p + 1] += off[p];
     std::vector<int64_t> fill(off.begin(), off.end() - 1);
-    std::vector<int> cam(n); std::vector<double> bearing(3 * n), points((size_t)M * 3);
+    const int od = b.kind == PVLM_BA_ANGLE1 ? 3 : 2;
+    std::vector<int> cam(n); std::vector<double> bearing((size_t)od * n), points((size_t)M * 3);
     for (size_t i = 0; i < n; ++i) {   // stable: insertion order inside a point's track
       const size_t dst = (size_t)fill[obs_dev_point[i]]++;
       auto ic = cidx.find(b.obs_pose[i]);
       if (ic == cidx.end()) { ic = cidx.insert({b.obs_pose[i], (int)b.dev_to_pose.size()}).first; b.dev_to_pose.push_back(b.obs_pose[i]); }
       cam[dst] = ic->second;
-      for (int k = 0; k < 3; ++k) bearing[3 * dst + k] = b.obs_bearing[3 * i + k];
+      for (int k = 0; k < od; ++k) bearing[od * dst + k] = b.obs_bearing[od * i + k];
     }
     std::vector<unsigned char> frozen((size_t)M, 0); bool any_frozen = false;
     for (int p = 0; p < M; ++p) {
       for (int k = 0; k < 3; ++k) points[(size_t)p * 3 + k] = I.blocks[b.point_blocks[p]][k];
       if (I.constant[b.point_blocks[p]]) { frozen[p] = 1; any_frozen = true; }
     }
-    e.Check(pvlm_ba_create(e.ctx(), M, (int64_t)n, off.data(), cam.data(), bearing.data(), points.data(), b.weight, &b.set), "pvlm_ba_create");
+    e.Check(pvlm_ba_create_kind(e.ctx(), b.kind, b.rows, b.cols, M, (int64_t)n, off.data(), cam.data(), bearing.data(), points.data(), b.weight, &b.set),
+            "pvlm_ba_create_kind");
     if (any_frozen) e.Check(pvlm_ba_set_constant(e.ctx(), b.set, frozen.data()), "pvlm_ba_set_constant");
     int nu = 0;
     pvlm_ba_structure(b.set, nullptr, nullptr, nullptr, &nu, nullptr, nullptr);
@@ -601,10 +627,13 @@ void Solve(const Solver::Options& opt, Problem* problem, Solver::Summary* summar
     }
   };
   // back-substitutes the points for the (unscaled) camera step; out3 += [model decrease, |dX|^2, |X|^2]
+  int n_sets = 0;
+  for (auto& b : I.bundles) if (!b.obs_pose.empty()) ++n_sets;
   auto bundle_step = [&](const std::vector<double>& step, double* out3) {
     StageTimer stage_timer_bs_("solve: point back-substitution / candidate cost (GPU)");
     for (auto& b : I.bundles) {
       if (!b.set) continue;
+      if (n_sets > 1) bundle_poses(b, x);     // the pose table holds the last set's poses: reload this set's, as reduced (same values)
       const int nd = (int)b.dev_to_pose.size();
       std::vector<double> dcam((size_t)nd * 6, 0.0);
       for (int d = 0; d < nd; ++d)
@@ -890,6 +919,18 @@ CostFunction* Plane2Plane_Global::Create(const Vector3d& n, const Vector3d& a, c
 }
 CostFunction* PanoramaReprojResidual_1Angle::Create(const Vector3d& pt, double w) {
   CostFunction* c = MakeCost(kReprojKind, 0, w, {pt[0], pt[1], pt[2]});
+  c->num_blocks = 3;
+  return c;
+}
+// base/CostFunction.h:178-214: the constructor's "x += 2 pi if x < 0" is applied by pvlm_ba_create_kind (in double)
+CostFunction* PanoramaReprojResidual_2Angle::Create(const Vector2d& pt, double w) {
+  CostFunction* c = MakeCost(kReprojKind2Angle, 0, w, {pt[0], pt[1], 0.0, 0.0});
+  c->num_blocks = 3;
+  return c;
+}
+// base/CostFunction.h:249-288 (both Create overloads: the cv::Point2f one widens to double, no rounding)
+CostFunction* PanoramaReprojResidual_Pixel::Create(const Vector2d& pt, const int rows, const int cols, double w) {
+  CostFunction* c = MakeCost(kReprojKindPixel, 0, w, {pt[0], pt[1], (double)rows, (double)cols});
   c->num_blocks = 3;
   return c;
 }
