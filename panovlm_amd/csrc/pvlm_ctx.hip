@@ -67,6 +67,30 @@ void pvlm_i_pool_release(pvlm_ctx* ctx, bool all) {
   if (all) { P.live.clear(); P.in_use = 0; }
 }
 
+void* pvlm_i_pinned_take(pvlm_ctx* ctx, size_t bytes, size_t* got) {
+  int fit = -1;                                    // the smallest pooled buffer that is large enough
+  for (int k = 0; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] >= bytes && (fit < 0 || ctx->ring_bytes[k] < ctx->ring_bytes[fit])) fit = k;
+  void* p = nullptr;
+  if (fit >= 0) {
+    p = ctx->h_ring[fit]; *got = ctx->ring_bytes[fit];
+    --ctx->ring_pool;
+    ctx->h_ring[fit] = ctx->h_ring[ctx->ring_pool]; ctx->ring_bytes[fit] = ctx->ring_bytes[ctx->ring_pool];
+  } else if (hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess) {
+    *got = bytes;
+  } else { p = nullptr; *got = 0; }
+  return p;
+}
+
+void pvlm_i_pinned_give(pvlm_ctx* ctx, void* p, size_t bytes) {
+  if (ctx && ctx->ring_pool < pvlm_ctx::kRingPool) { ctx->h_ring[ctx->ring_pool] = p; ctx->ring_bytes[ctx->ring_pool] = bytes; ++ctx->ring_pool; return; }
+  if (ctx) {
+    int least = 0;
+    for (int k = 1; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] < ctx->ring_bytes[least]) least = k;
+    if (ctx->ring_bytes[least] < bytes) { std::swap(ctx->h_ring[least], p); ctx->ring_bytes[least] = bytes; }
+  }
+  (void)hipHostFree(p);
+}
+
 pvlm_status pvlm_i_alloc_bytes(pvlm_ctx* ctx, void** out, size_t bytes) {
   *out = nullptr;
   pvlm_pool& P = ctx->pool;

@@ -1,31 +1,25 @@
 // K29: the fused LiDAR map of LidarOdometry::FuseLidar / CameraLidarOptimizer::FuseLidar (lidar_mapping/LidarOdometry.cpp:323-348) — the range filter and the
-// world transform of every point of the selected scans, kept points in scan order, then point order.  An order-preserving compaction in two passes and no waits
-// between workgroups: a tile of 4096 points (one workgroup, 16 rounds of 256) counts what it keeps (k_fuse_count: wave64 ballots + popcount), one workgroup
-// turns the tile counts into 64-bit tile bases (k_fuse_scan: exclusive scan, the total and the per-scan counts), and each tile recomputes its keep flags and
-// writes float4 (x', y', z', intensity) at base + rank (k_fuse_scatter).  Tiles never span two scans: a tile reads one scan's pose and layout.
+// world transform of every point of the selected scans, kept points in scan order, then point order.  The order-preserving compaction is pvlm_compact.h's: a
+// tile of 4096 points counts what it keeps (k_fuse_count), one workgroup turns the tile counts into 64-bit tile bases, the total and the per-scan counts
+// (pvlm_compact::k_tile_scan<ScanDesc>), and each tile recomputes its keep flags and writes float4 (x', y', z', intensity) at base + rank (k_fuse_scatter).
+// Tiles never span two scans: a tile reads one scan's pose and layout.
 // Host clouds (pvlm_fuse_scans) go through a bounded pinned window in pieces of whole scans — the upload of piece k + 1 on a second stream beside the kernels
 // and the download of piece k; device clouds (pvlm_fuse_scans_dev) are read where they lie, in one pass of the three kernels.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "pvlm_internal.h"
 #include "pvlm_workers.h"
+#include "pvlm_compact.h"
 #include "pvlm_fuse_core.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRounds = 16;
-constexpr int kTile = kThreads * kRounds;           // points per workgroup
-constexpr int kScanThreads = 1024;
-constexpr long long kPiecePoints = 1ll << 21;       // 32 MB of float4 per buffer of the pinned window (two in, two out: 128 MB)
+using namespace pvlm_compact;          // kThreads, kRounds, kTile, kWaves, kScanThreads; kPiecePoints: 32 MB per buffer of the pinned window (two in, two out: 128 MB)
 constexpr int kPieceScans = 16384;
-// k_fuse_scatter turns its (round, wave) counts into offsets with ONE wave: one lane per count
-static_assert(kRounds * (kThreads / 64) == 64, "k_fuse_scatter: one wave scans the (round, wave) counts");
 
 struct ScanDesc {
   double T[12];                 // world <- sensor, rows 0..2 of the 4x4
@@ -34,7 +28,10 @@ struct ScanDesc {
   int stride, vec;              // vec: xyz 16-B aligned with a stride of whole float4s (one float4 load per point; bit 1: intensity is its w)
   int tile0, n_tiles;
 };
-struct TileDesc { int p0, n, scan, pad; };            // first point inside the scan, points (<= kTile), scan
+struct TileDesc {                                     // first point inside the scan, points (<= kTile), scan
+  int p0, n, scan, pad;
+  static TileDesc make(int p0, int n, int scan, long long) { return TileDesc{p0, n, scan, 0}; }
+};
 
 __device__ __forceinline__ float4 load_point(const ScanDesc& d, int i) {
   const size_t o = (size_t)i * (size_t)d.stride;
@@ -46,11 +43,6 @@ __device__ __forceinline__ float4 load_point(const ScanDesc& d, int i) {
     p = make_float4(d.xyz[o], d.xyz[o + 1], d.xyz[o + 2], d.inten[o]);
   }
   return p;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(kThreads) void k_fuse_count(const ScanDesc* __restrict__ scans, const TileDesc* __restrict__ tiles, double sq_min, double sq_max,
@@ -69,40 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_fuse_count(const ScanDesc* __restr
     const int j = r * kThreads + (int)threadIdx.x;
     c += (j < td.n && pvlm_fuse::keep_point(p[r].x, p[r].y, p[r].z, sq_min, sq_max)) ? 1 : 0;
   }
-  __shared__ int part[kThreads / 64];
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// one workgroup: exclusive scan of the tile counts in order (64-bit bases), the total, the per-scan counts
-__global__ __launch_bounds__(kScanThreads) void k_fuse_scan(const int* __restrict__ tile_count, int n_tiles, long long* __restrict__ tile_base,
-                                                            const ScanDesc* __restrict__ scans, int n_scans, long long* __restrict__ total,
-                                                            long long* __restrict__ per_scan) {
-  __shared__ int wtot[kScanThreads / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-  long long carry = 0;
-  int next = tid < n_tiles ? tile_count[tid] : 0;
-  for (int b = 0; b < n_tiles; b += kScanThreads) {
-    const int i = b + tid, v = next;
-    next = i + kScanThreads < n_tiles ? tile_count[i + kScanThreads] : 0;     // the next chunk's load in flight during this one's scan
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int k = 0; k < kScanThreads / 64; ++k) { const int t = wtot[k]; before += k < w ? t : 0; all += t; }
-    if (i < n_tiles) tile_base[i] = carry + before + (incl - v);
-    carry += all;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
-  if (!per_scan) return;
-  for (int s = tid; s < n_scans; s += kScanThreads) {
-    const int t0 = scans[s].tile0, nt = scans[s].n_tiles;
-    per_scan[s] = nt ? tile_base[t0 + nt - 1] + tile_count[t0 + nt - 1] - tile_base[t0] : 0;
-  }
+  tile_total(c, tile_count);
 }
 
 __global__ __launch_bounds__(kThreads) void k_fuse_scatter(const ScanDesc* __restrict__ scans, const TileDesc* __restrict__ tiles,
@@ -112,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void k_fuse_scatter(const ScanDesc* __res
   const ScanDesc& d = scans[td.scan];
   const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
-  __shared__ int pre[kRounds * (kThreads / 64)];
+  __shared__ int pre[kRounds * kWaves];
   float4 p[kRounds];
   unsigned keep = 0;
   int rank[kRounds];
@@ -128,17 +87,9 @@ __global__ __launch_bounds__(kThreads) void k_fuse_scatter(const ScanDesc* __res
     const unsigned long long m = __ballot(k);
     keep |= (k ? 1u : 0u) << r;
     rank[r] = __popcll(m & below);
-    if (lane == 0) pre[r * (kThreads / 64) + w] = __popcll(m);
+    if (lane == 0) pre[r * kWaves + w] = __popcll(m);
   }
-  __syncthreads();
-  // the order of the points is round-major, then wave, then lane: one wave turns the 64 (round, wave) counts into exclusive offsets
-  if (w == 0) {
-    const int v = pre[lane];
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    pre[lane] = incl - v;
-  }
-  __syncthreads();
+  tile_offsets(pre);
   const long long base = tile_base[blockIdx.x];
   double T[12];
 #pragma unroll
@@ -146,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_fuse_scatter(const ScanDesc* __res
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
     if (!((keep >> r) & 1u)) continue;
-    const long long at = base + pre[r * (kThreads / 64) + w] + rank[r];
+    const long long at = base + pre[r * kWaves + w] + rank[r];
     if (at >= capacity) continue;
     float q[3];
     pvlm_fuse::transform_point(T, p[r].x, p[r].y, p[r].z, q);
@@ -163,23 +114,13 @@ void fill_desc(ScanDesc& sd, const pvlm_fuse_scan& s, const float* xyz, const fl
   sd.tile0 = 0; sd.n_tiles = 0;
 }
 
-// tiles of scans [s0, s1): appends to `tiles`, sets tile0 / n_tiles (scan indices local to the range)
-void make_tiles(const pvlm_fuse_scan* scans, int s0, int s1, ScanDesc* sd, std::vector<TileDesc>& tiles) {
-  tiles.clear();
-  for (int s = s0; s < s1; ++s) {
-    sd[s - s0].tile0 = (int)tiles.size();
-    for (int p0 = 0; p0 < scans[s].n; p0 += kTile) tiles.push_back(TileDesc{p0, std::min(kTile, scans[s].n - p0), s - s0, 0});
-    sd[s - s0].n_tiles = (int)tiles.size() - sd[s - s0].tile0;
-  }
-}
-
-pvlm_status check_scans(pvlm_ctx* ctx, const char* what, int n_scans, const pvlm_fuse_scan* scans, long long* total, int* max_n) {
+pvlm_status check_scans(pvlm_ctx* ctx, const char* what, int n_scans, const pvlm_fuse_scan* scans, long long* total) {
   if (n_scans < 0 || (n_scans > 0 && !scans)) { PVLM_SET_ERR(ctx, "%s: bad scan list", what); return PVLM_ERR_ARG; }
-  *total = 0; *max_n = 0;
+  *total = 0;
   for (int s = 0; s < n_scans; ++s) {
     const pvlm_fuse_scan& d = scans[s];
     if (d.n < 0 || (d.n > 0 && (!d.xyz || !d.intensity || !d.T_wl || d.stride_floats < 3))) { PVLM_SET_ERR(ctx, "%s: bad descriptor (scan %d)", what, s); return PVLM_ERR_ARG; }
-    *total += d.n; *max_n = std::max(*max_n, d.n);
+    *total += d.n;
   }
   return PVLM_OK;
 }
@@ -188,14 +129,12 @@ pvlm_status launch(pvlm_ctx* ctx, hipStream_t S, const ScanDesc* d_sd, int n_sca
                    double sq_min, double sq_max, float4* d_out, long long capacity, long long* d_total, long long* d_per_scan) {
   if (n_tiles > 0) hipLaunchKernelGGL(k_fuse_count, dim3((unsigned)n_tiles), dim3(kThreads), 0, S, d_sd, d_td, sq_min, sq_max, d_tcount);
   PVLM_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_fuse_scan, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, n_tiles, d_tbase, d_sd, n_scans, d_total, d_per_scan);
+  hipLaunchKernelGGL(k_tile_scan<ScanDesc>, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, n_tiles, d_tbase, d_sd, n_scans, d_total, d_per_scan);
   PVLM_HIP(ctx, hipGetLastError());
   if (n_tiles > 0) hipLaunchKernelGGL(k_fuse_scatter, dim3((unsigned)n_tiles), dim3(kThreads), 0, S, d_sd, d_td, (const long long*)d_tbase, sq_min, sq_max, d_out, capacity);
   PVLM_HIP(ctx, hipGetLastError());
   return PVLM_OK;
 }
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -203,8 +142,8 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
                                        long long capacity, long long* n_out, long long* per_scan_or_null) {
   if (!ctx) return PVLM_ERR_ARG;
   if (!n_out || capacity < 0 || (capacity > 0 && !out_xyzi)) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans: n_out, capacity >= 0 and an output buffer are required"); return PVLM_ERR_ARG; }
-  long long total = 0; int max_n = 0;
-  if (pvlm_status st = check_scans(ctx, "pvlm_fuse_scans", n_scans, scans, &total, &max_n)) return st;
+  long long total = 0;
+  if (pvlm_status st = check_scans(ctx, "pvlm_fuse_scans", n_scans, scans, &total)) return st;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans inside a graph capture"); return PVLM_ERR_STATE; }
   *n_out = 0;
@@ -213,36 +152,25 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
   const double sq_min = min_range * min_range, sq_max = max_range * max_range;
   try {
     // pieces of whole scans: at most P points (a larger scan is a piece of its own) and kPieceScans scans
-    const long long P = std::min(total, std::max(kPiecePoints, (long long)max_n));
-    std::vector<int> piece0{0};
-    for (int s = 0; s < n_scans;) {
-      long long pts = 0; int k = s;
-      while (k < n_scans && k - s < kPieceScans && (k == s || pts + scans[k].n <= P)) pts += scans[k++].n;
-      piece0.push_back(k); s = k;
-    }
-    const int n_pieces = (int)piece0.size() - 1;
-    int scap = 0;
-    for (int q = 0; q < n_pieces; ++q) scap = std::max(scap, piece0[q + 1] - piece0[q]);
-    const long long tcap = P / kTile + scap + 1;
-    const size_t pts_b = align256((size_t)P * 16), cnt_b = align256((size_t)(scap + 1) * 8), sd_b = align256((size_t)scap * sizeof(ScanDesc)),
-                 td_b = align256((size_t)tcap * sizeof(TileDesc));
-    // pinned window: the ring batches' pool (no pinned state of its own): in[2] | out[2] | counts[2] | descriptors[2]
+    const std::vector<int> n = point_counts(scans, n_scans);
+    const Pieces pc = make_pieces(n.data(), n_scans, kPieceScans);
+    const std::vector<int>& piece0 = pc.piece0;
+    const std::vector<long long>& pt0 = pc.pt0;
+    const int n_pieces = pc.count();
+    const long long P = pc.P;
+    const size_t pts_b = align256((size_t)P * 16), cnt_b = align256((size_t)(pc.scap + 1) * 8), sd_b = align256((size_t)pc.scap * sizeof(ScanDesc)),
+                 td_b = align256((size_t)pc.tcap * sizeof(TileDesc));
+    // pinned window: the context's pool (no pinned state of its own): in[2] | out[2] | counts[2] | descriptors[2]
     const size_t bytes = 4 * pts_b + 2 * cnt_b + 2 * (sd_b + td_b);
-    char* h = nullptr; size_t h_bytes = 0;
-    int fit = -1;
-    for (int k = 0; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] >= bytes && (fit < 0 || ctx->ring_bytes[k] < ctx->ring_bytes[fit])) fit = k;
-    if (fit >= 0) {
-      h = (char*)ctx->h_ring[fit]; h_bytes = ctx->ring_bytes[fit];
-      --ctx->ring_pool; ctx->h_ring[fit] = ctx->h_ring[ctx->ring_pool]; ctx->ring_bytes[fit] = ctx->ring_bytes[ctx->ring_pool];
-    } else if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) == hipSuccess) h_bytes = bytes;
-    else { PVLM_SET_ERR(ctx, "pvlm_fuse_scans: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
-    struct Back { pvlm_ctx* c; char* p; size_t b; ~Back() { if (c->ring_pool < pvlm_ctx::kRingPool) { c->h_ring[c->ring_pool] = p; c->ring_bytes[c->ring_pool] = b; ++c->ring_pool; } else (void)hipHostFree(p); } } back{ctx, h, h_bytes};
+    pvlm_pinned_lease lease(ctx, bytes);
+    char* h = lease.p;
+    if (!h) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
     float4* h_in[2] = {(float4*)h, (float4*)(h + pts_b)};
     float4* h_out[2] = {(float4*)(h + 2 * pts_b), (float4*)(h + 3 * pts_b)};
     long long* h_cnt[2] = {(long long*)(h + 4 * pts_b), (long long*)(h + 4 * pts_b + cnt_b)};
     char* h_desc[2] = {h + 4 * pts_b + 2 * cnt_b, h + 4 * pts_b + 2 * cnt_b + sd_b + td_b};
     // device: the same two sets, plus the tile counts and bases
-    const size_t tc_b = align256((size_t)tcap * 4), tb_b = align256((size_t)tcap * 8);
+    const size_t tc_b = align256((size_t)pc.tcap * 4), tb_b = align256((size_t)pc.tcap * 8);
     const size_t set_b = 2 * pts_b + cnt_b + sd_b + td_b + tc_b + tb_b;
     char* dev = nullptr;
     if (pvlm_status st = pvlm_i_alloc_bytes(ctx, (void**)&dev, 2 * set_b)) return st;
@@ -258,7 +186,7 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
     hipStream_t U = ctx->aux_stream ? ctx->aux_stream : S;      // uploads: a stream of their own when one can be had
     // events: [0..1] upload done, [2..3] kernels done (the device input set is free), [4..5] counts down, [6..7] points down, [8] start
     hipEvent_t ev[9] = {};
-    // on every way out, an exception included: nothing may still read or write the pinned window or the device sets when they go back (`back`, declared
+    // on every way out, an exception included: nothing may still read or write the pinned window or the device sets when they go back (`lease`, declared
     // before this guard, returns the window after it has run)
     struct Guard {
       pvlm_ctx* c; hipStream_t s, u; hipEvent_t* ev; char* dev;
@@ -266,11 +194,9 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
     } guard{ctx, S, U, ev, dev};
     hipError_t e = hipSuccess;
     for (int k = 0; k < 9 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-    const size_t n_threads_max = std::max<size_t>(1, std::min<size_t>(pvlm_thread_cap(), (size_t)std::max(1u, std::thread::hardware_concurrency())));
+    const size_t n_threads_max = pvlm_i_threads_max();
     std::vector<TileDesc> tiles;
     std::vector<int> n_tiles(2, 0);
-    std::vector<long long> pt0((size_t)n_scans + 1, 0);
-    for (int s = 0; s < n_scans; ++s) pt0[(size_t)s + 1] = pt0[(size_t)s] + scans[s].n;
     // host side of piece q: its scans packed as float4 into h_in[q & 1], descriptors pointing into the device input set
     auto pack = [&](int q) {
       const int par = q & 1, s0 = piece0[q], s1 = piece0[q + 1];
@@ -280,7 +206,7 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
         const float* dx = (const float*)D[par].in + (size_t)(pt0[(size_t)s] - base) * 4;
         fill_desc(sd[s - s0], scans[s], dx, dx + 3, 4);
       }
-      make_tiles(scans, s0, s1, sd, tiles);
+      make_tiles(n.data() + s0, s1 - s0, sd, tiles);
       n_tiles[par] = (int)tiles.size();
       std::memcpy(h_desc[par] + sd_b, tiles.data(), tiles.size() * sizeof(TileDesc));
       const int ns = s1 - s0;
@@ -297,26 +223,14 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
     };
     auto upload = [&](int q) -> hipError_t {
       const int par = q & 1;
-      const size_t pts = (size_t)(pt0[(size_t)piece0[q + 1]] - pt0[(size_t)piece0[q]]);
-      const int ns = piece0[q + 1] - piece0[q];
+      const size_t pts = pc.points(q);
+      const int ns = pc.items(q);
       hipError_t r = hipStreamWaitEvent(U, q >= 2 ? ev[2 + par] : ev[8], 0);       // the device input set of piece q - 2 has been read
       if (r == hipSuccess) r = hipMemcpyAsync(D[par].in, h_in[par], pts * 16, hipMemcpyHostToDevice, U);
       if (r == hipSuccess) r = hipMemcpyAsync(D[par].sd, h_desc[par], (size_t)ns * sizeof(ScanDesc), hipMemcpyHostToDevice, U);
       if (r == hipSuccess && n_tiles[par]) r = hipMemcpyAsync(D[par].td, h_desc[par] + sd_b, (size_t)n_tiles[par] * sizeof(TileDesc), hipMemcpyHostToDevice, U);
       if (r == hipSuccess) r = hipEventRecord(ev[par], U);
       return r;
-    };
-    // caller's buffer <- h_out[par]: `m` points at `at`
-    auto unpack = [&](int par, long long at, long long m) {
-      const size_t chunk = (size_t)1 << 16;                               // points (1 MB) per worker item
-      const size_t items = (size_t)((m + (long long)chunk - 1) / (long long)chunk);
-      std::atomic<size_t> next{0};
-      pvlm_run_workers(std::max<size_t>(1, std::min(n_threads_max, items)), [&]() {
-        for (size_t c = next++; c < items; c = next++) {
-          const size_t a = c * chunk, b = std::min((size_t)m, a + chunk);
-          std::memcpy(out_xyzi + (size_t)(at + (long long)a) * 4, h_out[par] + a, (b - a) * 16);
-        }
-      });
     };
     pvlm_status st = PVLM_OK;
     long long kept = 0, written = 0;
@@ -325,7 +239,7 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
     if (e == hipSuccess) e = hipEventRecord(ev[8], S);                  // uploads are ordered behind what the context's stream holds
     if (e == hipSuccess) { pack(0); e = upload(0); }
     for (int q = 0; q < n_pieces && e == hipSuccess && st == PVLM_OK; ++q) {
-      const int par = q & 1, s0 = piece0[q], ns = piece0[q + 1] - piece0[q];
+      const int par = q & 1, s0 = piece0[q], ns = pc.items(q);
       e = hipStreamWaitEvent(S, ev[par], 0);
       if (e == hipSuccess) st = launch(ctx, S, D[par].sd, ns, D[par].td, n_tiles[par], D[par].tcount, D[par].tbase, sq_min, sq_max, (float4*)D[par].out,
                                        P, D[par].cnt, D[par].cnt + 1);
@@ -353,13 +267,13 @@ extern "C" pvlm_status pvlm_fuse_scans(pvlm_ctx* ctx, int n_scans, const pvlm_fu
       // the previous piece's points reach the caller's buffer while this one comes down
       if (e == hipSuccess && q > 0 && down_m[par ^ 1] > 0) {
         e = hipEventSynchronize(ev[6 + (par ^ 1)]);
-        if (e == hipSuccess) unpack(par ^ 1, down_at[par ^ 1], down_m[par ^ 1]);
+        if (e == hipSuccess) unpack_records(out_xyzi, h_out[par ^ 1], down_at[par ^ 1], down_m[par ^ 1], n_threads_max);
         down_m[par ^ 1] = 0;
       }
     }
     if (e == hipSuccess && st == PVLM_OK) {
       const int par = (n_pieces - 1) & 1;
-      if (down_m[par] > 0) { e = hipEventSynchronize(ev[6 + par]); if (e == hipSuccess) unpack(par, down_at[par], down_m[par]); }
+      if (down_m[par] > 0) { e = hipEventSynchronize(ev[6 + par]); if (e == hipSuccess) unpack_records(out_xyzi, h_out[par], down_at[par], down_m[par], n_threads_max); }
     }
     if (st) return st;
     if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans: %s", hipGetErrorString(e)); return PVLM_ERR_HIP; }
@@ -379,8 +293,8 @@ extern "C" pvlm_status pvlm_fuse_scans_dev(pvlm_ctx* ctx, int n_scans, const pvl
     PVLM_SET_ERR(ctx, "pvlm_fuse_scans_dev: d_n_out, capacity >= 0 and a 16-byte aligned d_out (float4 stores) are required");
     return PVLM_ERR_ARG;
   }
-  long long total = 0; int max_n = 0;
-  if (pvlm_status st = check_scans(ctx, "pvlm_fuse_scans_dev", n_scans, device_clouds, &total, &max_n)) return st;
+  long long total = 0;
+  if (pvlm_status st = check_scans(ctx, "pvlm_fuse_scans_dev", n_scans, device_clouds, &total)) return st;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans_dev inside a graph capture"); return PVLM_ERR_STATE; }
   try {
@@ -390,7 +304,7 @@ extern "C" pvlm_status pvlm_fuse_scans_dev(pvlm_ctx* ctx, int n_scans, const pvl
       fill_desc(sd[(size_t)s], d, d.xyz, d.intensity, d.stride_floats);
     }
     std::vector<TileDesc> tiles;
-    make_tiles(device_clouds, 0, n_scans, sd.data(), tiles);
+    make_tiles(point_counts(device_clouds, n_scans).data(), n_scans, sd.data(), tiles);
     if (tiles.size() >= (size_t)INT32_MAX) { PVLM_SET_ERR(ctx, "pvlm_fuse_scans_dev: batch too large (split it)"); return PVLM_ERR_ARG; }
     const int n_tiles = (int)tiles.size();
     ScanDesc* d_sd = nullptr; TileDesc* d_td = nullptr; int* d_tcount = nullptr; long long* d_tbase = nullptr;

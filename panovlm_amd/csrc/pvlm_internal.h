@@ -2,14 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <map>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/pvlm.h"
+#include "pvlm_workers.h"
 
 #define PVLM_VERSION_STR "panovlm_amd 0.1 (gfx950)"
 
@@ -73,7 +76,7 @@ struct pvlm_ctx {
   // pinned staging of the voxel-grid build tables (descriptors, point blocks; grow-only): its own buffer, so that the tables of a build queued
   // behind an upload's front copy do not have to wait for that copy to leave h_up
   void* h_grid = nullptr; size_t grid_bytes = 0;
-  // pinned buffers destroyed pvlm_ring_batches leave behind for the next ones (hipHostMalloc of a Room batch's 260 MB: 51 ms).  Several: the host
+  // pinned buffers that pvlm_i_pinned_give keeps for the next pvlm_i_pinned_take (hipHostMalloc of a Room ring batch's 260 MB: 51 ms).  Several: the host
   // mirror runs a call's scans as a sequence of batches whose results stay alive until the call ends (the picks of one overlap the device stages of the next)
   static constexpr int kRingPool = 16;
   void* h_ring[kRingPool] = {}; size_t ring_bytes[kRingPool] = {}; int ring_pool = 0;
@@ -262,6 +265,21 @@ inline pvlm_status pvlm_i_alloc(pvlm_ctx* ctx, T** p, size_t count) {
   if (count == 0) count = 1;
   return pvlm_i_alloc_bytes(ctx, (void**)p, count * sizeof(T));
 }
+// Pinned host memory of a call or a ring batch, through the context's pool of such buffers.  take: the smallest pooled buffer of at least `bytes`, else a
+// hipHostMalloc of `bytes`; *got is the buffer's size (what give wants back); nullptr when there is none to be had.  give: back to the pool; a full pool lets its
+// smallest buffer go when the returned one is larger, and the returned one otherwise.  Nothing on the device may still use the buffer.
+void* pvlm_i_pinned_take(pvlm_ctx* ctx, size_t bytes, size_t* got);
+void pvlm_i_pinned_give(pvlm_ctx* ctx, void* p, size_t bytes);
+// the pinned buffer of one call: declare it before whatever synchronises the call's streams on the way out
+struct pvlm_pinned_lease {
+  pvlm_ctx* ctx; size_t bytes = 0; char* p;
+  pvlm_pinned_lease(pvlm_ctx* c, size_t want) : ctx(c), p((char*)pvlm_i_pinned_take(c, want, &bytes)) {}
+  ~pvlm_pinned_lease() { if (p) pvlm_i_pinned_give(ctx, p, bytes); }
+  pvlm_pinned_lease(const pvlm_pinned_lease&) = delete;
+  pvlm_pinned_lease& operator=(const pvlm_pinned_lease&) = delete;
+};
+// upper limit of the worker threads of one host-side pass of a call: pvlm_thread_cap() and the machine's hardware threads
+inline size_t pvlm_i_threads_max() { return std::max<size_t>(1, std::min<size_t>(pvlm_thread_cap(), (size_t)std::max(1u, std::thread::hardware_concurrency()))); }
 // queued copies through the staging arena + the synchronisation that completes them (see pvlm_stage)
 pvlm_status pvlm_i_h2d_q(pvlm_ctx* ctx, void* dst, const void* src, size_t bytes);
 pvlm_status pvlm_i_d2h_q(pvlm_ctx* ctx, void* dst, const void* src, size_t bytes);

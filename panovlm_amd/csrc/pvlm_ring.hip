@@ -572,15 +572,8 @@ static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, cons
   // with K24: + states (1 B / point), the per-ring lists and the centroids (16 B each, voxel_cap of them at most)
   const size_t picks_fixed = picks ? NP + n_ring_slots * ((1 + kCornerSlots) * 4 + (1 + kFlatSlots) * 4 + 8 + 1) + 64 : 0;
   const size_t pinned = NP * 24 + n_sectors + 256 + picks_fixed + (picks ? voxel_cap * 16 : 0);
-  int fit = -1;                                    // the smallest pooled buffer that is large enough
-  for (int k = 0; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] >= pinned && (fit < 0 || ctx->ring_bytes[k] < ctx->ring_bytes[fit])) fit = k;
-  if (fit >= 0) {
-    B->h_results = (char*)ctx->h_ring[fit]; B->results_bytes = ctx->ring_bytes[fit];
-    --ctx->ring_pool;
-    ctx->h_ring[fit] = ctx->h_ring[ctx->ring_pool]; ctx->ring_bytes[fit] = ctx->ring_bytes[ctx->ring_pool];
-  } else if (hipHostMalloc((void**)&B->h_results, pinned, hipHostMallocDefault) == hipSuccess) {
-    B->results_bytes = pinned;
-  } else { B->h_results = nullptr; PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %zu bytes of pinned memory unavailable", pinned); return (PVLM_ERR_NOMEM); }
+  B->h_results = (char*)pvlm_i_pinned_take(ctx, pinned, &B->results_bytes);
+  if (!B->h_results) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %zu bytes of pinned memory unavailable", pinned); return (PVLM_ERR_NOMEM); }
   pvlm_i_trace("ring: pinned buffer");
   hipStream_t S = ctx->stream;
   hipEvent_t ev[9];
@@ -831,19 +824,7 @@ pvlm_status pvlm_ring_batch_destroy(pvlm_ctx* ctx, pvlm_ring_batch* b) {
     pvlm_i_free(ctx, b->d_scans); pvlm_i_free(ctx, b->d_cloud_scan); pvlm_i_free(ctx, b->d_rc); pvlm_i_free(ctx, b->d_range_image);
     pvlm_i_free(ctx, b->d_image_to_point); pvlm_i_free(ctx, b->d_cloud2); pvlm_i_free(ctx, b->d_image_to_point2);
   }
-  if (b->h_results) {
-    void* gone = b->h_results;                             // the buffer stays with the context for the next batch; a full pool lets its smallest one go
-    if (ctx) {
-      size_t bytes = b->results_bytes;
-      if (ctx->ring_pool < pvlm_ctx::kRingPool) { ctx->h_ring[ctx->ring_pool] = gone; ctx->ring_bytes[ctx->ring_pool] = bytes; ++ctx->ring_pool; gone = nullptr; }
-      else {
-        int least = 0;
-        for (int k = 1; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] < ctx->ring_bytes[least]) least = k;
-        if (ctx->ring_bytes[least] < bytes) { std::swap(ctx->h_ring[least], gone); ctx->ring_bytes[least] = bytes; }
-      }
-    }
-    if (gone) (void)hipHostFree(gone);
-  }
+  if (b->h_results) pvlm_i_pinned_give(ctx, b->h_results, b->results_bytes);      // the buffer stays with the context for the next batch
   delete b;
   return PVLM_OK;
 }

@@ -1,9 +1,9 @@
 // K30: the colour stage of Texture::ColorizeLidarPointCloud (mvs/Texture.cpp:14-80) for many (scan, frame) pairs — range test, transform to the camera,
 // CamToImage, the pixel, OpenCV's 8-bit HSV sky test and the record PointXYZRGB{x, y, z of the LiDAR-frame point, bgr} (per-point statement:
 // pvlm_texture_core.h).  Kept points in pair order, then point order, as 16-byte records (x, y, z, colour word).
-// The compaction is K29's, in two passes without waits between workgroups: a tile of 4096 points (one workgroup, 16 rounds of 256; tiles never span two
-// pairs) writes the colour word of each point (0 = dropped) and its count (wave64 ballots), one workgroup scans the counts into 64-bit tile bases, and each
-// tile writes its kept points at base + rank (k_tex_scatter).
+// The order-preserving compaction is pvlm_compact.h's: a tile of 4096 points (tiles never span two pairs) writes the colour word of each point (0 = dropped)
+// and its count, one workgroup scans the counts into 64-bit tile bases (pvlm_compact::k_tile_scan<PairDesc>), and each tile writes its kept points at
+// base + rank (k_tex_scatter).
 // Device clouds and images (pvlm_colorize_scans_dev): k_tex_word_dev does the whole statement, the gather from the device image included.
 // Host clouds and images (pvlm_colorize_scans): the images never cross the link.  Per piece of whole pairs: the clouds go up, K30a (k_tex_project) turns every
 // point into the byte offset of its pixel or -1 (the double-precision trigonometry), the offsets come down, host workers gather the BGR of those pixels,
@@ -16,23 +16,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "pvlm_internal.h"
 #include "pvlm_workers.h"
+#include "pvlm_compact.h"
 #include "pvlm_texture_core.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRounds = 16;
-constexpr int kTile = kThreads * kRounds;           // points per workgroup
-constexpr int kScanThreads = 1024;
-constexpr long long kPiecePoints = 1ll << 21;       // points per piece of the host path (in: 32 MB of float4, out: 32 MB of records)
+using namespace pvlm_compact;          // kThreads, kRounds, kTile, kWaves, kScanThreads, kPiecePoints
 constexpr int kPiecePairs = 16384;
 constexpr unsigned kHit = 1u << 24;                  // host path: the gathered word of a point that reached the image (b | g << 8 | r << 16 | kHit)
-static_assert(kRounds * (kThreads / 64) == 64, "k_tex_scatter: one wave scans the (round, wave) counts");
 
 struct PairDesc {
   double T[12];                  // camera <- LiDAR, rows 0..2
@@ -43,26 +38,15 @@ struct PairDesc {
   int rows, cols;
   int tile0, n_tiles;
 };
-struct TileDesc { int p0, n, pair, pad; long long g0; };   // first point inside the pair, points (<= kTile), pair, first point in the launch's arrays
+struct TileDesc {                                          // first point inside the pair, points (<= kTile), pair, first point in the launch's arrays
+  int p0, n, pair, pad; long long g0;
+  static TileDesc make(int p0, int n, int pair, long long g0) { return TileDesc{p0, n, pair, 0, g0}; }
+};
 
 __device__ __forceinline__ float3 load_xyz(const PairDesc& d, int i) {
   const size_t o = (size_t)i * (size_t)d.stride;
   if (d.vec) { const float4 p = *(const float4*)(d.xyz + o); return make_float3(p.x, p.y, p.z); }
   return make_float3(d.xyz[o], d.xyz[o + 1], d.xyz[o + 2]);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the workgroup's count of non-zero words -> tile_count[blockIdx.x]
-__device__ __forceinline__ void tile_total(int c, int* tile_count) {
-  __shared__ int part[kThreads / 64];
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
 // K30a: the byte offset of every point's pixel in its image, -1 when the point is dropped before the image test
@@ -124,33 +108,6 @@ __global__ __launch_bounds__(kThreads) void k_tex_word_dev(const PairDesc* __res
   tile_total(c, tile_count);
 }
 
-// one workgroup: exclusive scan of the tile counts in order (64-bit bases), the total, the per-pair counts
-__global__ __launch_bounds__(kScanThreads) void k_tex_scan(const int* __restrict__ tile_count, int n_tiles, long long* __restrict__ tile_base,
-                                                           const PairDesc* __restrict__ pairs, int n_pairs, long long* __restrict__ total,
-                                                           long long* __restrict__ per_pair) {
-  __shared__ int wtot[kScanThreads / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-  long long carry = 0;
-  for (int b = 0; b < n_tiles; b += kScanThreads) {
-    const int i = b + tid, v = i < n_tiles ? tile_count[i] : 0;
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int k = 0; k < kScanThreads / 64; ++k) { const int t = wtot[k]; before += k < w ? t : 0; all += t; }
-    if (i < n_tiles) tile_base[i] = carry + before + (incl - v);
-    carry += all;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
-  if (!per_pair) return;
-  for (int s = tid; s < n_pairs; s += kScanThreads) {
-    const int t0 = pairs[s].tile0, nt = pairs[s].n_tiles;
-    per_pair[s] = nt ? tile_base[t0 + nt - 1] + tile_count[t0 + nt - 1] - tile_base[t0] : 0;
-  }
-}
-
 // second pass: the kept points of the tile at base + rank, as float4 (x, y, z, bits of the colour word)
 __global__ __launch_bounds__(kThreads) void k_tex_scatter(const PairDesc* __restrict__ pairs, const TileDesc* __restrict__ tiles, const unsigned* __restrict__ word,
                                                           const long long* __restrict__ tile_base, float4* __restrict__ out, long long capacity) {
@@ -158,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void k_tex_scatter(const PairDesc* __rest
   const PairDesc& d = pairs[td.pair];
   const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
-  __shared__ int pre[kRounds * (kThreads / 64)];
+  __shared__ int pre[kRounds * kWaves];
   unsigned wd[kRounds];
   int rank[kRounds];
 #pragma unroll
@@ -170,21 +127,14 @@ __global__ __launch_bounds__(kThreads) void k_tex_scatter(const PairDesc* __rest
   for (int r = 0; r < kRounds; ++r) {
     const unsigned long long m = __ballot(wd[r] != 0u);
     rank[r] = __popcll(m & below);
-    if (lane == 0) pre[r * (kThreads / 64) + w] = __popcll(m);
+    if (lane == 0) pre[r * kWaves + w] = __popcll(m);
   }
-  __syncthreads();
-  if (w == 0) {
-    const int v = pre[lane];
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    pre[lane] = incl - v;
-  }
-  __syncthreads();
+  tile_offsets(pre);
   const long long base = tile_base[blockIdx.x];
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
     if (!wd[r]) continue;
-    const long long at = base + pre[r * (kThreads / 64) + w] + rank[r];
+    const long long at = base + pre[r * kWaves + w] + rank[r];
     if (at >= capacity) continue;
     const float3 p = load_xyz(d, td.p0 + r * kThreads + (int)threadIdx.x);
     out[at] = make_float4(p.x, p.y, p.z, __uint_as_float(wd[r]));
@@ -208,21 +158,9 @@ void fill_desc(PairDesc& pd, const pvlm_colorize_pair& s, const float* xyz, int 
   pd.bgr = s.bgr; pd.row_bytes = s.row_bytes; pd.rows = s.rows; pd.cols = s.cols;
 }
 
-// tiles of pairs [s0, s1): sets tile0 / n_tiles (pair indices local to the range); g0 counts from the range's first point
-void make_tiles(const pvlm_colorize_pair* pairs, int s0, int s1, PairDesc* pd, std::vector<TileDesc>& tiles) {
-  tiles.clear();
-  long long g = 0;
-  for (int s = s0; s < s1; ++s) {
-    pd[s - s0].tile0 = (int)tiles.size();
-    for (int p0 = 0; p0 < pairs[s].n; p0 += kTile) tiles.push_back(TileDesc{p0, std::min(kTile, pairs[s].n - p0), s - s0, 0, g + p0});
-    pd[s - s0].n_tiles = (int)tiles.size() - pd[s - s0].tile0;
-    g += std::max(pairs[s].n, 0);
-  }
-}
-
-pvlm_status check_pairs(pvlm_ctx* ctx, const char* what, int n_pairs, const pvlm_colorize_pair* pairs, long long* total, int* max_n) {
+pvlm_status check_pairs(pvlm_ctx* ctx, const char* what, int n_pairs, const pvlm_colorize_pair* pairs, long long* total) {
   if (n_pairs < 0 || (n_pairs > 0 && !pairs)) { PVLM_SET_ERR(ctx, "%s: bad pair list", what); return PVLM_ERR_ARG; }
-  *total = 0; *max_n = 0;
+  *total = 0;
   for (int s = 0; s < n_pairs; ++s) {
     const pvlm_colorize_pair& d = pairs[s];
     if (d.n < 0 || (d.n > 0 && (!d.xyz || !d.T_cl || d.stride_floats < 3 || !d.bgr || d.rows < 0 || d.cols < 0 ||
@@ -230,7 +168,7 @@ pvlm_status check_pairs(pvlm_ctx* ctx, const char* what, int n_pairs, const pvlm
       PVLM_SET_ERR(ctx, "%s: bad descriptor (pair %d: a cloud, T_cl, stride >= 3, a BGR8 image with row_bytes >= 3 cols and < 2 GB)", what, s);
       return PVLM_ERR_ARG;
     }
-    *total += d.n; *max_n = std::max(*max_n, d.n);
+    *total += d.n;
   }
   return PVLM_OK;
 }
@@ -238,14 +176,12 @@ pvlm_status check_pairs(pvlm_ctx* ctx, const char* what, int n_pairs, const pvlm
 // scan + scatter of the words of one launch set
 pvlm_status compact(pvlm_ctx* ctx, hipStream_t S, const PairDesc* d_pd, int n_pairs, const TileDesc* d_td, int n_tiles, const unsigned* d_word, int* d_tcount,
                     long long* d_tbase, float4* d_out, long long capacity, long long* d_total, long long* d_per_pair) {
-  hipLaunchKernelGGL(k_tex_scan, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, n_tiles, d_tbase, d_pd, n_pairs, d_total, d_per_pair);
+  hipLaunchKernelGGL(k_tile_scan<PairDesc>, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, n_tiles, d_tbase, d_pd, n_pairs, d_total, d_per_pair);
   PVLM_HIP(ctx, hipGetLastError());
   if (n_tiles > 0) hipLaunchKernelGGL(k_tex_scatter, dim3((unsigned)n_tiles), dim3(kThreads), 0, S, d_pd, d_td, d_word, (const long long*)d_tbase, d_out, capacity);
   PVLM_HIP(ctx, hipGetLastError());
   return PVLM_OK;
 }
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // PVLM_COLORIZE_PROFILE=1: the host gather's wall and thread milliseconds of every pvlm_colorize_scans call on stderr (tools/colorize_bench.py)
 bool profile_on() { static const bool on = [] { const char* v = std::getenv("PVLM_COLORIZE_PROFILE"); return v && v[0] == '1'; }(); return on; }
@@ -257,8 +193,8 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
                                            long long capacity, long long* n_out, long long* per_pair_or_null) {
   if (!ctx) return PVLM_ERR_ARG;
   if (!n_out || capacity < 0 || (capacity > 0 && !out_records)) { PVLM_SET_ERR(ctx, "pvlm_colorize_scans: n_out, capacity >= 0 and an output buffer are required"); return PVLM_ERR_ARG; }
-  long long total = 0; int max_n = 0;
-  if (pvlm_status st = check_pairs(ctx, "pvlm_colorize_scans", n_pairs, pairs, &total, &max_n)) return st;
+  long long total = 0;
+  if (pvlm_status st = check_pairs(ctx, "pvlm_colorize_scans", n_pairs, pairs, &total)) return st;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_colorize_scans inside a graph capture"); return PVLM_ERR_STATE; }
   *n_out = 0;
@@ -267,31 +203,19 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
   const double sq_min = min_dist * min_dist, sq_max = max_dist * max_dist;
   try {
     // pieces of whole pairs: at most P points (a larger pair is a piece of its own) and kPiecePairs pairs
-    const long long P = std::min(total, std::max(kPiecePoints, (long long)max_n));
-    std::vector<int> piece0{0};
-    for (int s = 0; s < n_pairs;) {
-      long long pts = 0; int k = s;
-      while (k < n_pairs && k - s < kPiecePairs && (k == s || pts + pairs[k].n <= P)) pts += pairs[k++].n;
-      piece0.push_back(k); s = k;
-    }
-    const int n_pieces = (int)piece0.size() - 1;
-    int scap = 0;
-    for (int q = 0; q < n_pieces; ++q) scap = std::max(scap, piece0[q + 1] - piece0[q]);
-    const long long tcap = P / kTile + scap + 1;
-    const size_t pts_b = align256((size_t)P * 16), w_b = align256((size_t)P * 4), cnt_b = align256((size_t)(scap + 1) * 8),
-                 pd_b = align256((size_t)scap * sizeof(PairDesc)), td_b = align256((size_t)tcap * sizeof(TileDesc));
-    // pinned window (the ring batches' pool, as K29): per parity in | offsets | gathered | out | counts | descriptors
+    const std::vector<int> n = point_counts(pairs, n_pairs);
+    const Pieces pc = make_pieces(n.data(), n_pairs, kPiecePairs);
+    const std::vector<int>& piece0 = pc.piece0;
+    const std::vector<long long>& pt0 = pc.pt0;
+    const int n_pieces = pc.count();
+    const long long P = pc.P;
+    const size_t pts_b = align256((size_t)P * 16), w_b = align256((size_t)P * 4), cnt_b = align256((size_t)(pc.scap + 1) * 8),
+                 pd_b = align256((size_t)pc.scap * sizeof(PairDesc)), td_b = align256((size_t)pc.tcap * sizeof(TileDesc));
+    // pinned window (the context's pool, as K29): per parity in | offsets | gathered | out | counts | descriptors
     const size_t hset_b = 2 * pts_b + 2 * w_b + cnt_b + pd_b + td_b;
-    const size_t bytes = 2 * hset_b;
-    char* h = nullptr; size_t h_bytes = 0;
-    int fit = -1;
-    for (int k = 0; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] >= bytes && (fit < 0 || ctx->ring_bytes[k] < ctx->ring_bytes[fit])) fit = k;
-    if (fit >= 0) {
-      h = (char*)ctx->h_ring[fit]; h_bytes = ctx->ring_bytes[fit];
-      --ctx->ring_pool; ctx->h_ring[fit] = ctx->h_ring[ctx->ring_pool]; ctx->ring_bytes[fit] = ctx->ring_bytes[ctx->ring_pool];
-    } else if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) == hipSuccess) h_bytes = bytes;
-    else { PVLM_SET_ERR(ctx, "pvlm_colorize_scans: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
-    struct Back { pvlm_ctx* c; char* p; size_t b; ~Back() { if (c->ring_pool < pvlm_ctx::kRingPool) { c->h_ring[c->ring_pool] = p; c->ring_bytes[c->ring_pool] = b; ++c->ring_pool; } else (void)hipHostFree(p); } } back{ctx, h, h_bytes};
+    pvlm_pinned_lease lease(ctx, 2 * hset_b);
+    char* h = lease.p;
+    if (!h) { PVLM_SET_ERR(ctx, "pvlm_colorize_scans: %zu bytes of pinned memory unavailable", 2 * hset_b); return PVLM_ERR_NOMEM; }
     struct Host { float4* in; int* off; unsigned* gath; float4* out; long long* cnt; char* desc; } H[2];
     for (int k = 0; k < 2; ++k) {
       char* b = h + k * hset_b;
@@ -299,7 +223,7 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
       H[k].cnt = (long long*)(b + 2 * pts_b + 2 * w_b); H[k].desc = b + 2 * pts_b + 2 * w_b + cnt_b;
     }
     // device: the same per parity (offsets reused for the words), plus the tile counts and bases
-    const size_t tc_b = align256((size_t)tcap * 4), tb_b = align256((size_t)tcap * 8);
+    const size_t tc_b = align256((size_t)pc.tcap * 4), tb_b = align256((size_t)pc.tcap * 8);
     const size_t dset_b = 2 * pts_b + 2 * w_b + cnt_b + pd_b + td_b + tc_b + tb_b;
     char* dev = nullptr;
     if (pvlm_status st = pvlm_i_alloc_bytes(ctx, (void**)&dev, 2 * dset_b)) return st;
@@ -321,19 +245,16 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
     } guard{ctx, S, ev, dev};
     hipError_t e = hipSuccess;
     for (int k = 0; k < 6 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-    const size_t n_threads_max = std::max<size_t>(1, std::min<size_t>(pvlm_thread_cap(), (size_t)std::max(1u, std::thread::hardware_concurrency())));
+    const size_t n_threads_max = pvlm_i_threads_max();
     std::vector<TileDesc> tiles;
     int n_tiles[2] = {0, 0};
-    std::vector<long long> pt0((size_t)n_pairs + 1, 0);
-    for (int s = 0; s < n_pairs; ++s) pt0[(size_t)s + 1] = pt0[(size_t)s] + pairs[s].n;
-    auto piece_points = [&](int q) { return (size_t)(pt0[(size_t)piece0[q + 1]] - pt0[(size_t)piece0[q]]); };
     // host side of piece q: its clouds packed as float4 into H[q & 1].in, descriptors pointing into the device set
     auto pack = [&](int q) {
       const int par = q & 1, s0 = piece0[q], s1 = piece0[q + 1];
       const long long base = pt0[(size_t)s0];
       PairDesc* pd = (PairDesc*)H[par].desc;
       for (int s = s0; s < s1; ++s) fill_desc(pd[s - s0], pairs[s], (const float*)(D[par].in + (pt0[(size_t)s] - base)), 4);
-      make_tiles(pairs, s0, s1, pd, tiles);
+      make_tiles(n.data() + s0, s1 - s0, pd, tiles);
       n_tiles[par] = (int)tiles.size();
       std::memcpy(H[par].desc + pd_b, tiles.data(), tiles.size() * sizeof(TileDesc));
       std::atomic<int> next{s0};
@@ -348,8 +269,8 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
     };
     // piece q up, K30a, the offsets down (all on S: behind the previous piece's second half, which last used this parity's device set)
     auto project = [&](int q) -> hipError_t {
-      const int par = q & 1, ns = piece0[q + 1] - piece0[q];
-      const size_t pts = piece_points(q);
+      const int par = q & 1, ns = pc.items(q);
+      const size_t pts = pc.points(q);
       hipError_t r = hipMemcpyAsync(D[par].in, H[par].in, pts * 16, hipMemcpyHostToDevice, S);
       if (r == hipSuccess) r = hipMemcpyAsync(D[par].pd, H[par].desc, (size_t)ns * sizeof(PairDesc), hipMemcpyHostToDevice, S);
       if (r == hipSuccess && n_tiles[par]) r = hipMemcpyAsync(D[par].td, H[par].desc + pd_b, (size_t)n_tiles[par] * sizeof(TileDesc), hipMemcpyHostToDevice, S);
@@ -392,24 +313,13 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
       });
       gather_wall_ms += ms_since(w0); gather_thread_ms += 1e-3 * (double)thread_us.load();
     };
-    auto unpack = [&](int par, long long at, long long m) {
-      const size_t chunk = (size_t)1 << 16;
-      const size_t items = (size_t)((m + (long long)chunk - 1) / (long long)chunk);
-      std::atomic<size_t> next{0};
-      pvlm_run_workers(std::max<size_t>(1, std::min(n_threads_max, items)), [&]() {
-        for (size_t c = next++; c < items; c = next++) {
-          const size_t a = c * chunk, b = std::min((size_t)m, a + chunk);
-          std::memcpy(out_records + (size_t)(at + (long long)a) * 4, H[par].out + a, (b - a) * 16);
-        }
-      });
-    };
     pvlm_status st = PVLM_OK;
     long long kept = 0;
     bool overflow = false;
     if (e == hipSuccess) { pack(0); e = project(0); }
     for (int q = 0; q < n_pieces && e == hipSuccess && st == PVLM_OK; ++q) {
-      const int par = q & 1, s0 = piece0[q], ns = piece0[q + 1] - piece0[q];
-      const size_t pts = piece_points(q);
+      const int par = q & 1, s0 = piece0[q], ns = pc.items(q);
+      const size_t pts = pc.points(q);
       // the next piece goes up and is projected while this one's pixels are gathered
       if (q + 1 < n_pieces) { pack(q + 1); e = project(q + 1); }
       if (e == hipSuccess) e = hipEventSynchronize(ev[par]);
@@ -435,7 +345,7 @@ extern "C" pvlm_status pvlm_colorize_scans(pvlm_ctx* ctx, int n_pairs, const pvl
         e = hipMemcpyAsync(H[par].out, D[par].out, (size_t)m * 16, hipMemcpyDeviceToHost, S);
         if (e == hipSuccess) e = hipEventRecord(ev[4 + par], S);
         if (e == hipSuccess) e = hipEventSynchronize(ev[4 + par]);
-        if (e == hipSuccess) unpack(par, kept, m);
+        if (e == hipSuccess) unpack_records(out_records, H[par].out, kept, m, n_threads_max);
       }
       kept += m;
     }
@@ -460,15 +370,15 @@ extern "C" pvlm_status pvlm_colorize_scans_dev(pvlm_ctx* ctx, int n_pairs, const
     PVLM_SET_ERR(ctx, "pvlm_colorize_scans_dev: d_n_out, capacity >= 0 and a 16-byte aligned d_out (float4 stores) are required");
     return PVLM_ERR_ARG;
   }
-  long long total = 0; int max_n = 0;
-  if (pvlm_status st = check_pairs(ctx, "pvlm_colorize_scans_dev", n_pairs, device_pairs, &total, &max_n)) return st;
+  long long total = 0;
+  if (pvlm_status st = check_pairs(ctx, "pvlm_colorize_scans_dev", n_pairs, device_pairs, &total)) return st;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_colorize_scans_dev inside a graph capture"); return PVLM_ERR_STATE; }
   try {
     std::vector<PairDesc> pd((size_t)std::max(n_pairs, 1));
     for (int s = 0; s < n_pairs; ++s) fill_desc(pd[(size_t)s], device_pairs[s], device_pairs[s].xyz, device_pairs[s].stride_floats);
     std::vector<TileDesc> tiles;
-    make_tiles(device_pairs, 0, n_pairs, pd.data(), tiles);
+    make_tiles(point_counts(device_pairs, n_pairs).data(), n_pairs, pd.data(), tiles);
     if (tiles.size() >= (size_t)INT32_MAX) { PVLM_SET_ERR(ctx, "pvlm_colorize_scans_dev: batch too large (split it)"); return PVLM_ERR_ARG; }
     const int n_tiles = (int)tiles.size();
     PairDesc* d_pd = nullptr; TileDesc* d_td = nullptr; unsigned* d_word = nullptr; int* d_tcount = nullptr; long long* d_tbase = nullptr;

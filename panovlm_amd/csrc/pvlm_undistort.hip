@@ -4,7 +4,6 @@
 // rotation, its angle and sine) are computed once per scan on the host with the host's libm, exactly the values upstream recomputes for every point.
 #include <atomic>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "pvlm_internal.h"
@@ -52,20 +51,14 @@ extern "C" pvlm_status pvlm_undistort_batch(pvlm_ctx* ctx, int n_scans, const pv
     }
     // pinned staging: the ring batches' pool (the same scans pass through both in one EstimatePose / UndistortLidars / EstimatePose sequence)
     const size_t bytes = (size_t)total * 16 + (size_t)n_scans * sizeof(SweepDesc) + 256;
-    char* h = nullptr; size_t h_bytes = 0;
-    int fit = -1;
-    for (int k = 0; k < ctx->ring_pool; ++k) if (ctx->ring_bytes[k] >= bytes && (fit < 0 || ctx->ring_bytes[k] < ctx->ring_bytes[fit])) fit = k;
-    if (fit >= 0) {
-      h = (char*)ctx->h_ring[fit]; h_bytes = ctx->ring_bytes[fit];
-      --ctx->ring_pool; ctx->h_ring[fit] = ctx->h_ring[ctx->ring_pool]; ctx->ring_bytes[fit] = ctx->ring_bytes[ctx->ring_pool];
-    } else if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) == hipSuccess) h_bytes = bytes;
-    else { PVLM_SET_ERR(ctx, "pvlm_undistort_batch: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
-    struct Back { pvlm_ctx* c; char* p; size_t b; ~Back() { if (c->ring_pool < pvlm_ctx::kRingPool) { c->h_ring[c->ring_pool] = p; c->ring_bytes[c->ring_pool] = b; ++c->ring_pool; } else (void)hipHostFree(p); } } back{ctx, h, h_bytes};
+    pvlm_pinned_lease lease(ctx, bytes);
+    char* h = lease.p;
+    if (!h) { PVLM_SET_ERR(ctx, "pvlm_undistort_batch: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
     float4* hp = (float4*)h;
     SweepDesc* hd = (SweepDesc*)(h + (((size_t)total * 16 + 255) & ~(size_t)255));
     std::memcpy(hd, desc.data(), (size_t)n_scans * sizeof(SweepDesc));
     auto each_scan = [&](auto&& body) {
-      const size_t n_threads = std::max<size_t>(1, std::min<size_t>({pvlm_thread_cap(), (size_t)n_scans / 16 + 1, (size_t)std::max(1u, std::thread::hardware_concurrency())}));
+      const size_t n_threads = std::min(pvlm_i_threads_max(), (size_t)n_scans / 16 + 1);
       std::atomic<int> next{0};
       auto work = [&]() { for (int s = next++; s < n_scans; s = next++) body(s); };
       pvlm_run_workers(n_threads, work);

@@ -120,7 +120,8 @@ def summarize_trace(trace_csv, bench_lines):
     names = ("k_tex_word_dev", "k_tex_scan", "k_tex_scatter")
     for r in csv.DictReader(open(trace_csv)):
         for k in names:
-            if k + "(" in r["Kernel_Name"]:
+            # the scan is pvlm_compact::k_tile_scan<PairDesc> (k_tex_scan in traces recorded before the compaction was shared)
+            if k + "(" in r["Kernel_Name"] or (k == "k_tex_scan" and "k_tile_scan<" in r["Kernel_Name"]):
                 cur[k] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
                 if k == "k_tex_scatter":
                     calls.append(cur); cur = {}

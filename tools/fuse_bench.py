@@ -95,7 +95,8 @@ def summarize_trace(trace_csv, bench_lines):
     for r in csv.DictReader(open(trace_csv)):
         name = r["Kernel_Name"]
         for k in ("k_fuse_count", "k_fuse_scan", "k_fuse_scatter"):
-            if k + "(" in name:
+            # the scan is pvlm_compact::k_tile_scan<ScanDesc> (k_fuse_scan in traces recorded before the compaction was shared)
+            if k + "(" in name or (k == "k_fuse_scan" and "k_tile_scan<" in name):
                 cur[k] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
                 if k == "k_fuse_scatter":
                     calls.append(cur); cur = {}
