@@ -516,19 +516,6 @@ static void launch_scan(pvlm_ctx* ctx, int T, const int* count, int* start, int*
   hipLaunchKernelGGL(k_scan_tiles, dim3(nt), dim3(256), 0, ctx->stream, T, count, tiles, start);
 }
 
-// build-time scratch, released on every exit path
-struct DevScratch {
-  pvlm_ctx* ctx;
-  std::vector<void*> ptrs;
-  explicit DevScratch(pvlm_ctx* c) : ctx(c) {}
-  ~DevScratch() { for (void* p : ptrs) pvlm_i_free(ctx, p); }
-  template <typename T> pvlm_status alloc(T** p, size_t count) {
-    const pvlm_status st = pvlm_i_alloc(ctx, p, count);
-    if (!st) ptrs.push_back(*p);
-    return st;
-  }
-};
-
 // largest cloud the voxel grid addresses with 32-bit cell tables (hashed table: 2 n slots rounded up to a power of two)
 #define PVLM_MAX_CLOUD_POINTS (256 << 20)
 
@@ -712,7 +699,7 @@ static pvlm_status grids_build(pvlm_ctx* ctx, const std::vector<GridJob>& jobs, 
   if (e == hipSuccess && keys_bytes) e = hipMemsetAsync(d_slab + o_keys0, 0xFF, keys_bytes, ctx->stream);
   if (e == hipSuccess && cursor_bytes) e = hipMemsetAsync(d_scr, 0, cursor_bytes, ctx->stream);
   if (e != hipSuccess) { PVLM_SET_ERR(ctx, "voxel-grid build: copy / memset failed: %s", hipGetErrorString(e)); return bail(PVLM_ERR_HIP); }
-  DevScratch tiles_scratch(ctx);
+  pvlm_dev_scratch tiles_scratch(ctx);
   if (nb) {
     const GridDesc* dd = (const GridDesc*)(d_slab + o_desc); const GridBlock* db = (const GridBlock*)(d_slab + o_blocks);
     hipLaunchKernelGGL(k_grid_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, dd, db);
@@ -1133,7 +1120,7 @@ static pvlm_status scan_transform_batch_impl(pvlm_ctx* ctx, int n_scans, pvlm_sc
   }
   if (hb.empty()) return PVLM_OK;
   // ---- 2. tables up, one launch
-  DevScratch scratch(ctx);
+  pvlm_dev_scratch scratch(ctx);
   XformCloud* d_clouds = nullptr; XformBlock* d_blocks = nullptr; double* d_T = nullptr; unsigned* d_boxes = nullptr;
   pvlm_status st = scratch.alloc(&d_clouds, hc.size());
   if (!st) st = scratch.alloc(&d_blocks, hb.size());

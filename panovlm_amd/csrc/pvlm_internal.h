@@ -278,6 +278,21 @@ struct pvlm_pinned_lease {
   pvlm_pinned_lease(const pvlm_pinned_lease&) = delete;
   pvlm_pinned_lease& operator=(const pvlm_pinned_lease&) = delete;
 };
+// the device scratch of one call: from the context's pool, back to it on every exit path.  Declare it before whatever synchronises the call on the way out
+// (staged device-to-host copies have landed before the function returns; the blocks go back stream-ordered behind the call's launches).  A buffer that is
+// released early on purpose, so that the pool can hand the block on, stays a plain pvlm_i_alloc / pvlm_i_free.
+struct pvlm_dev_scratch {
+  pvlm_ctx* ctx; std::vector<const void*> ptrs;
+  explicit pvlm_dev_scratch(pvlm_ctx* c) : ctx(c) {}
+  ~pvlm_dev_scratch() { for (const void* p : ptrs) pvlm_i_free(ctx, p); }
+  pvlm_dev_scratch(const pvlm_dev_scratch&) = delete;
+  pvlm_dev_scratch& operator=(const pvlm_dev_scratch&) = delete;
+  template <typename T> pvlm_status alloc(T** p, size_t count) {
+    const pvlm_status st = pvlm_i_alloc(ctx, p, count);
+    if (!st) ptrs.push_back(*p);
+    return st;
+  }
+};
 // upper limit of the worker threads of one host-side pass of a call: pvlm_thread_cap() and the machine's hardware threads
 inline size_t pvlm_i_threads_max() { return std::max<size_t>(1, std::min<size_t>(pvlm_thread_cap(), (size_t)std::max(1u, std::thread::hardware_concurrency()))); }
 // queued copies through the staging arena + the synchronisation that completes them (see pvlm_stage)

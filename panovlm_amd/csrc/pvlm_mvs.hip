@@ -1131,6 +1131,95 @@ __global__ void k_mvs_refine(int rows, int cols, pvlm_mvs::RefineViews nv, const
     pvlm_mvs::refine_pixel(rows, cols, nv, proj_key, unit, depth, conf, depth_constant, thr, min_depth, max_depth, e, depth_filter, conf_filter);
 }
 
+// ---- host side.  A stage has a per-call form (host arrays: allocate, upload, launch, download) and a resident one (pvlm_mvs_views: the maps stay in HBM); both queue
+// the launches of the stage through its one core below, on device pointers ----
+
+// R_nr / t_nr of neighbour b into the table a kernel takes (pvlm_mvs_neighbours, RefineViews)
+template <typename Table> static void mvs_set_pose(Table& tab, int b, const float* R_nr, const float* t_nr) {
+  for (int k = 0; k < 9; ++k) tab.R[b][k] = R_nr[9 * b + k];
+  for (int k = 0; k < 3; ++k) tab.t[b][k] = t_nr[3 * b + k];
+}
+
+static bool mvs_window_ok(pvlm_ctx* ctx, int half_window, int step) {
+  const int n_tex = pvlm_mvs::num_texels(half_window, step);
+  if (n_tex > 64 * PVLM_MVS_MAXM) PVLM_SET_ERR(ctx, "NCC window of %d texels exceeds %d", n_tex, 64 * PVLM_MVS_MAXM);
+  return n_tex <= 64 * PVLM_MVS_MAXM;
+}
+
+// One reference view, queued on ctx->stream: the scoring pass (max_iter < 0), or max_iter sweeps (strategy 2: sequential, otherwise the two checkerboard colours)
+// and the confidence threshold.  Device pointers; d_const may be null.
+static hipError_t mvs_estimate(pvlm_ctx* ctx, int rows, int cols, int half_window, int step, const unsigned char* d_img, const float* d_unit,
+                               const pvlm_mvs_neighbours& nb, float* d_depth, float* d_normal, float* d_conf, const unsigned char* d_const, float min_depth,
+                               float max_depth, unsigned long long seed, int max_iter, float conf_threshold, int strategy) {
+  hipStream_t s = ctx->stream;
+  const size_t npix = (size_t)rows * cols;
+  if (max_iter < 0) {
+    float* d_wtab = nullptr;
+    const size_t wtab_floats = mvs_lane_bands(rows, cols, half_window, step).floats;
+    if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;
+    {
+      pvlm_prof_scope prof(ctx, 1);   // timed with the "materialise" slot of pvlm_profile_* (bench / tools)
+      launch_mvs_conf(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_wtab);
+    }
+    pvlm_i_free(ctx, d_wtab);
+    return hipGetLastError();
+  }
+  if (strategy == 2) {
+    MvsFlow flow;
+    const bool have_flow = mvs_flow_begin(ctx, rows, cols, half_window, step, &flow);
+    for (int iter = 0; iter < max_iter; ++iter) {
+      pvlm_prof_scope prof(ctx, 1);                  // one profile interval per iteration (one persistent launch, or rows + cols - 1 launches)
+      launch_mvs_propagate_sequential(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_const, min_depth, max_depth,
+                                      pvlm_mvs::pass_seed(seed, iter), iter, have_flow ? &flow : nullptr);
+    }
+    mvs_flow_end(ctx, &flow);
+  } else {
+    float* d_wtab = nullptr;                       // patch weights of the thread-per-pixel form, [texel][pixel of the colour in a band of rows]
+    const size_t wtab_floats = mvs_lane_bands(rows, (cols + 1) / 2, half_window, step).floats;
+    if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;    // no room: the wave-per-pixel form needs none
+    for (int iter = 0; iter < max_iter; ++iter)
+      for (int offset = 0; offset <= 1; ++offset) {
+        pvlm_prof_scope prof(ctx, 1);
+        launch_mvs_propagate(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_const, min_depth, max_depth,
+                             pvlm_mvs::pass_seed(seed, 2 * iter + offset), offset, d_wtab);
+      }
+    pvlm_i_free(ctx, d_wtab);                        // stream-ordered: behind the launches above
+  }
+  hipLaunchKernelGGL(k_mvs_threshold, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, (long long)npix, d_const, conf_threshold, d_depth, d_normal, d_conf);
+  return hipGetLastError();
+}
+
+// FilterDepthImageRefine of one reference view, queued on ctx->stream: the keys filled, the splat of every neighbour's depth map (d_nei_depth[b]) into its key plane,
+// the per-pixel fusion that reads the neighbours' confidences (d_nei_conf[b]).  Device pointers; d_key: n_neighbors planes; d_conf is in-out; d_const may be null.
+static hipError_t mvs_refine(pvlm_ctx* ctx, int rows, int cols, const float* d_unit, int n_neighbors, const float* const* d_nei_depth, const float* const* d_nei_conf,
+                             const float* R_nr, const float* t_nr, unsigned long long* d_key, const float* d_depth, float* d_conf, const unsigned char* d_const,
+                             float depth_diff_threshold, float min_depth, float max_depth, float* d_depth_filter, float* d_conf_filter) {
+  hipStream_t s = ctx->stream;
+  const size_t npix = (size_t)rows * cols;
+  const unsigned grid = (unsigned)((npix + 255) / 256);
+  hipError_t e = hipSuccess;
+  if (n_neighbors > 0) {
+    hipLaunchKernelGGL(k_mvs_fill_u64, dim3((unsigned)((npix * n_neighbors + 255) / 256)), dim3(256), 0, s, (long long)(npix * n_neighbors), ~0ull, d_key);
+    e = hipGetLastError();
+  }
+  pvlm_mvs::RefineViews nv;
+  nv.n = n_neighbors;
+  for (int b = 0; b < n_neighbors && e == hipSuccess; ++b) {
+    pvlm_mvs_pose pose;
+    pvlm_mvs::inverse_pose(R_nr + 9 * b, t_nr + 3 * b, pose.R_rn, pose.t_rn);
+    nv.conf[b] = d_nei_conf[b];
+    mvs_set_pose(nv, b, R_nr, t_nr);
+    hipLaunchKernelGGL(k_mvs_project_conf, dim3(grid), dim3(256), 0, s, rows, cols, d_unit, d_nei_depth[b], pose, d_key + npix * (size_t)b);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mvs_refine, dim3(grid), dim3(256), 0, s, rows, cols, nv, d_key, d_unit, d_depth, d_conf, d_const, depth_diff_threshold, min_depth, max_depth,
+                       d_depth_filter, d_conf_filter);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
 extern "C" {
 
 pvlm_status pvlm_mvs_filter_depth(pvlm_ctx* ctx, int rows, int cols, int n_neighbors, const float* const* nei_depth, const float* R_nr, const float* t_nr,
@@ -1141,16 +1230,17 @@ pvlm_status pvlm_mvs_filter_depth(pvlm_ctx* ctx, int rows, int cols, int n_neigh
     return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t npix = (size_t)rows * cols;
+  pvlm_dev_scratch tmp(ctx);
   float *d_unit = nullptr, *d_nd = nullptr, *d_depth = nullptr, *d_conf = nullptr, *d_out = nullptr, *d_cout = nullptr;
   unsigned* d_proj = nullptr; unsigned char* d_const = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_unit, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_nd, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_proj, npix * (size_t)std::max(n_neighbors, 1));
-  if (!st) st = pvlm_i_alloc(ctx, &d_depth, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_out, npix);
-  if (!st && conf) st = pvlm_i_alloc(ctx, &d_conf, npix);
-  if (!st && conf) st = pvlm_i_alloc(ctx, &d_cout, npix);
-  if (!st && depth_constant) st = pvlm_i_alloc(ctx, &d_const, npix);
+  pvlm_status st = tmp.alloc(&d_unit, npix * 3);
+  if (!st) st = tmp.alloc(&d_nd, npix);
+  if (!st) st = tmp.alloc(&d_proj, npix * (size_t)std::max(n_neighbors, 1));
+  if (!st) st = tmp.alloc(&d_depth, npix);
+  if (!st) st = tmp.alloc(&d_out, npix);
+  if (!st && conf) st = tmp.alloc(&d_conf, npix);
+  if (!st && conf) st = tmp.alloc(&d_cout, npix);
+  if (!st && depth_constant) st = tmp.alloc(&d_const, npix);
   if (!st) {
     hipStream_t s = ctx->stream;
     const unsigned grid = (unsigned)((npix + 255) / 256);
@@ -1181,7 +1271,6 @@ pvlm_status pvlm_mvs_filter_depth(pvlm_ctx* ctx, int rows, int cols, int n_neigh
     if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_mvs_filter_depth: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
   }
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_unit); pvlm_i_free(ctx, d_nd); pvlm_i_free(ctx, d_proj); pvlm_i_free(ctx, d_depth); pvlm_i_free(ctx, d_conf); pvlm_i_free(ctx, d_out); pvlm_i_free(ctx, d_cout); pvlm_i_free(ctx, d_const);
   return st;
 }
 
@@ -1196,49 +1285,32 @@ pvlm_status pvlm_mvs_filter_depth_refine(pvlm_ctx* ctx, int rows, int cols, int 
   for (int b = 0; b < n_neighbors; ++b) if (!nei_depth[b] || !nei_conf[b]) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t nn = (size_t)std::max(n_neighbors, 1);
+  pvlm_dev_scratch tmp(ctx);
   float *d_unit = nullptr, *d_nd = nullptr, *d_nc = nullptr, *d_depth = nullptr, *d_conf = nullptr, *d_out = nullptr, *d_cout = nullptr;
   unsigned long long* d_key = nullptr; unsigned char* d_const = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_unit, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_nd, npix * nn);
-  if (!st) st = pvlm_i_alloc(ctx, &d_nc, npix * nn);
-  if (!st) st = pvlm_i_alloc(ctx, &d_key, npix * nn);
-  if (!st) st = pvlm_i_alloc(ctx, &d_depth, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_conf, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_out, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_cout, npix);
-  if (!st && depth_constant) st = pvlm_i_alloc(ctx, &d_const, npix);
+  pvlm_status st = tmp.alloc(&d_unit, npix * 3);
+  if (!st) st = tmp.alloc(&d_nd, npix * nn);
+  if (!st) st = tmp.alloc(&d_nc, npix * nn);
+  if (!st) st = tmp.alloc(&d_key, npix * nn);
+  if (!st) st = tmp.alloc(&d_depth, npix);
+  if (!st) st = tmp.alloc(&d_conf, npix);
+  if (!st) st = tmp.alloc(&d_out, npix);
+  if (!st) st = tmp.alloc(&d_cout, npix);
+  if (!st && depth_constant) st = tmp.alloc(&d_const, npix);
   if (!st) {
-    hipStream_t s = ctx->stream;
-    const unsigned grid = (unsigned)((npix + 255) / 256);
-    hipLaunchKernelGGL(k_mvs_unit_table, dim3(grid), dim3(256), 0, s, rows, cols, d_unit);
+    hipLaunchKernelGGL(k_mvs_unit_table, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ctx->stream, rows, cols, d_unit);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && n_neighbors > 0) {
-      hipLaunchKernelGGL(k_mvs_fill_u64, dim3((unsigned)((npix * n_neighbors + 255) / 256)), dim3(256), 0, s, (long long)(npix * n_neighbors), ~0ull, d_key);
-      e = hipGetLastError();
-    }
-    pvlm_mvs::RefineViews nv;
-    nv.n = n_neighbors;
+    const float *nd[16], *nc[16];
     for (int b = 0; b < n_neighbors && e == hipSuccess; ++b) {
+      nd[b] = d_nd + npix * (size_t)b; nc[b] = d_nc + npix * (size_t)b;
       e = mvs_up(ctx, d_nd + npix * (size_t)b, nei_depth[b], npix * sizeof(float));
       if (e == hipSuccess) e = mvs_up(ctx, d_nc + npix * (size_t)b, nei_conf[b], npix * sizeof(float));
-      pvlm_mvs_pose pose;
-      pvlm_mvs::inverse_pose(R_nr + 9 * b, t_nr + 3 * b, pose.R_rn, pose.t_rn);
-      nv.conf[b] = d_nc + npix * (size_t)b;
-      for (int k = 0; k < 9; ++k) nv.R[b][k] = R_nr[9 * b + k];
-      for (int k = 0; k < 3; ++k) nv.t[b][k] = t_nr[3 * b + k];
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_mvs_project_conf, dim3(grid), dim3(256), 0, s, rows, cols, d_unit, d_nd + npix * (size_t)b, pose, d_key + npix * (size_t)b);
-        e = hipGetLastError();
-      }
     }
     if (e == hipSuccess) e = mvs_up(ctx, d_depth, depth, npix * sizeof(float));
     if (e == hipSuccess) e = mvs_up(ctx, d_conf, conf, npix * sizeof(float));
     if (e == hipSuccess && depth_constant) e = mvs_up(ctx, d_const, depth_constant, npix);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_mvs_refine, dim3(grid), dim3(256), 0, s, rows, cols, nv, d_key, d_unit, d_depth, d_conf, d_const, depth_diff_threshold, min_depth,
-                         max_depth, d_out, d_cout);
-      e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+      e = mvs_refine(ctx, rows, cols, d_unit, n_neighbors, nd, nc, R_nr, t_nr, d_key, d_depth, d_conf, d_const, depth_diff_threshold, min_depth, max_depth, d_out, d_cout);
     if (e == hipSuccess) e = mvs_down(ctx, depth_filter, d_out, npix * sizeof(float));
     if (e == hipSuccess) e = mvs_down(ctx, conf_filter, d_cout, npix * sizeof(float));
     if (e == hipSuccess) e = mvs_down(ctx, conf, d_conf, npix * sizeof(float));
@@ -1246,7 +1318,6 @@ pvlm_status pvlm_mvs_filter_depth_refine(pvlm_ctx* ctx, int rows, int cols, int 
     if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_mvs_filter_depth_refine: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
   }
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_unit); pvlm_i_free(ctx, d_nd); pvlm_i_free(ctx, d_nc); pvlm_i_free(ctx, d_key); pvlm_i_free(ctx, d_depth); pvlm_i_free(ctx, d_conf); pvlm_i_free(ctx, d_out); pvlm_i_free(ctx, d_cout); pvlm_i_free(ctx, d_const);
   return st;
 }
 
@@ -1258,19 +1329,20 @@ static pvlm_status mvs_run(pvlm_ctx* ctx, const char* what, int rows, int cols, 
   if (!ctx || rows <= 0 || cols <= 0 || half_window < 1 || step < 1 || !ref_gray || n_neighbors < 0 || n_neighbors > 16 || !depth || !normal || !conf ||
       (n_neighbors > 0 && (!nei_gray || !R_nr || !t_nr)))
     return PVLM_ERR_ARG;
-  if (pvlm_mvs::num_texels(half_window, step) > 64 * PVLM_MVS_MAXM) { PVLM_SET_ERR(ctx, "NCC window of %d texels exceeds %d", pvlm_mvs::num_texels(half_window, step), 64 * PVLM_MVS_MAXM); return PVLM_ERR_ARG; }
+  if (!mvs_window_ok(ctx, half_window, step)) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t npix = (size_t)rows * cols;
+  pvlm_dev_scratch tmp(ctx);
   unsigned char *d_img = nullptr, *d_const = nullptr; float *d_unit = nullptr, *d_depth = nullptr, *d_normal = nullptr, *d_conf = nullptr, *d_ndepth = nullptr;
   unsigned* d_quad = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_img, npix * (size_t)(n_neighbors + 1));
-  if (!st) st = pvlm_i_alloc(ctx, &d_quad, npix * (size_t)std::max(n_neighbors, 1));
-  if (!st && nei_depth) st = pvlm_i_alloc(ctx, &d_ndepth, npix * (size_t)std::max(n_neighbors, 1));
-  if (!st && depth_constant) st = pvlm_i_alloc(ctx, &d_const, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_unit, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_depth, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_normal, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_conf, npix);
+  pvlm_status st = tmp.alloc(&d_img, npix * (size_t)(n_neighbors + 1));
+  if (!st) st = tmp.alloc(&d_quad, npix * (size_t)std::max(n_neighbors, 1));
+  if (!st && nei_depth) st = tmp.alloc(&d_ndepth, npix * (size_t)std::max(n_neighbors, 1));
+  if (!st && depth_constant) st = tmp.alloc(&d_const, npix);
+  if (!st) st = tmp.alloc(&d_unit, npix * 3);
+  if (!st) st = tmp.alloc(&d_depth, npix);
+  if (!st) st = tmp.alloc(&d_normal, npix * 3);
+  if (!st) st = tmp.alloc(&d_conf, npix);
   if (!st) {
     hipStream_t s = ctx->stream;
     pvlm_mvs_neighbours nb;
@@ -1287,8 +1359,7 @@ static pvlm_status mvs_run(pvlm_ctx* ctx, const char* what, int rows, int cols, 
         e = mvs_up(ctx, d_ndepth + npix * (size_t)b, nei_depth[b], npix * sizeof(float));
         nb.depth[b] = d_ndepth + npix * (size_t)b;
       }
-      for (int k = 0; k < 9; ++k) nb.R[b][k] = R_nr[9 * b + k];
-      for (int k = 0; k < 3; ++k) nb.t[b][k] = t_nr[3 * b + k];
+      mvs_set_pose(nb, b, R_nr, t_nr);
     }
     if (e == hipSuccess) e = mvs_up(ctx, d_depth, depth, npix * sizeof(float));
     if (e == hipSuccess) e = mvs_up(ctx, d_normal, normal, npix * 3 * sizeof(float));
@@ -1296,39 +1367,8 @@ static pvlm_status mvs_run(pvlm_ctx* ctx, const char* what, int rows, int cols, 
     if (e == hipSuccess && depth_constant) e = mvs_up(ctx, d_const, depth_constant, npix);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_mvs_unit_table, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, rows, cols, d_unit);
-      if (max_iter < 0) {
-        float* d_wtab = nullptr;
-        const size_t wtab_floats = mvs_lane_bands(rows, cols, half_window, step).floats;
-        if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;
-        {
-          pvlm_prof_scope prof(ctx, 1);   // timed with the "materialise" slot of pvlm_profile_* (bench / tools)
-          launch_mvs_conf(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_wtab);
-        }
-        pvlm_i_free(ctx, d_wtab);
-      } else if (strategy == 2) {
-        MvsFlow flow;
-        const bool have_flow = mvs_flow_begin(ctx, rows, cols, half_window, step, &flow);
-        for (int iter = 0; iter < max_iter; ++iter) {
-          pvlm_prof_scope prof(ctx, 1);                  // one profile interval per iteration (one persistent launch, or rows + cols - 1 launches)
-          launch_mvs_propagate_sequential(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_const, min_depth, max_depth,
-                                          pvlm_mvs::pass_seed(seed, iter), iter, have_flow ? &flow : nullptr);
-        }
-        mvs_flow_end(ctx, &flow);
-        hipLaunchKernelGGL(k_mvs_threshold, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, (long long)npix, d_const, conf_threshold, d_depth, d_normal, d_conf);
-      } else {
-        float* d_wtab = nullptr;                       // patch weights of the thread-per-pixel form, [texel][pixel of the colour in a band of rows]
-        const size_t wtab_floats = mvs_lane_bands(rows, (cols + 1) / 2, half_window, step).floats;
-        if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;    // no room: the wave-per-pixel form needs none
-        for (int iter = 0; iter < max_iter; ++iter)
-          for (int offset = 0; offset <= 1; ++offset) {
-            pvlm_prof_scope prof(ctx, 1);
-            launch_mvs_propagate(s, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_const, min_depth, max_depth,
-                                 pvlm_mvs::pass_seed(seed, 2 * iter + offset), offset, d_wtab);
-          }
-        pvlm_i_free(ctx, d_wtab);                        // stream-ordered: behind the launches above
-        hipLaunchKernelGGL(k_mvs_threshold, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, (long long)npix, d_const, conf_threshold, d_depth, d_normal, d_conf);
-      }
-      e = hipGetLastError();
+      e = mvs_estimate(ctx, rows, cols, half_window, step, d_img, d_unit, nb, d_depth, d_normal, d_conf, d_const, min_depth, max_depth, seed, max_iter, conf_threshold,
+                       strategy);
     }
     if (e == hipSuccess) e = mvs_down(ctx, depth, d_depth, npix * sizeof(float));
     if (e == hipSuccess) e = mvs_down(ctx, normal, d_normal, npix * 3 * sizeof(float));
@@ -1337,8 +1377,6 @@ static pvlm_status mvs_run(pvlm_ctx* ctx, const char* what, int rows, int cols, 
     if (e != hipSuccess) { PVLM_SET_ERR(ctx, "%s: %s", what, hipGetErrorString(e)); st = PVLM_ERR_HIP; }
   }
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_quad);
-  pvlm_i_free(ctx, d_img); pvlm_i_free(ctx, d_unit); pvlm_i_free(ctx, d_depth); pvlm_i_free(ctx, d_normal); pvlm_i_free(ctx, d_conf); pvlm_i_free(ctx, d_ndepth); pvlm_i_free(ctx, d_const);
   return st;
 }
 
@@ -1347,13 +1385,14 @@ pvlm_status pvlm_mvs_init_depth_normal(pvlm_ctx* ctx, int rows, int cols, const 
   if (!ctx || rows <= 0 || cols <= 0 || !depth || !normal) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t npix = (size_t)rows * cols;
+  pvlm_dev_scratch tmp(ctx);
   unsigned short* d_l = nullptr; float *d_m = nullptr, *d_d = nullptr, *d_n = nullptr; unsigned char* d_c = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_d, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_n, npix * 3);
-  if (!st && lidar_depth) st = pvlm_i_alloc(ctx, &d_l, npix);
-  if (!st && mask) st = pvlm_i_alloc(ctx, &d_m, npix);
+  pvlm_status st = tmp.alloc(&d_d, npix);
+  if (!st) st = tmp.alloc(&d_n, npix * 3);
+  if (!st && lidar_depth) st = tmp.alloc(&d_l, npix);
+  if (!st && mask) st = tmp.alloc(&d_m, npix);
   const bool want_const = lidar_depth && keep_lidar_constant && depth_constant;
-  if (!st && want_const) st = pvlm_i_alloc(ctx, &d_c, npix);
+  if (!st && want_const) st = tmp.alloc(&d_c, npix);
   if (!st) {
     hipStream_t s = ctx->stream;
     hipError_t e = hipSuccess;
@@ -1371,7 +1410,6 @@ pvlm_status pvlm_mvs_init_depth_normal(pvlm_ctx* ctx, int rows, int cols, const 
     if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_mvs_init_depth_normal: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
   }
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_l); pvlm_i_free(ctx, d_m); pvlm_i_free(ctx, d_d); pvlm_i_free(ctx, d_n); pvlm_i_free(ctx, d_c);
   return st;
 }
 
@@ -1525,12 +1563,13 @@ static pvlm_status depth_to_cloud(pvlm_ctx* ctx, const char* who, int rows, int 
                                   float* normal_out, long long* n_points) {
   const size_t npix = (size_t)rows * cols;
   const unsigned n_blocks = (unsigned)((npix + 255) / 256);
+  pvlm_dev_scratch tmp(ctx);
   unsigned char *d_bgr = nullptr, *d_rgb = nullptr; unsigned* d_cnt = nullptr; float *d_xyz = nullptr, *d_nout = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_bgr, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_cnt, (size_t)n_blocks + 1);
-  if (!st) st = pvlm_i_alloc(ctx, &d_xyz, npix * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_rgb, npix * 3);
-  if (!st && normal_out) st = pvlm_i_alloc(ctx, &d_nout, npix * 3);
+  pvlm_status st = tmp.alloc(&d_bgr, npix * 3);
+  if (!st) st = tmp.alloc(&d_cnt, (size_t)n_blocks + 1);
+  if (!st) st = tmp.alloc(&d_xyz, npix * 3);
+  if (!st) st = tmp.alloc(&d_rgb, npix * 3);
+  if (!st && normal_out) st = tmp.alloc(&d_nout, npix * 3);
   if (!st) {
     hipStream_t s = ctx->stream;
     pvlm_cloud_pose pose;
@@ -1556,7 +1595,6 @@ static pvlm_status depth_to_cloud(pvlm_ctx* ctx, const char* who, int rows, int 
     else { PVLM_SET_ERR(ctx, "%s: %s", who, hipGetErrorString(e)); st = PVLM_ERR_HIP; }
   }
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_bgr); pvlm_i_free(ctx, d_cnt); pvlm_i_free(ctx, d_xyz); pvlm_i_free(ctx, d_rgb); pvlm_i_free(ctx, d_nout);
   return st;
 }
 
@@ -1566,14 +1604,14 @@ pvlm_status pvlm_mvs_depth_to_cloud(pvlm_ctx* ctx, int rows, int cols, const flo
   if ((size_t)rows * cols > 0xfffffff0ull) { PVLM_SET_ERR(ctx, "pvlm_mvs_depth_to_cloud: %d x %d pixels exceed the 32-bit point index", rows, cols); return PVLM_ERR_ARG; }
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t npix = (size_t)rows * cols;
+  pvlm_dev_scratch tmp(ctx);
   float *d_depth = nullptr, *d_normal = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_depth, npix);
-  if (!st && normal_out) st = pvlm_i_alloc(ctx, &d_normal, npix * 3);
+  pvlm_status st = tmp.alloc(&d_depth, npix);
+  if (!st && normal_out) st = tmp.alloc(&d_normal, npix * 3);
   if (!st && mvs_up(ctx, d_depth, depth, npix * sizeof(float)) != hipSuccess) st = PVLM_ERR_HIP;
   if (!st && normal_out && mvs_up(ctx, d_normal, normal, npix * 3 * sizeof(float)) != hipSuccess) st = PVLM_ERR_HIP;
   if (!st) st = depth_to_cloud(ctx, "pvlm_mvs_depth_to_cloud", rows, cols, d_depth, d_normal, nullptr, bgr, T_wc, max_depth, filter_sky, xyz, rgb, normal_out, n_points);
   mvs_sync(ctx);
-  pvlm_i_free(ctx, d_depth); pvlm_i_free(ctx, d_normal);
   return st;
 }
 
@@ -1696,8 +1734,7 @@ static void views_neighbours(const pvlm_mvs_views* v, int n_neighbors, const int
   for (int b = 0; b < n_neighbors; ++b) {
     nb.quad[b] = v->d_quad + v->npix * (size_t)nei[b];
     nb.depth[b] = geometry ? v->d_depth_filter + v->npix * (size_t)nei[b] : nullptr;
-    for (int k = 0; k < 9; ++k) nb.R[b][k] = R_nr[9 * b + k];
-    for (int k = 0; k < 3; ++k) nb.t[b][k] = t_nr[3 * b + k];
+    mvs_set_pose(nb, b, R_nr, t_nr);
   }
 }
 
@@ -1706,52 +1743,16 @@ static pvlm_status views_estimate(pvlm_ctx* ctx, pvlm_mvs_views* v, int ref, int
                                   int half_window, int step, int use_geometry, const unsigned char* depth_constant, float min_depth, float max_depth,
                                   unsigned long long seed, int max_iter, float conf_threshold, int strategy) {
   if (!ctx || !views_ids_ok(v, ref, n_neighbors, nei) || half_window < 1 || step < 1 || (n_neighbors > 0 && (!R_nr || !t_nr))) return PVLM_ERR_ARG;
-  if (pvlm_mvs::num_texels(half_window, step) > 64 * PVLM_MVS_MAXM) { PVLM_SET_ERR(ctx, "NCC window of %d texels exceeds %d", pvlm_mvs::num_texels(half_window, step), 64 * PVLM_MVS_MAXM); return PVLM_ERR_ARG; }
+  if (!mvs_window_ok(ctx, half_window, step)) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  hipStream_t s = ctx->stream;
   pvlm_mvs_neighbours nb;
   views_neighbours(v, n_neighbors, nei, R_nr, t_nr, use_geometry != 0, nb);
   const size_t o = v->npix * (size_t)ref;
   hipError_t e = hipSuccess;
   if (depth_constant) { e = mvs_up(ctx, v->d_const, depth_constant, v->npix); if (e == hipSuccess) e = mvs_sync(ctx); }
-  unsigned char* d_const = depth_constant ? v->d_const : nullptr;
-  if (e == hipSuccess) {
-    if (max_iter < 0) {
-      float* d_wtab = nullptr;
-      const size_t wtab_floats = mvs_lane_bands(v->rows, v->cols, half_window, step).floats;
-      if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;
-      {
-        pvlm_prof_scope prof(ctx, 1);
-        launch_mvs_conf(s, v->rows, v->cols, half_window, step, v->d_gray + o, v->d_unit, nb, v->d_depth + o, v->d_normal + 3 * o, v->d_conf + o, d_wtab);
-      }
-      pvlm_i_free(ctx, d_wtab);
-    } else {
-      if (strategy == 2) {
-        MvsFlow flow;
-        const bool have_flow = mvs_flow_begin(ctx, v->rows, v->cols, half_window, step, &flow);
-        for (int iter = 0; iter < max_iter; ++iter) {
-          pvlm_prof_scope prof(ctx, 1);
-          launch_mvs_propagate_sequential(s, v->rows, v->cols, half_window, step, v->d_gray + o, v->d_unit, nb, v->d_depth + o, v->d_normal + 3 * o, v->d_conf + o,
-                                          d_const, min_depth, max_depth, pvlm_mvs::pass_seed(seed, iter), iter, have_flow ? &flow : nullptr);
-        }
-        mvs_flow_end(ctx, &flow);
-      } else {
-        float* d_wtab = nullptr;
-        const size_t wtab_floats = mvs_lane_bands(v->rows, (v->cols + 1) / 2, half_window, step).floats;
-        if (wtab_floats && pvlm_i_alloc(ctx, &d_wtab, wtab_floats)) d_wtab = nullptr;
-        for (int iter = 0; iter < max_iter; ++iter)
-          for (int offset = 0; offset <= 1; ++offset) {
-            pvlm_prof_scope prof(ctx, 1);
-            launch_mvs_propagate(s, v->rows, v->cols, half_window, step, v->d_gray + o, v->d_unit, nb, v->d_depth + o, v->d_normal + 3 * o, v->d_conf + o, d_const,
-                                 min_depth, max_depth, pvlm_mvs::pass_seed(seed, 2 * iter + offset), offset, d_wtab);
-          }
-        pvlm_i_free(ctx, d_wtab);
-      }
-      hipLaunchKernelGGL(k_mvs_threshold, dim3((unsigned)((v->npix + 255) / 256)), dim3(256), 0, s, (long long)v->npix, d_const, conf_threshold, v->d_depth + o,
-                         v->d_normal + 3 * o, v->d_conf + o);
-    }
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess)
+    e = mvs_estimate(ctx, v->rows, v->cols, half_window, step, v->d_gray + o, v->d_unit, nb, v->d_depth + o, v->d_normal + 3 * o, v->d_conf + o,
+                     depth_constant ? v->d_const : nullptr, min_depth, max_depth, seed, max_iter, conf_threshold, strategy);
   if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_mvs_views_estimate: %s", hipGetErrorString(e)); return PVLM_ERR_HIP; }
   return PVLM_OK;
 }
@@ -1776,7 +1777,7 @@ pvlm_status pvlm_mvs_views_estimate_sequential_batch(pvlm_ctx* ctx, pvlm_mvs_vie
                                                      const unsigned long long* seeds, int max_iter, float conf_threshold) {
   if (!ctx || !v || n_jobs < 0 || max_iter < 0 || half_window < 1 || step < 1 || (n_jobs > 0 && (!refs || !nei_counts || !seeds))) return PVLM_ERR_ARG;
   if (n_jobs == 0) return PVLM_OK;
-  if (pvlm_mvs::num_texels(half_window, step) > 64 * PVLM_MVS_MAXM) { PVLM_SET_ERR(ctx, "NCC window of %d texels exceeds %d", pvlm_mvs::num_texels(half_window, step), 64 * PVLM_MVS_MAXM); return PVLM_ERR_ARG; }
+  if (!mvs_window_ok(ctx, half_window, step)) return PVLM_ERR_ARG;
   std::vector<pvlm_mvs_job> jobs((size_t)n_jobs);
   std::vector<char> seen((size_t)v->n, 0);
   size_t at = 0;
@@ -1790,11 +1791,12 @@ pvlm_status pvlm_mvs_views_estimate_sequential_batch(pvlm_ctx* ctx, pvlm_mvs_vie
   }
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   hipStream_t s = ctx->stream;
+  pvlm_dev_scratch tmp(ctx);
   pvlm_mvs_job* d_jobs = nullptr; unsigned char* d_cb = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_jobs, (size_t)n_jobs);
+  pvlm_status st = tmp.alloc(&d_jobs, (size_t)n_jobs);
   hipError_t e = hipSuccess;
   if (!st && depth_constant) {
-    st = pvlm_i_alloc(ctx, &d_cb, (size_t)n_jobs * v->npix);
+    st = tmp.alloc(&d_cb, (size_t)n_jobs * v->npix);
     for (int j = 0; j < n_jobs && !st; ++j)
       if (depth_constant[j]) {
         if (mvs_up(ctx, d_cb + (size_t)j * v->npix, depth_constant[j], v->npix) != hipSuccess) st = PVLM_ERR_HIP;
@@ -1804,18 +1806,18 @@ pvlm_status pvlm_mvs_views_estimate_sequential_batch(pvlm_ctx* ctx, pvlm_mvs_vie
   if (!st && mvs_up(ctx, d_jobs, jobs.data(), jobs.size() * sizeof(pvlm_mvs_job)) != hipSuccess) st = PVLM_ERR_HIP;
   // Per anti-diagonal: one wave per pixel (k_mvs_propagate_diag_batch); the thread-per-pixel form of a diagonal is a measured variant (above).
   const int n_tex = pvlm_mvs::num_texels(half_window, step);
-  float* d_wtab = nullptr;
   // four threads per pixel from PVLM_MVS_QUAD_MIN pixels per diagonal over all jobs (0 = never); below that, one wave per pixel
   static const long long quad_min = getenv("PVLM_MVS_QUAD_MIN") ? atoll(getenv("PVLM_MVS_QUAD_MIN")) : 32768;
   const int longest_diag = std::min(v->rows, v->cols);
   float* d_qtab = nullptr;
   if (!st && quad_min > 0 && mvs_lane_form(n_tex) && (long long)n_jobs * longest_diag >= quad_min)
-    if (pvlm_i_alloc(ctx, &d_qtab, (size_t)n_tex * (size_t)n_jobs * (size_t)((longest_diag + 63) / 64) * 64)) d_qtab = nullptr;
+    if (tmp.alloc(&d_qtab, (size_t)n_tex * (size_t)n_jobs * (size_t)((longest_diag + 63) / 64) * 64)) d_qtab = nullptr;
 #if PVLM_MEASURED_VARIANTS
+  float* d_wtab = nullptr;
   static const long long lane_min = getenv("PVLM_MVS_LANE_BATCH_MIN") ? atoll(getenv("PVLM_MVS_LANE_BATCH_MIN")) : (1ll << 40);
   const int longest = std::min(v->rows, v->cols);
   if (!st && mvs_lane_form(n_tex) && (long long)n_jobs * longest >= lane_min)
-    if (pvlm_i_alloc(ctx, &d_wtab, (size_t)n_tex * (size_t)n_jobs * (size_t)((longest + 63) / 64) * 64)) d_wtab = nullptr;
+    if (tmp.alloc(&d_wtab, (size_t)n_tex * (size_t)n_jobs * (size_t)((longest + 63) / 64) * 64)) d_wtab = nullptr;
 #endif
   if (!st) {
     const int n_diag = v->rows + v->cols - 1;
@@ -1858,7 +1860,6 @@ pvlm_status pvlm_mvs_views_estimate_sequential_batch(pvlm_ctx* ctx, pvlm_mvs_vie
   }
   // the job table and the depth_constant copies go back to the pool in stream order; the staged uploads must have left the arena
   if (mvs_sync(ctx) != hipSuccess && !st) st = PVLM_ERR_HIP;
-  pvlm_i_free(ctx, d_jobs); pvlm_i_free(ctx, d_cb); pvlm_i_free(ctx, d_wtab); pvlm_i_free(ctx, d_qtab);
   return st;
 }
 
@@ -1868,31 +1869,14 @@ pvlm_status pvlm_mvs_views_filter_refine(pvlm_ctx* ctx, pvlm_mvs_views* v, int r
                                          const unsigned char* depth_constant, float depth_diff_threshold, float min_depth, float max_depth) {
   if (!ctx || !views_ids_ok(v, ref, n_neighbors, nei) || (n_neighbors > 0 && (!R_nr || !t_nr))) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  hipStream_t s = ctx->stream;
   const size_t npix = v->npix, o = npix * (size_t)ref;
-  const unsigned grid = (unsigned)((npix + 255) / 256);
   hipError_t e = hipSuccess;
   if (depth_constant) { e = mvs_up(ctx, v->d_const, depth_constant, npix); if (e == hipSuccess) e = mvs_sync(ctx); }
-  if (e == hipSuccess && n_neighbors > 0) {
-    hipLaunchKernelGGL(k_mvs_fill_u64, dim3((unsigned)((npix * n_neighbors + 255) / 256)), dim3(256), 0, s, (long long)(npix * n_neighbors), ~0ull, v->d_key);
-    e = hipGetLastError();
-  }
-  pvlm_mvs::RefineViews nv;
-  nv.n = n_neighbors;
-  for (int b = 0; b < n_neighbors && e == hipSuccess; ++b) {
-    pvlm_mvs_pose pose;
-    pvlm_mvs::inverse_pose(R_nr + 9 * b, t_nr + 3 * b, pose.R_rn, pose.t_rn);
-    nv.conf[b] = v->d_conf + npix * (size_t)nei[b];
-    for (int k = 0; k < 9; ++k) nv.R[b][k] = R_nr[9 * b + k];
-    for (int k = 0; k < 3; ++k) nv.t[b][k] = t_nr[3 * b + k];
-    hipLaunchKernelGGL(k_mvs_project_conf, dim3(grid), dim3(256), 0, s, v->rows, v->cols, v->d_unit, v->d_depth + npix * (size_t)nei[b], pose, v->d_key + npix * (size_t)b);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mvs_refine, dim3(grid), dim3(256), 0, s, v->rows, v->cols, nv, v->d_key, v->d_unit, v->d_depth + o, v->d_conf + o,
-                       depth_constant ? v->d_const : nullptr, depth_diff_threshold, min_depth, max_depth, v->d_depth_filter + o, v->d_conf_filter + o);
-    e = hipGetLastError();
-  }
+  const float *nd[16], *nc[16];
+  for (int b = 0; b < n_neighbors; ++b) { nd[b] = v->d_depth + npix * (size_t)nei[b]; nc[b] = v->d_conf + npix * (size_t)nei[b]; }
+  if (e == hipSuccess)
+    e = mvs_refine(ctx, v->rows, v->cols, v->d_unit, n_neighbors, nd, nc, R_nr, t_nr, v->d_key, v->d_depth + o, v->d_conf + o, depth_constant ? v->d_const : nullptr,
+                   depth_diff_threshold, min_depth, max_depth, v->d_depth_filter + o, v->d_conf_filter + o);
   if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_mvs_views_filter_refine: %s", hipGetErrorString(e)); return PVLM_ERR_HIP; }
   return PVLM_OK;
 }

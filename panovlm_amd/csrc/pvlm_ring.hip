@@ -505,13 +505,6 @@ struct pvlm_ring_batch {
 
 extern "C" pvlm_status pvlm_ring_batch_destroy(pvlm_ctx* ctx, pvlm_ring_batch* b);
 
-// scratch of one run, back to the pool on every exit path
-struct RingScratch {
-  pvlm_ctx* ctx; std::vector<void*> p;
-  ~RingScratch() { for (void* q : p) pvlm_i_free(ctx, q); }
-  template <typename T> pvlm_status get(T** d, size_t count) { const pvlm_status st = pvlm_i_alloc(ctx, d, count); if (!st) p.push_back(*d); return st; }
-};
-
 static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, const pvlm_raw_scan* raw_scans, int n_rings, int horizon, int segment, long long total,
                             int picks, float max_curvature, float angle_threshold) {
   B->picks = picks ? 1 : 0; B->max_curvature = max_curvature; B->angle_threshold = angle_threshold;
@@ -537,7 +530,7 @@ static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, cons
   }
   if (n_scans == 0 || total == 0) return PVLM_OK;
   // ---- device memory: everything from the context's pool; the scratch goes back at the end of the call
-  RingScratch tmp{ctx, {}};
+  pvlm_dev_scratch tmp(ctx);
   const size_t NP = (size_t)total, NC = (size_t)B->total_cells, NS = (size_t)B->total_slots;
   float4* d_raw = nullptr; PointRec* d_rec = nullptr; int* d_listed = nullptr; int* d_counter = nullptr;
   int2* d_colpos = nullptr; int* d_ring_count = nullptr; int2* d_status = nullptr; PtBlock* d_blocks = nullptr; int* d_source = nullptr; int* d_winner = nullptr;
@@ -547,7 +540,7 @@ static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, cons
   const size_t n_sectors = (size_t)n_scans * n_rings * 6;
   const int query_cap = 1 << 16;
   pvlm_status st = PVLM_OK;
-#define RING_GET(ptr, count) if (!st) st = tmp.get(&ptr, count)
+#define RING_GET(ptr, count) if (!st) st = tmp.alloc(&ptr, count)
 #define RING_KEEP(ptr, count) if (!st) st = pvlm_i_alloc(ctx, &ptr, count)
   RING_KEEP(B->d_scans, (size_t)n_scans); RING_KEEP(B->d_cloud_scan, NP); RING_KEEP(B->d_rc, NP); RING_KEEP(B->d_range_image, NC);
   RING_KEEP(B->d_image_to_point, NC); RING_KEEP(B->d_cloud2, NP); RING_KEEP(B->d_image_to_point2, NC);
