@@ -1,8 +1,8 @@
-// K4 — vote matrix of AssociateLine2Line (lidar_mapping/LidarFeatureAssociate.cpp:457-473) and
-// K7/K8 — equirectangular projection (sensors/Equirectangular.h) and the point x image-line voting
-// loop of CameraLidarLineAssociate::AssociateByAngle (joint_optimization/
-// CameraLidarLineAssociate.cpp:394-426).  Compiled with -ffp-contract=off: every threshold test
-// must take the same branch as a non-FMA x86-64 build of the reference.
+// K4 — vote matrix of AssociateLine2Line (lidar_mapping/LidarFeatureAssociate.cpp:457-473), its row maxima, and K4b, the residual rows of the line-to-line term;
+// K7 — equirectangular projection (sensors/Equirectangular.h) and the LiDAR-seeded depth image; K8 — the point x image-line voting loop of
+// CameraLidarLineAssociate::AssociateByAngle (joint_optimization/CameraLidarLineAssociate.cpp:394-426) and the sparse read-back of its votes.  Kernels first, in
+// that order; then the host side: K7's calls, the vote sequence K4 and K8 share (queue_votes and its tails), K4's calls, K4b's, K8's.  Compiled with
+// -ffp-contract=off: every threshold test must take the same branch as a non-FMA x86-64 build of the reference.
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -26,19 +26,8 @@ __device__ __forceinline__ double point_to_line(double px, double py, double pz,
   return sqrt((qx - px) * (qx - px) + (qy - py) * (qy - py) + (qz - pz) * (qz - pz));
 }
 
-__global__ __launch_bounds__(256) void k_line_votes(int n_pts, const float* __restrict__ xyz, const int* __restrict__ p2s_off,
-                                                    const int* __restrict__ p2s_ids, int n_ref_seg,
-                                                    const double* __restrict__ ref_lines_world, double thr, int* __restrict__ votes) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_pts * n_ref_seg) return;
-  const int i = g / n_ref_seg, s = g - i * n_ref_seg;
-  const double d = point_to_line((double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], ref_lines_world + 6 * s);
-  if (d > thr) return;
-  for (int k = p2s_off[i]; k < p2s_off[i + 1]; ++k) atomicAdd(&votes[(size_t)p2s_ids[k] * n_ref_seg + s], 1);
-}
-
-// Batched form: one launch for every (ref, nei) pair of an outer iteration (the reference calls
-// AssociateLine2Line twice per pair per outer iteration, LidarLineMatch.cpp:68 and Optimization.cpp:379).
+// One launch for every (ref, nei) pair of an outer iteration (the reference calls AssociateLine2Line twice per pair per outer iteration,
+// LidarLineMatch.cpp:68 and Optimization.cpp:379); pvlm_line2line_votes is a batch of one.
 // Work item = (pair, nei corner point, ref segment); the pair is found by bisection on the prefix of work sizes.
 struct pvlm_line_pair_desc {
   const float* xyz; const int* p2s_off; const int* p2s_ids;
@@ -165,11 +154,6 @@ __global__ __launch_bounds__(64) void k_line_rows(const pvlm_match_desc* __restr
 // ---- K7 -----------------------------------------------------------------------------------------
 // FastAtan2 (base/Math.h:15-29).  For T = float the polynomial is evaluated in double (double
 // literals) and rounded to float on assignment, as are M_PI_2 - r and M_PI - r.
-// host <-> device copies through the context's pinned staging arena; downloads reach the caller's buffer at ln_sync
-static inline hipError_t ln_up(pvlm_ctx* ctx, void* d, const void* h, size_t bytes) { return pvlm_i_h2d_q(ctx, d, h, bytes) == PVLM_OK ? hipSuccess : hipErrorUnknown; }
-static inline hipError_t ln_down(pvlm_ctx* ctx, void* h, const void* d, size_t bytes) { return pvlm_i_d2h_q(ctx, h, d, bytes) == PVLM_OK ? hipSuccess : hipErrorUnknown; }
-static inline hipError_t ln_sync(pvlm_ctx* ctx) { return pvlm_i_sync(ctx) == PVLM_OK ? hipSuccess : hipErrorUnknown; }
-
 using pvlm_equirect::fast_atan2;   // csrc/pvlm_equirect_core.h (shared with K30)
 
 template <typename T>
@@ -402,36 +386,8 @@ __device__ __forceinline__ double vangle(const double* a, const double* b) {  //
 }
 
 // line table row: [image_plane(4, normalised) | p4(3) | image_line_scope(1)]
-__global__ __launch_bounds__(256) void k_cam_lidar_votes(int n_pts, const float* __restrict__ xyz_local, const int* __restrict__ p2s_off,
-                                                         const int* __restrict__ p2s_ids, int n_lines, const double* __restrict__ line_tab,
-                                                         const double* __restrict__ T_cl, int n_seg, double angle_thr,
-                                                         int* __restrict__ votes) {
-  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (long long)n_pts * n_lines) return;
-  const int li = (int)(g / n_pts), i = (int)(g - (long long)li * n_pts);
-  if (p2s_off[i] == p2s_off[i + 1]) return;
-  const float x = xyz_local[3 * i], y = xyz_local[3 * i + 1], z = xyz_local[3 * i + 2];
-  const float range = x * x + y * y + z * z;                         // :371-372 (float)
-  if (range > 15 * 15) return;                                       // :413
-  // pcl::transformPointCloud(float cloud, Matrix4d): float(m0*x + m1*y + m2*z + m3) in double
-  double p[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    p[r] = (double)(float)(T_cl[r * 4] * (double)x + T_cl[r * 4 + 1] * (double)y + T_cl[r * 4 + 2] * (double)z + T_cl[r * 4 + 3]);
-  const double* L = line_tab + 8 * li;
-  // ProjectPointToPlane(p, image_plane, normalized=true)   Geometry.hpp:301-316
-  const double dis = fabs(L[0] * p[0] + L[1] * p[1] + L[2] * p[2] + L[3]);
-  double pp[3] = {p[0] - dis * L[0], p[1] - dis * L[1], p[2] - dis * L[2]};
-  if (fabs(L[0] * pp[0] + L[1] * pp[1] + L[2] * pp[2] + L[3]) > 1e-4) {
-    pp[0] = p[0] + dis * L[0]; pp[1] = p[1] + dis * L[1]; pp[2] = p[2] + dis * L[2];
-  }
-  if (vangle(p, pp) >= angle_thr) return;                            // :419
-  if (vangle(L + 4, pp) >= L[7] + angle_thr) return;                 // :422
-  for (int k = p2s_off[i]; k < p2s_off[i + 1]; ++k) atomicAdd(&votes[(size_t)li * n_seg + p2s_ids[k]], 1);
-}
-
-// Batched form of K8: one launch for every (frame, LiDAR) pair of AssociateLineMulti
-// (joint_optimization/CameraLidarOptimizer.cpp:345-377).  Work item = (pair, image line, corner point).
+// One launch for every (frame, LiDAR) pair of AssociateLineMulti (joint_optimization/CameraLidarOptimizer.cpp:345-377); pvlm_cam_lidar_votes is a batch
+// of one.  Work item = (pair, image line, corner point).
 struct pvlm_cam_pair_desc {
   const float* xyz; const int* p2s_off; const int* p2s_ids;
   int n_pts, n_lines, n_seg;
@@ -589,7 +545,7 @@ __global__ __launch_bounds__(256) void k_votes_emit(long long n, const int* __re
   for (int k = 0; k < 16; ++k) if (v[k] != 0) { nz_index[o] = base + k; nz_count[o] = v[k]; ++o; }
 }
 
-// ---- host ---------------------------------------------------------------------------------------
+// ---- host: what the calls below share -------------------------------------------------------------------------------
 namespace {
 template <typename T> struct HostEq {
   int rows, cols;
@@ -614,23 +570,33 @@ inline double h_vangle(const double* a, const double* b) {
 }
 }  // namespace
 
+// status of a HIP call that hands back a hipError_t of its own (hipGetLastError after a launch, hipMemsetAsync); the copies and the
+// synchronisation go through pvlm_i_h2d_q / pvlm_i_d2h_q / pvlm_i_sync, whose status and error text are passed on as they are
+static pvlm_status hip_status(pvlm_ctx* ctx, const char* what, hipError_t e) {
+  if (e == hipSuccess) return PVLM_OK;
+  PVLM_SET_ERR(ctx, "%s: %s", what, hipGetErrorString(e));
+  return PVLM_ERR_HIP;
+}
+// the one synchronisation of a call, on every way out: the staged read-backs reach the caller's buffers, and the call's pvlm_dev_scratch
+// (declared before it) may hand its blocks back
+static pvlm_status finish(pvlm_ctx* ctx, pvlm_status st) {
+  const pvlm_status s2 = pvlm_i_sync(ctx);
+  return st ? st : s2;
+}
+
+// ---- host: K7 and the depth image -----------------------------------------------------------------------------------
 template <typename T, typename K>
 static pvlm_status run_map(pvlm_ctx* ctx, long long n, const T* in, int in_w, T* out, int out_w, K launch) {
   if (n == 0) return PVLM_OK;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  pvlm_dev_scratch tmp(ctx);
   T *d_in = nullptr, *d_out = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_in, (size_t)n * in_w);
-  if (!st) st = pvlm_i_alloc(ctx, &d_out, (size_t)n * out_w);
-  if (!st) {
-    hipError_t e = ln_up(ctx, d_in, in, (size_t)n * in_w * sizeof(T));
-    if (e == hipSuccess) { launch(d_in, d_out); e = hipGetLastError(); }
-    if (e == hipSuccess) e = ln_down(ctx, out, d_out, (size_t)n * out_w * sizeof(T));
-    if (e == hipSuccess) e = ln_sync(ctx);
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "equirect map: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  ln_sync(ctx);
-  pvlm_i_free(ctx, d_in); pvlm_i_free(ctx, d_out);
-  return st;
+  pvlm_status st = tmp.alloc(&d_in, (size_t)n * in_w);
+  if (!st) st = tmp.alloc(&d_out, (size_t)n * out_w);
+  if (!st) st = pvlm_i_h2d_q(ctx, d_in, in, (size_t)n * in_w * sizeof(T));
+  if (!st) { launch(d_in, d_out); st = hip_status(ctx, "equirect map", hipGetLastError()); }
+  if (!st) st = pvlm_i_d2h_q(ctx, out, d_out, (size_t)n * out_w * sizeof(T));
+  return finish(ctx, st);
 }
 
 extern "C" {
@@ -666,30 +632,25 @@ pvlm_status pvlm_project_lidar_depth(pvlm_ctx* ctx, int rows, int cols, int64_t 
   if (!ctx || n < 0 || rows <= 0 || cols <= 0 || !T_cl || !depth || (n > 0 && !xyz)) return PVLM_ERR_ARG;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
   const size_t npix = (size_t)rows * cols;
+  pvlm_dev_scratch tmp(ctx);
   float* d_xyz = nullptr; double* d_T = nullptr; unsigned long long* d_img = nullptr; unsigned short* d_out = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_xyz, (size_t)n * 3);
-  if (!st) st = pvlm_i_alloc(ctx, &d_T, (size_t)16);
-  if (!st) st = pvlm_i_alloc(ctx, &d_img, npix);
-  if (!st) st = pvlm_i_alloc(ctx, &d_out, npix);
-  if (!st) {
-    hipError_t e = hipMemsetAsync(d_img, 0, npix * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess && n > 0) e = ln_up(ctx, d_xyz, xyz, (size_t)n * 3 * sizeof(float));
-    if (e == hipSuccess) e = ln_up(ctx, d_T, T_cl, 16 * sizeof(double));
-    if (e == hipSuccess && n > 0) {
-      hipLaunchKernelGGL(k_depth_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rows, cols, (long long)n, d_xyz, d_T, (int)(size / 2), d_img);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_depth_finish, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ctx->stream, (long long)npix, d_img, d_out);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ln_down(ctx, depth, d_out, npix * sizeof(unsigned short));
-    if (e == hipSuccess) e = ln_sync(ctx);
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "project_lidar_depth: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
+  pvlm_status st = tmp.alloc(&d_xyz, (size_t)n * 3);
+  if (!st) st = tmp.alloc(&d_T, (size_t)16);
+  if (!st) st = tmp.alloc(&d_img, npix);
+  if (!st) st = tmp.alloc(&d_out, npix);
+  if (!st) st = hip_status(ctx, "project_lidar_depth", hipMemsetAsync(d_img, 0, npix * sizeof(unsigned long long), ctx->stream));
+  if (!st && n > 0) st = pvlm_i_h2d_q(ctx, d_xyz, xyz, (size_t)n * 3 * sizeof(float));
+  if (!st) st = pvlm_i_h2d_q(ctx, d_T, T_cl, 16 * sizeof(double));
+  if (!st && n > 0) {
+    hipLaunchKernelGGL(k_depth_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rows, cols, (long long)n, d_xyz, d_T, (int)(size / 2), d_img);
+    st = hip_status(ctx, "project_lidar_depth", hipGetLastError());
   }
-  ln_sync(ctx);
-  pvlm_i_free(ctx, d_xyz); pvlm_i_free(ctx, d_T); pvlm_i_free(ctx, d_img); pvlm_i_free(ctx, d_out);
-  return st;
+  if (!st) {
+    hipLaunchKernelGGL(k_depth_finish, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ctx->stream, (long long)npix, d_img, d_out);
+    st = hip_status(ctx, "project_lidar_depth", hipGetLastError());
+  }
+  if (!st) st = pvlm_i_d2h_q(ctx, depth, d_out, npix * sizeof(unsigned short));
+  return finish(ctx, st);
 }
 
 // device-resident variants (async on the ctx stream, no copies): the panorama-sized maps of the MVS / depth-prior
@@ -724,6 +685,7 @@ pvlm_status pvlm_image_to_cam_f32_dev(pvlm_ctx* ctx, int rows, int cols, int64_t
 
 }  // extern "C"
 
+// ---- host: the vote calls of K4 and K8 ------------------------------------------------------------------------------
 // TransformLines(ref.segment_coeffs, ref.GetPose())   LidarFeatureAssociate.cpp:219-236, :455
 static void world_lines(const pvlm_scan* ref, double* lw) {
   const double* R = ref->R_wl; const double* t = ref->t_wl;
@@ -756,149 +718,169 @@ static void line_table_row(int rows, int cols, const float* l, double* t) {
   t[7] = h_vangle(p1, t + 4);
 }
 
+// The vote sequence of K4 and K8, on device pointers: descriptors, the offsets the chosen kernel finds its pair by and the table (world lines / line-table
+// rows) go up, the vote block is zeroed, launch(...) queues the vote kernel when there is a test to make (off.back() > 0).  Nothing is synchronised and
+// nothing is read back: *d_votes (n_votes counters, owned by `tmp`) is what the three tails below start from.  What the launcher needs besides the tables
+// comes from a scratch of its own that goes back to the pool right behind the launch — the pool is stream-ordered — so that a tail can have the block.
 template <typename D, typename Launch>
-static pvlm_status run_vote_batch(pvlm_ctx* ctx, const std::vector<D>& desc, const std::vector<long long>& work_off, long long total_work,
-                                  const std::vector<double>& tab, long long n_votes, int32_t* votes, Launch launch) {
-  D* d_desc = nullptr; long long* d_work = nullptr; double* d_tab = nullptr; int* d_v = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_desc, desc.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_work, work_off.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_tab, tab.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_v, (size_t)n_votes);
-  if (!st) {
-    st = pvlm_i_h2d_q(ctx, d_desc, desc.data(), desc.size() * sizeof(D));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_work, work_off.data(), work_off.size() * sizeof(long long));
-    if (!st && !tab.empty()) st = pvlm_i_h2d_q(ctx, d_tab, tab.data(), tab.size() * sizeof(double));
-    hipError_t e = st ? hipSuccess : hipMemsetAsync(d_v, 0, (size_t)n_votes * sizeof(int), ctx->stream);
-    if (!st && e == hipSuccess && total_work > 0) { launch(ctx, (int)desc.size(), d_desc, d_work, total_work, d_tab, d_v); e = hipGetLastError(); }
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "batched votes: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-    if (!st && n_votes > 0) st = pvlm_i_d2h_q(ctx, votes, d_v, (size_t)n_votes * sizeof(int));
+static pvlm_status queue_votes(pvlm_ctx* ctx, pvlm_dev_scratch& tmp, const char* what, const std::vector<D>& desc, const std::vector<long long>& off,
+                               const std::vector<double>& tab, long long n_votes, Launch launch, int** d_votes) {
+  D* d_desc = nullptr; long long* d_off = nullptr; double* d_tab = nullptr;
+  pvlm_status st = tmp.alloc(&d_desc, desc.size());
+  if (!st) st = tmp.alloc(&d_off, off.size());
+  if (!st) st = tmp.alloc(&d_tab, tab.size());
+  if (!st) st = tmp.alloc(d_votes, (size_t)n_votes);
+  if (!st) st = pvlm_i_h2d_q(ctx, d_desc, desc.data(), desc.size() * sizeof(D));
+  if (!st) st = pvlm_i_h2d_q(ctx, d_off, off.data(), off.size() * sizeof(long long));
+  if (!st && !tab.empty()) st = pvlm_i_h2d_q(ctx, d_tab, tab.data(), tab.size() * sizeof(double));
+  if (!st) st = hip_status(ctx, what, hipMemsetAsync(*d_votes, 0, (size_t)n_votes * sizeof(int), ctx->stream));
+  if (!st && off.back() > 0) {
+    pvlm_dev_scratch launch_tmp(ctx);
+    st = launch(ctx, launch_tmp, (int)desc.size(), d_desc, d_off, off.back(), d_tab, *d_votes);
+    if (!st) st = hip_status(ctx, what, hipGetLastError());
   }
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  pvlm_i_free(ctx, d_desc); pvlm_i_free(ctx, d_work); pvlm_i_free(ctx, d_tab); pvlm_i_free(ctx, d_v);
   return st;
 }
 
+// dense tail: the whole vote block comes back (both *_votes_batch forms and the single-pair forms, which are a batch of one)
+template <typename D, typename Launch>
+static pvlm_status dense_votes(pvlm_ctx* ctx, const char* what, const std::vector<D>& desc, const std::vector<long long>& off, const std::vector<double>& tab,
+                               long long n_votes, Launch launch, int32_t* votes) {
+  pvlm_dev_scratch tmp(ctx);
+  int* d_v = nullptr;
+  pvlm_status st = queue_votes(ctx, tmp, what, desc, off, tab, n_votes, launch, &d_v);
+  if (!st && n_votes > 0) st = pvlm_i_d2h_q(ctx, votes, d_v, (size_t)n_votes * sizeof(int));
+  return finish(ctx, st);
+}
+
+// K4's pairs: descriptors, the world lines of the reference scans (a scan's lines once per call, not once per pair; left out of a sizing call, which needs
+// none) and the prefixes over the pairs — tests (thread-per-test kernel), corner points (thread-per-point kernel) and rows (k_line_row_best).  A pair without
+// reference segments has no rows and no points (FindAssociations: nr > 0).  false: a null scan.
+struct LinePlan {
+  std::vector<pvlm_line_pair_desc> desc;
+  std::vector<long long> work_off, pt_off, row_off;
+  std::vector<double> lines;
+  long long n_votes = 0;
+};
+static bool line_batch_plan(int n_pairs, const pvlm_scan* const* ref, const pvlm_scan* const* nei, bool with_lines, LinePlan& pl) {
+  pl.desc.assign((size_t)n_pairs, pvlm_line_pair_desc());
+  pl.work_off.assign((size_t)n_pairs + 1, 0); pl.pt_off.assign((size_t)n_pairs + 1, 0); pl.row_off.assign((size_t)n_pairs + 1, 0);
+  std::unordered_map<const pvlm_scan*, long long> line_off_of;
+  long long nv = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (!ref[p] || !nei[p]) return false;
+    pvlm_line_pair_desc& d = pl.desc[p];
+    d.xyz = nei[p]->corner.d_xyz; d.p2s_off = nei[p]->d_p2s_off; d.p2s_ids = nei[p]->d_p2s_ids;
+    d.n_pts = nei[p]->n_segments > 0 ? nei[p]->corner.n : 0; d.n_ref = ref[p]->n_segments;
+    d.vote_off = nv; d.work_off = pl.work_off[p];
+    if (with_lines) {
+      auto it = line_off_of.find(ref[p]);
+      if (it == line_off_of.end()) {
+        it = line_off_of.emplace(ref[p], (long long)pl.lines.size() / 6).first;
+        pl.lines.resize(pl.lines.size() + (size_t)ref[p]->n_segments * 6);
+        world_lines(ref[p], pl.lines.data() + (size_t)it->second * 6);
+      }
+      d.line_off = it->second;
+    }
+    nv += (long long)nei[p]->n_segments * ref[p]->n_segments;
+    pl.work_off[p + 1] = pl.work_off[p] + (long long)d.n_pts * d.n_ref;
+    pl.pt_off[p + 1] = pl.pt_off[p] + (d.n_ref > 0 ? d.n_pts : 0);
+    pl.row_off[p + 1] = pl.row_off[p] + (d.n_ref > 0 ? nei[p]->n_segments : 0);
+  }
+  pl.n_votes = nv;
+  return true;
+}
+// K4's vote kernel.  by_points: a thread per corner point (off = the plan's pt_off), else a thread per test (off = work_off).
+struct LineLaunch {
+  double thr; bool by_points;
+  const std::vector<long long>& off(const LinePlan& pl) const { return by_points ? pl.pt_off : pl.work_off; }
+  pvlm_status operator()(pvlm_ctx* c, pvlm_dev_scratch&, int np, const pvlm_line_pair_desc* dd, const long long* d_off, long long total, const double* dl, int* dv) const {
+    if (by_points) hipLaunchKernelGGL(k_line_votes_points, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, np, dd, d_off, total, dl, sqrt_threshold(thr), dv);
+    else hipLaunchKernelGGL(k_line_votes_batch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, np, dd, d_off, total, dl, thr, dv);
+    return PVLM_OK;
+  }
+};
+
 extern "C" {
+
+// a batch of one through the thread-per-test kernel; the early ways out touch no device
+pvlm_status pvlm_line2line_votes(pvlm_ctx* ctx, const pvlm_scan* ref, const pvlm_scan* nei, float dist_threshold, int32_t* votes) {
+  if (!ctx || !ref || !nei || !votes) return PVLM_ERR_ARG;
+  const int nr = ref->n_segments, nn = nei->n_segments;
+  if (nr == 0 || nn == 0) return PVLM_OK;
+  std::memset(votes, 0, (size_t)nr * nn * sizeof(int32_t));
+  if (nei->corner.n == 0) return PVLM_OK;
+  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  LinePlan pl;
+  line_batch_plan(1, &ref, &nei, true, pl);
+  return dense_votes(ctx, "line votes", pl.desc, pl.work_off, pl.lines, pl.n_votes, LineLaunch{(double)dist_threshold, false}, votes);
+}
 
 pvlm_status pvlm_line2line_votes_batch(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const* ref, pvlm_scan* const* nei, float dist_threshold,
                                        int64_t* vote_offsets, int32_t* votes, int64_t capacity) {
   if (!ctx || n_pairs < 0 || !vote_offsets || (n_pairs > 0 && (!ref || !nei))) return PVLM_ERR_ARG;
-  std::vector<pvlm_line_pair_desc> desc((size_t)n_pairs);
-  std::vector<long long> work_off((size_t)n_pairs + 1, 0);
-  std::vector<double> lines;
-  std::unordered_map<const pvlm_scan*, long long> line_off_of;       // a reference scan's world lines once per call, not once per pair
-  long long nv = 0;
-  for (int p = 0; p < n_pairs; ++p) {
-    if (!ref[p] || !nei[p]) return PVLM_ERR_ARG;
-    pvlm_line_pair_desc& d = desc[p];
-    d.xyz = nei[p]->corner.d_xyz; d.p2s_off = nei[p]->d_p2s_off; d.p2s_ids = nei[p]->d_p2s_ids;
-    d.n_pts = nei[p]->n_segments > 0 ? nei[p]->corner.n : 0; d.n_ref = ref[p]->n_segments;
-    d.vote_off = nv; d.work_off = work_off[p];
-    if (votes) {                                                    // the sizing call needs no lines
-      auto it = line_off_of.find(ref[p]);
-      if (it == line_off_of.end()) {
-        it = line_off_of.emplace(ref[p], (long long)lines.size() / 6).first;
-        lines.resize(lines.size() + (size_t)ref[p]->n_segments * 6);
-        world_lines(ref[p], lines.data() + (size_t)it->second * 6);
-      }
-      d.line_off = it->second;
-    }
-    vote_offsets[p] = nv;
-    nv += (long long)nei[p]->n_segments * ref[p]->n_segments;
-    work_off[p + 1] = work_off[p] + (long long)d.n_pts * d.n_ref;
-  }
+  LinePlan pl;
+  if (!line_batch_plan(n_pairs, ref, nei, votes != nullptr, pl)) return PVLM_ERR_ARG;
+  const long long nv = pl.n_votes;
+  for (int p = 0; p < n_pairs; ++p) vote_offsets[p] = pl.desc[p].vote_off;
   vote_offsets[n_pairs] = nv;
   if (!votes) return PVLM_OK;                       // sizing call
   if (capacity < nv) { PVLM_SET_ERR(ctx, "pvlm_line2line_votes_batch: %lld votes do not fit the capacity %lld", nv, (long long)capacity); return PVLM_ERR_CAPACITY; }
   if (nv == 0) return PVLM_OK;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  const double thr = (double)dist_threshold;
-  return run_vote_batch(ctx, desc, work_off, work_off[n_pairs], lines, nv, votes,
-      [thr](pvlm_ctx* c, int np, const pvlm_line_pair_desc* dd, const long long* dw, long long tot, const double* dl, int* dv) {
-        hipLaunchKernelGGL(k_line_votes_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, np, dd, dw, tot, dl, thr, dv);
-      });
+  return dense_votes(ctx, "batched votes", pl.desc, pl.work_off, pl.lines, nv, LineLaunch{(double)dist_threshold, false}, votes);
 }
 
+// row-best tail: k_line_row_best over the vote block, 8 bytes per neighbour segment come back
 pvlm_status pvlm_line2line_best_batch(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const* ref, pvlm_scan* const* nei, float dist_threshold,
                                       int64_t* row_offsets, int32_t* best_col, int32_t* best_count, int64_t capacity) {
   if (!ctx || n_pairs < 0 || !row_offsets || (n_pairs > 0 && (!ref || !nei)) || ((best_col == nullptr) != (best_count == nullptr))) return PVLM_ERR_ARG;
-  std::vector<pvlm_line_pair_desc> desc((size_t)n_pairs);
-  std::vector<pvlm_row_desc> rdesc((size_t)n_pairs);
-  std::vector<long long> work_off((size_t)n_pairs + 1, 0), row_off((size_t)n_pairs + 1, 0), pt_off((size_t)n_pairs + 1, 0);
-  std::vector<double> lines;
-  std::unordered_map<const pvlm_scan*, long long> line_off_of;
-  long long nv = 0;
   if (best_col) pvlm_i_trace("line2line_best_batch: enter");
-  for (int p = 0; p < n_pairs; ++p) {
-    if (!ref[p] || !nei[p]) return PVLM_ERR_ARG;
-    pvlm_line_pair_desc& d = desc[p];
-    d.xyz = nei[p]->corner.d_xyz; d.p2s_off = nei[p]->d_p2s_off; d.p2s_ids = nei[p]->d_p2s_ids;
-    d.n_pts = nei[p]->n_segments > 0 ? nei[p]->corner.n : 0; d.n_ref = ref[p]->n_segments;
-    d.vote_off = nv; d.work_off = work_off[p];
-    if (best_col) {
-      auto it = line_off_of.find(ref[p]);
-      if (it == line_off_of.end()) {
-        it = line_off_of.emplace(ref[p], (long long)lines.size() / 6).first;
-        lines.resize(lines.size() + (size_t)ref[p]->n_segments * 6);
-        world_lines(ref[p], lines.data() + (size_t)it->second * 6);
-      }
-      d.line_off = it->second;
-    }
-    rdesc[p].vote_off = nv; rdesc[p].n_ref = d.n_ref;
-    row_offsets[p] = row_off[p];
-    row_off[p + 1] = row_off[p] + (d.n_ref > 0 ? nei[p]->n_segments : 0);     // a pair without reference segments has no rows (FindAssociations: nr > 0)
-    nv += (long long)nei[p]->n_segments * ref[p]->n_segments;
-    work_off[p + 1] = work_off[p] + (long long)d.n_pts * d.n_ref;
-    pt_off[p + 1] = pt_off[p] + (d.n_ref > 0 ? d.n_pts : 0);
-  }
-  const long long rows = row_off[n_pairs];
-  row_offsets[n_pairs] = rows;
+  LinePlan pl;
+  if (!line_batch_plan(n_pairs, ref, nei, best_col != nullptr, pl)) return PVLM_ERR_ARG;
+  const long long rows = pl.row_off[n_pairs];
+  for (int p = 0; p <= n_pairs; ++p) row_offsets[p] = pl.row_off[p];
   if (!best_col) return PVLM_OK;                    // sizing call
   if (capacity < rows) { PVLM_SET_ERR(ctx, "pvlm_line2line_best_batch: %lld rows do not fit the capacity %lld", rows, (long long)capacity); return PVLM_ERR_CAPACITY; }
   if (rows == 0) return PVLM_OK;
   if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  std::vector<pvlm_row_desc> rdesc((size_t)n_pairs);
+  for (int p = 0; p < n_pairs; ++p) { rdesc[p].vote_off = pl.desc[p].vote_off; rdesc[p].n_ref = pl.desc[p].n_ref; }
   pvlm_i_trace("line2line_best_batch: tables built on the host");
-  pvlm_line_pair_desc* d_desc = nullptr; pvlm_row_desc* d_rdesc = nullptr; long long *d_work = nullptr, *d_row = nullptr; double* d_lines = nullptr;
-  int *d_v = nullptr, *d_col = nullptr, *d_cnt = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_desc, desc.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_rdesc, rdesc.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_work, work_off.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_row, row_off.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_lines, std::max<size_t>(lines.size(), 1));
-  if (!st) st = pvlm_i_alloc(ctx, &d_v, (size_t)std::max<long long>(nv, 1));
-  if (!st) st = pvlm_i_alloc(ctx, &d_col, (size_t)rows);
-  if (!st) st = pvlm_i_alloc(ctx, &d_cnt, (size_t)rows);
+  // PVLM_LINE_VOTES=tests: the thread-per-test kernel of rounds 2-5 (A/B; the same vote blocks)
+  static const bool per_test = getenv("PVLM_LINE_VOTES") && std::strcmp(getenv("PVLM_LINE_VOTES"), "tests") == 0;
+  const double thr = (double)dist_threshold;
+  const LineLaunch launch{thr, !per_test && thr == thr};            // a NaN threshold: dist > NaN is false for every test — the old kernel says so by itself
+  pvlm_dev_scratch tmp(ctx);
+  pvlm_row_desc* d_rdesc = nullptr; long long* d_row = nullptr; int *d_v = nullptr, *d_col = nullptr, *d_cnt = nullptr;
+  pvlm_status st = tmp.alloc(&d_rdesc, rdesc.size());
+  if (!st) st = tmp.alloc(&d_row, pl.row_off.size());
+  if (!st) st = tmp.alloc(&d_col, (size_t)rows);
+  if (!st) st = tmp.alloc(&d_cnt, (size_t)rows);
+  if (!st) st = pvlm_i_h2d_q(ctx, d_rdesc, rdesc.data(), rdesc.size() * sizeof(pvlm_row_desc));
+  if (!st) st = pvlm_i_h2d_q(ctx, d_row, pl.row_off.data(), pl.row_off.size() * sizeof(long long));
+  if (!st) st = queue_votes(ctx, tmp, "pvlm_line2line_best_batch", pl.desc, launch.off(pl), pl.lines, pl.n_votes, launch, &d_v);
   if (!st) {
-    st = pvlm_i_h2d_q(ctx, d_desc, desc.data(), desc.size() * sizeof(pvlm_line_pair_desc));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_rdesc, rdesc.data(), rdesc.size() * sizeof(pvlm_row_desc));
-    // PVLM_LINE_VOTES=tests: the thread-per-test kernel of rounds 2-5 (A/B; the same vote blocks)
-    static const bool per_test = getenv("PVLM_LINE_VOTES") && std::strcmp(getenv("PVLM_LINE_VOTES"), "tests") == 0;
-    const double thr = (double)dist_threshold;
-    const bool by_points = !per_test && thr == thr;                 // a NaN threshold: dist > NaN is false for every test — the old kernel says so by itself
-    if (!st) st = pvlm_i_h2d_q(ctx, d_work, by_points ? pt_off.data() : work_off.data(), work_off.size() * sizeof(long long));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_row, row_off.data(), row_off.size() * sizeof(long long));
-    if (!st && !lines.empty()) st = pvlm_i_h2d_q(ctx, d_lines, lines.data(), lines.size() * sizeof(double));
-    hipError_t e = st ? hipSuccess : hipMemsetAsync(d_v, 0, (size_t)std::max<long long>(nv, 1) * sizeof(int), ctx->stream);
-    if (!st && e == hipSuccess) {
-      const long long tot = work_off[n_pairs], pts = pt_off[n_pairs];
-      if (by_points) {
-        if (pts > 0)
-          hipLaunchKernelGGL(k_line_votes_points, dim3((unsigned)((pts + 255) / 256)), dim3(256), 0, ctx->stream, n_pairs, d_desc, d_work, pts, d_lines, sqrt_threshold(thr), d_v);
-      } else if (tot > 0)
-        hipLaunchKernelGGL(k_line_votes_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, n_pairs, d_desc, d_work, tot, d_lines, (double)dist_threshold, d_v);
-      hipLaunchKernelGGL(k_line_row_best, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, n_pairs, d_rdesc, d_row, rows, d_v, d_col, d_cnt);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_line2line_best_batch: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-    if (getenv("PVLM_TRACE")) { char msg[128]; snprintf(msg, sizeof msg, "line2line_best_batch: %d pairs, %lld votes, %lld tests, %lld rows: queued", n_pairs, nv, work_off[n_pairs], rows); pvlm_i_trace(msg); }
-    if (!st) st = pvlm_i_d2h_q(ctx, best_col, d_col, (size_t)rows * sizeof(int));
-    if (!st) st = pvlm_i_d2h_q(ctx, best_count, d_cnt, (size_t)rows * sizeof(int));
+    hipLaunchKernelGGL(k_line_row_best, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, n_pairs, d_rdesc, d_row, rows, d_v, d_col, d_cnt);
+    st = hip_status(ctx, "pvlm_line2line_best_batch", hipGetLastError());
   }
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
+  if (getenv("PVLM_TRACE")) { char msg[128]; snprintf(msg, sizeof msg, "line2line_best_batch: %d pairs, %lld votes, %lld tests, %lld rows: queued", n_pairs, pl.n_votes, pl.work_off[n_pairs], rows); pvlm_i_trace(msg); }
+  if (!st) st = pvlm_i_d2h_q(ctx, best_col, d_col, (size_t)rows * sizeof(int));
+  if (!st) st = pvlm_i_d2h_q(ctx, best_count, d_cnt, (size_t)rows * sizeof(int));
+  st = finish(ctx, st);
   pvlm_i_trace("line2line_best_batch: synchronised");
-  pvlm_i_free(ctx, d_desc); pvlm_i_free(ctx, d_rdesc); pvlm_i_free(ctx, d_work); pvlm_i_free(ctx, d_row); pvlm_i_free(ctx, d_lines); pvlm_i_free(ctx, d_v);
-  pvlm_i_free(ctx, d_col); pvlm_i_free(ctx, d_cnt);
   return st;
+}
+
+// ---- host: K4b ----------------------------------------------------------------------------------------------------------
+// 0: match m can be used; 1: its pair index is out of range or not sorted, or the pair has a null scan; 2: a segment index is out of range, or the
+// neighbour scan was uploaded without its segment points
+static int match_fault(int m, int n_pairs, pvlm_scan* const* ref, pvlm_scan* const* nei, const int* match_pair, const int* match_nei_seg, const int* match_ref_seg) {
+  const int p = match_pair[m];
+  if (p < 0 || p >= n_pairs || (m > 0 && p < match_pair[m - 1]) || !ref[p] || !nei[p]) return 1;
+  const int a = match_nei_seg[m], b = match_ref_seg[m];
+  if (a < 0 || a >= nei[p]->n_segments || b < 0 || b >= ref[p]->n_segments || !nei[p]->d_seg_xyz) return 2;
+  return 0;
 }
 
 pvlm_status pvlm_line2line_residuals(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const* ref, pvlm_scan* const* nei, int n_matches, const int* match_pair,
@@ -920,13 +902,11 @@ pvlm_status pvlm_line2line_residuals(pvlm_ctx* ctx, int n_pairs, pvlm_scan* cons
   // cache miss or two per match (359 000 matches per outer iteration at Floor size: 8 ms on one thread): shared out over the host threads.  The bookkeeping that
   // runs ALONG the list (rows, pair table) stays serial below and only adds up the counts.
   {
-    std::atomic<int> bad{-1}, bad_kind{0};
+    std::atomic<int> bad{-1};
     auto fill = [&](int m) {
-      const int p = match_pair[m];
-      if (p < 0 || p >= n_pairs || (m > 0 && p < match_pair[m - 1]) || !ref[p] || !nei[p]) { int none = -1; if (bad.compare_exchange_strong(none, m)) bad_kind = 1; return; }
-      const pvlm_scan* R = ref[p]; const pvlm_scan* N = nei[p];
+      if (match_fault(m, n_pairs, ref, nei, match_pair, match_nei_seg, match_ref_seg)) { int none = -1; bad.compare_exchange_strong(none, m); return; }
+      const pvlm_scan* R = ref[match_pair[m]]; const pvlm_scan* N = nei[match_pair[m]];
       const int a = match_nei_seg[m], b = match_ref_seg[m];
-      if (a < 0 || a >= N->n_segments || b < 0 || b >= R->n_segments || !N->d_seg_xyz) { int none = -1; if (bad.compare_exchange_strong(none, m)) bad_kind = 2; return; }
       pvlm_match_desc& d = md[(size_t)m];
       d.pts = N->d_seg_xyz + 3 * (size_t)N->h_seg_pt_off[(size_t)a];
       d.n_pts = N->h_seg_pt_off[(size_t)a + 1] - N->h_seg_pt_off[(size_t)a];
@@ -943,15 +923,10 @@ pvlm_status pvlm_line2line_residuals(pvlm_ctx* ctx, int n_pairs, pvlm_scan* cons
     auto work = [&]() { for (int lo = next.fetch_add(4096); lo < n_matches; lo = next.fetch_add(4096)) for (int m = lo; m < std::min(n_matches, lo + 4096); ++m) fill(m); };
     pvlm_run_workers(n_threads, work);                       // fill() allocates nothing and throws nothing
     if (bad.load() >= 0) {
-      // the FIRST offending match is reported, as the serial loop did
-      int first = bad.load();
-      for (int m = 0; m < first; ++m) {
-        const int p = match_pair[m];
-        if (p < 0 || p >= n_pairs || (m > 0 && p < match_pair[m - 1]) || !ref[p] || !nei[p]) { first = m; bad_kind = 1; break; }
-        const int a = match_nei_seg[m], b = match_ref_seg[m];
-        if (a < 0 || a >= nei[p]->n_segments || b < 0 || b >= ref[p]->n_segments || !nei[p]->d_seg_xyz) { first = m; bad_kind = 2; break; }
-      }
-      if (bad_kind.load() == 1) PVLM_SET_ERR(ctx, "match %d: pair index out of range or not sorted", first);
+      // the FIRST offending match is reported, as the serial loop did: there is one at bad or before it
+      int first = 0, fault;
+      while ((fault = match_fault(first, n_pairs, ref, nei, match_pair, match_nei_seg, match_ref_seg)) == 0) ++first;
+      if (fault == 1) PVLM_SET_ERR(ctx, "match %d: pair index out of range or not sorted", first);
       else PVLM_SET_ERR(ctx, "match %d: segment out of range, or the neighbour scan was uploaded without seg_points_xyz", first);
       pvlm_i_resset_free(ctx, rs); return PVLM_ERR_ARG;
     }
@@ -994,29 +969,28 @@ pvlm_status pvlm_line2line_residuals(pvlm_ctx* ctx, int n_pairs, pvlm_scan* cons
   if (st) { pvlm_i_resset_free(ctx, rs); return st; }
   rs->col_blocks.push_back(d_block); rs->block_rows.push_back(R_rows);
   pvlm_i_trace("line2line_residuals: column block allocated");
+  pvlm_dev_scratch tmp(ctx);                         // the match and pose tables: read by k_line_rows only
   pvlm_match_desc* d_md = nullptr; pvlm_match_pose* d_po = nullptr;
   if (n_matches > 0) {
-    st = pvlm_i_alloc(ctx, &d_md, md.size());
-    if (!st) st = pvlm_i_alloc(ctx, &d_po, poses.size());
+    st = tmp.alloc(&d_md, md.size());
+    if (!st) st = tmp.alloc(&d_po, poses.size());
     if (!st) {
       pvlm_i_trace("line2line_residuals: tables allocated");
       st = pvlm_i_h2d_q(ctx, d_md, md.data(), md.size() * sizeof(pvlm_match_desc));
       if (!st) st = pvlm_i_h2d_q(ctx, d_po, poses.data(), poses.size() * sizeof(pvlm_match_pose));
       if (getenv("PVLM_TRACE")) { char msg[96]; snprintf(msg, sizeof msg, "line2line_residuals: %d matches, %lld rows: copies queued", n_matches, R_rows); pvlm_i_trace(msg); }
-      hipError_t e = hipSuccess;
-      if (!st) { hipLaunchKernelGGL(k_line_rows, dim3((unsigned)n_matches), dim3(64), 0, ctx->stream, d_md, d_po, d_block, R_rows); e = hipGetLastError(); }
-      if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_line2line_residuals: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
+      if (!st) { hipLaunchKernelGGL(k_line_rows, dim3((unsigned)n_matches), dim3(64), 0, ctx->stream, d_md, d_po, d_block, R_rows); st = hip_status(ctx, "pvlm_line2line_residuals", hipGetLastError()); }
     }
   }
   pvlm_i_trace("line2line_residuals: copies + kernel queued");
   if (!st) st = pvlm_i_resset_finalize(ctx, rs);     // synchronises: the staging vectors above may go
   pvlm_i_trace("line2line_residuals: finalize (sync)");
-  pvlm_i_free(ctx, d_md); pvlm_i_free(ctx, d_po);
-  if (st) { ln_sync(ctx); pvlm_i_resset_free(ctx, rs); return st; }
+  if (st) { pvlm_i_sync(ctx); pvlm_i_resset_free(ctx, rs); return st; }
   *out = rs;
   return PVLM_OK;
 }
 
+// ---- host: K8 -----------------------------------------------------------------------------------------------------------
 // descriptors, work offsets and vote offsets of a batch of (frame, LiDAR) pairs; false: bad arguments
 // Line blocks with the same content get ONE set of table rows: every frame meets its three neighbouring scans with the same image lines
 // (AssociateLineMulti: 1 362 pairs, 454 distinct blocks).  Rewrites desc[p].tab_off to rows of the reduced table and returns the line ranges to build.
@@ -1041,7 +1015,7 @@ static void cam_dedupe_lines(int n_pairs, const int64_t* line_offsets, const flo
     desc[p].tab_off = first_row[(size_t)p];
   }
 }
-static bool cam_batch_plan(int n_pairs, const int64_t* line_offsets, pvlm_scan* const* lidar_local, const double* T_cl, std::vector<pvlm_cam_pair_desc>& desc,
+static bool cam_batch_plan(int n_pairs, const int64_t* line_offsets, const pvlm_scan* const* lidar_local, const double* T_cl, std::vector<pvlm_cam_pair_desc>& desc,
                            std::vector<long long>& work_off, int64_t* vote_offsets, long long* n_votes) {
   desc.assign((size_t)n_pairs, pvlm_cam_pair_desc());
   work_off.assign((size_t)n_pairs + 1, 0);
@@ -1079,28 +1053,49 @@ static void cam_line_tables(int rows, int cols, const float* lines, const std::v
   };
   pvlm_run_workers(n_threads, work);
 }
-// n_rows: rows of the (de-duplicated) line table; total_pts: corner points of all pairs.  PVLM_CAM_VOTES=tests: the thread-per-test kernel of rounds 2-5 (A/B).
+// K8's vote kernel.  Default: a thread per corner point (k_cam_line_cos into a block of the launch's own scratch, then k_cam_lidar_votes_points).  per_test,
+// or PVLM_CAM_VOTES=tests for the batch forms (A/B): the thread-per-test kernel of rounds 2-5, the same vote blocks.  Called with tests to make only, so
+// there are corner points and table rows.
 struct CamLaunch {
-  long long n_rows = 0, total_pts = 0;
-  void operator()(pvlm_ctx* c, int np, const pvlm_cam_pair_desc* dd, const long long* dw, long long tot, const double* dl, int* dv) const {
+  long long n_rows = 0, total_pts = 0;   // rows of the (de-duplicated) line table; corner points of all pairs
+  bool per_test = false;
+  CamLaunch(const std::vector<pvlm_cam_pair_desc>& desc, const std::vector<double>& tab, bool per_test_)
+      : n_rows((long long)(tab.size() / 8)), total_pts(desc.empty() ? 0 : desc.back().pt_off + desc.back().n_pts), per_test(per_test_) {}
+  pvlm_status operator()(pvlm_ctx* c, pvlm_dev_scratch& own, int np, const pvlm_cam_pair_desc* dd, const long long* dw, long long tot, const double* dl, int* dv) const {
     pvlm_prof_scope prof(c, 3);
     const double thr = 3.0 / 180.0 * M_PI;
     const char* mode = getenv("PVLM_CAM_VOTES");
-    double* d_cos = nullptr;
-    if (!(mode && std::strcmp(mode, "tests") == 0) && total_pts > 0 && n_rows > 0 && pvlm_i_alloc(c, &d_cos, (size_t)n_rows) == PVLM_OK) {
-      hipLaunchKernelGGL(k_cam_line_cos, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, n_rows, dl, thr, d_cos);
-      hipLaunchKernelGGL(k_cam_lidar_votes_points, dim3((unsigned)((total_pts + 255) / 256)), dim3(256), 0, c->stream, np, dd, total_pts, dl, (const double*)d_cos, thr, std::cos(thr), dv);
-      pvlm_i_free(c, d_cos);                                           // stream-ordered pool: whoever gets the block next runs behind these launches
-      return;
+    if (per_test || (mode && std::strcmp(mode, "tests") == 0)) {
+      hipLaunchKernelGGL(k_cam_lidar_votes_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, np, dd, dw, tot, dl, thr, dv);
+      return PVLM_OK;
     }
-    hipLaunchKernelGGL(k_cam_lidar_votes_batch, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, np, dd, dw, tot, dl, thr, dv);
+    double* d_cos = nullptr;
+    const pvlm_status st = own.alloc(&d_cos, (size_t)n_rows);
+    if (st) return st;
+    hipLaunchKernelGGL(k_cam_line_cos, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, n_rows, dl, thr, d_cos);
+    hipLaunchKernelGGL(k_cam_lidar_votes_points, dim3((unsigned)((total_pts + 255) / 256)), dim3(256), 0, c->stream, np, dd, total_pts, dl, (const double*)d_cos, thr, std::cos(thr), dv);
+    return PVLM_OK;
   }
 };
-static CamLaunch cam_launcher(const std::vector<pvlm_cam_pair_desc>& desc, const std::vector<double>& tab) {
-  CamLaunch l;
-  l.n_rows = (long long)(tab.size() / 8);
-  l.total_pts = desc.empty() ? 0 : desc.back().pt_off + desc.back().n_pts;
-  return l;
+
+// a batch of one through the thread-per-test kernel (whatever PVLM_CAM_VOTES says); the early ways out touch no device
+pvlm_status pvlm_cam_lidar_votes(pvlm_ctx* ctx, int rows, int cols, const float* lines, int n_lines, const pvlm_scan* lidar,
+                                 const double* T_cl, int32_t* votes) {
+  if (!ctx || !lidar || !T_cl || n_lines < 0 || rows <= 0 || cols <= 0 || (n_lines > 0 && (!lines || !votes))) return PVLM_ERR_ARG;
+  const int ns = lidar->n_segments;
+  if (n_lines == 0 || ns == 0) return PVLM_OK;
+  std::memset(votes, 0, (size_t)n_lines * ns * sizeof(int32_t));
+  if (lidar->corner.n == 0) return PVLM_OK;
+  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  const int64_t line_offsets[2] = {0, n_lines};
+  int64_t vote_offsets[2];
+  std::vector<pvlm_cam_pair_desc> desc;
+  std::vector<long long> work_off;
+  std::vector<double> tab;
+  long long nv = 0;
+  cam_batch_plan(1, line_offsets, &lidar, T_cl, desc, work_off, vote_offsets, &nv);
+  cam_line_tables(rows, cols, lines, {{0, (long long)n_lines}}, tab);
+  return dense_votes(ctx, "cam-lidar votes", desc, work_off, tab, nv, CamLaunch(desc, tab, true), votes);
 }
 
 pvlm_status pvlm_cam_lidar_votes_batch(pvlm_ctx* ctx, int n_pairs, int rows, int cols, const int64_t* line_offsets, const float* lines,
@@ -1120,9 +1115,10 @@ pvlm_status pvlm_cam_lidar_votes_batch(pvlm_ctx* ctx, int n_pairs, int rows, int
   std::vector<std::pair<long long, long long>> build;
   cam_dedupe_lines(n_pairs, line_offsets, lines, desc, build);
   cam_line_tables(rows, cols, lines, build, tab);
-  return run_vote_batch(ctx, desc, work_off, work_off[n_pairs], tab, nv, votes, cam_launcher(desc, tab));
+  return dense_votes(ctx, "batched votes", desc, work_off, tab, nv, CamLaunch(desc, tab, false), votes);
 }
 
+// sparse tail: k_votes_count, the tile offsets on the host, k_votes_emit; (dense index, count) of the non-zero counters come back
 pvlm_status pvlm_cam_lidar_votes_batch_sparse(pvlm_ctx* ctx, int n_pairs, int rows, int cols, const int64_t* line_offsets, const float* lines,
                                               pvlm_scan* const* lidar_local, const double* T_cl, int64_t* vote_offsets, int64_t* nz_index, int32_t* nz_count,
                                               int64_t capacity, int64_t* n_nz) {
@@ -1143,116 +1139,38 @@ pvlm_status pvlm_cam_lidar_votes_batch_sparse(pvlm_ctx* ctx, int n_pairs, int ro
   cam_dedupe_lines(n_pairs, line_offsets, lines, desc, build);
   cam_line_tables(rows, cols, lines, build, tab);
   const long long tiles = (nv + PVLM_NZ_TILE - 1) / PVLM_NZ_TILE;
-  pvlm_cam_pair_desc* d_desc = nullptr; long long* d_work = nullptr; double* d_tab = nullptr; int* d_v = nullptr; int* d_tc = nullptr; long long* d_to = nullptr;
-  long long* d_ni = nullptr; int* d_nc = nullptr;
   std::vector<int> tile_count((size_t)tiles);
   std::vector<long long> tile_off((size_t)tiles);
-  pvlm_status st = pvlm_i_alloc(ctx, &d_desc, desc.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_work, work_off.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_tab, tab.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_v, (size_t)nv);
-  if (!st) st = pvlm_i_alloc(ctx, &d_tc, (size_t)tiles);
-  if (!st) st = pvlm_i_alloc(ctx, &d_to, (size_t)tiles);
   long long total = 0;
+  pvlm_dev_scratch tmp(ctx);
+  int *d_v = nullptr, *d_tc = nullptr, *d_nc = nullptr; long long *d_to = nullptr, *d_ni = nullptr;
+  pvlm_status st = tmp.alloc(&d_tc, (size_t)tiles);
+  if (!st) st = tmp.alloc(&d_to, (size_t)tiles);
+  if (!st) st = queue_votes(ctx, tmp, "batched votes", desc, work_off, tab, nv, CamLaunch(desc, tab, false), &d_v);
   if (!st) {
-    st = pvlm_i_h2d_q(ctx, d_desc, desc.data(), desc.size() * sizeof(pvlm_cam_pair_desc));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_work, work_off.data(), work_off.size() * sizeof(long long));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_tab, tab.data(), tab.size() * sizeof(double));
-    hipError_t e = st ? hipSuccess : hipMemsetAsync(d_v, 0, (size_t)nv * sizeof(int), ctx->stream);
-    if (!st && e == hipSuccess) {
-      cam_launcher(desc, tab)(ctx, n_pairs, d_desc, d_work, work_off[n_pairs], d_tab, d_v);
-      hipLaunchKernelGGL(k_votes_count, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nv, d_v, d_tc);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "batched votes: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-    if (!st) st = pvlm_i_d2h_q(ctx, tile_count.data(), d_tc, (size_t)tiles * sizeof(int));
-    if (!st) st = pvlm_i_sync(ctx);
+    hipLaunchKernelGGL(k_votes_count, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nv, d_v, d_tc);
+    st = hip_status(ctx, "batched votes", hipGetLastError());
+  }
+  if (!st) st = pvlm_i_d2h_q(ctx, tile_count.data(), d_tc, (size_t)tiles * sizeof(int));
+  if (!st) st = pvlm_i_sync(ctx);                   // the host turns the tile counts into offsets (and learns how much comes back)
+  if (!st) {
+    for (long long t = 0; t < tiles; ++t) { tile_off[(size_t)t] = total; total += tile_count[(size_t)t]; }
+    *n_nz = total;
+    if (total > capacity) { PVLM_SET_ERR(ctx, "pvlm_cam_lidar_votes_batch_sparse: %lld non-zero votes do not fit the capacity %lld", total, (long long)capacity); st = PVLM_ERR_CAPACITY; }
+  }
+  if (!st && total > 0) {
+    st = tmp.alloc(&d_ni, (size_t)total);
+    if (!st) st = tmp.alloc(&d_nc, (size_t)total);
+    if (!st) st = pvlm_i_h2d_q(ctx, d_to, tile_off.data(), (size_t)tiles * sizeof(long long));
     if (!st) {
-      for (long long t = 0; t < tiles; ++t) { tile_off[(size_t)t] = total; total += tile_count[(size_t)t]; }
-      *n_nz = total;
-      if (total > capacity) { PVLM_SET_ERR(ctx, "pvlm_cam_lidar_votes_batch_sparse: %lld non-zero votes do not fit the capacity %lld", total, (long long)capacity); st = PVLM_ERR_CAPACITY; }
+      hipLaunchKernelGGL(k_votes_emit, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nv, d_v, d_to, d_ni, d_nc);
+      st = hip_status(ctx, "batched votes", hipGetLastError());
     }
-    if (!st && total > 0) {
-      st = pvlm_i_alloc(ctx, &d_ni, (size_t)total);
-      if (!st) st = pvlm_i_alloc(ctx, &d_nc, (size_t)total);
-      if (!st) st = pvlm_i_h2d_q(ctx, d_to, tile_off.data(), (size_t)tiles * sizeof(long long));
-      if (!st) {
-        hipLaunchKernelGGL(k_votes_emit, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nv, d_v, d_to, d_ni, d_nc);
-        if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "batched votes: emit launch failed"); st = PVLM_ERR_HIP; }
-      }
-      static_assert(sizeof(long long) == sizeof(int64_t), "index width");
-      if (!st) st = pvlm_i_d2h_q(ctx, nz_index, d_ni, (size_t)total * sizeof(int64_t));
-      if (!st) st = pvlm_i_d2h_q(ctx, nz_count, d_nc, (size_t)total * sizeof(int32_t));
-    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "index width");
+    if (!st) st = pvlm_i_d2h_q(ctx, nz_index, d_ni, (size_t)total * sizeof(int64_t));
+    if (!st) st = pvlm_i_d2h_q(ctx, nz_count, d_nc, (size_t)total * sizeof(int32_t));
   }
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  pvlm_i_free(ctx, d_desc); pvlm_i_free(ctx, d_work); pvlm_i_free(ctx, d_tab); pvlm_i_free(ctx, d_v); pvlm_i_free(ctx, d_tc); pvlm_i_free(ctx, d_to);
-  pvlm_i_free(ctx, d_ni); pvlm_i_free(ctx, d_nc);
-  return st;
-}
-
-pvlm_status pvlm_line2line_votes(pvlm_ctx* ctx, const pvlm_scan* ref, const pvlm_scan* nei, float dist_threshold, int32_t* votes) {
-  if (!ctx || !ref || !nei || !votes) return PVLM_ERR_ARG;
-  const int nr = ref->n_segments, nn = nei->n_segments, nc = nei->corner.n;
-  if (nr == 0 || nn == 0) return PVLM_OK;
-  std::memset(votes, 0, (size_t)nr * nn * sizeof(int32_t));
-  if (nc == 0) return PVLM_OK;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  std::vector<double> lw((size_t)nr * 6);
-  world_lines(ref, lw.data());
-  double* d_l = nullptr; int* d_v = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_l, lw.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_v, (size_t)nr * nn);
-  if (!st) {
-    hipError_t e = ln_up(ctx, d_l, lw.data(), lw.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(d_v, 0, (size_t)nr * nn * sizeof(int), ctx->stream);
-    if (e == hipSuccess) {
-      const long long tot = (long long)nc * nr;
-      hipLaunchKernelGGL(k_line_votes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, nc, nei->corner.d_xyz, nei->d_p2s_off,
-                         nei->d_p2s_ids, nr, d_l, (double)dist_threshold, d_v);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ln_down(ctx, votes, d_v, (size_t)nr * nn * sizeof(int));
-    if (e == hipSuccess) e = ln_sync(ctx);
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "line votes: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  ln_sync(ctx);
-  pvlm_i_free(ctx, d_l); pvlm_i_free(ctx, d_v);
-  return st;
-}
-
-pvlm_status pvlm_cam_lidar_votes(pvlm_ctx* ctx, int rows, int cols, const float* lines, int n_lines, const pvlm_scan* lidar,
-                                 const double* T_cl, int32_t* votes) {
-  if (!ctx || !lidar || !T_cl || n_lines < 0 || rows <= 0 || cols <= 0 || (n_lines > 0 && (!lines || !votes))) return PVLM_ERR_ARG;
-  const int ns = lidar->n_segments, np = lidar->corner.n;
-  if (n_lines == 0 || ns == 0) return PVLM_OK;
-  std::memset(votes, 0, (size_t)n_lines * ns * sizeof(int32_t));
-  if (np == 0) return PVLM_OK;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  std::vector<double> tab((size_t)n_lines * 8);
-  for (int li = 0; li < n_lines; ++li) line_table_row(rows, cols, lines + 4 * li, &tab[8 * (size_t)li]);
-  double *d_tab = nullptr, *d_T = nullptr; int* d_v = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_tab, tab.size());
-  if (!st) st = pvlm_i_alloc(ctx, &d_T, 16);
-  if (!st) st = pvlm_i_alloc(ctx, &d_v, (size_t)n_lines * ns);
-  if (!st) {
-    hipError_t e = ln_up(ctx, d_tab, tab.data(), tab.size() * sizeof(double));
-    if (e == hipSuccess) e = ln_up(ctx, d_T, T_cl, 16 * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(d_v, 0, (size_t)n_lines * ns * sizeof(int), ctx->stream);
-    if (e == hipSuccess) {
-      const long long tot = (long long)np * n_lines;
-      const double thr = 3.0 / 180.0 * M_PI;
-      hipLaunchKernelGGL(k_cam_lidar_votes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, np, lidar->corner.d_xyz,
-                         lidar->d_p2s_off, lidar->d_p2s_ids, n_lines, d_tab, d_T, ns, thr, d_v);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ln_down(ctx, votes, d_v, (size_t)n_lines * ns * sizeof(int));
-    if (e == hipSuccess) e = ln_sync(ctx);
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "cam-lidar votes: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  ln_sync(ctx);
-  pvlm_i_free(ctx, d_tab); pvlm_i_free(ctx, d_T); pvlm_i_free(ctx, d_v);
-  return st;
+  return finish(ctx, st);
 }
 
 }  // extern "C"

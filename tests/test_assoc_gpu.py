@@ -185,6 +185,33 @@ def test_line2line_votes(ctx, oracle):
     da.close(); db.close(); de.close()
 
 
+def test_line2line_votes_single_pair_early_outs(ctx):
+    """pvlm_line2line_votes, called through the C ABI with a buffer the test filled itself: a neighbour scan that has segments but no corner point
+    leaves the n_nei_seg x n_ref_seg block zero-filled; a pair one of whose scans has no segment leaves the buffer untouched.  Status OK every time."""
+    import ctypes as C
+    import panovlm_amd as pv
+    rng = np.random.default_rng(23)
+    lines = synth.random_world_lines(rng, 5)
+    full = synth.make_line_scan(rng, 0, np.eye(3), np.zeros(3), lines)
+    no_pts = dict(full); no_pts.update(id=1, corner_xyz=np.zeros((0, 3), np.float32), p2s=[])
+    no_seg = dict(id=2, R_wl=np.eye(3), t_wl=np.zeros(3), corner_xyz=full["corner_xyz"])
+    df, dp, dn = pv.Scan(ctx, full), pv.Scan(ctx, no_pts), pv.Scan(ctx, no_seg)
+    assert (dp.n_segments, dp.n_corner) == (5, 0) and (dn.n_segments, dn.n_corner) == (0, len(full["corner_xyz"]))
+
+    def call(ref, nei):
+        buf = np.full(64, -7, np.int32)
+        st = ctx.lib.pvlm_line2line_votes(ctx._h, ref._h, nei._h, C.c_float(0.3), buf.ctypes.data_as(C.POINTER(C.c_int32)))
+        assert st == 0
+        return buf
+    got = call(df, dp)                                   # segments, no corner points: zero-filled block, the rest of the buffer untouched
+    assert np.all(got[:25] == 0) and np.all(got[25:] == -7)
+    for ref, nei in ((df, dn), (dn, df), (dn, dn), (dp, dn)):   # a scan without segments: nothing is written
+        assert np.all(call(ref, nei) == -7)
+    got = call(df, df)                                   # and the ordinary call writes exactly its block
+    assert np.all(got[25:] == -7) and np.array_equal(got[:25].reshape(5, 5), ctx.line2line_votes(df, df, 0.3)) and got[:25].sum() > 0
+    df.close(); dp.close(); dn.close()
+
+
 def test_batched_scan_upload_equals_scan_by_scan(ctx, oracle):
     """pvlm_scan_upload_batch (one staging copy, one slab, one grid build for all scans) hands out scans that behave exactly
     like individually uploaded ones: k-NN in both target clouds, the association's residual set and the vote matrices are

@@ -127,6 +127,51 @@ def test_cam_lidar_votes(ctx, oracle):
     dscan.close()
 
 
+def test_cam_lidar_votes_single_pair_early_outs_and_kernel_switch(ctx, oracle):
+    """pvlm_cam_lidar_votes through the C ABI with a buffer the test filled itself: a scan that has segments but no corner point leaves the
+    n_lines x n_segments block zero-filled, a scan without segments (or a call without lines) leaves the buffer untouched; status OK every time.
+    The single-pair call runs the thread-per-test kernel whatever PVLM_CAM_VOTES says, so its block is the same with the switch unset and with
+    PVLM_CAM_VOTES=tests (the switch picks the kernel of the batch forms only), and both equal the oracle's."""
+    import ctypes as C
+    import os
+    import panovlm_amd as pv
+    rng = np.random.default_rng(9)
+    rows, cols = 2880, 5760
+    scan = synth.make_line_scan(rng, 0, np.eye(3), np.zeros(3), synth.random_world_lines(rng, 6, extent=3.0), pts_per_line=(20, 60), extra_pts=20)
+    local = dict(scan); local["corner_xyz"] = scan["corner_local"]
+    no_pts = dict(local); no_pts.update(id=1, corner_xyz=np.zeros((0, 3), np.float32), p2s=[])
+    no_seg = dict(id=2, R_wl=np.eye(3), t_wl=np.zeros(3), corner_xyz=scan["corner_local"])
+    T = np.eye(4); T[:3, :3] = synth.rodrigues(np.deg2rad([1.0, -1.5, 0.5])); T[:3, 3] = [0.02, -0.03, 0.01]
+    ends_cam = scan["end_points"].reshape(-1, 3) @ T[:3, :3].T + T[:3, 3]
+    lines = oracle.cam_to_image(rows, cols, ends_cam).reshape(-1, 4).astype(np.float32)
+    dl, dp, dn = pv.Scan(ctx, local), pv.Scan(ctx, no_pts), pv.Scan(ctx, no_seg)
+    assert (dp.n_segments, dp.n_corner) == (6, 0) and dn.n_segments == 0 and dn.n_corner > 0
+    Tf = np.ascontiguousarray(T, np.float64).reshape(16)
+
+    def call(l, dscan):
+        buf = np.full(64, -7, np.int32)
+        l = np.ascontiguousarray(l, np.float32).reshape(-1, 4)
+        st = ctx.lib.pvlm_cam_lidar_votes(ctx._h, C.c_int(rows), C.c_int(cols), l.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(len(l)), dscan._h,
+                                          Tf.ctypes.data_as(C.POINTER(C.c_double)), buf.ctypes.data_as(C.POINTER(C.c_int32)))
+        assert st == 0
+        return buf
+    got = call(lines, dp)                                # segments, no corner points: zero-filled block, the rest untouched
+    assert np.all(got[:36] == 0) and np.all(got[36:] == -7)
+    assert np.all(call(lines, dn) == -7)                 # no segments: nothing is written
+    assert np.all(call(lines[:0], dl) == -7)             # no lines: nothing is written
+    unset = call(lines, dl)
+    assert "PVLM_CAM_VOTES" not in os.environ
+    os.environ["PVLM_CAM_VOTES"] = "tests"
+    try:
+        tests = call(lines, dl)
+    finally:
+        del os.environ["PVLM_CAM_VOTES"]
+    assert np.array_equal(unset, tests) and np.all(unset[36:] == -7)
+    o = oracle.assoc_by_angle(rows, cols, lines, local, T, multiple=True)
+    assert np.array_equal(unset[:36].reshape(6, 6), o["votes"]) and o["votes"].sum() > 50
+    dl.close(); dp.close(); dn.close()
+
+
 @pytest.mark.parametrize("size", [3, 2, 0])
 def test_project_lidar_depth_matches_oracle(ctx, oracle, size):
     """ProjectLidar2PanoramaDepth (util/Visualization.h:407-441): bit-exact uint16 image, including the
