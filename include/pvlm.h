@@ -301,6 +301,35 @@ pvlm_status pvlm_filter_tracks(pvlm_ctx* ctx, pvlm_filter_mode mode, int rows, i
                                const float* keypoints_f32, const double* points, int n_frames, const double* T_cw_3x4, double threshold,
                                unsigned char* keep);
 
+/* ---- K32: structure from tracks (TriangulateTracks / FilterTracksToFar, sfm/Structure.cpp:8-119) ---- *
+ * One lane per track; the caller compacts, as with pvlm_filter_tracks.  Same input convention: track t owns the observations
+ * [track_offsets[t], track_offsets[t+1]) in their order, frame_ids[i] indexes the frame tables, T_cw = n_frames x 12 row-major [R | t].
+ * pvlm_triangulate_tracks: TriangulateNView (sfm/Triangulate.cpp:198-226) per track.  Exactly one of keypoints_f32 (n_obs x 2 pixels;
+ *   the bearing is eq.ImageToCam(kp.pt) through the cv::Point2i overload, taken on the device as in PVLM_FILTER_ANGLE; rows, cols > 0)
+ *   and bearings_f32 (n_obs x 3, bearings of any origin, e.g. sfm/SfM.cpp:1503) is non-null; anything else is PVLM_ERR_ARG.
+ *   frame_valid: n_frames bytes or NULL (every frame valid).  Two observations: Triangulate2View (the midpoint in camera 1, moved to the
+ *   world), more: TriangulateNViewAlgebraic (the eigenvector of the smallest eigenvalue of AtA, hnormalized), fewer: +inf.  All in double,
+ *   without FMA contraction; nothing is special-cased, IEEE runs its course on degenerate input.
+ *   status[t]: 0 = triangulated; 1 = dropped by upstream's rule "any coordinate is +-inf" (:56-57), the point is written as computed;
+ *              2 = an observation lies in a frame with frame_valid == 0, the point is NaN.
+ * Traps and divergences, next to K31's:
+ *   - a NaN point is NOT dropped (status 0): isinf(NaN) is false upstream, e.g. two parallel rays from one centre.  Kept.
+ *   - status 2 is the one deliberate divergence: upstream inverts the singular pose of an invalid frame with Eigen's general inverse and
+ *     hands the result to the eigen-solver; what comes out depends on those two routines on inf / NaN input and cannot be pinned here.
+ *   - the N-view eigenvector comes from a cyclic Jacobi, upstream's from Eigen's tridiagonal QL: parity to rounding, not in bits.
+ *   - the output order of the host mirror's TriangulateTracks is ascending track id, what one thread gives upstream; upstream's own
+ *     order is whatever its OpenMP critical section gives.
+ * pvlm_filter_tracks_far: FilterTracksToFar.  points: n_tracks x 3; t_wc: n_frames x 3 camera centres.  Per track, over its distinct
+ *   frames with a valid pose in ascending id: baseline = the largest centre distance (FurthestPoints, base/Geometry.hpp:594-617; 0 with
+ *   fewer than two centres), average = the mean of |centre - point| (NaN without centres).  keep[t] = 0 when
+ *   threshold * baseline < average; NaN compares false, so such a track is kept. */
+pvlm_status pvlm_triangulate_tracks(pvlm_ctx* ctx, int rows, int cols, int n_tracks, const int64_t* track_offsets, const int* frame_ids,
+                                    const float* keypoints_f32 /* n_obs x 2, or NULL */, const float* bearings_f32 /* n_obs x 3, or NULL */,
+                                    int n_frames, const double* T_cw_3x4, const unsigned char* frame_valid, double* points /* n_tracks x 3 */,
+                                    unsigned char* status /* n_tracks */);
+pvlm_status pvlm_filter_tracks_far(pvlm_ctx* ctx, int n_tracks, const int64_t* track_offsets, const int* frame_ids, const double* points, int n_frames,
+                                   const double* t_wc /* n_frames x 3 */, const unsigned char* frame_valid, double threshold, unsigned char* keep);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "pvlm_fuse_scans", "pvlm_fuse_scans_dev",
     "pvlm_colorize_scans", "pvlm_colorize_scans_dev", "pvlm_colorize_debug_hsv",
     "pvlm_ba_create_kind", "pvlm_ba_info", "pvlm_filter_tracks",
+    "pvlm_triangulate_tracks", "pvlm_filter_tracks_far",
 ]
 
 
@@ -1270,6 +1271,36 @@ def filter_tracks(ctx, mode, rows, cols, point_offsets, frame_ids, keypoints, po
     ctx._check(ctx.lib.pvlm_filter_tracks(ctx._h, C.c_int(FILTER_MODES[mode]), C.c_int(rows), C.c_int(cols), C.c_int(n), _p(off, C.c_int64), _p(fid, C.c_int),
                                           _p(kp, C.c_float), _p(X, C.c_double), C.c_int(T.reshape(-1, 12).shape[0]), _p(T, C.c_double), C.c_double(threshold),
                                           _p(keep, C.c_ubyte)), "pvlm_filter_tracks")
+    return keep
+
+
+def triangulate_tracks(ctx, rows, cols, track_offsets, frame_ids, T_cw, frame_valid=None, keypoints=None, bearings=None):
+    """pvlm_triangulate_tracks (K32): TriangulateNView per track.  track_offsets: tracks + 1 (int64); frame_ids: one per observation; T_cw: frames x 3 x 4;
+    frame_valid: frames (uint8) or None; exactly one of keypoints (float32 n x 2 pixels) and bearings (float32 n x 3).  Returns (points tracks x 3 float64,
+    status uint8: 0 triangulated, 1 dropped by the inf rule, 2 an observation in an invalid frame)."""
+    off = _i64(track_offsets); fid = _i32(frame_ids); T = _f64(T_cw)
+    kp = None if keypoints is None else _f32(keypoints)
+    br = None if bearings is None else _f32(bearings)
+    fv = None if frame_valid is None else np.ascontiguousarray(frame_valid, np.uint8)
+    n = len(off) - 1
+    X = np.zeros((max(n, 0), 3), np.float64); status = np.zeros(max(n, 0), np.uint8)
+    ctx._check(ctx.lib.pvlm_triangulate_tracks(ctx._h, C.c_int(rows), C.c_int(cols), C.c_int(n), _p(off, C.c_int64), _p(fid, C.c_int),
+                                               None if kp is None else _p(kp, C.c_float), None if br is None else _p(br, C.c_float),
+                                               C.c_int(T.reshape(-1, 12).shape[0]), _p(T, C.c_double), None if fv is None else _p(fv, C.c_ubyte),
+                                               _p(X, C.c_double), _p(status, C.c_ubyte)), "pvlm_triangulate_tracks")
+    return X, status
+
+
+def filter_tracks_far(ctx, track_offsets, frame_ids, points, t_wc, threshold, frame_valid=None):
+    """pvlm_filter_tracks_far (K32): FilterTracksToFar as a keep mask.  points: tracks x 3; t_wc: frames x 3 camera centres; frame_valid: frames (uint8) or
+    None.  Returns a uint8 mask, 1 = the track survives (threshold * baseline >= average distance, or the comparison involves a NaN)."""
+    off = _i64(track_offsets); fid = _i32(frame_ids); X = _f64(points); t = _f64(t_wc)
+    fv = None if frame_valid is None else np.ascontiguousarray(frame_valid, np.uint8)
+    n = len(off) - 1
+    keep = np.zeros(max(n, 0), np.uint8)
+    ctx._check(ctx.lib.pvlm_filter_tracks_far(ctx._h, C.c_int(n), _p(off, C.c_int64), _p(fid, C.c_int), _p(X, C.c_double), C.c_int(t.reshape(-1, 3).shape[0]),
+                                              _p(t, C.c_double), None if fv is None else _p(fv, C.c_ubyte), C.c_double(threshold), _p(keep, C.c_ubyte)),
+               "pvlm_filter_tracks_far")
     return keep
 
 

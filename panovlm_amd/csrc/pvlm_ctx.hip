@@ -416,6 +416,7 @@ pvlm_status pvlm_preload(pvlm_ctx* ctx) {
   pvlm_i_preload_mvs(ctx->stream);
   pvlm_i_preload_ring(ctx->stream);
   pvlm_i_preload_sfm_filter(ctx->stream);
+  pvlm_i_preload_triangulate(ctx->stream);
   pvlm_i_preload_undistort(ctx->stream);
   PVLM_HIP(ctx, hipGetLastError());
   PVLM_HIP(ctx, hipStreamSynchronize(ctx->stream));

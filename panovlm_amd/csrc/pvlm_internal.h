@@ -319,6 +319,7 @@ void pvlm_i_preload_texture(hipStream_t s);
 void pvlm_i_preload_mvs(hipStream_t s);
 void pvlm_i_preload_ring(hipStream_t s);
 void pvlm_i_preload_sfm_filter(hipStream_t s);
+void pvlm_i_preload_triangulate(hipStream_t s);
 void pvlm_i_preload_undistort(hipStream_t s);
 // builds work list + scratch for a resset whose segment table is final (h_* mirrors filled)
 pvlm_status pvlm_i_resset_finalize(pvlm_ctx* ctx, pvlm_resset* rs);

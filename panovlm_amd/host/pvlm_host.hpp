@@ -599,6 +599,30 @@ struct Frame {
   Matrix4d GetPose() const { return {R_wc[0], R_wc[1], R_wc[2], t_wc[0], R_wc[3], R_wc[4], R_wc[5], t_wc[1], R_wc[6], R_wc[7], R_wc[8], t_wc[2], 0, 0, 0, 1}; }
 };
 
+// ---- K32: structure from the image matches (sfm/Structure.cpp:8-119, sfm/Triangulate.cpp, util/Tracks.cpp) ---------------------------------
+// base/Serialization.h's MatchPair as far as TriangulateTracks reads it: the two images and the (queryIdx, trainIdx) of every cv::DMatch,
+// queryIdx a keypoint of image_pair.first, trainIdx one of image_pair.second
+struct MatchPair {
+  std::pair<size_t, size_t> image_pair;
+  std::vector<std::pair<int, int>> matches;
+};
+// TriangulateTracks (sfm/Structure.cpp:8-69): TrackBuilder.Build / Filter(3) / ExportTracks (util/Tracks.cpp, on the union-find the line tracks
+// use), every track with an id < GetMaxID() (strict, as upstream writes it) triangulated in ONE pvlm_triangulate_tracks call (K32), the tracks
+// with an infinite coordinate dropped (a NaN point stays: upstream's trap), then FilterTracksAngleResidual(frames, structure, 25).  The output is
+// in ascending track id: what one thread gives upstream, whose own order is whatever its OpenMP critical section gives.  A track with an
+// observation in a frame without a valid pose is dropped (status 2 of pvlm_triangulate_tracks, the deliberate divergence documented in pvlm.h).
+std::vector<PointTrack> TriangulateTracks(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs);
+// FilterTracksToFar (:87-119) on the GPU (pvlm_filter_tracks_far): a track goes when the mean distance of its point to its valid frames' centres
+// exceeds threshold x the largest distance between two of those centres.  The surviving tracks keep their order; returns the number removed.
+size_t FilterTracksToFar(const std::vector<Frame>& frames, std::vector<PointTrack>& tracks, const double& threshold);
+// Triangulate2View (sfm/Triangulate.cpp:8-28) and TriangulateNView (:198-226) on host vectors: csrc/pvlm_triangulate_core.h compiled for the
+// host, for callers with a handful of points.  Bearings are cv::Point3f; fewer than two views give +inf on all coordinates.
+Vector3d Triangulate2View(const Matrix3d& R_21, const Vector3d& t_21, const std::array<float, 3>& p1, const std::array<float, 3>& p2);
+Vector3d TriangulateNView(const std::vector<Matrix3d>& R_cw_list, const std::vector<Vector3d>& t_cw_list, const std::vector<std::array<float, 3>>& points);
+// MVS::EstimateStructure (mvs/MVS.cpp:44-59): structure = TriangulateTracks(frames, image_pairs), true when it is not empty.  No SetImageScale and
+// no points.bin export, for the reasons RefineCameraPose gives; the match pairs are the caller's (upstream: ReadMatchPair).
+bool EstimateStructure(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<PointTrack>& structure);
+
 // ---- mvs/MVS.h:45-57, mvs/MVS.cpp:334-382 — who the neighbours of a reference view are (the `nei` / R_nr / t_nr arguments of
 // pvlm_mvs_*).  SelectNeighborKNN: the 3 x neighbor_size nearest camera centres (float32, as pcl::KdTreeFLANN returns them),
 // the first hit skipped as "self", candidates closer than the squared distance threshold skipped, the first neighbor_size
@@ -687,6 +711,9 @@ class CameraLidarOptimizer {
   bool JointOptimize();
   void SetStructure(const std::vector<PointTrack>& s) { structure = s; }
   const std::vector<PointTrack>& GetStructure() const { return structure; }
+  // CameraLidarOptimizer.cpp:720-729: structure = TriangulateTracks(frames, image_pairs), then FilterTracksToFar(frames, structure, 8); false when
+  // that filter removed NOTHING (upstream's `if(!FilterTracksToFar(...)) return false`, kept as written), the structure stays filled either way
+  bool EstimateStructure(const std::vector<MatchPair>& image_pairs);
   std::vector<std::vector<int>> NeighborEachFrame(const int neighbor_size, const bool temporal) const;   // :551-610
   LinePairs AssociateLineMulti(const int neighbor_size, const bool temporal = true);                      // :331-384
   int Optimize(const LinePairs& line_pairs, std::vector<PointTrack>& structure, const bool refine_camera_rotation, const bool refine_camera_trans,

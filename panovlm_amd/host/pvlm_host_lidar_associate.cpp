@@ -1,6 +1,7 @@
 // pvlm_host_lidar_associate.cpp — part of the C++ host mirror (pvlm_host.hpp): lidar_mapping/LidarFeatureAssociate.cpp (FindNeighbors, AssociatePoint2Plane, AssociateLine2Line, FindAssociations, the k-NN variants) and the line tracks: lidar_mapping/LidarLineMatch.cpp:36-91, util/Tracks.cpp:58-196.
 // Host logic only; every residual, Jacobian, distance and vote is produced by libpvlm.so on the GPU.
 #include "pvlm_host_internal.hpp"
+#include "pvlm_host_tracks.hpp"
 
 namespace pvlm {
 
@@ -456,19 +457,7 @@ std::vector<std::vector<Line2Line>> AssociateLine2LineBatch(const std::vector<st
 // ================================================================================================
 // tracks — util/Tracks.h:34-107 (UnionFind), util/Tracks.cpp:58-196 (TrackBuilder, allow_multiple_map)
 // ================================================================================================
-namespace {
-struct UnionFind {
-  std::vector<unsigned> parent, rank, size;
-  void Init(unsigned n) { size.assign(n, 1); parent.resize(n); std::iota(parent.begin(), parent.end(), 0u); rank.assign(n, 0); }
-  unsigned Find(unsigned i) { if (parent[i] != i) parent[i] = Find(parent[i]); return parent[i]; }
-  void Union(unsigned i, unsigned j) {
-    i = Find(i); j = Find(j);
-    if (i == j) return;
-    if (rank[i] < rank[j]) { parent[i] = j; size[j] += size[i]; }
-    else { parent[j] = i; size[i] += size[j]; if (rank[i] == rank[j]) ++rank[i]; }
-  }
-};
-}  // namespace
+// UnionFind: pvlm_host_tracks.hpp, shared with the feature tracks of TriangulateTracks
 
 bool LidarLineMatch::GenerateTracks() {
   StageTimer stage_timer_("line tracks (associate + union-find)");

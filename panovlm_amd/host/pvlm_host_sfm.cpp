@@ -1,9 +1,13 @@
 // pvlm_host_sfm.cpp — part of the C++ host mirror (pvlm_host.hpp): the global bundle adjustment of the SfM result and what calls it —
 // SfMGlobalBA (util/Optimization.cpp:10-82), the track filters FilterTracksPixelResidual / FilterTracksAngleResidual (sfm/Structure.cpp:121-193),
 // SfM::GlobalBundleAdjustment (sfm/SfM.cpp:1362-1383), MVS::RefineCameraPose (mvs/MVS.cpp:383-428) and
-// CameraLidarOptimizer::GlobalBundleAdjustment (joint_optimization/CameraLidarOptimizer.cpp:732-740).
-// Host logic only; the reprojection blocks are solved and the tracks are tested by libpvlm.so on the GPU (K9 / K31).
+// CameraLidarOptimizer::GlobalBundleAdjustment (joint_optimization/CameraLidarOptimizer.cpp:732-740); and what builds the structure they refine —
+// TriangulateTracks / FilterTracksToFar (sfm/Structure.cpp:8-119), CameraLidarOptimizer::EstimateStructure (:720-729), MVS::EstimateStructure
+// (mvs/MVS.cpp:44-59).
+// Host logic only; the reprojection blocks are solved and the tracks are triangulated and tested by libpvlm.so on the GPU (K9 / K31 / K32).
 #include "pvlm_host_internal.hpp"
+#include "pvlm_host_structure.hpp"
+#include "../csrc/pvlm_triangulate_core.h"
 
 namespace pvlm {
 
@@ -26,37 +30,29 @@ Matrix4d Mul4(const Matrix4d& A, const Matrix4d& B) {
   return C;
 }
 
+// the per-track device calls behind the seam of pvlm_host_structure.hpp
+const structure_detail::StructureKernels& DeviceKernels() {
+  static const structure_detail::StructureKernels k = {
+      [](int rows, int cols, int n_tracks, const int64_t* off, const int* fid, const float* kp, int n_frames, const double* T_cw, const unsigned char* frame_valid,
+         double* points, unsigned char* status) {
+        Engine& e = Engine::Default();
+        e.Check(pvlm_triangulate_tracks(e.ctx(), rows, cols, n_tracks, off, fid, kp, nullptr, n_frames, T_cw, frame_valid, points, status), "pvlm_triangulate_tracks");
+      },
+      [](pvlm_filter_mode mode, int rows, int cols, int n_tracks, const int64_t* off, const int* fid, const float* kp, const double* points, int n_frames,
+         const double* T_cw, double threshold, unsigned char* keep) {
+        Engine& e = Engine::Default();
+        e.Check(pvlm_filter_tracks(e.ctx(), mode, rows, cols, n_tracks, off, fid, kp, points, n_frames, T_cw, threshold, keep), "pvlm_filter_tracks");
+      },
+      [](int n_tracks, const int64_t* off, const int* fid, const double* points, int n_frames, const double* t_wc, const unsigned char* frame_valid, double threshold,
+         unsigned char* keep) {
+        Engine& e = Engine::Default();
+        e.Check(pvlm_filter_tracks_far(e.ctx(), n_tracks, off, fid, points, n_frames, t_wc, frame_valid, threshold, keep), "pvlm_filter_tracks_far");
+      }};
+  return k;
+}
+
 size_t FilterTracks(const std::vector<Frame>& frames, std::vector<PointTrack>& tracks, pvlm_filter_mode mode, double threshold) {
-  if (tracks.empty() || frames.empty()) return 0;
-  std::vector<double> T((size_t)frames.size() * 12, 0.0);         // Matrix4d::Zero() for frames without a valid pose
-  for (size_t f = 0; f < frames.size(); ++f) {
-    if (!frames[f].IsPoseValid()) continue;
-    Matrix3d Ri; Vector3d ti;
-    RigidInverse(frames[f].R_wc, frames[f].t_wc, &Ri, &ti);
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T[12 * f + 4 * r + c] = Ri[3 * r + c]; T[12 * f + 4 * r + 3] = ti[r]; }
-  }
-  std::vector<int64_t> off(tracks.size() + 1, 0);
-  std::vector<int> fid; std::vector<float> kp; std::vector<double> X(tracks.size() * 3);
-  for (size_t i = 0; i < tracks.size(); ++i) {
-    for (const auto& pr : tracks[i].feature_pairs) {            // std::set order, as upstream iterates
-      fid.push_back((int)pr.first);
-      const std::array<float, 2>& k = frames[pr.first].keypoints[pr.second];
-      kp.push_back(k[0]); kp.push_back(k[1]);
-    }
-    off[i + 1] = (int64_t)fid.size();
-    for (int k = 0; k < 3; ++k) X[3 * i + k] = tracks[i].point_3d[k];
-  }
-  std::vector<unsigned char> keep(tracks.size(), 1);
-  Engine& e = Engine::Default();
-  // Equirectangular eq(frames[0].GetImageRows(), frames[0].GetImageCols())
-  e.Check(pvlm_filter_tracks(e.ctx(), mode, frames[0].GetImageRows(), frames[0].GetImageCols(), (int)tracks.size(), off.data(), fid.data(), kp.data(), X.data(),
-                             (int)frames.size(), T.data(), threshold, keep.data()), "pvlm_filter_tracks");
-  std::vector<PointTrack> valid;
-  valid.reserve(tracks.size());
-  for (size_t i = 0; i < tracks.size(); ++i) if (keep[i]) valid.push_back(std::move(tracks[i]));
-  const size_t removed = tracks.size() - valid.size();
-  valid.swap(tracks);
-  return removed;
+  return structure_detail::FilterTracksWith(DeviceKernels(), frames, tracks, mode, threshold);
 }
 
 }  // namespace
@@ -144,6 +140,46 @@ bool RefineCameraPose(std::vector<Frame>& frames, std::vector<Velodyne>& lidars,
 
 bool CameraLidarOptimizer::GlobalBundleAdjustment(std::vector<PointTrack>& structure, bool refine_structure, bool refine_rotation, bool refine_translation) {
   return SfMGlobalBA(frames, structure, ANGLE_RESIDUAL_1, config.num_threads, refine_structure, refine_rotation, refine_translation);
+}
+
+// ---- K32 --------------------------------------------------------------------------------------------------------------------------------
+std::vector<PointTrack> TriangulateTracks(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs) {
+  StageTimer stage_timer_("TriangulateTracks");
+  return structure_detail::TriangulateTracksWith(DeviceKernels(), frames, image_pairs);
+}
+
+size_t FilterTracksToFar(const std::vector<Frame>& frames, std::vector<PointTrack>& tracks, const double& threshold) {
+  return structure_detail::FilterTracksToFarWith(DeviceKernels(), frames, tracks, threshold);
+}
+
+Vector3d Triangulate2View(const Matrix3d& R_21, const Vector3d& t_21, const std::array<float, 3>& p1, const std::array<float, 3>& p2) {
+  Vector3d P;
+  pvlm_triangulate::triangulate_2view(R_21.data(), t_21.data(), p1.data(), p2.data(), P.data());
+  return P;
+}
+
+Vector3d TriangulateNView(const std::vector<Matrix3d>& R_cw_list, const std::vector<Vector3d>& t_cw_list, const std::vector<std::array<float, 3>>& points) {
+  if (R_cw_list.size() != t_cw_list.size() || R_cw_list.size() != points.size()) throw std::invalid_argument("TriangulateNView: list sizes differ");   // upstream asserts
+  const size_t n = points.size();
+  std::vector<double> T(12 * n); std::vector<int> fid(n); std::vector<float> b(3 * n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T[12 * i + 4 * r + c] = R_cw_list[i][3 * r + c]; T[12 * i + 4 * r + 3] = t_cw_list[i][r]; }
+    fid[i] = (int)i;
+    for (int k = 0; k < 3; ++k) b[3 * i + k] = points[i][k];
+  }
+  Vector3d X;
+  pvlm_triangulate::triangulate_track(0, 0, 0, (long long)n, fid.data(), nullptr, b.data(), T.data(), nullptr, X.data());
+  return X;
+}
+
+bool EstimateStructure(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<PointTrack>& structure) {
+  structure = TriangulateTracks(frames, image_pairs);
+  return structure.size() > 0;
+}
+
+bool CameraLidarOptimizer::EstimateStructure(const std::vector<MatchPair>& image_pairs) {
+  StageTimer stage_timer_("EstimateStructure");
+  return structure_detail::EstimateStructureWith(DeviceKernels(), frames, image_pairs, structure);
 }
 
 }  // namespace pvlm
