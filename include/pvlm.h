@@ -131,6 +131,10 @@ pvlm_status pvlm_resset_upload(pvlm_ctx* ctx, pvlm_functor kind, unsigned flags,
                                const double* rows, int stride, pvlm_resset** out);
 pvlm_status pvlm_resset_destroy(pvlm_ctx* ctx, pvlm_resset* rs);
 pvlm_status pvlm_resset_info(const pvlm_resset* rs, int64_t* n, int* n_pairs, int* kind, unsigned* flags);
+/* Point-to-plane sets: consecutive rows whose plane is bit-identical share one entry of a plane table that the fused evaluation
+ * (pvlm_eval_pair_blocks*, pvlm_neq_accumulate*) then reads instead of the four plane columns.  *in_use: 1 when the set was given the table
+ * (by its mean run length, or PVLM_PLANE_RUNS=0/1); *runs: the runs counted (0 when the set was never counted).  Results do not depend on it. */
+pvlm_status pvlm_resset_plane_runs(const pvlm_resset* rs, int* in_use, int64_t* runs);
 /* Copies the segment table / rows back (rows in the upload layout); any pointer may be NULL. */
 pvlm_status pvlm_resset_download(pvlm_ctx* ctx, const pvlm_resset* rs, int64_t* pair_offsets, int* pair_ref,
                                  int* pair_nei, double* rows);

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "pvlm_colorize_scans", "pvlm_colorize_scans_dev", "pvlm_colorize_debug_hsv",
     "pvlm_ba_create_kind", "pvlm_ba_info", "pvlm_filter_tracks",
     "pvlm_triangulate_tracks", "pvlm_filter_tracks_far",
+    "pvlm_resset_plane_runs",
 ]
 
 
@@ -698,6 +699,12 @@ class ResidualSet:
         self.ctx._check(self.ctx.lib.pvlm_resset_download(self.ctx._h, self._h, _p(po, C.c_int64), _p(pr, C.c_int), _p(pn, C.c_int),
                                                           _p(rows, C.c_double)), "pvlm_resset_download")
         return po, pr[:self.n_pairs], pn[:self.n_pairs], rows[:self.n]
+
+    def plane_runs(self):
+        """Point-to-plane sets: whether the fused evaluation reads the plane-run table, and the runs of equal consecutive planes counted at finalize."""
+        u, r = C.c_int(0), C.c_int64(0)
+        self.ctx._check(self.ctx.lib.pvlm_resset_plane_runs(self._h, C.byref(u), C.byref(r)), "pvlm_resset_plane_runs")
+        return dict(in_use=bool(u.value), runs=int(r.value))
 
     def set_pose_ids(self, pair_ref, pair_nei):
         """Renumbers the segments' poses (one pose table for every set of a problem)."""

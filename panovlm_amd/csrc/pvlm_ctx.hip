@@ -594,6 +594,13 @@ pvlm_status pvlm_resset_info(const pvlm_resset* rs, int64_t* n, int* n_pairs, in
   return PVLM_OK;
 }
 
+pvlm_status pvlm_resset_plane_runs(const pvlm_resset* rs, int* in_use, int64_t* runs) {
+  if (!rs) return PVLM_ERR_ARG;
+  if (in_use) *in_use = rs->plane_runs ? 1 : 0;
+  if (runs) *runs = rs->n_plane_runs;
+  return PVLM_OK;
+}
+
 }  // extern "C"
 
 pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs) {
@@ -606,6 +613,7 @@ pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs) {
   pvlm_i_free(ctx, rs->d_pair_cols); pvlm_i_free(ctx, rs->d_pair_stride); pvlm_i_free(ctx, rs->d_out_start); pvlm_i_free(ctx, rs->d_ref);
   pvlm_i_free(ctx, rs->d_nei); pvlm_i_free(ctx, rs->d_blk_pair); pvlm_i_free(ctx, rs->d_blk_chunk); pvlm_i_free(ctx, rs->d_pair_blk_start);
   pvlm_i_free(ctx, rs->d_pair_tab); pvlm_i_free(ctx, rs->d_partials); pvlm_i_free(ctx, rs->d_pair_blocks); pvlm_i_free(ctx, rs->d_stage);
+  pvlm_i_free(ctx, rs->d_plane_idx); pvlm_i_free(ctx, rs->d_plane_tab); pvlm_i_free(ctx, rs->d_chunk_plane0); pvlm_i_free(ctx, rs->d_pair_idx0);
   delete rs;
   return PVLM_OK;
 }
@@ -668,6 +676,7 @@ pvlm_status pvlm_i_resset_finalize(pvlm_ctx* ctx, pvlm_resset* rs) {
   if ((st = cp(rs->d_blk_pair, blk_pair.data(), blk_pair.size() * sizeof(int)))) return st;
   if ((st = cp(rs->d_blk_chunk, blk_chunk.data(), blk_chunk.size() * sizeof(int)))) return st;
   if ((st = cp(rs->d_pair_blk_start, pair_blk_start.data(), pair_blk_start.size() * sizeof(int)))) return st;
+  if ((st = pvlm_i_plane_runs_build(ctx, rs, total))) return st;
   if ((st = pvlm_i_sync(ctx))) return st;            // one wait for everything the caller and this function queued
   rs->pair_tab_epoch = ~0ull;
   return PVLM_OK;

@@ -5,7 +5,8 @@
 // segment starts on an even row so each lane streams two consecutive rows with one 16-byte load
 // per column (1 KiB per wave instruction).  The per-pair constants (R_rn, t_rn, t_rw, J_l blocks)
 // are read through wave-uniform (scalar) loads.  Algorithmic HBM traffic per evaluation in fused
-// mode = 8*ncols bytes (56 B point-to-plane); materialise mode adds 8 + 96 B of stores.
+// mode = 8*ncols bytes; materialise mode adds 8 + 96 B of stores.  Point-to-plane (7 columns, 56 B): a set whose planes repeat from row to row is read as
+// 24 B of point + a 2-byte run number per row + one 32-byte table entry per run of equal planes (pvlm_plane_args below): 26 + 32 / L bytes at mean run length L.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -44,6 +45,26 @@ __device__ __forceinline__ double2 stream_load2(const double* p) {
   pvlm_col_ptr q = (pvlm_col_ptr)(p);
   const pvlm_dbl2 v = NT ? __builtin_nontemporal_load(q) : *q;
   return make_double2(v.x, v.y);
+}
+// The plane-run form of a 7-column set (pvlm_resset::plane_runs, built by pvlm_i_resset_finalize): rows whose plane is bit-identical to the previous row's share one
+// 32-byte table entry.  A lane then streams 3 x 16 B of point and ONE 4-byte word — the run numbers of its two rows inside the chunk — and takes each row's plane
+// from the table with two 16-byte loads.  The run numbers are read once (non-temporal like the columns); the table loads are ordinary: neighbouring lanes and the
+// lane's own second row hit the same lines.
+struct pvlm_plane_args {
+  const uint16_t* idx;           // per padded row, pair p at pair_idx0[p]
+  const int64_t* pair_idx0;
+  const int64_t* chunk_plane0;   // per work-list entry: first table entry of the chunk
+  const double* tab;             // {a, b, c, d} per run
+};
+template <bool NT>
+__device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`: low and high half
+#if PVLM_GLOBAL_LOADS
+  typedef const __attribute__((address_space(1))) unsigned* ptr;
+#else
+  typedef const unsigned* ptr;
+#endif
+  ptr q = (ptr)(reinterpret_cast<const char*>(base) + 2u * row);
+  return NT ? __builtin_nontemporal_load(q) : *q;
 }
 // ... and the stores of the materialising kernels (r, the 1 x 12 rows, the wrench rows).  Non-temporal STORES were measured and lose:
 // k_eval_materialise 4.80 TB/s against 5.04 TB/s with ordinary stores (profiles/r2_ab_eval_loads.txt) — off.
@@ -353,13 +374,15 @@ __device__ __forceinline__ double wave_transpose_sum(const double (&a)[N], int l
   return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-template <int KIND, bool NORM, int NCOLS, int LOSS>
+template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
 __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUSED_WAVES)) void k_eval_fused(const double* const* __restrict__ pair_cols,
                                                     const int64_t* __restrict__ pair_stride,
                                                     const int64_t* __restrict__ out_start,
                                                     const int* __restrict__ blk_pair, const int* __restrict__ blk_chunk,
                                                     int chunk_rows, const double* __restrict__ pair_tab, double weight,
-                                                    double loss_a, double* __restrict__ partials) {
+                                                    double loss_a, double* __restrict__ partials, pvlm_plane_args pr) {
+  static_assert(!PR || NCOLS == 7, "plane runs: the 7-column kinds only");
+  constexpr int NS = PR ? 3 : NCOLS;                // columns streamed row by row (PR: the point; the plane comes from the run table)
   const int p = blk_pair[blockIdx.x];
   const double* __restrict__ cols = pair_cols[p];   // first row of the pair's segment, column 0
   const int64_t n_dev = pair_stride[p];             // column stride of the pair's block
@@ -380,40 +403,59 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   constexpr bool kPrefetch = PVLM_PREFETCH >= 0 ? (PVLM_PREFETCH != 0) : (KIND == PVLM_POINT2PLANE_METER || KIND == PVLM_POINT2LINE_METER);
   // addresses = a wave-uniform column base (scalar registers) + one 32-bit row offset shared by the columns: the loads take the
   // saddr + voffset form and an iteration advances ONE register instead of a 64-bit pointer per column
-  const double* colb[NCOLS];
+  const double* colb[NS];
 #pragma unroll
-  for (int c = 0; c < NCOLS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
+  for (int c = 0; c < NS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
+  const uint16_t* runb = nullptr;  // PR: run numbers of the chunk's rows, and the chunk's first table entry — wave-uniform bases like colb
+  const double* tabb = nullptr;
+  if (PR) { runb = pr.idx + pr.pair_idx0[p] + lo; tabb = pr.tab + 4 * pr.chunk_plane0[blockIdx.x]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
   unsigned j = 2u * threadIdx.x;
-  double2 nx[NCOLS];
+  double2 nx[NS];
+  unsigned nx_runs = 0;
   if (kPrefetch && j < span) {
 #pragma unroll
-    for (int c = 0; c < NCOLS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+    for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+    if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
   }
   for (; j < span; j += 512) {
-    double2 v[NCOLS];
+    double2 v[NS];
+    unsigned runs = 0;
     if (kPrefetch) {
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) v[c] = nx[c];
+      for (int c = 0; c < NS; ++c) v[c] = nx[c];
+      runs = nx_runs;
       if (j + 512 < span) {
 #pragma unroll
-        for (int c = 0; c < NCOLS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * (j + 512)));
+        for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * (j + 512)));
+        if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j + 512);
       }
     } else {
 #ifdef PVLM_EXP_SKIP   // timing experiment only (wrong results): how does the rate respond to fewer bytes per evaluation?
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NCOLS - PVLM_EXP_SKIP ? c : 0] + j);
+      for (int c = 0; c < NS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NS - PVLM_EXP_SKIP ? c : 0] + j);
 #else
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
 #endif
+      if (PR) runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
+    }
+    double2 pl[2][2];              // PR: {a, b}, {c, d} of the lane's two rows (a pad row behind an odd last row names entry 0)
+    if (PR) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned at = 32u * (h ? runs >> 16 : runs & 0xffffu);
+        pl[h][0] = stream_load2<false>(at_byte(tabb, at));
+        pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
+      }
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (j + h >= span) break;
       double rec[NCOLS];
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) rec[c] = h ? v[c].y : v[c].x;
+      for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
+      if (PR) { rec[3] = pl[h][0].x; rec[4] = pl[h][0].y; rec[5] = pl[h][1].x; rec[6] = pl[h][1].y; }
       accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, acc);
     }
   }
@@ -434,13 +476,15 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
 // blocks each — where a 256-thread workgroup per segment leaves most lanes idle and pays a 28-value cross-wave reduction through
 // LDS + a barrier per segment.  A wave streams 128 rows per iteration and reduces with shuffles only.  Selected per residual set
 // at finalize (pvlm_resset::wave_units: mean segment < 4096 rows); the headline's long segments keep k_eval_fused.
-template <int KIND, bool NORM, int NCOLS, int LOSS>
+template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
 __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_wave(const double* const* __restrict__ pair_cols,
                                                     const int64_t* __restrict__ pair_stride,
                                                     const int64_t* __restrict__ out_start,
                                                     const int* __restrict__ blk_pair, const int* __restrict__ blk_chunk,
                                                     int chunk_rows, int n_units, const double* __restrict__ pair_tab, double weight,
-                                                    double loss_a, double* __restrict__ partials) {
+                                                    double loss_a, double* __restrict__ partials, pvlm_plane_args pr) {
+  static_assert(!PR || NCOLS == 7, "plane runs: the 7-column kinds only");
+  constexpr int NS = PR ? 3 : NCOLS;                // as in k_eval_fused
   // the unit is the same for the 64 lanes: said explicitly, the pair's pointers, bounds and the 15 pose constants are scalar loads
   // into scalar registers (30 VGPRs less) instead of 64 identical vector loads
   const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -458,20 +502,34 @@ __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_w
 #pragma unroll
   for (int k = 0; k < PVLM_PARTIAL; ++k) acc[k] = 0.0;
   const double a2 = loss_a * loss_a;
-  const double* colb[NCOLS];       // uniform column bases + one 32-bit row offset, as in k_eval_fused
+  const double* colb[NS];          // uniform column bases + one 32-bit row offset, as in k_eval_fused
 #pragma unroll
-  for (int c = 0; c < NCOLS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
+  for (int c = 0; c < NS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
+  const uint16_t* runb = nullptr;
+  const double* tabb = nullptr;
+  if (PR) { runb = pr.idx + pr.pair_idx0[p] + lo; tabb = pr.tab + 4 * pr.chunk_plane0[unit]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
   for (unsigned j = 2u * lane; j < span; j += 128) {
-    double2 v[NCOLS];
+    double2 v[NS];
 #pragma unroll
-    for (int c = 0; c < NCOLS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+    for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+    double2 pl[2][2];
+    if (PR) {
+      const unsigned runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned at = 32u * (h ? runs >> 16 : runs & 0xffffu);
+        pl[h][0] = stream_load2<false>(at_byte(tabb, at));
+        pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
+      }
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (j + h >= span) break;
       double rec[NCOLS];
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) rec[c] = h ? v[c].y : v[c].x;
+      for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
+      if (PR) { rec[3] = pl[h][0].x; rec[4] = pl[h][0].y; rec[5] = pl[h][1].x; rec[6] = pl[h][1].y; }
       accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, acc);
     }
   }
@@ -641,26 +699,28 @@ static void launch_wrench(pvlm_ctx* ctx, const pvlm_resset* rs, double* d_w, int
                        rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, d_w, blk0, row0);
 }
 
+template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
+static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
+  const pvlm_plane_args pr = {rs->d_plane_idx, rs->d_pair_idx0, rs->d_chunk_plane0, rs->d_plane_tab};
+  if (rs->wave_units)            // many short segments: one wave per (pair, chunk)
+    hipLaunchKernelGGL((k_eval_fused_wave<KIND, NORM, NCOLS, LOSS, PR>), dim3((unsigned)((rs->n_blocks + 3) / 4)), dim3(256), 0, ctx->stream, rs->d_pair_cols,
+                       rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a,
+                       rs->d_partials, pr);
+  else
+    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
+                       rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
+}
 template <int KIND, bool NORM, int NCOLS>
 static void launch_fused(pvlm_ctx* ctx, const pvlm_resset* rs, int loss, double a) {
-  if (rs->wave_units) {          // many short segments: one wave per (pair, chunk)
-    const dim3 grid((unsigned)((rs->n_blocks + 3) / 4));
-    if (loss == PVLM_LOSS_HUBER)
-      hipLaunchKernelGGL((k_eval_fused_wave<KIND, NORM, NCOLS, PVLM_LOSS_HUBER>), grid, dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
-                         rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a, rs->d_partials);
-    else
-      hipLaunchKernelGGL((k_eval_fused_wave<KIND, NORM, NCOLS, PVLM_LOSS_NONE>), grid, dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
-                         rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a, rs->d_partials);
-    return;
+  if constexpr (NCOLS == 7) {
+    if (rs->plane_runs) {        // the plane from the run table (pvlm_i_resset_finalize chose it for this set)
+      if (loss == PVLM_LOSS_HUBER) launch_fused_as<KIND, NORM, NCOLS, PVLM_LOSS_HUBER, true>(ctx, rs, a);
+      else launch_fused_as<KIND, NORM, NCOLS, PVLM_LOSS_NONE, true>(ctx, rs, a);
+      return;
+    }
   }
-  if (loss == PVLM_LOSS_HUBER)
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, PVLM_LOSS_HUBER>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols,
-                       rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab,
-                       rs->weight, a, rs->d_partials);
-  else
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, PVLM_LOSS_NONE>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols,
-                       rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab,
-                       rs->weight, a, rs->d_partials);
+  if (loss == PVLM_LOSS_HUBER) launch_fused_as<KIND, NORM, NCOLS, PVLM_LOSS_HUBER, false>(ctx, rs, a);
+  else launch_fused_as<KIND, NORM, NCOLS, PVLM_LOSS_NONE, false>(ctx, rs, a);
 }
 
 #define PVLM_DISPATCH(FN, ...)                                                                         \

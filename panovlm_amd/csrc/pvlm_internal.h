@@ -157,6 +157,14 @@ struct pvlm_resset {
   int n_blocks = 0;
   int chunk_rows = 0;
   bool wave_units = false;   // the fused kernel takes one work-list entry per WAVE (short segments), see pvlm_i_resset_finalize
+  // 7-column (point-to-plane) sets: consecutive rows with a bit-identical plane share ONE 32-byte table entry (pvlm_i_resset_finalize); the fused
+  // kernels then read 24 B of point + a 2-byte run number per row and the plane from the table.  The seven columns stay: every other path reads them.
+  bool plane_runs = false;              // the fused kernels take the plane from d_plane_tab
+  int64_t n_plane_runs = 0;             // table entries (runs of equal consecutive planes inside a chunk), 0 when the table was not counted
+  uint16_t* d_plane_idx = nullptr;      // per padded row, in pair order (pair p starts at d_pair_idx0[p]): the row's run number inside its chunk
+  double* d_plane_tab = nullptr;        // n_plane_runs x {a, b, c, d}
+  int64_t* d_chunk_plane0 = nullptr;    // n_blocks: first table entry of the work-list entry
+  int64_t* d_pair_idx0 = nullptr;       // n_pairs: first element of the pair in d_plane_idx (a multiple of 16)
   int* d_blk_pair = nullptr;
   int* d_blk_chunk = nullptr;
   int* d_pair_blk_start = nullptr;  // n_pairs+1
@@ -324,5 +332,8 @@ void pvlm_i_preload_undistort(hipStream_t s);
 // builds work list + scratch for a resset whose segment table is final (h_* mirrors filled)
 pvlm_status pvlm_i_resset_finalize(pvlm_ctx* ctx, pvlm_resset* rs);
 pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs);
+// point-to-plane sets (csrc/pvlm_plane_runs.hip): counts the runs of equal consecutive planes and, where it pays, builds the plane-run table; called by
+// pvlm_i_resset_finalize behind its queued copies of the work list (padded_rows: the sum of pvlm_i_seg_rows over the pairs)
+pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows);
 int pvlm_i_ncols(int kind);
 int pvlm_i_stride(int kind);
