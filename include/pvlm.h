@@ -334,6 +334,40 @@ pvlm_status pvlm_triangulate_tracks(pvlm_ctx* ctx, int rows, int cols, int n_tra
 pvlm_status pvlm_filter_tracks_far(pvlm_ctx* ctx, int n_tracks, const int64_t* track_offsets, const int* frame_ids, const double* points, int n_frames,
                                    const double* t_wc /* n_frames x 3 */, const unsigned char* frame_valid, double threshold, unsigned char* keep);
 
+/* ---- K33: brute-force 2-NN SIFT matching (MatchSIFT util/SIFT.cpp:130-162, SfM::MatchImagePairs sfm/SfM.cpp:229-295) ---- *
+ * The definition (csrc/pvlm_match_core.h): descriptors are rows of 128 float; d2(a, b) = the fmaf chain c = fmaf(a[k] - b[k], a[k] - b[k], c) over
+ * k = 0..127 from c = 0; distance = sqrtf(d2); the two nearest train rows by (d2, index), an exact tie to the lower index; ratio test
+ * distance0 < ratio * distance1 in float, strictly; matches in query order.  [recalled] the summation order of cv::cuda's brute-force matcher is
+ * not pinned; the FLANN branch of MatchSIFT is approximate and not mirrored.
+ * Deliberate divergence: a train side with exactly ONE row gives no matches (upstream reads raw_matches[i][1] out of bounds there); a side
+ * with no rows gives none either, as upstream.
+ * pvlm_descset_create: the descriptors of n frames (rows[f] x 128 floats, row-major, descs[f] may be NULL when rows[f] == 0) copied to the device,
+ *   where they stay (what upstream's d_descriptors[i].upload does, sfm/SfM.cpp:237-243).  width must be 128 (PVLM_ERR_ARG otherwise); a non-finite
+ *   value anywhere is PVLM_ERR_ARG, found by a device-side check.  The set belongs to the context it was created with: another one is PVLM_ERR_ARG.
+ * pvlm_match_knn2: the raw knnMatch(d[src], d[tgt], 2) of every pair: per query of pair p, in pair order, then query order, the two train indices
+ *   (-1 where absent) and the two distances (+inf where absent); idx and dist hold 2 x sum(rows[src[p]]) entries.
+ * pvlm_match_pairs: the loop body of SfM::MatchImagePairs for every pair: MatchSIFT, then the pair filter (:266-275): the pair is dropped with
+ *   fewer than matches_threshold matches; of the others the matches with (double)distance < 0.8 * (double)dmax stay (dmax the pair's largest
+ *   distance); dropped again with fewer than matches_threshold left.  matches_threshold < 0 is PVLM_ERR_ARG (upstream's first comparison converts
+ *   it to size_t and drops every pair).  keep[p] = 1 for a surviving pair; its records are out[match_offsets[p] .. match_offsets[p + 1]), in query
+ *   order; pairs come out in the order of the input list (upstream: the order of an OpenMP critical section).  *needed = match_offsets[n_pairs];
+ *   when it exceeds capacity the call returns PVLM_ERR_CAPACITY with keep, match_offsets and *needed set and no record past capacity written.
+ * flags: PVLM_FLAG_MATCH_EXACT evaluates the definition for every (query, train row) on the vector ALU.  Without it every query is screened on the
+ *   fp32 matrix core (s = |a|^2 + |b|^2 - 2 a.b, the 4 smallest), the 4 candidates are evaluated with the definition and accepted only when a
+ *   worst-case rounding bound certifies that no other row can enter or tie the top two; every other query is evaluated exactly.  The results are
+ *   bit-identical in both modes; stats->fallback_queries counts the exactly evaluated ones. */
+#define PVLM_FLAG_MATCH_EXACT 0x400u
+typedef struct pvlm_descset pvlm_descset;
+typedef struct pvlm_match { int query, train; float distance; } pvlm_match;
+typedef struct pvlm_match_stats { long long queries, fallback_queries; int batches; } pvlm_match_stats;
+pvlm_status pvlm_descset_create(pvlm_ctx* ctx, int n_frames, const int* rows, int width, const float* const* descs, pvlm_descset** out);
+void pvlm_descset_destroy(pvlm_ctx* ctx, pvlm_descset* set);
+pvlm_status pvlm_match_knn2(pvlm_ctx* ctx, const pvlm_descset* set, int n_pairs, const int* src, const int* tgt, unsigned flags, int* idx, float* dist,
+                            pvlm_match_stats* stats_or_null);
+pvlm_status pvlm_match_pairs(pvlm_ctx* ctx, const pvlm_descset* set, int n_pairs, const int* src, const int* tgt, float ratio, int matches_threshold,
+                             unsigned flags, unsigned char* keep /* n_pairs */, long long* match_offsets /* n_pairs + 1 */, pvlm_match* out, long long capacity,
+                             long long* needed, pvlm_match_stats* stats_or_null);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

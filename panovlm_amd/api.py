@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "pvlm_colorize_scans", "pvlm_colorize_scans_dev", "pvlm_colorize_debug_hsv",
     "pvlm_ba_create_kind", "pvlm_ba_info", "pvlm_filter_tracks",
     "pvlm_triangulate_tracks", "pvlm_filter_tracks_far",
+    "pvlm_descset_create", "pvlm_descset_destroy", "pvlm_match_knn2", "pvlm_match_pairs",
     "pvlm_resset_plane_runs",
 ]
 
@@ -1309,6 +1310,77 @@ def filter_tracks_far(ctx, track_offsets, frame_ids, points, t_wc, threshold, fr
                                               _p(t, C.c_double), None if fv is None else _p(fv, C.c_ubyte), C.c_double(threshold), _p(keep, C.c_ubyte)),
                "pvlm_filter_tracks_far")
     return keep
+
+
+FLAG_MATCH_EXACT = 0x400
+
+
+class MatchStats(C.Structure):
+    _fields_ = [("queries", C.c_longlong), ("fallback_queries", C.c_longlong), ("batches", C.c_int)]
+
+
+MATCH_DTYPE = np.dtype([("query", np.int32), ("train", np.int32), ("distance", np.float32)])
+
+
+class DescSet:
+    """pvlm_descset (K33): the SIFT descriptors of a set of frames, resident on the device.  descs: one array of rows x 128 float32 per frame (rows may be 0)."""
+
+    def __init__(self, ctx, descs):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        arrs = [np.ascontiguousarray(d, np.float32) for d in descs]
+        arrs = [a if a.ndim == 2 else a.reshape(-1, 128) for a in arrs]
+        widths = set(a.shape[1] for a in arrs)
+        width = widths.pop() if len(widths) == 1 else (128 if not widths else -1)
+        self.rows = np.array([a.shape[0] for a in arrs], np.int32)
+        ptrs = (C.POINTER(C.c_float) * max(len(arrs), 1))(*[_p(a, C.c_float) if a.shape[0] else None for a in arrs])
+        ctx._check(ctx.lib.pvlm_descset_create(ctx._h, C.c_int(len(arrs)), _p(self.rows, C.c_int), C.c_int(width), ptrs, C.byref(self._h)), "pvlm_descset_create")
+
+    def close(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.pvlm_descset_destroy(self.ctx._h, self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_knn2(ctx, descset, src, tgt, flags=0):
+    """pvlm_match_knn2 (K33): the raw knnMatch(d[src], d[tgt], 2) of every pair.  Returns (idx queries x 2 int32, -1 where absent; dist queries x 2 float32, +inf where
+    absent; stats dict), the queries of all pairs one pair after the other."""
+    src = _i32(src); tgt = _i32(tgt)
+    nq = int(descset.rows[src].sum()) if len(src) else 0
+    idx = np.zeros((nq, 2), np.int32); dist = np.zeros((nq, 2), np.float32)
+    st = MatchStats()
+    ctx._check(ctx.lib.pvlm_match_knn2(ctx._h, descset._h, C.c_int(len(src)), _p(src, C.c_int), _p(tgt, C.c_int), C.c_uint(flags), _p(idx, C.c_int), _p(dist, C.c_float),
+                                       C.byref(st)), "pvlm_match_knn2")
+    return idx, dist, dict(queries=st.queries, fallback_queries=st.fallback_queries, batches=st.batches)
+
+
+MATCH_GUARD = 8      # sentinel records match_pairs keeps behind the capacity it passes on
+
+
+def match_pairs(ctx, descset, src, tgt, ratio, matches_threshold, flags=0, capacity=None):
+    """pvlm_match_pairs (K33): MatchSIFT and the pair filter of SfM::MatchImagePairs for every pair.  Returns a dict: keep (uint8 per pair), offsets (int64, pairs + 1),
+    matches (MATCH_DTYPE records of the surviving pairs in pair order, then query order; the first `capacity` of them when overflow), needed, stats, overflow (True
+    when `capacity` records were too few), guard_intact (the MATCH_GUARD sentinel records kept behind `capacity` were not written)."""
+    src = _i32(src); tgt = _i32(tgt)
+    cap = int(descset.rows[src].sum()) if capacity is None and len(src) else int(capacity or 0)
+    keep = np.zeros(len(src), np.uint8); off = np.zeros(len(src) + 1, np.int64)
+    out = np.zeros(cap + MATCH_GUARD, MATCH_DTYPE)
+    out["query"] = -7; out["train"] = -7; out["distance"] = -7.0
+    needed = C.c_longlong(0); st = MatchStats()
+    rc = ctx.lib.pvlm_match_pairs(ctx._h, descset._h, C.c_int(len(src)), _p(src, C.c_int), _p(tgt, C.c_int), C.c_float(ratio), C.c_int(matches_threshold), C.c_uint(flags),
+                                  _p(keep, C.c_ubyte), _p(off, C.c_longlong), out.ctypes.data_as(C.c_void_p), C.c_longlong(cap), C.byref(needed), C.byref(st))
+    if rc != -5:
+        ctx._check(rc, "pvlm_match_pairs")
+    g = out[cap:]
+    return dict(keep=keep, offsets=off, matches=out[:min(needed.value, cap)], needed=needed.value, overflow=rc == -5,
+                guard_intact=bool(np.all(g["query"] == -7) and np.all(g["train"] == -7) and np.all(g["distance"] == -7.0)),
+                stats=dict(queries=st.queries, fallback_queries=st.fallback_queries, batches=st.batches))
 
 
 def device_sort(ctx, keys):

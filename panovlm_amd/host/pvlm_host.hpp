@@ -593,6 +593,7 @@ struct Frame {
   bool pose_valid = true;
   std::vector<std::array<float, 4>> lines;
   std::vector<std::array<float, 2>> keypoints;   // GetKeyPoints()[k].pt (SIFT keypoints, pixels)
+  std::vector<float> descriptor;                 // GetDescriptor(): rows x 128 floats, row-major, row k the SIFT descriptor of keypoints[k] (K33)
   bool IsPoseValid() const { return pose_valid; }
   int GetImageRows() const { return rows; }
   int GetImageCols() const { return cols; }
@@ -620,8 +621,25 @@ size_t FilterTracksToFar(const std::vector<Frame>& frames, std::vector<PointTrac
 Vector3d Triangulate2View(const Matrix3d& R_21, const Vector3d& t_21, const std::array<float, 3>& p1, const std::array<float, 3>& p2);
 Vector3d TriangulateNView(const std::vector<Matrix3d>& R_cw_list, const std::vector<Vector3d>& t_cw_list, const std::vector<std::array<float, 3>>& points);
 // MVS::EstimateStructure (mvs/MVS.cpp:44-59): structure = TriangulateTracks(frames, image_pairs), true when it is not empty.  No SetImageScale and
-// no points.bin export, for the reasons RefineCameraPose gives; the match pairs are the caller's (upstream: ReadMatchPair).
+// no points.bin export, for the reasons RefineCameraPose gives; the match pairs are the caller's (upstream: ReadMatchPair) or MatchImagePairs' (K33).
 bool EstimateStructure(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<PointTrack>& structure);
+
+// ---- K33: the image matches (util/SIFT.cpp:130-162, sfm/SfM.cpp:229-295) --------------------------------------------------------------------------
+// cv::DMatch as far as the pipeline reads it
+struct DMatch { int queryIdx, trainIdx; float distance; };
+// MatchSIFT (util/SIFT.cpp:130-162, the brute-force branch): knnMatch(descriptor1, descriptor2, 2) and the ratio test
+// distance0 < dist_ratio_threshold * distance1, on two host arrays of rows x 128 floats: csrc/pvlm_match_core.h compiled for the host, for a
+// caller with one small pair.  A descriptor2 of one row gives no matches (upstream reads out of bounds there, see pvlm.h).
+std::vector<DMatch> MatchSIFT(const std::vector<float>& descriptor1, const std::vector<float>& descriptor2, const float dist_ratio_threshold);
+// SfM::MatchImagePairs (sfm/SfM.cpp:229-295) on the GPU: the descriptors of all frames go to the device once (pvlm_descset_create), every pair is
+// matched and filtered there in ONE pvlm_match_pairs call (K33), and image_pairs is replaced by the surviving pairs with their matches, in the
+// order of the input list (upstream: the order of an OpenMP critical section).  ratio is config.sift_match_dist_threshold.  The frames keep their
+// descriptors (upstream releases them); no after_sift_match.txt.  False (image_pairs untouched) for a negative matches_threshold, a pair that names a
+// frame that is not there, or a frame whose descriptor is not 128 floats per keypoint.
+// The result feeds TriangulateTracks / EstimateStructure as it is.
+bool MatchImagePairs(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold);
+// the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/match_bench.py times
+bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold, const int num_threads = 16);
 
 // ---- mvs/MVS.h:45-57, mvs/MVS.cpp:334-382 — who the neighbours of a reference view are (the `nei` / R_nr / t_nr arguments of
 // pvlm_mvs_*).  SelectNeighborKNN: the 3 x neighbor_size nearest camera centres (float32, as pcl::KdTreeFLANN returns them),

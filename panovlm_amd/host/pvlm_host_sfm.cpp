@@ -8,6 +8,7 @@
 #include "pvlm_host_internal.hpp"
 #include "pvlm_host_structure.hpp"
 #include "../csrc/pvlm_triangulate_core.h"
+#include "pvlm_host_match.hpp"
 
 namespace pvlm {
 
@@ -170,6 +171,73 @@ Vector3d TriangulateNView(const std::vector<Matrix3d>& R_cw_list, const std::vec
   Vector3d X;
   pvlm_triangulate::triangulate_track(0, 0, 0, (long long)n, fid.data(), nullptr, b.data(), T.data(), nullptr, X.data());
   return X;
+}
+
+// ---- K33 --------------------------------------------------------------------------------------------------------------------------------
+std::vector<DMatch> MatchSIFT(const std::vector<float>& descriptor1, const std::vector<float>& descriptor2, const float dist_ratio_threshold) {
+  std::vector<DMatch> out;
+  for (const match_detail::Match& m : match_detail::MatchRows(descriptor1.data(), (int)(descriptor1.size() / 128), descriptor2.data(), (int)(descriptor2.size() / 128),
+                                                              dist_ratio_threshold))
+    out.push_back(DMatch{m.query, m.train, m.distance});
+  return out;
+}
+
+namespace {
+// the pair list as the entry points take it; false when a pair names a frame that is not there or a frame's descriptor is not 128 floats per keypoint
+bool PairLists(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<int>* rows, std::vector<const float*>* desc, std::vector<int>* src,
+               std::vector<int>* tgt) {
+  for (const Frame& f : frames) {
+    if (f.descriptor.size() != 128 * f.keypoints.size()) return false;             // one descriptor row per keypoint
+    rows->push_back((int)f.keypoints.size()); desc->push_back(f.descriptor.data());
+  }
+  for (const MatchPair& p : image_pairs) {
+    if (p.image_pair.first >= frames.size() || p.image_pair.second >= frames.size()) return false;
+    src->push_back((int)p.image_pair.first); tgt->push_back((int)p.image_pair.second);
+  }
+  return true;
+}
+}  // namespace
+
+bool MatchImagePairs(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold) {
+  StageTimer stage_timer_("MatchImagePairs");
+  if (matches_threshold < 0) return false;
+  std::vector<int> rows, src, tgt; std::vector<const float*> desc;
+  if (!PairLists(frames, image_pairs, &rows, &desc, &src, &tgt)) return false;
+  Engine& e = Engine::Default();
+  pvlm_descset* set = nullptr;
+  e.Check(pvlm_descset_create(e.ctx(), (int)frames.size(), rows.data(), 128, desc.data(), &set), "pvlm_descset_create");
+  struct Release { pvlm_ctx* c; pvlm_descset* s; ~Release() { pvlm_descset_destroy(c, s); } } release{e.ctx(), set};
+  long long capacity = 0, needed = 0;
+  for (int s : src) capacity += rows[(size_t)s];
+  std::vector<unsigned char> keep(image_pairs.size()); std::vector<long long> off(image_pairs.size() + 1, 0); std::vector<pvlm_match> rec((size_t)std::max<long long>(capacity, 1));
+  e.Check(pvlm_match_pairs(e.ctx(), set, (int)image_pairs.size(), src.data(), tgt.data(), ratio, matches_threshold, 0, keep.data(), off.data(), rec.data(), capacity, &needed,
+                           nullptr), "pvlm_match_pairs");
+  std::vector<MatchPair> good_pair;
+  for (size_t p = 0; p < image_pairs.size(); ++p) {
+    if (!keep[p]) continue;
+    MatchPair g; g.image_pair = image_pairs[p].image_pair;
+    for (long long k = off[p]; k < off[p + 1]; ++k) g.matches.push_back({rec[(size_t)k].query, rec[(size_t)k].train});
+    good_pair.push_back(std::move(g));
+  }
+  good_pair.swap(image_pairs);
+  return true;
+}
+
+bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold, const int num_threads) {
+  std::vector<int> rows, src, tgt; std::vector<const float*> desc;
+  if (!PairLists(frames, image_pairs, &rows, &desc, &src, &tgt)) return false;
+  std::vector<unsigned char> keep; std::vector<std::vector<match_detail::Match>> matches;
+  if (match_detail::MatchPairsHost((int)frames.size(), desc.data(), rows.data(), (int)image_pairs.size(), src.data(), tgt.data(), ratio, matches_threshold,
+                                   (size_t)std::max(num_threads, 1), keep, matches)) return false;
+  std::vector<MatchPair> good_pair;
+  for (size_t p = 0; p < image_pairs.size(); ++p) {
+    if (!keep[p]) continue;
+    MatchPair g; g.image_pair = image_pairs[p].image_pair;
+    for (const match_detail::Match& m : matches[p]) g.matches.push_back({m.query, m.train});
+    good_pair.push_back(std::move(g));
+  }
+  good_pair.swap(image_pairs);
+  return true;
 }
 
 bool EstimateStructure(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<PointTrack>& structure) {
