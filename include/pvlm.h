@@ -368,6 +368,43 @@ pvlm_status pvlm_match_pairs(pvlm_ctx* ctx, const pvlm_descset* set, int n_pairs
                              unsigned flags, unsigned char* keep /* n_pairs */, long long* match_offsets /* n_pairs + 1 */, pvlm_match* out, long long capacity,
                              long long* needed, pvlm_match_stats* stats_or_null);
 
+/* ---- K34: relative poses from the matches (SfM::FilterImagePairs sfm/SfM.cpp:298-480, base/EssentialMatrix.cpp, base/ACRansac_NFA.cpp) ---- *
+ * The definition (csrc/pvlm_essential_core.h): per pair n_runs (upstream: 40) independent runs of FindEssentialACRANSAC (base/EssentialMatrix.cpp:180-288, ac_ransac_mode
+ * = true as upstream forces it, so there is no `precision`) with up to max_iterations (upstream: 300) hypotheses; ComputeEssential (:10-40) with both of Eigen's
+ * decompositions restated as a cyclic Jacobi in fp64 of fixed rotation order (parity with Eigen by tolerance); the residual Square(asin(p2 . (E p1).normalized())) and
+ * ACRansac_NFA::ComputeNFA (base/ACRansac_NFA.cpp:103-137, the non-quantified branch, max_threshold = inf) with asin and log10 evaluated without libm, identically on the
+ * host and on the device; DecomposeEssential (:151-178) and SfM::CheckRT (sfm/SfM.cpp:1478-1547) on the run's inliers with the 3-degree tests as comparisons of the
+ * cosine against a threshold derived from the host's acos; the selection inside a run (:361-380) and over the runs (:413-416).  As upstream, hypothesis k of a run is
+ * fitted to all 8 (k + 1) points sampled so far (min_point_set1/2 are never cleared, :194).
+ * Deliberate divergences: the sampling is a Philox-4x32-10 stream keyed by (seed, src frame, tgt frame, run) (upstream: std::random_device per draw; nothing to be equal
+ * to), so the result of a pair does not depend on the other pairs of the call; a pair with fewer than 9 matches is dropped (upstream returns zero below 8 and reads out
+ * of bounds at exactly 8); among runs with equal CheckRT counts the lowest run index wins (upstream: an unstable sort); parallax is not produced (its reader is
+ * commented out upstream, :369-373); PVLM_FLAG_ESSENTIAL_FRESH_SAMPLE fits every hypothesis to its own 8 points only (the textbook 8-point hypothesis).
+ * Inputs: bearings[f] = rows[f] x 3 floats, eq.ImageToCam of the frame's keypoints (sfm/SfM.cpp:311-319; pvlm_image_to_cam_f32); the matches of pair p are
+ * matches[match_offsets[p] .. match_offsets[p + 1]), query a keypoint of src[p], train one of tgt[p]: what pvlm_match_pairs writes.  A frame or keypoint index out of
+ * range, n_runs < 1, max_iterations outside [1, 2^24], more than 2^29 matches in one pair are PVLM_ERR_ARG.
+ * pvlm_essential_acransac: the raw result of every run: E (row-major, chain c = p * n_runs + run; all zero = no model), the run's minNFA (+inf for a dropped pair), and
+ *   the run's inlier set (indices into the pair's matches, in the order of the sorted residuals, as upstream leaves inlier_idx) at inliers[inlier_offsets[c] ..).
+ * pvlm_filter_image_pairs: the loop body of FilterImagePairs up to, and not including, RefineRelativePose: keep[p], R_21 (row-major), t_21 of the winning run, its
+ *   CheckRT inliers (indices into the pair's matches, ascending) at inlier_idx[inlier_offsets[p] ..) and their triangulated points (camera 1's frame).
+ * Both: *needed = the records in all; when it exceeds capacity the call returns PVLM_ERR_CAPACITY with everything but the records set and no record past capacity
+ * written.  stats: chains run, hypotheses evaluated, chains that ran in LDS and chains (pairs above 1024 matches) that sorted through global scratch.
+ * A call works through its pair list in batches of up to 2^15 chains; the environment variable PVLM_ESSENTIAL_BATCH_PAIRS (read at every call) lowers the number of
+ * pairs per batch.  It changes no result; the tests use it to run several batches on a small list. */
+#define PVLM_FLAG_ESSENTIAL_FRESH_SAMPLE 0x800u
+typedef struct pvlm_essential_params { int n_runs /* 40 */, max_iterations /* 300 */, triangulation_num_threshold; unsigned long long seed; } pvlm_essential_params;
+typedef struct pvlm_essential_stats { long long chains, hypotheses, lds_chains, fallback_chains; } pvlm_essential_stats;
+pvlm_status pvlm_essential_acransac(pvlm_ctx* ctx, int n_frames, const float* const* bearings /* 3 floats per keypoint */, const int* rows, int n_pairs, const int* src,
+                                    const int* tgt, const long long* match_offsets /* n_pairs + 1 */, const pvlm_match* matches, const pvlm_essential_params* params,
+                                    unsigned flags, double* E /* n_pairs * n_runs * 9 */, double* nfa /* n_pairs * n_runs */,
+                                    long long* inlier_offsets /* n_pairs * n_runs + 1 */, int* inliers, long long capacity, long long* needed,
+                                    pvlm_essential_stats* stats_or_null);
+pvlm_status pvlm_filter_image_pairs(pvlm_ctx* ctx, int n_frames, const float* const* bearings, const int* rows, int n_pairs, const int* src, const int* tgt,
+                                    const long long* match_offsets, const pvlm_match* matches, const pvlm_essential_params* params, unsigned flags,
+                                    unsigned char* keep /* n_pairs */, double* R_21 /* n_pairs * 9 */, double* t_21 /* n_pairs * 3 */,
+                                    long long* inlier_offsets /* n_pairs + 1 */, int* inlier_idx, double* triangulated /* 3 per inlier */, long long capacity,
+                                    long long* needed, pvlm_essential_stats* stats_or_null);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

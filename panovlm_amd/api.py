@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "pvlm_ba_create_kind", "pvlm_ba_info", "pvlm_filter_tracks",
     "pvlm_triangulate_tracks", "pvlm_filter_tracks_far",
     "pvlm_descset_create", "pvlm_descset_destroy", "pvlm_match_knn2", "pvlm_match_pairs",
+    "pvlm_essential_acransac", "pvlm_filter_image_pairs",
     "pvlm_resset_plane_runs",
 ]
 
@@ -1381,6 +1382,69 @@ def match_pairs(ctx, descset, src, tgt, ratio, matches_threshold, flags=0, capac
     return dict(keep=keep, offsets=off, matches=out[:min(needed.value, cap)], needed=needed.value, overflow=rc == -5,
                 guard_intact=bool(np.all(g["query"] == -7) and np.all(g["train"] == -7) and np.all(g["distance"] == -7.0)),
                 stats=dict(queries=st.queries, fallback_queries=st.fallback_queries, batches=st.batches))
+
+
+class EssentialParams(C.Structure):
+    _fields_ = [("n_runs", C.c_int), ("max_iterations", C.c_int), ("triangulation_num_threshold", C.c_int), ("seed", C.c_ulonglong)]
+
+
+class EssentialStats(C.Structure):
+    _fields_ = [("chains", C.c_longlong), ("hypotheses", C.c_longlong), ("lds_chains", C.c_longlong), ("fallback_chains", C.c_longlong)]
+
+
+FLAG_ESSENTIAL_FRESH_SAMPLE = 0x800
+ESSENTIAL_GUARD = 8      # sentinel records the two K34 calls keep behind the capacity they pass on
+
+
+def _essential_inputs(bearings, src, tgt, match_offsets, matches):
+    arrs = [np.ascontiguousarray(b, np.float32).reshape(-1, 3) for b in bearings]
+    rows = np.array([a.shape[0] for a in arrs], np.int32)
+    ptrs = (C.POINTER(C.c_float) * max(len(arrs), 1))(*[_p(a, C.c_float) if a.shape[0] else None for a in arrs])
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    return arrs, rows, ptrs, _i32(src), _i32(tgt), _i64(match_offsets), m
+
+
+def _essential_stats(st):
+    return dict(chains=st.chains, hypotheses=st.hypotheses, lds_chains=st.lds_chains, fallback_chains=st.fallback_chains)
+
+
+def essential_acransac(ctx, bearings, src, tgt, match_offsets, matches, n_runs=40, max_iterations=300, seed=0, flags=0, capacity=None):
+    """pvlm_essential_acransac (K34): the raw result of every AC-RANSAC run of every pair.  bearings: one rows x 3 float32 array per frame; the matches of pair p are
+    matches[match_offsets[p]:match_offsets[p + 1]] (MATCH_DTYPE).  Returns a dict: E (pairs x runs x 3 x 3, zero = no model), nfa (pairs x runs), offsets (int64, pairs *
+    runs + 1), inliers (the runs' inlier sets one after the other, the first `capacity` of them when overflow), needed, overflow, guard_intact, stats."""
+    arrs, rows, ptrs, src, tgt, off, m = _essential_inputs(bearings, src, tgt, match_offsets, matches)
+    npairs = len(src)
+    cap = int(len(m) * n_runs) if capacity is None else int(capacity)
+    E = np.zeros((npairs, max(n_runs, 0), 3, 3)); nfa = np.zeros((npairs, max(n_runs, 0))); ioff = np.zeros(npairs * max(n_runs, 0) + 1, np.int64)
+    inl = np.full(cap + ESSENTIAL_GUARD, -7, np.int32)
+    prm = EssentialParams(n_runs, max_iterations, 0, seed); needed = C.c_longlong(0); st = EssentialStats()
+    rc = ctx.lib.pvlm_essential_acransac(ctx._h, C.c_int(len(arrs)), ptrs, _p(rows, C.c_int), C.c_int(npairs), _p(src, C.c_int), _p(tgt, C.c_int), _p(off, C.c_longlong),
+                                         m.ctypes.data_as(C.c_void_p), C.byref(prm), C.c_uint(flags), _p(E, C.c_double), _p(nfa, C.c_double), _p(ioff, C.c_longlong),
+                                         _p(inl, C.c_int), C.c_longlong(cap), C.byref(needed), C.byref(st))
+    if rc != -5:
+        ctx._check(rc, "pvlm_essential_acransac")
+    return dict(E=E, nfa=nfa, offsets=ioff, inliers=inl[:min(needed.value, cap)], needed=needed.value, overflow=rc == -5, guard_intact=bool(np.all(inl[cap:] == -7)),
+                stats=_essential_stats(st))
+
+
+def filter_image_pairs(ctx, bearings, src, tgt, match_offsets, matches, triangulation_num_threshold, n_runs=40, max_iterations=300, seed=0, flags=0, capacity=None):
+    """pvlm_filter_image_pairs (K34): the loop body of SfM::FilterImagePairs up to RefineRelativePose.  Returns a dict: keep (uint8 per pair), R_21 (pairs x 3 x 3), t_21
+    (pairs x 3), offsets (int64, pairs + 1), inlier_idx (indices into the pair's matches) and triangulated (x 3) of the kept pairs' winning runs, needed, overflow,
+    guard_intact, stats."""
+    arrs, rows, ptrs, src, tgt, off, m = _essential_inputs(bearings, src, tgt, match_offsets, matches)
+    npairs = len(src)
+    cap = int(len(m)) if capacity is None else int(capacity)
+    keep = np.zeros(npairs, np.uint8); R = np.zeros((npairs, 3, 3)); t = np.zeros((npairs, 3)); ioff = np.zeros(npairs + 1, np.int64)
+    idx = np.full(cap + ESSENTIAL_GUARD, -7, np.int32); tri = np.full((cap + ESSENTIAL_GUARD, 3), -7.0)
+    prm = EssentialParams(n_runs, max_iterations, triangulation_num_threshold, seed); needed = C.c_longlong(0); st = EssentialStats()
+    rc = ctx.lib.pvlm_filter_image_pairs(ctx._h, C.c_int(len(arrs)), ptrs, _p(rows, C.c_int), C.c_int(npairs), _p(src, C.c_int), _p(tgt, C.c_int), _p(off, C.c_longlong),
+                                         m.ctypes.data_as(C.c_void_p), C.byref(prm), C.c_uint(flags), _p(keep, C.c_ubyte), _p(R, C.c_double), _p(t, C.c_double),
+                                         _p(ioff, C.c_longlong), _p(idx, C.c_int), _p(tri, C.c_double), C.c_longlong(cap), C.byref(needed), C.byref(st))
+    if rc != -5:
+        ctx._check(rc, "pvlm_filter_image_pairs")
+    k = min(needed.value, cap)
+    return dict(keep=keep, R_21=R, t_21=t, offsets=ioff, inlier_idx=idx[:k], triangulated=tri[:k], needed=needed.value, overflow=rc == -5,
+                guard_intact=bool(np.all(idx[cap:] == -7) and np.all(tri[cap:] == -7.0)), stats=_essential_stats(st))
 
 
 def device_sort(ctx, keys):

@@ -641,6 +641,39 @@ bool MatchImagePairs(const std::vector<Frame>& frames, std::vector<MatchPair>& i
 // the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/match_bench.py times
 bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold, const int num_threads = 16);
 
+// ---- K34: relative poses from the matches (sfm/SfM.cpp:298-480, base/EssentialMatrix.cpp, base/ACRansac_NFA.cpp) ---------------------------------
+// base/Serialization.h's MatchPair as FilterImagePairs leaves it, up to and not including RefineRelativePose
+struct RelativePair {
+  std::pair<size_t, size_t> image_pair;
+  std::vector<std::pair<int, int>> matches;     // (queryIdx, trainIdx), as in MatchPair
+  Matrix3d R_21; Vector3d t_21;
+  std::vector<size_t> inlier_idx;               // CheckRT's inliers of the winning run, indices into matches, ascending
+  std::vector<Vector3d> triangulated;           // their points in the first camera's frame
+  MatchPair AsMatchPair() const { MatchPair p; p.image_pair = image_pair; p.matches = matches; return p; }
+};
+// what upstream fixes in the source (40 runs of 300 iterations) and what it draws from std::random_device (here: a seed, see csrc/pvlm_essential_core.h)
+struct EssentialOptions { int n_runs = 40; int max_iterations = 300; unsigned long long seed = 0; bool fresh_sample = false; };
+// ComputeEssential (base/EssentialMatrix.cpp:10-40) and DecomposeEssential (:151-178) on the host compile of csrc/pvlm_essential_core.h (cyclic Jacobi for both of
+// Eigen's decompositions: parity by tolerance)
+Matrix3d ComputeEssential(const std::vector<std::array<float, 3>>& points1, const std::vector<std::array<float, 3>>& points2);
+bool DecomposeEssential(const Matrix3d& E_21, std::vector<Matrix3d>& rotations, std::vector<Vector3d>& translations);
+// FindEssentialACRANSAC (:180-288) on the host: ONE run (`run` selects the stream of the pair (first, second)); zero matrix = no model.  `precision` is gone:
+// upstream forces ac_ransac_mode.  Fewer than 9 matches give zero (see pvlm.h).
+Matrix3d FindEssentialACRANSAC(const std::vector<DMatch>& matches, const std::vector<std::array<float, 3>>& points1, const std::vector<std::array<float, 3>>& points2,
+                               const int max_iterations, std::vector<size_t>& inlier_idx, const std::pair<size_t, size_t>& image_pair = {0, 1}, const int run = 0,
+                               const EssentialOptions& options = EssentialOptions());
+// SfM::CheckRT (sfm/SfM.cpp:1478-1547) without parallax (its reader is commented out upstream)
+int CheckRT(const Matrix3d& R_21, const Vector3d& t_21, const std::vector<bool>& is_inlier, const std::vector<DMatch>& matches, const std::vector<std::array<float, 3>>& keypoints1,
+            const std::vector<std::array<float, 3>>& keypoints2, std::vector<Vector3d>& triangulated_points, std::vector<size_t>& inlier_idx);
+// the loop of SfM::FilterImagePairs over every pair, up to and not including RefineRelativePose, in ONE pvlm_filter_image_pairs call (K34): the surviving pairs with
+// R_21, t_21, inlier_idx and triangulated, in the order of the input list.  The bearings are eq.ImageToCam of the frames' keypoints (:311-319).  False for a pair or
+// a match that names what is not there.  Chains after MatchImagePairs.
+bool FilterImagePairs(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
+                      const EssentialOptions& options = EssentialOptions());
+// the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/essential_bench.py times
+bool FilterImagePairsHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
+                          const EssentialOptions& options = EssentialOptions(), const int num_threads = 16);
+
 // ---- mvs/MVS.h:45-57, mvs/MVS.cpp:334-382 — who the neighbours of a reference view are (the `nei` / R_nr / t_nr arguments of
 // pvlm_mvs_*).  SelectNeighborKNN: the 3 x neighbor_size nearest camera centres (float32, as pcl::KdTreeFLANN returns them),
 // the first hit skipped as "self", candidates closer than the squared distance threshold skipped, the first neighbor_size

@@ -9,6 +9,7 @@
 #include "pvlm_host_structure.hpp"
 #include "../csrc/pvlm_triangulate_core.h"
 #include "pvlm_host_match.hpp"
+#include "pvlm_host_essential.hpp"
 
 namespace pvlm {
 
@@ -237,6 +238,129 @@ bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair
     good_pair.push_back(std::move(g));
   }
   good_pair.swap(image_pairs);
+  return true;
+}
+
+// ---- K34 --------------------------------------------------------------------------------------------------------------------------------
+Matrix3d ComputeEssential(const std::vector<std::array<float, 3>>& points1, const std::vector<std::array<float, 3>>& points2) {
+  if (points1.size() != points2.size()) throw std::invalid_argument("ComputeEssential: list sizes differ");   // upstream asserts
+  Matrix3d E;
+  pvlm_essential::compute_essential(points1.empty() ? nullptr : points1[0].data(), points2.empty() ? nullptr : points2[0].data(), (int)points1.size(), E.data());
+  return E;
+}
+
+bool DecomposeEssential(const Matrix3d& E_21, std::vector<Matrix3d>& rotations, std::vector<Vector3d>& translations) {
+  double R[36], t[12];
+  pvlm_essential::decompose(E_21.data(), R, t);
+  rotations.assign(4, Matrix3d()); translations.assign(4, Vector3d());
+  for (int j = 0; j < 4; ++j) { std::copy(R + 9 * j, R + 9 * j + 9, rotations[(size_t)j].begin()); std::copy(t + 3 * j, t + 3 * j + 3, translations[(size_t)j].begin()); }
+  return true;
+}
+
+Matrix3d FindEssentialACRANSAC(const std::vector<DMatch>& matches, const std::vector<std::array<float, 3>>& points1, const std::vector<std::array<float, 3>>& points2,
+                               const int max_iterations, std::vector<size_t>& inlier_idx, const std::pair<size_t, size_t>& image_pair, const int run,
+                               const EssentialOptions& options) {
+  Matrix3d E{}; inlier_idx.clear();
+  const int n = (int)matches.size();
+  if (n <= pvlm_essential::kMinSample || max_iterations < 1) return E;
+  std::vector<pvlm_essential::Match> m((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (matches[(size_t)i].queryIdx < 0 || (size_t)matches[(size_t)i].queryIdx >= points1.size() || matches[(size_t)i].trainIdx < 0 || (size_t)matches[(size_t)i].trainIdx >= points2.size())
+      throw std::invalid_argument("FindEssentialACRANSAC: a match names a keypoint that is not there");
+    m[(size_t)i] = pvlm_essential::Match{matches[(size_t)i].queryIdx, matches[(size_t)i].trainIdx, matches[(size_t)i].distance};
+  }
+  std::vector<double> tab(2 + 2 * ((size_t)n + 1));
+  pvlm_essential::nfa_tables(n, tab.data());
+  pvlm_essential::ChainResult ch;
+  pvlm_essential::run_chain(points1[0].data(), points2[0].data(), m.data(), n, tab.data(), options.seed, (int)image_pair.first, (int)image_pair.second, run, max_iterations,
+                            options.fresh_sample ? pvlm_essential::kFreshSample : 0u, ch);
+  std::copy(ch.E, ch.E + 9, E.begin());
+  inlier_idx.assign(ch.inliers.begin(), ch.inliers.end());
+  return E;
+}
+
+int CheckRT(const Matrix3d& R_21, const Vector3d& t_21, const std::vector<bool>& is_inlier, const std::vector<DMatch>& matches, const std::vector<std::array<float, 3>>& keypoints1,
+            const std::vector<std::array<float, 3>>& keypoints2, std::vector<Vector3d>& triangulated_points, std::vector<size_t>& inlier_idx) {
+  if (is_inlier.size() != matches.size()) throw std::invalid_argument("CheckRT: is_inlier and matches differ in size");   // upstream asserts
+  double cos_reject;
+  if (!essential_detail::CosReject(&cos_reject)) throw std::runtime_error("CheckRT: this libm's acos is not monotone around 3 degrees");
+  triangulated_points.clear(); inlier_idx.clear();
+  for (size_t i = 0; i < matches.size(); ++i) {
+    if (!is_inlier[i]) continue;
+    Vector3d P;
+    if (pvlm_essential::check_point(R_21.data(), t_21.data(), keypoints1.at((size_t)matches[i].queryIdx).data(), keypoints2.at((size_t)matches[i].trainIdx).data(), cos_reject, P.data())) {
+      triangulated_points.push_back(P); inlier_idx.push_back(i);
+    }
+  }
+  return (int)inlier_idx.size();
+}
+
+namespace {
+// the inputs of the two K34 loops: bearings of every keypoint (eq.ImageToCam(kp.pt), the cv::Point2i overload as everywhere in the SfM stage), pair and match lists
+struct EssentialInputs {
+  std::vector<std::vector<float>> bearings; std::vector<const float*> ptr; std::vector<int> rows, src, tgt; std::vector<long long> off; std::vector<pvlm_match> matches;
+  bool Fill(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs) {
+    bearings.resize(frames.size());
+    for (size_t f = 0; f < frames.size(); ++f) {
+      const Frame& fr = frames[f];
+      bearings[f].resize(3 * fr.keypoints.size() + 3);
+      for (size_t k = 0; k < fr.keypoints.size(); ++k) pvlm_sfm_filter::image_to_cam_point2i(fr.rows, fr.cols, fr.keypoints[k][0], fr.keypoints[k][1], bearings[f].data() + 3 * k);
+      ptr.push_back(bearings[f].data()); rows.push_back((int)fr.keypoints.size());
+    }
+    off.push_back(0);
+    for (const MatchPair& p : image_pairs) {
+      if (p.image_pair.first >= frames.size() || p.image_pair.second >= frames.size()) return false;
+      src.push_back((int)p.image_pair.first); tgt.push_back((int)p.image_pair.second);
+      for (const auto& m : p.matches) {
+        if (m.first < 0 || m.first >= rows[p.image_pair.first] || m.second < 0 || m.second >= rows[p.image_pair.second]) return false;
+        matches.push_back(pvlm_match{m.first, m.second, 0.0f});
+      }
+      off.push_back((long long)matches.size());
+    }
+    return true;
+  }
+};
+RelativePair MakeRelativePair(const MatchPair& p, const double* R, const double* t, const int* idx, const double* tri, long long count) {
+  RelativePair g; g.image_pair = p.image_pair; g.matches = p.matches;
+  std::copy(R, R + 9, g.R_21.begin()); std::copy(t, t + 3, g.t_21.begin());
+  for (long long k = 0; k < count; ++k) { g.inlier_idx.push_back((size_t)idx[k]); g.triangulated.push_back(Vector3d{tri[3 * k], tri[3 * k + 1], tri[3 * k + 2]}); }
+  return g;
+}
+}  // namespace
+
+bool FilterImagePairs(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
+                      const EssentialOptions& options) {
+  StageTimer stage_timer_("FilterImagePairs");
+  EssentialInputs in;
+  if (!in.Fill(frames, image_pairs)) return false;
+  Engine& e = Engine::Default();
+  const size_t np = image_pairs.size();
+  const long long capacity = (long long)in.matches.size();
+  long long needed = 0;
+  std::vector<unsigned char> keep(np); std::vector<double> R(9 * np + 9), t(3 * np + 3), tri(3 * (size_t)capacity + 3); std::vector<long long> off(np + 1, 0);
+  std::vector<int> idx((size_t)capacity + 1);
+  const pvlm_essential_params prm{options.n_runs, options.max_iterations, triangulation_num_threshold, options.seed};
+  e.Check(pvlm_filter_image_pairs(e.ctx(), (int)frames.size(), in.ptr.data(), in.rows.data(), (int)np, in.src.data(), in.tgt.data(), in.off.data(), in.matches.data(), &prm,
+                                  options.fresh_sample ? PVLM_FLAG_ESSENTIAL_FRESH_SAMPLE : 0u, keep.data(), R.data(), t.data(), off.data(), idx.data(), tri.data(), capacity, &needed,
+                                  nullptr), "pvlm_filter_image_pairs");
+  good_pair.clear();
+  for (size_t p = 0; p < np; ++p)
+    if (keep[p]) good_pair.push_back(MakeRelativePair(image_pairs[p], R.data() + 9 * p, t.data() + 3 * p, idx.data() + off[p], tri.data() + 3 * off[p], off[p + 1] - off[p]));
+  return true;
+}
+
+bool FilterImagePairsHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
+                          const EssentialOptions& options, const int num_threads) {
+  EssentialInputs in;
+  if (!in.Fill(frames, image_pairs)) return false;
+  static_assert(sizeof(pvlm_match) == sizeof(pvlm_essential::Match), "the match record of the core is the ABI's");
+  std::vector<pvlm_essential::PairResult> res;
+  if (essential_detail::FilterPairsHost((int)frames.size(), in.ptr.data(), in.rows.data(), (int)image_pairs.size(), in.src.data(), in.tgt.data(), in.off.data(),
+                                        reinterpret_cast<const pvlm_essential::Match*>(in.matches.data()), options.n_runs, options.max_iterations, triangulation_num_threshold,
+                                        options.seed, options.fresh_sample ? pvlm_essential::kFreshSample : 0u, (size_t)std::max(num_threads, 1), res)) return false;
+  good_pair.clear();
+  for (size_t p = 0; p < image_pairs.size(); ++p)
+    if (res[p].keep) good_pair.push_back(MakeRelativePair(image_pairs[p], res[p].R, res[p].t, res[p].inlier_idx.data(), res[p].triangulated.data(), (long long)res[p].inlier_idx.size()));
   return true;
 }
 
