@@ -231,4 +231,38 @@ long long chk_fit_fast(const double* pts, int m, double tol, int quad, double* o
   return wrong;
 }
 
+// The RECORD of an accepted fast fit: decide() stores y = x - M^-1 rho, not the x whose residuals it certified.  Per set, out4 = [1 when the fast fit accepted (else the
+// rest is 0), ||y - x_qr|| with y = n / d recovered from the stored plane, E (the bound the decision was certified under), ||y - x_ref|| against the __float128 solve of the
+// normal equations (quad != 0) ] and, in out4[3] when quad == 0, E_fast (the share of E the derivation gives the fast side).  share[s] = E_fast always.
+void chk_fit_fast_record(const double* pts, int m, double tol, int quad, double* out4, double* share) {
+  for (int s = 0; s < m; ++s) {
+    double px[10], py[10], pz[10];
+    for (int i = 0; i < 10; ++i) { px[i] = pts[(size_t)s * 30 + 3 * i]; py[i] = pts[(size_t)s * 30 + 3 * i + 1]; pz[i] = pts[(size_t)s * 30 + 3 * i + 2]; }
+    double* o = out4 + 4 * (size_t)s;
+    o[0] = o[1] = o[2] = o[3] = 0.0; share[s] = 0.0;
+    double pf[4] = {0, 0, 0, 0}, pall[4], diag[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (Fit10::form_plane_fast(px, py, pz, tol, pf, diag) != 1) continue;
+    Fit10::form_plane(px, py, pz, 1e300, pall);
+    if (!(pall[3] > 0.0) || !(pf[3] > 0.0)) continue;
+    const double y[3] = {pf[0] / pf[3], pf[1] / pf[3], pf[2] / pf[3]}, xq[3] = {pall[0] / pall[3], pall[1] / pall[3], pall[2] / pall[3]};
+    o[0] = 1.0;
+    o[1] = std::sqrt((y[0] - xq[0]) * (y[0] - xq[0]) + (y[1] - xq[1]) * (y[1] - xq[1]) + (y[2] - xq[2]) * (y[2] - xq[2]));
+    o[2] = diag[3]; share[s] = diag[6];
+    if (quad) {
+      __float128 M[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, sv[3] = {0, 0, 0};
+      for (int i = 0; i < 10; ++i) {
+        const __float128 p[3] = {px[i], py[i], pz[i]};
+        for (int a = 0; a < 3; ++a) { sv[a] += p[a]; for (int b = 0; b < 3; ++b) M[a][b] += p[a] * p[b]; }
+      }
+      const __float128 c00 = M[1][1] * M[2][2] - M[1][2] * M[1][2], c01 = M[1][2] * M[0][2] - M[0][1] * M[2][2], c02 = M[0][1] * M[1][2] - M[1][1] * M[0][2];
+      const __float128 c11 = M[0][0] * M[2][2] - M[0][2] * M[0][2], c12 = M[0][1] * M[0][2] - M[0][0] * M[1][2], c22 = M[0][0] * M[1][1] - M[0][1] * M[0][1];
+      const __float128 det = M[0][0] * c00 + M[0][1] * c01 + M[0][2] * c02;
+      const __float128 xr[3] = {-(c00 * sv[0] + c01 * sv[1] + c02 * sv[2]) / det, -(c01 * sv[0] + c11 * sv[1] + c12 * sv[2]) / det, -(c02 * sv[0] + c12 * sv[1] + c22 * sv[2]) / det};
+      double a = 0.0;
+      for (int k = 0; k < 3; ++k) { const double d1 = (double)((__float128)y[k] - xr[k]); a += d1 * d1; }
+      o[3] = std::sqrt(a);
+    }
+  }
+}
+
 }  // extern "C"

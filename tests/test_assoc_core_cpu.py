@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from panovlm_amd import synthetic as sy
+from tests import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -227,19 +228,19 @@ def _fit_fast(lib, pts, tol, quad=False):
     return wrong, out, plane
 
 
+def _fit_fast_record(lib, pts, tol, quad=False):
+    """The stored record of the accepted sets (y = x - M^-1 rho, recovered from the plane): accepted mask, ||y - x_qr||, E, ||y - quad solve||, E_fast."""
+    pts = np.ascontiguousarray(pts, np.float64)
+    out = np.zeros((len(pts), 4)); share = np.zeros(len(pts))
+    lib.chk_fit_fast_record(_p(pts, ctypes.c_double), len(pts), ctypes.c_double(tol), 1 if quad else 0, _p(out, ctypes.c_double), _p(share, ctypes.c_double))
+    return out[:, 0] == 1, out[:, 1], out[:, 2], out[:, 3], share
+
+
 def _planar_sets(rng, m, tol, near_threshold=False, far=False):
-    """Neighbourhoods like the association sees them: a patch of spread 0.1-0.6 m at 1-40 m (far: up to 300 m) from the sensor, out-of-plane noise
-    drawn so that the largest distance lands anywhere from well inside to well outside the tolerance (near_threshold: within 1e-6 relative of it)."""
-    c = rng.normal(size=(m, 3)); c /= np.linalg.norm(c, axis=1, keepdims=True)
-    c *= rng.uniform(1.0, 300.0 if far else 40.0, size=(m, 1))
-    B = np.linalg.qr(rng.normal(size=(m, 3, 3)))[0]
-    spread = rng.uniform(0.1, 0.6, size=(m, 1, 1)) * np.array([1.0, 1.0, 0.0]) * rng.uniform(0.6, 1.0, size=(m, 1, 3))
-    local = rng.normal(size=(m, 10, 3)) * spread
-    noise = rng.normal(size=(m, 10)) * tol * rng.uniform(0.0, 1.2, size=(m, 1))
-    if near_threshold:       # scale the noise so that the exact fit's largest distance sits within ~1e-7 .. 1e-12 of the tolerance
-        noise = rng.normal(size=(m, 10)) * tol * 0.4
-    local[:, :, 2] = noise
-    return c[:, None, :] + np.einsum("mij,mkj->mik", local, B)
+    """Neighbourhoods like the association sees them (tests/synth.py: planar_patches — the GPU tests of the default mode draw their patches from the same
+    construction): a patch of spread 0.1-0.6 m at 1-40 m (far: up to 300 m) from the sensor, out-of-plane noise drawn so that the largest distance lands
+    anywhere from well inside to well outside the tolerance (near_threshold: 0.4 tol, which the caller bisects onto it)."""
+    return synth.planar_patches(rng, m, tol, near_threshold=near_threshold, far=far)[0]
 
 
 def test_certified_fast_fit_takes_the_exact_fits_decisions(chk):
@@ -249,7 +250,7 @@ def test_certified_fast_fit_takes_the_exact_fits_decisions(chk):
     to 5e-7 relative by construction, 1e-11 typically (that is the record the residual set stores; the bar of the path is 1e-6)."""
     rng = np.random.default_rng(31)
     total = decided = 0
-    worst_ratio = 0.0
+    worst_ratio = worst_record = 0.0
     for tol in (0.05, 0.01):
         for far in (False, True):
             pts = _planar_sets(rng, 400_000, tol, far=far)
@@ -259,6 +260,12 @@ def test_certified_fast_fit_takes_the_exact_fits_decisions(chk):
             assert np.all(out[have, 3] <= out[have, 2]), "||x - x_qr|| above the bound E"
             assert np.all(out[have, 7] <= out[have, 6] + 1e-300), "distance bound B violated"
             worst_ratio = max(worst_ratio, float((out[have, 3] / out[have, 2]).max()))
+            # the vector that is STORED: the accepted record, corrected by the streamed residuals, stays under the same bound — and closer than x did
+            acc_y, dy, E_y, _, _ = _fit_fast_record(chk, pts, tol)
+            assert np.array_equal(acc_y, out[:, 0] == 1)
+            assert np.all(dy[acc_y] <= E_y[acc_y]), "||y - x_qr|| above the bound E"
+            worst_record = max(worst_record, float((dy[acc_y] / E_y[acc_y]).max()))
+            assert np.median(dy[acc_y]) <= np.median(out[acc_y, 3])
             dec = out[:, 0] >= 0
             if not far:                                                                # beyond 40 m at grazing incidence the systems are refused (condition cap): correct, just not fast
                 total += len(pts); decided += int(dec.sum())
@@ -270,6 +277,8 @@ def test_certified_fast_fit_takes_the_exact_fits_decisions(chk):
             assert rel.max() <= 5e-7 and np.median(rel.max(axis=1)) <= 1e-11, (rel.max(), np.median(rel.max(axis=1)))   # guaranteed (e <= 2.5e-7) / typical
     assert decided >= 0.98 * total, (decided, total)                               # up to 40 m at random incidence; indoor ranges: > 0.9999 (bench.py reports the rate)
     assert worst_ratio < 0.2, worst_ratio                                          # the bound has room (it is built from worst-case constants)
+    print("largest ||x - x_qr|| / E %.3g, of the stored record ||y - x_qr|| / E %.3g" % (worst_ratio, worst_record))
+    assert worst_record < 0.2, worst_record
     # the sets of the collinearity / degeneracy tests: lines, blobs, exactly coplanar lattices (rank-deficient systems are refused, never decided wrongly)
     pts = _point_sets(rng, 60_000)
     for tol in (0.05, 0.01):
@@ -318,6 +327,9 @@ def test_certified_fast_fit_near_the_tolerance_and_against_quad_precision(chk):
     have = out[:, 2] > 0
     assert np.all(out[have, 4] <= out[have, 2]) and np.all(out[have, 5] <= out[have, 6]), "a distance to the exact minimiser exceeds its share of the bound"
     assert (out[have, 4] / out[have, 2]).max() < 0.2 and (out[have, 5] / out[have, 6]).max() < 0.05       # with room: the shares are built from worst-case constants
+    acc_y, _, _, dq, share = _fit_fast_record(chk, pts, tol, quad=True)
+    assert acc_y.sum() > 3000 and np.all(dq[acc_y] <= share[acc_y]), "the stored record lies further from the exact minimiser than E_fast allows"
+    assert (dq[acc_y] / share[acc_y]).max() < 0.2
 
 
 def test_collinearity_from_the_moments_takes_the_exact_decision(chk):

@@ -3,7 +3,9 @@ compaction, line votes) against the CPU oracle through the C ABI.  Bar: correspo
 bit-exact in both modes of the plane fit; fp64 records bit-exact with PVLM_FLAG_ASSOC_EXACT_FIT (the
 reference's QR restated, no FMA contraction), and within 1e-6 relative in the default mode, where the
 plane comes from the certified fast fit (csrc/pvlm_assoc_core.h: form_plane_fast — its bound keeps the
-record within 5e-7 of the QR's; observed ~1e-11) and only the accept / reject DECISION is the QR's."""
+record within 5e-7 of the QR's; observed ~1e-11) and only the accept / reject DECISION is the QR's.
+The default mode itself — its in-kernel fall-back, the probe switch, residuals and Jacobians against the exact mode — is pinned in
+tests/test_assoc_default_mode_gpu.py."""
 import numpy as np
 import pytest
 
