@@ -52,9 +52,18 @@ def knn2_from_d2(d2):
     return idx, val
 
 
+def d2_matrix_int(A, B):
+    """d2_matrix(A, B, np.int64) for integer-valued descriptors in 0..255 without the n1 x n2 x 128 cube: |a|^2 + |b|^2 - 2 a.b through a float64 matmul.
+    Every term and every partial sum is an integer below 128 * 255^2 * 4 < 2^25, so float64 is exact whatever order the matmul adds in."""
+    A = _desc(A).astype(np.float64); B = _desc(B).astype(np.float64)
+    for M in (A, B):
+        assert (M == np.rint(M)).all() and (M >= 0).all() and (M <= 255).all()
+    return ((A * A).sum(1)[:, None] + (B * B).sum(1)[None, :] - 2.0 * (A @ B.T)).astype(np.int64)
+
+
 def ref_knn2_int(A, B):
     """Integer-valued descriptors: (idx, dist float32) exactly as the definition gives them."""
-    idx, val = knn2_from_d2(d2_matrix(A, B, np.int64))
+    idx, val = knn2_from_d2(d2_matrix_int(A, B))
     return idx, np.sqrt(val.astype(np.float32))                     # a d2 < 2^24 is exact in float32; float32 sqrt is correctly rounded
 
 
