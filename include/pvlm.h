@@ -405,6 +405,41 @@ pvlm_status pvlm_filter_image_pairs(pvlm_ctx* ctx, int n_frames, const float* co
                                     long long* inlier_offsets /* n_pairs + 1 */, int* inlier_idx, double* triangulated /* 3 per inlier */, long long capacity,
                                     long long* needed, pvlm_essential_stats* stats_or_null);
 
+/* ---- K35: VLAD image retrieval (sfm/VLAD.cpp: Kmeans :46-95, ComputeVLADEmbedding :97-154, FindNeighbors :156-183; SfM::InitImagePairs sfm/SfM.cpp:49-168) ---- *
+ * The definition (csrc/pvlm_vlad_core.h).  Nearest centre: of the alive centres the one with the smallest (d2, centre index), d2 the fmaf chain of K33, an exact tie
+ * to the lower index.  k-means: assign[i] = 0 at the start (part of upstream's "changed" test); the initial centres are copies of the training rows init_rows names
+ * (indices into the concatenation of the train frames' rows, in list order; duplicates are allowed); a pass assigns every row, sets `changed` where that differs from
+ * assign[i], and recomputes every alive centre; passes repeat while changed and fewer than max_iterations have run; max_iterations == 0 returns the initial rows.
+ * Embedding: per row the residual against its nearest alive centre in float, type 2 divides it by its fp64 norm; block[c] += residual in float, rows ascending; per
+ * block type 0 sign sqrtf(|v|), type 1 v / norm(block), type 2 sign root5(|v|) (a fifth root by IEEE + * / only: within one float ulp of (float)pow((double)x, 0.2),
+ * see the header); then the whole vector is divided by its fp64 norm.  Neighbours: sim(i, j) the fp64 chain of the exact products, k ascending; row i lists the first
+ * min(neighbor_size, n) frames in ascending (-sim, index), the frame itself included wherever it lands.
+ * [recalled] upstream leaves every summation to OpenCV (cv::BFMatcher, cv::norm, the dot and += of cv::Mat); those orders are not pinned.  The header fixes its own.
+ * Deliberate divergences: the mean of a centre is (float)(S / (double)count) with S an fp64 sum in a fixed order (members ascending, runs of 256, run sums ascending;
+ * upstream: float Mat arithmetic); a centre without members is DEAD (alive[c] = 0, its row zeros, never a candidate again, its VLAD block zero; upstream: a NaN row
+ * that no comparison ever selects, the same outcome); a row equal to its centre contributes nothing to a type 2 vector (upstream: 0/0 turns the whole vector NaN); a
+ * zero block stays zero under type 1, a zero vector (a frame without descriptors) stays zero (upstream: NaN).
+ * pvlm_vlad_kmeans: codebook (book_size x 128), alive (book_size), optionally assign (one per training row).  stats: queries and fallback_queries summed over the
+ *   passes, iterations = passes run, dead_centres, batches = row batches per pass.
+ * pvlm_vlad_embed: one vector per frame of the set, kept on the device in a pvlm_vladset (pvlm_vladset_read copies them out).  alive_or_null: NULL = every centre.
+ * pvlm_vlad_neighbors: n_frames x min(neighbor_size, n_frames) indices; sim_or_null: the n_frames x n_frames similarities, copied out only on request.
+ * PVLM_ERR_ARG: book_size < 1 or above 4096, more centres than training rows, an init_rows entry or a frame index out of range, max_iterations < 0, a value that
+ * is not finite in an alive row of the codebook, normalization outside 0..2, neighbor_size < 1, a set or vladset used with another context.
+ * flags: PVLM_FLAG_MATCH_EXACT as in K33 (the assignment is K33's search with the packed alive centres as the train side); bit-identical results in both modes.
+ * The rows are worked through in batches of whole frames of up to 2^18 rows; the environment variable PVLM_VLAD_BATCH_ROWS (read at every call) lowers that.  It
+ * changes no result; the tests use it to cross batch boundaries on small inputs. */
+typedef struct pvlm_vladset pvlm_vladset;
+typedef struct pvlm_vlad_stats { long long queries, fallback_queries; int iterations, dead_centres, batches; } pvlm_vlad_stats;
+pvlm_status pvlm_vlad_kmeans(pvlm_ctx* ctx, const pvlm_descset* set, int n_train, const int* train_frames, int book_size, int max_iterations,
+                             const long long* init_rows /* book_size */, unsigned flags, float* codebook /* book_size x 128 */, unsigned char* alive /* book_size */,
+                             int* assign_or_null /* one per training row */, pvlm_vlad_stats* stats_or_null);
+pvlm_status pvlm_vlad_embed(pvlm_ctx* ctx, const pvlm_descset* set, int book_size, const float* codebook, const unsigned char* alive_or_null,
+                            int normalization /* 0, 1, 2 as VLAD.h */, unsigned flags, pvlm_vladset** out, pvlm_vlad_stats* stats_or_null);
+pvlm_status pvlm_vladset_read(pvlm_ctx* ctx, const pvlm_vladset* set, float* out /* n_frames x 128 book_size */);
+pvlm_status pvlm_vlad_neighbors(pvlm_ctx* ctx, const pvlm_vladset* set, int neighbor_size, int* neighbors /* n_frames x min(neighbor_size, n_frames) */,
+                                double* sim_or_null /* n_frames x n_frames */);
+void pvlm_vladset_destroy(pvlm_ctx* ctx, pvlm_vladset* set);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

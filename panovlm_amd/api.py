@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "pvlm_triangulate_tracks", "pvlm_filter_tracks_far",
     "pvlm_descset_create", "pvlm_descset_destroy", "pvlm_match_knn2", "pvlm_match_pairs",
     "pvlm_essential_acransac", "pvlm_filter_image_pairs",
+    "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
     "pvlm_resset_plane_runs",
 ]
 
@@ -1382,6 +1383,72 @@ def match_pairs(ctx, descset, src, tgt, ratio, matches_threshold, flags=0, capac
     return dict(keep=keep, offsets=off, matches=out[:min(needed.value, cap)], needed=needed.value, overflow=rc == -5,
                 guard_intact=bool(np.all(g["query"] == -7) and np.all(g["train"] == -7) and np.all(g["distance"] == -7.0)),
                 stats=dict(queries=st.queries, fallback_queries=st.fallback_queries, batches=st.batches))
+
+
+class VladStats(C.Structure):
+    _fields_ = [("queries", C.c_longlong), ("fallback_queries", C.c_longlong), ("iterations", C.c_int), ("dead_centres", C.c_int), ("batches", C.c_int)]
+
+
+def _vlad_stats(st):
+    return dict(queries=st.queries, fallback_queries=st.fallback_queries, iterations=st.iterations, dead_centres=st.dead_centres, batches=st.batches)
+
+
+def vlad_kmeans(ctx, descset, train_frames, book_size, max_iterations, init_rows, flags=0):
+    """pvlm_vlad_kmeans (K35): the k-means codebook of sfm/VLAD.cpp over the rows of the train frames.  init_rows: book_size indices into the concatenation of the train
+    frames' rows, in list order.  Returns (codebook book_size x 128 float32, alive uint8, assign int32 per training row, stats dict)."""
+    tf = _i32(train_frames); init = _i64(init_rows)
+    ok = (tf >= 0) & (tf < len(descset.rows))
+    n = int(descset.rows[tf[ok]].sum()) if len(tf) else 0
+    if len(init) != book_size:
+        raise PvlmError("vlad_kmeans: %d init_rows for %d centres" % (len(init), book_size))
+    codebook = np.zeros((max(book_size, 0), 128), np.float32); alive = np.zeros(max(book_size, 0), np.uint8); assign = np.zeros(n, np.int32)
+    st = VladStats()
+    ctx._check(ctx.lib.pvlm_vlad_kmeans(ctx._h, descset._h, C.c_int(len(tf)), _p(tf, C.c_int), C.c_int(book_size), C.c_int(max_iterations), _p(init, C.c_longlong),
+                                        C.c_uint(flags), _p(codebook, C.c_float), _p(alive, C.c_ubyte), _p(assign, C.c_int), C.byref(st)), "pvlm_vlad_kmeans")
+    return codebook, alive, assign, _vlad_stats(st)
+
+
+class VladSet:
+    """pvlm_vladset (K35): the VLAD vectors of the frames of a DescSet, resident on the device."""
+
+    def __init__(self, ctx, handle, n_frames, book_size, stats):
+        self.ctx, self._h, self.n_frames, self.book_size, self.stats = ctx, handle, n_frames, book_size, stats
+
+    def read(self):
+        out = np.zeros((self.n_frames, 128 * self.book_size), np.float32)
+        self.ctx._check(self.ctx.lib.pvlm_vladset_read(self.ctx._h, self._h, _p(out, C.c_float)), "pvlm_vladset_read")
+        return out
+
+    def close(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.pvlm_vladset_destroy(self.ctx._h, self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vlad_embed(ctx, descset, codebook, alive=None, normalization=2, flags=0):
+    """pvlm_vlad_embed (K35): the VLAD vector of every frame of the set (normalization 0, 1, 2 as VLAD.h).  Returns a VladSet (read(), close(), stats)."""
+    cb = np.ascontiguousarray(codebook, np.float32).reshape(-1, 128)
+    a = None if alive is None else np.ascontiguousarray(alive, np.uint8)
+    h = C.c_void_p(); st = VladStats()
+    ctx._check(ctx.lib.pvlm_vlad_embed(ctx._h, descset._h, C.c_int(len(cb)), _p(cb, C.c_float), None if a is None else _p(a, C.c_ubyte), C.c_int(normalization),
+                                       C.c_uint(flags), C.byref(h), C.byref(st)), "pvlm_vlad_embed")
+    return VladSet(ctx, h, len(descset.rows), len(cb), _vlad_stats(st))
+
+
+def vlad_neighbors(ctx, vladset, neighbor_size, want_sim=False):
+    """pvlm_vlad_neighbors (K35): per frame its min(neighbor_size, n) most similar frames by inner product (itself included).  Returns (neighbors int32, sim float64
+    n x n or None)."""
+    n = vladset.n_frames
+    nb = np.zeros((n, max(min(neighbor_size, n), 0)), np.int32)
+    sim = np.zeros((n, n), np.float64) if want_sim else None
+    ctx._check(ctx.lib.pvlm_vlad_neighbors(ctx._h, vladset._h, C.c_int(neighbor_size), _p(nb, C.c_int), None if sim is None else _p(sim, C.c_double)), "pvlm_vlad_neighbors")
+    return nb, sim
 
 
 class EssentialParams(C.Structure):

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip")
 
 
 def _hipcc():
@@ -116,6 +116,7 @@ SFM_DRIVER = os.path.join(HERE, "build", "pvlm_sfm_driver")
 STRUCTURE_DRIVER = os.path.join(HERE, "build", "pvlm_structure_driver")
 MATCH_DRIVER = os.path.join(HERE, "build", "pvlm_match_driver")
 ESSENTIAL_DRIVER = os.path.join(HERE, "build", "pvlm_essential_driver")
+VLAD_DRIVER = os.path.join(HERE, "build", "pvlm_vlad_driver")
 
 
 def build_host(force=False):
@@ -185,6 +186,12 @@ def build_host(force=False):
     if os.path.exists(edrv) and (force or not os.path.exists(ESSENTIAL_DRIVER) or
                                  os.path.getmtime(ESSENTIAL_DRIVER) < max(os.path.getmtime(edrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", edrv, "-o", ESSENTIAL_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    # the retrieval driver (InitImagePairs into MatchImagePairs: K35)
+    vdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_vlad_driver.cpp")
+    if os.path.exists(vdrv) and (force or not os.path.exists(VLAD_DRIVER) or
+                                 os.path.getmtime(VLAD_DRIVER) < max(os.path.getmtime(vdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", vdrv, "-o", VLAD_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     return HOST_LIB
 

@@ -20,16 +20,8 @@
 #include "pvlm_internal.h"
 #include "pvlm_compact.h"
 #include "pvlm_match_core.h"
-
-struct pvlm_descset {
-  pvlm_ctx* owner = nullptr;       // the context whose pool holds the arrays: the only one the set may be used with
-  int n_frames = 0;
-  std::vector<int> rows;
-  std::vector<long long> row0;     // first row of every frame in d_desc / d_norm
-  std::vector<float> nmax;         // the largest norm2 of every frame
-  float* d_desc = nullptr;
-  float* d_norm = nullptr;
-};
+#include "pvlm_match_launch.h"
+#include "pvlm_descset.h"
 
 namespace {
 
@@ -39,22 +31,18 @@ using pvlm_matching::Knn2;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kScreenQ = 128;                 // queries per block of k_match_screen
+using pvlm_match_launch::PairDesc;
+using pvlm_match_launch::QTile;
+using pvlm_match_launch::KnnRec;
 constexpr int kScreenT = 64;                  // train rows per LDS tile
 constexpr int kLd = kDim + 4;                 // LDS row stride: 16 rows x 4 floats cover the banks once
 constexpr long long kBatchQueries = 1ll << 20;
 constexpr int kBatchPairs = 8192;
 
-struct PairDesc {
-  const float* a; const float* b; const float* na; const float* nb;
-  int n1, n2, q0; float nbmax;
-  int tile0, n_tiles;
-};
 struct TileDesc {                             // first query inside the pair, queries (<= kTile), pair
   int p0, n, pair, pad;
   static TileDesc make(int p0, int n, int pair, long long) { return TileDesc{p0, n, pair, 0}; }
 };
-struct QTile { int pair, q0; };
-struct KnnRec { int i0, i1; float d0, d1; };  // squared distances
 
 __global__ __launch_bounds__(256) void k_desc_norms(const float* __restrict__ desc, long long n_rows, float* __restrict__ norm, int* __restrict__ bad) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -339,7 +327,7 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
   const bool exact = (flags & PVLM_FLAG_MATCH_EXACT) != 0;
   const Batches bt = make_batches(set, n_pairs, src);
   const size_t Q = (size_t)std::max<long long>(bt.qcap, 1), PB = (size_t)bt.pcap;
-  const size_t TB = Q / kTile + PB + 1, QT = Q / kScreenQ + PB + 1;
+  const size_t TB = Q / kTile + PB + 1, QT = pvlm_match_launch::qtile_capacity(Q, PB);
   pvlm_pinned_lease lease(ctx, keep ? Q * sizeof(pvlm_match) : 1);
   if (!lease.p) { PVLM_SET_ERR(ctx, "%s: pinned memory unavailable", who); return PVLM_ERR_NOMEM; }
   pvlm_dev_scratch tmp(ctx);
@@ -359,11 +347,11 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
   if (!st && keep) st = tmp.alloc(&d_out, Q);
   if (st) return st;
   hipStream_t S = ctx->stream;
-  std::vector<PairDesc> pd; std::vector<QTile> qts; std::vector<TileDesc> tiles; std::vector<int> n1s, h_keep; std::vector<long long> h_per; std::vector<KnnRec> h_knn;
+  std::vector<PairDesc> pd; std::vector<TileDesc> tiles; std::vector<int> n1s, h_keep; std::vector<long long> h_per; std::vector<KnnRec> h_knn;
   long long q_done = 0, written = 0, total = 0;
   for (size_t bi = 0; bi + 1 < bt.first.size() && !st; ++bi) {
     const int p0 = bt.first[bi], np = bt.first[bi + 1] - p0;
-    pd.assign((size_t)np, PairDesc()); qts.clear(); n1s.assign((size_t)np, 0);
+    pd.assign((size_t)np, PairDesc()); n1s.assign((size_t)np, 0);
     long long nq = 0;
     for (int k = 0; k < np; ++k) {
       const int s = src[p0 + k], t = tgt[p0 + k];
@@ -372,27 +360,11 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
       P.na = set->d_norm + set->row0[(size_t)s]; P.nb = set->d_norm + set->row0[(size_t)t];
       P.n1 = set->rows[(size_t)s]; P.n2 = set->rows[(size_t)t]; P.q0 = (int)nq; P.nbmax = set->nmax[(size_t)t];
       n1s[(size_t)k] = P.n1;
-      for (int q0 = 0; q0 < P.n1; q0 += kScreenQ) qts.push_back(QTile{k, q0});
       nq += P.n1;
     }
     make_tiles(n1s.data(), np, pd.data(), tiles);
     int fb = 0;
-    st = pvlm_i_h2d_q(ctx, d_pairs, pd.data(), (size_t)np * sizeof(PairDesc));
-    if (!st && nq > 0) {
-      if (exact) {
-        hipLaunchKernelGGL(k_match_exact, dim3((unsigned)std::min<long long>((nq + 3) / 4, 8192)), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)nullptr,
-                           (const int*)nullptr, (int)nq, d_knn);
-      } else {
-        st = pvlm_i_h2d_q(ctx, d_qt, qts.data(), qts.size() * sizeof(QTile));
-        if (!st && hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), S) != hipSuccess) st = PVLM_ERR_HIP;
-        if (!st) {
-          hipLaunchKernelGGL(k_match_screen, dim3((unsigned)qts.size()), dim3(256), 0, S, (const PairDesc*)d_pairs, (const QTile*)d_qt, d_knn, d_fb, d_cnt);
-          hipLaunchKernelGGL(k_match_exact, dim3(2048), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)d_fb, (const int*)d_cnt, 0, d_knn);
-          st = pvlm_i_d2h_q(ctx, &fb, d_cnt, sizeof(int));
-        }
-      }
-    }
-    if (!st && hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; }
+    st = pvlm_match_launch::knn_batch(ctx, who, pd.data(), np, nq, exact, d_pairs, d_qt, d_knn, d_fb, d_cnt, &fb);
     if (st) break;
     if (!keep) {                                              // knn2: indices and distances of every query
       h_knn.resize((size_t)nq);
@@ -443,6 +415,40 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
 
 }  // namespace
 
+size_t pvlm_match_launch::qtile_capacity(size_t queries, size_t pairs) { return queries / kScreenQ + pairs + 1; }
+
+pvlm_status pvlm_match_launch::knn_batch(pvlm_ctx* ctx, const char* who, const PairDesc* pd, int np, long long nq, bool exact, PairDesc* d_pairs, QTile* d_qt, KnnRec* d_knn,
+                                         int2* d_fb, int* d_cnt, int* fallback) {
+  hipStream_t S = ctx->stream;
+  *fallback = exact ? (int)nq : 0;
+  pvlm_status st = pvlm_i_h2d_q(ctx, d_pairs, pd, (size_t)np * sizeof(PairDesc));
+  if (!st && nq > 0) {
+    if (exact) {
+      hipLaunchKernelGGL(k_match_exact, dim3((unsigned)std::min<long long>((nq + 3) / 4, 8192)), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)nullptr,
+                         (const int*)nullptr, (int)nq, d_knn);
+    } else {
+      std::vector<QTile> qts;                                 // copied into the staging arena when the copy is queued
+      for (int k = 0; k < np; ++k) for (int q0 = 0; q0 < pd[k].n1; q0 += kScreenQ) qts.push_back(QTile{k, q0});
+      st = pvlm_i_h2d_q(ctx, d_qt, qts.data(), qts.size() * sizeof(QTile));
+      if (!st && hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), S) != hipSuccess) st = PVLM_ERR_HIP;
+      if (!st) {
+        hipLaunchKernelGGL(k_match_screen, dim3((unsigned)qts.size()), dim3(256), 0, S, (const PairDesc*)d_pairs, (const QTile*)d_qt, d_knn, d_fb, d_cnt);
+        hipLaunchKernelGGL(k_match_exact, dim3(2048), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)d_fb, (const int*)d_cnt, 0, d_knn);
+        st = pvlm_i_d2h_q(ctx, fallback, d_cnt, sizeof(int));
+      }
+    }
+  }
+  if (!st && hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; }
+  return st;
+}
+
+pvlm_status pvlm_match_launch::row_norms(pvlm_ctx* ctx, const char* who, const float* desc, long long n_rows, float* norm, int* bad) {
+  if (n_rows <= 0) return PVLM_OK;
+  hipLaunchKernelGGL(k_desc_norms, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, desc, n_rows, norm, bad);
+  if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); return PVLM_ERR_HIP; }
+  return PVLM_OK;
+}
+
 extern "C" pvlm_status pvlm_descset_create(pvlm_ctx* ctx, int n_frames, const int* rows, int width, const float* const* descs, pvlm_descset** out) {
   if (!ctx || !out || n_frames < 0 || (n_frames > 0 && (!rows || !descs))) return PVLM_ERR_ARG;
   *out = nullptr;
@@ -465,10 +471,7 @@ extern "C" pvlm_status pvlm_descset_create(pvlm_ctx* ctx, int n_frames, const in
   for (int f = 0; f < n_frames && !st; ++f)
     if (rows[f] > 0) st = pvlm_i_h2d_q(ctx, s->d_desc + s->row0[(size_t)f] * kDim, descs[f], (size_t)rows[f] * kDim * sizeof(float));
   if (!st && hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream) != hipSuccess) st = PVLM_ERR_HIP;
-  if (!st && total > 0) {
-    hipLaunchKernelGGL(k_desc_norms, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)s->d_desc, total, s->d_norm, d_bad);
-    if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_descset_create: kernel launch failed"); st = PVLM_ERR_HIP; }
-  }
+  if (!st) st = pvlm_match_launch::row_norms(ctx, "pvlm_descset_create", s->d_desc, total, s->d_norm, d_bad);
   if (!st && total > 0) st = pvlm_i_d2h_q(ctx, norm.data(), s->d_norm, (size_t)total * sizeof(float));
   if (!st) st = pvlm_i_d2h_q(ctx, &bad, d_bad, sizeof(int));
   { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }

@@ -674,6 +674,47 @@ bool FilterImagePairs(const std::vector<Frame>& frames, const std::vector<MatchP
 bool FilterImagePairsHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
                           const EssentialOptions& options = EssentialOptions(), const int num_threads = 16);
 
+// ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------
+// base/common.h's FrameMatchMethod and sfm/VLAD.h's normalisation types
+enum FrameMatchMethod { EXHAUSTIVE = 1, CONTIGUOUS = 2, VLAD = 4, GPS = 8, GPS_VLAD = 16 };
+enum VLADNormalization { SIGNED_SQUARE_ROOTING = 0, INTRA_NORMALIZATION = 1, RESIDUAL_NORMALIZATION_PWR_LAW = 2 };
+// sfm/VLAD.h's VLADMatcher on the GPU (K35): the three steps keep upstream's signatures.  The descriptors go to the device once, in the constructor (or the caller's
+// set is used); the codebook is learned by pvlm_vlad_kmeans, the vectors stay on the device (pvlm_vlad_embed), the neighbour lists come from pvlm_vlad_neighbors.
+// The draws (the `ratio` subset of the frames, the initial centre rows: distinct indices, unsorted, as CreateRandomArray gives them) come from a generator seeded
+// with `seed` (upstream: an unseeded std::mt19937; there is nothing to be equal to).  host = true runs the same three steps through the host loops of
+// csrc/pvlm_vlad_core.h on num_threads workers (no device): the baseline and the equality partner.
+class VLADMatcher {
+ public:
+  VLADMatcher(const std::vector<Frame>& frames, const int normalization_type = RESIDUAL_NORMALIZATION_PWR_LAW, const unsigned long long seed = 0, const bool host = false,
+              const int num_threads = 16, pvlm_descset* set = nullptr);
+  ~VLADMatcher();
+  VLADMatcher(const VLADMatcher&) = delete;
+  VLADMatcher& operator=(const VLADMatcher&) = delete;
+  bool GenerateCodeBook(float ratio, const int book_size = 128, const int max_iteration = 25);
+  bool ComputeVLADEmbedding();
+  std::vector<std::vector<size_t>> FindNeighbors(int neighbor_size);
+  const std::vector<float>& GetCodeBook() const { return codebook_; }
+  const std::vector<unsigned char>& GetAlive() const { return alive_; }
+ private:
+  const std::vector<Frame>& frames_;
+  int normalization_type_, num_threads_, book_size_ = 0;
+  unsigned long long seed_;
+  bool host_, own_set_ = false, valid_ = true;
+  pvlm_descset* set_ = nullptr;
+  pvlm_vladset* vlad_ = nullptr;
+  std::vector<float> codebook_, host_vlad_;
+  std::vector<unsigned char> alive_;
+};
+// SfM::InitImagePairs (sfm/SfM.cpp:49-168) for EXHAUSTIVE, CONTIGUOUS (window 20) and VLAD (max(n / 40, 15) neighbours, ratio 0.5, 128 words, 25 iterations), with
+// upstream's pair order and its de-duplication set; the VLAD part on the GPU (K35), the descriptor set created once.  GPS and GPS_VLAD return false and leave
+// image_pairs untouched (the mirror's Frame has no GPS), as does a frame whose descriptor is not 128 floats per keypoint.  Otherwise true when there is a pair.
+// book_size is upstream's default; the tests pass a smaller one for their small scenes.
+bool InitImagePairs(const std::vector<Frame>& frames, const int frame_match_type, std::vector<MatchPair>& image_pairs, const unsigned long long seed = 0,
+                    const int book_size = 128);
+// the same through the host loops of the core on num_threads workers: the baseline tools/vlad_bench.py times and the equality partner of the tests
+bool InitImagePairsHost(const std::vector<Frame>& frames, const int frame_match_type, std::vector<MatchPair>& image_pairs, const unsigned long long seed = 0,
+                        const int book_size = 128, const int num_threads = 16);
+
 // ---- mvs/MVS.h:45-57, mvs/MVS.cpp:334-382 — who the neighbours of a reference view are (the `nei` / R_nr / t_nr arguments of
 // pvlm_mvs_*).  SelectNeighborKNN: the 3 x neighbor_size nearest camera centres (float32, as pcl::KdTreeFLANN returns them),
 // the first hit skipped as "self", candidates closer than the squared distance threshold skipped, the first neighbor_size

@@ -10,6 +10,7 @@
 #include "../csrc/pvlm_triangulate_core.h"
 #include "pvlm_host_match.hpp"
 #include "pvlm_host_essential.hpp"
+#include "pvlm_host_vlad.hpp"
 
 namespace pvlm {
 
@@ -239,6 +240,129 @@ bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair
   }
   good_pair.swap(image_pairs);
   return true;
+}
+
+// ---- K35 --------------------------------------------------------------------------------------------------------------------------------
+namespace {
+bool DescLists(const std::vector<Frame>& frames, std::vector<int>* rows, std::vector<const float*>* desc) {
+  for (const Frame& f : frames) {
+    if (f.descriptor.size() != 128 * f.keypoints.size()) return false;
+    rows->push_back((int)f.keypoints.size()); desc->push_back(f.descriptor.data());
+  }
+  return true;
+}
+}  // namespace
+
+VLADMatcher::VLADMatcher(const std::vector<Frame>& frames, const int normalization_type, const unsigned long long seed, const bool host, const int num_threads, pvlm_descset* set)
+    : frames_(frames), normalization_type_(normalization_type), num_threads_(std::max(num_threads, 1)), seed_(seed), host_(host), set_(set) {
+  std::vector<int> rows; std::vector<const float*> desc;
+  valid_ = DescLists(frames, &rows, &desc);
+  if (!valid_ || host_ || set_) return;
+  Engine& e = Engine::Default();
+  e.Check(pvlm_descset_create(e.ctx(), (int)frames.size(), rows.data(), 128, desc.data(), &set_), "pvlm_descset_create");
+  own_set_ = true;
+}
+
+VLADMatcher::~VLADMatcher() {
+  if (!vlad_ && !own_set_) return;
+  Engine& e = Engine::Default();
+  if (vlad_) pvlm_vladset_destroy(e.ctx(), vlad_);
+  if (own_set_) pvlm_descset_destroy(e.ctx(), set_);
+}
+
+bool VLADMatcher::GenerateCodeBook(float ratio, const int book_size, const int max_iteration) {
+  if (!valid_ || ratio > 1 || ratio < 0) return false;
+  std::vector<int> rows; std::vector<const float*> desc;
+  DescLists(frames_, &rows, &desc);
+  vlad_detail::Rng rng(seed_);
+  std::vector<int> train;
+  if (ratio < 1) for (long long f : vlad_detail::DrawDistinct((long long)(ratio * frames_.size()), (long long)frames_.size(), rng)) train.push_back((int)f);
+  else for (size_t f = 0; f < frames_.size(); ++f) train.push_back((int)f);
+  long long n = 0;
+  for (int f : train) n += rows[(size_t)f];
+  if (book_size < 1 || book_size > n) return false;
+  const std::vector<long long> init = vlad_detail::DrawDistinct(book_size, n, rng);
+  codebook_.assign((size_t)book_size * 128, 0.0f); alive_.assign((size_t)book_size, 0); book_size_ = book_size;
+  if (host_)
+    return vlad_detail::KmeansHost((int)frames_.size(), desc.data(), rows.data(), (int)train.size(), train.data(), book_size, max_iteration, init.data(), (size_t)num_threads_,
+                                   codebook_.data(), alive_.data(), nullptr, nullptr, nullptr) == 0;
+  Engine& e = Engine::Default();
+  e.Check(pvlm_vlad_kmeans(e.ctx(), set_, (int)train.size(), train.data(), book_size, max_iteration, init.data(), 0, codebook_.data(), alive_.data(), nullptr, nullptr),
+          "pvlm_vlad_kmeans");
+  return true;
+}
+
+bool VLADMatcher::ComputeVLADEmbedding() {
+  if (!valid_ || frames_.empty() || codebook_.empty()) return false;
+  if (host_) {
+    std::vector<int> rows; std::vector<const float*> desc;
+    DescLists(frames_, &rows, &desc);
+    host_vlad_.assign(frames_.size() * (size_t)book_size_ * 128, 0.0f);
+    return vlad_detail::EmbedHost((int)frames_.size(), desc.data(), rows.data(), book_size_, codebook_.data(), alive_.data(), normalization_type_, (size_t)num_threads_,
+                                  host_vlad_.data()) == 0;
+  }
+  Engine& e = Engine::Default();
+  if (vlad_) { pvlm_vladset_destroy(e.ctx(), vlad_); vlad_ = nullptr; }
+  e.Check(pvlm_vlad_embed(e.ctx(), set_, book_size_, codebook_.data(), alive_.data(), normalization_type_, 0, &vlad_, nullptr), "pvlm_vlad_embed");
+  return true;
+}
+
+std::vector<std::vector<size_t>> VLADMatcher::FindNeighbors(int neighbor_size) {
+  const size_t n = frames_.size();
+  std::vector<std::vector<size_t>> all(n);
+  if (neighbor_size < 1 || n == 0 || (host_ ? host_vlad_.empty() : !vlad_)) return all;
+  const size_t m = std::min((size_t)neighbor_size, n);
+  std::vector<int> nb(n * m);
+  if (host_) vlad_detail::NeighborsHost(host_vlad_.data(), (int)n, book_size_, neighbor_size, (size_t)num_threads_, nb.data(), nullptr);
+  else { Engine& e = Engine::Default(); e.Check(pvlm_vlad_neighbors(e.ctx(), vlad_, neighbor_size, nb.data(), nullptr), "pvlm_vlad_neighbors"); }
+  for (size_t i = 0; i < n; ++i) all[i].assign(nb.begin() + (long)(i * m), nb.begin() + (long)((i + 1) * m));
+  return all;
+}
+
+namespace {
+bool InitImagePairsWith(const std::vector<Frame>& frames, const int frame_match_type, std::vector<MatchPair>& image_pairs, const unsigned long long seed, const int book_size,
+                        const bool host, const int num_threads) {
+  if (frame_match_type & (GPS | GPS_VLAD)) return false;
+  for (const Frame& f : frames) if (f.descriptor.size() != 128 * f.keypoints.size()) return false;
+  const size_t n = frames.size();
+  std::vector<MatchPair> out;
+  auto push = [&out](size_t i, size_t j) { MatchPair p; p.image_pair = {i, j}; out.push_back(std::move(p)); };
+  if (frame_match_type & EXHAUSTIVE) {
+    for (size_t i = 0; i < n; ++i) for (size_t j = i + 1; j < n; ++j) push(i, j);
+    image_pairs.swap(out);
+    return image_pairs.size() > 0;
+  }
+  std::set<std::pair<size_t, size_t>> pairs;
+  if (frame_match_type & CONTIGUOUS) {
+    const size_t neighbor_size = 20;
+    for (size_t i = 0; i < n; ++i)
+      for (size_t j = i + 1; j < i + neighbor_size && j < n; ++j) { push(i, j); pairs.insert({i, j}); }
+  }
+  if (frame_match_type & VLAD) {
+    const int neighbor_size = std::max((int)(n / 40), 15);
+    VLADMatcher vlad(frames, RESIDUAL_NORMALIZATION_PWR_LAW, seed, host, num_threads);
+    if (!vlad.GenerateCodeBook(0.5f, book_size) || !vlad.ComputeVLADEmbedding()) return false;
+    const std::vector<std::vector<size_t>> neighbors_all = vlad.FindNeighbors(neighbor_size);
+    for (size_t i = 0; i < n; ++i)
+      for (const size_t neighbor : neighbors_all[i]) {
+        if (neighbor == i) continue;
+        const size_t min_id = std::min(i, neighbor), max_id = std::max(i, neighbor);
+        if (pairs.count({min_id, max_id}) == 0) { push(min_id, max_id); pairs.insert({min_id, max_id}); }
+      }
+  }
+  image_pairs.swap(out);
+  return image_pairs.size() > 0;
+}
+}  // namespace
+
+bool InitImagePairs(const std::vector<Frame>& frames, const int frame_match_type, std::vector<MatchPair>& image_pairs, const unsigned long long seed, const int book_size) {
+  StageTimer stage_timer_("InitImagePairs");
+  return InitImagePairsWith(frames, frame_match_type, image_pairs, seed, book_size, false, 16);
+}
+
+bool InitImagePairsHost(const std::vector<Frame>& frames, const int frame_match_type, std::vector<MatchPair>& image_pairs, const unsigned long long seed, const int book_size,
+                        const int num_threads) {
+  return InitImagePairsWith(frames, frame_match_type, image_pairs, seed, book_size, true, num_threads);
 }
 
 // ---- K34 --------------------------------------------------------------------------------------------------------------------------------
