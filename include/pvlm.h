@@ -440,6 +440,39 @@ pvlm_status pvlm_vlad_neighbors(pvlm_ctx* ctx, const pvlm_vladset* set, int neig
                                 double* sim_or_null /* n_frames x n_frames */);
 void pvlm_vladset_destroy(pvlm_ctx* ctx, pvlm_vladset* set);
 
+/* ---- K36: refinement of the relative poses (SfM::RefineRelativePose sfm/SfM.cpp:482-485, SfMLocalBA util/Optimization.cpp:84-170) ---- *
+ * The definition (csrc/pvlm_relpose_core.h): per pair a two-view bundle adjustment.  Camera 1 is the identity and constant; camera 2's (angle-axis, t) starts from
+ * R_21, t_21; the pair's triangulated points are free and start where they are; every inlier contributes two blocks, on the keypoint matches[inlier].query of frame
+ * src[p] and on the keypoint .train of frame tgt[p], each with its own frame's img_rows / img_cols.  kind: PVLM_BA_PIXEL = PanoramaReprojResidual_Pixel with
+ * HuberLoss(4.0) (what upstream calls), PVLM_BA_ANGLE2 = PanoramaReprojResidual_2Angle on eq.ImageToSphere of the keypoint with HuberLoss(4 pi / 180); the loss acts
+ * on the block's squared norm; no seam wrap of the residual, zero derivatives at the poles (as K31).  The trust-region policy is the one of the host mirror's
+ * ceres_like::Solve with the defaults of Solver::Options and at most max_num_iterations (upstream: 50) iterations; the points are eliminated per point, the reduced
+ * system is one 6 x 6.  Every sum over the points has one order, a function of the pair's inlier count alone (a fixed partition over 64 lanes and a fixed tree), so
+ * the result of a pair depends neither on the other pairs of the call nor on the batch it falls into, and is bit-reproducible from run to run.
+ * Write-back (util/Optimization.cpp:158-168): R_21 from the angle-axis, scale = |t|, t_21 = t / scale, triangulated[i] /= scale, ok[p] = isfinite(final cost).
+ * Deliberate divergences: a pair without inliers comes back unchanged with ok = 1, zero steps and termination 6 (upstream: an empty Ceres problem); a pair whose
+ * scale is zero or not finite comes back with its input pose and points and ok = 0 (upstream: a division by zero); the rotation goes through the host mirror's own
+ * matrix / angle-axis pair, as K31 does.
+ * Inputs: exactly what pvlm_filter_image_pairs writes (match_offsets / matches as it reads them; inlier_offsets, inlier_idx, R_21, t_21, triangulated as it writes
+ * them) plus the frames' keypoints in pixels (2 floats per keypoint, rows_kp[f] of them) and image sizes.  R_21, t_21, triangulated are read and replaced.
+ * summaries: initial and final cost, ACCEPTED and rejected steps (Ceres' own summary counts iteration 0 as a successful step: its number is successful_steps + 1),
+ * termination: 0 max_num_iterations reached, 1 function tolerance, 2 gradient tolerance, 3 parameter tolerance, 4 trust region collapsed, 5 initial cost not
+ * finite, 6 no inliers.
+ * PVLM_ERR_ARG, with no output touched: a frame, match or keypoint index out of range, an inlier index past the pair's matches, a pose, point or keypoint that is
+ * not finite, max_num_iterations < 0, PVLM_BA_ANGLE1 (not implemented for this entry).
+ * A call works through its pair list in batches of up to 2^14 pairs or 2^21 inliers; the environment variable PVLM_RELPOSE_BATCH_PAIRS (read at every call) lowers
+ * the number of pairs per batch.  It changes no result; the tests use it to run several batches on a small list.
+ * pvlm_relpose_workgroup_size: the lanes of the workgroup that refines one pair (the partition of the sums; the tests place their sizes around it). */
+typedef struct pvlm_relpose_params { pvlm_ba_kind kind; int max_num_iterations /* 50 */; } pvlm_relpose_params;
+typedef struct pvlm_relpose_summary { double initial_cost, final_cost; int successful_steps, unsuccessful_steps, termination; } pvlm_relpose_summary;
+pvlm_status pvlm_refine_relative_poses(pvlm_ctx* ctx, int n_frames, const float* const* keypoints /* 2 floats per keypoint, pixels */, const int* rows_kp,
+                                       const int* img_rows, const int* img_cols, int n_pairs, const int* src, const int* tgt,
+                                       const long long* match_offsets /* n_pairs + 1 */, const pvlm_match* matches, const long long* inlier_offsets /* n_pairs + 1 */,
+                                       const int* inlier_idx, double* R_21 /* in/out, n_pairs * 9 */, double* t_21 /* in/out, n_pairs * 3 */,
+                                       double* triangulated /* in/out, 3 per inlier */, const pvlm_relpose_params* params, unsigned char* ok /* n_pairs */,
+                                       pvlm_relpose_summary* summaries_or_null);
+int pvlm_relpose_workgroup_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

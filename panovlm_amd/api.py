@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "pvlm_essential_acransac", "pvlm_filter_image_pairs",
     "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
     "pvlm_resset_plane_runs",
+    "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
 ]
 
 
@@ -1512,6 +1513,51 @@ def filter_image_pairs(ctx, bearings, src, tgt, match_offsets, matches, triangul
     k = min(needed.value, cap)
     return dict(keep=keep, R_21=R, t_21=t, offsets=ioff, inlier_idx=idx[:k], triangulated=tri[:k], needed=needed.value, overflow=rc == -5,
                 guard_intact=bool(np.all(idx[cap:] == -7) and np.all(tri[cap:] == -7.0)), stats=_essential_stats(st))
+
+
+class RelposeParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("max_num_iterations", C.c_int)]
+
+
+RELPOSE_SUMMARY_DTYPE = np.dtype([("initial_cost", np.float64), ("final_cost", np.float64), ("successful_steps", np.int32), ("unsuccessful_steps", np.int32),
+                                  ("termination", np.int32)], align=True)
+RELPOSE_TERMINATIONS = ("max iterations", "function tolerance", "gradient tolerance", "parameter tolerance", "trust region collapsed", "initial cost not finite",
+                        "no inliers")
+RELPOSE_GUARD = 8      # sentinel records refine_relative_poses keeps behind every output
+
+
+def relpose_workgroup_size():
+    """pvlm_relpose_workgroup_size (K36): the lanes of the workgroup that refines one pair."""
+    return int(load_library().pvlm_relpose_workgroup_size())
+
+
+def refine_relative_poses(ctx, keypoints, img_rows, img_cols, src, tgt, match_offsets, matches, inlier_offsets, inlier_idx, R_21, t_21, triangulated, kind="pixel",
+                          max_num_iterations=50, check=True):
+    """pvlm_refine_relative_poses (K36): SfM::RefineRelativePose for every pair.  keypoints: one rows x 2 float32 array of pixels per frame; img_rows / img_cols: the
+    frames' image sizes; the other inputs are what filter_image_pairs takes and returns.  The inputs are not modified.  Returns a dict: R_21 (pairs x 3 x 3), t_21
+    (pairs x 3, unit), triangulated (inliers x 3), ok (uint8 per pair), summaries (RELPOSE_SUMMARY_DTYPE per pair), guard_intact (the RELPOSE_GUARD sentinel records
+    kept behind each output were not written), rc (the pvlm_status).  An argument the library refuses raises PvlmError; with check=False the dict comes back with
+    its rc instead (the outputs then hold the inputs: the library touches nothing it refuses)."""
+    arrs = [np.ascontiguousarray(k, np.float32).reshape(-1, 2) for k in keypoints]
+    rows_kp = np.array([a.shape[0] for a in arrs], np.int32)
+    ptrs = (C.POINTER(C.c_float) * max(len(arrs), 1))(*[_p(a, C.c_float) if a.shape[0] else None for a in arrs])
+    ir = _i32(img_rows); ic = _i32(img_cols); src = _i32(src); tgt = _i32(tgt); moff = _i64(match_offsets); ioff = _i64(inlier_offsets)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE); idx = _i32(inlier_idx)
+    npairs = len(src); nin = len(idx); G = RELPOSE_GUARD
+    R = np.full((npairs + G, 3, 3), -7.0); R[:npairs] = np.asarray(R_21, np.float64).reshape(npairs, 3, 3)
+    t = np.full((npairs + G, 3), -7.0); t[:npairs] = np.asarray(t_21, np.float64).reshape(npairs, 3)
+    tri = np.full((nin + G, 3), -7.0); tri[:nin] = np.asarray(triangulated, np.float64).reshape(nin, 3)
+    ok = np.full(npairs + G, 0xA5, np.uint8)
+    sm = np.zeros(npairs + G, RELPOSE_SUMMARY_DTYPE); sm["termination"][npairs:] = -7
+    prm = RelposeParams(BA_KINDS[kind] if isinstance(kind, str) else int(kind), max_num_iterations)
+    rc = ctx.lib.pvlm_refine_relative_poses(ctx._h, C.c_int(len(arrs)), ptrs, _p(rows_kp, C.c_int), _p(ir, C.c_int), _p(ic, C.c_int), C.c_int(npairs), _p(src, C.c_int),
+                                            _p(tgt, C.c_int), _p(moff, C.c_longlong), m.ctypes.data_as(C.c_void_p), _p(ioff, C.c_longlong), _p(idx, C.c_int),
+                                            _p(R, C.c_double), _p(t, C.c_double), _p(tri, C.c_double), C.byref(prm), _p(ok, C.c_ubyte), sm.ctypes.data_as(C.c_void_p))
+    if check:
+        ctx._check(rc, "pvlm_refine_relative_poses")
+    intact = bool(np.all(R[npairs:] == -7.0) and np.all(t[npairs:] == -7.0) and np.all(tri[nin:] == -7.0) and np.all(ok[npairs:] == 0xA5) and
+                  np.all(sm["termination"][npairs:] == -7))
+    return dict(R_21=R[:npairs], t_21=t[:npairs], triangulated=tri[:nin], ok=ok[:npairs], summaries=sm[:npairs], guard_intact=intact, rc=int(rc))
 
 
 def device_sort(ctx, keys):

@@ -117,6 +117,7 @@ STRUCTURE_DRIVER = os.path.join(HERE, "build", "pvlm_structure_driver")
 MATCH_DRIVER = os.path.join(HERE, "build", "pvlm_match_driver")
 ESSENTIAL_DRIVER = os.path.join(HERE, "build", "pvlm_essential_driver")
 VLAD_DRIVER = os.path.join(HERE, "build", "pvlm_vlad_driver")
+RELPOSE_DRIVER = os.path.join(HERE, "build", "pvlm_relpose_driver")
 
 
 def build_host(force=False):
@@ -192,6 +193,12 @@ def build_host(force=False):
     if os.path.exists(vdrv) and (force or not os.path.exists(VLAD_DRIVER) or
                                  os.path.getmtime(VLAD_DRIVER) < max(os.path.getmtime(vdrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", vdrv, "-o", VLAD_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    # the refinement driver (MatchImagePairs into FilterImagePairsFull: K34, K36, the scale and the pair graph)
+    rdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_relpose_driver.cpp")
+    if os.path.exists(rdrv) and (force or not os.path.exists(RELPOSE_DRIVER) or
+                                 os.path.getmtime(RELPOSE_DRIVER) < max(os.path.getmtime(rdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", rdrv, "-o", RELPOSE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     return HOST_LIB
 

@@ -649,6 +649,8 @@ struct RelativePair {
   Matrix3d R_21; Vector3d t_21;
   std::vector<size_t> inlier_idx;               // CheckRT's inliers of the winning run, indices into matches, ascending
   std::vector<Vector3d> triangulated;           // their points in the first camera's frame
+  int points_with_depth = 0;                    // K36, SetTranslationScaleDepthMap: the triangulated points with a real depth in both depth maps ...
+  double upper_scale = -1, lower_scale = -1;    // ... and the largest / smallest scale kept (0 = the median fall-back; -1 = never scaled: util/MatchPair.h's constructors)
   MatchPair AsMatchPair() const { MatchPair p; p.image_pair = image_pair; p.matches = matches; return p; }
 };
 // what upstream fixes in the source (40 runs of 300 iterations) and what it draws from std::random_device (here: a seed, see csrc/pvlm_essential_core.h)
@@ -673,6 +675,41 @@ bool FilterImagePairs(const std::vector<Frame>& frames, const std::vector<MatchP
 // the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/essential_bench.py times
 bool FilterImagePairsHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, std::vector<RelativePair>& good_pair, const int triangulation_num_threshold,
                           const EssentialOptions& options = EssentialOptions(), const int num_threads = 16);
+
+// ---- K36: the rest of SfM::FilterImagePairs (sfm/SfM.cpp:436-476): RefineRelativePose, the scale from the depth maps, the pair graph ---------------------------------
+// SfMLocalBA (util/Optimization.cpp:84-170) for one pair on the host compile of csrc/pvlm_relpose_core.h: camera 1 the identity and constant, camera 2 and the pair's
+// triangulated points free, two blocks per inlier; residual_type PIXEL_RESIDUAL (HuberLoss(4.0)) or ANGLE_RESIDUAL_2 (HuberLoss(4 deg)); ANGLE_RESIDUAL_1 throws.  The
+// write-back: R_21 from the angle-axis, t_21 normalised, the points divided by |t|.  Returns isfinite(final cost).  The header lists the deliberate divergences.
+bool SfMLocalBA(const Frame& frame1, const Frame& frame2, int residual_type, RelativePair& image_pair);
+// SfM::RefineRelativePose (sfm/SfM.cpp:482-485): SfMLocalBA(frames[first], frames[second], PIXEL_RESIDUAL, pair)
+bool RefineRelativePose(const std::vector<Frame>& frames, RelativePair& image_pair);
+// every pair of the list in ONE pvlm_refine_relative_poses call (K36).  ok (or null): per pair what SfMLocalBA returns.  False, with the list untouched, for what the
+// call refuses (a frame, match or inlier index out of range, a value that is not finite).
+bool RefineRelativePoses(const std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, int residual_type = PIXEL_RESIDUAL, std::vector<bool>* ok = nullptr);
+// the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/relpose_bench.py times and the equality partner of the call
+bool RefineRelativePosesHost(const std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, int residual_type = PIXEL_RESIDUAL, std::vector<bool>* ok = nullptr,
+                             const int num_threads = 16);
+// The depth maps of the frames (upstream: frames[i].depth_map, a CV_16U image of depth x 256 read from a file): maps[f] is rows[f] x cols[f], row-major; an empty
+// vector means the frame has none.  DepthCompletion is the caller's business.
+struct DepthMaps { std::vector<std::vector<uint16_t>> maps; std::vector<int> rows, cols; };
+// SfM::SetTranslationScaleDepthMap(eq, pair) (:487-603) operation by operation: the half-size test, round, IsInside, the 0.2 consistency test, two histogram passes
+// (the 1e-8 offset, the clamped bin index, the > 0.1 num_scale keep rule), the nth_element median fall-back.  It stays on the host on purpose.
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, RelativePair& image_pair);
+// the list form (:605-679): the frames are visited from the one with the fewest pairs on, the pairs that touch a frame in list order; a pair without a scale stays
+// only when keep_no_scale.  Returns whether any pair is left.
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, std::vector<RelativePair>& image_pairs, const bool keep_no_scale);
+// SfM::LargestBiconnectedGraph (:780-799; PoseGraph::KeepLargestEdgeBiconnected sfm/PoseGraph.cpp:63-133) without lemon: bridges by one depth-first search, then the
+// connected component with the most nodes.  Deliberate divergence: among components of equal size the one that holds the lowest frame id wins.
+std::vector<RelativePair> LargestBiconnectedGraph(const std::vector<RelativePair>& pairs, std::set<size_t>& nodes);
+// SfM::FilterImagePairs (:298-480) end to end: FilterImagePairs (K34), RefineRelativePoses (K36; a failed refinement is kept, upstream's `continue` is commented
+// out), SetTranslationScaleDepthMap, LargestBiconnectedGraph, and the final sort with upstream's comparator as written (first <, else second <; run as the insertion
+// sort std::sort uses on short ranges, see pvlm_host_relpose.hpp).  good_pair and covered_frames are upstream's image_pairs and covered_frames afterwards.
+bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                          std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options = EssentialOptions());
+// the same through FilterImagePairsHost and RefineRelativePosesHost (no device)
+bool FilterImagePairsFullHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                              std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale,
+                              const EssentialOptions& options = EssentialOptions(), const int num_threads = 16);
 
 // ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------
 // base/common.h's FrameMatchMethod and sfm/VLAD.h's normalisation types

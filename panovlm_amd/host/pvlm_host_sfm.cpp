@@ -11,6 +11,7 @@
 #include "pvlm_host_match.hpp"
 #include "pvlm_host_essential.hpp"
 #include "pvlm_host_vlad.hpp"
+#include "pvlm_host_relpose.hpp"
 
 namespace pvlm {
 
@@ -485,6 +486,180 @@ bool FilterImagePairsHost(const std::vector<Frame>& frames, const std::vector<Ma
   good_pair.clear();
   for (size_t p = 0; p < image_pairs.size(); ++p)
     if (res[p].keep) good_pair.push_back(MakeRelativePair(image_pairs[p], res[p].R, res[p].t, res[p].inlier_idx.data(), res[p].triangulated.data(), (long long)res[p].inlier_idx.size()));
+  return true;
+}
+
+// ================================================================================================
+// K36: RefineRelativePose, SetTranslationScaleDepthMap, LargestBiconnectedGraph, FilterImagePairsFull
+// ================================================================================================
+namespace {
+int RelposeKind(int residual_type) {
+  if (residual_type == PIXEL_RESIDUAL) return pvlm_relpose::kKindPixel;
+  if (residual_type == ANGLE_RESIDUAL_2) return pvlm_relpose::kKindAngle2;
+  throw std::invalid_argument("SfMLocalBA: PIXEL_RESIDUAL or ANGLE_RESIDUAL_2 (ANGLE_RESIDUAL_1 is not implemented for the two-view adjustment)");
+}
+// the arrays of pvlm_refine_relative_poses from a pair list
+struct RelposeInputs {
+  std::vector<std::vector<float>> kp; std::vector<const float*> ptr; std::vector<int> rows_kp, img_rows, img_cols, src, tgt, idx; std::vector<long long> moff, ioff;
+  std::vector<pvlm_match> matches; std::vector<double> R, t, tri;
+  bool Fill(const std::vector<Frame>& frames, const std::vector<RelativePair>& pairs) {
+    for (const Frame& fr : frames) {
+      kp.emplace_back(2 * fr.keypoints.size() + 2);
+      for (size_t k = 0; k < fr.keypoints.size(); ++k) { kp.back()[2 * k] = fr.keypoints[k][0]; kp.back()[2 * k + 1] = fr.keypoints[k][1]; }
+      rows_kp.push_back((int)fr.keypoints.size()); img_rows.push_back(fr.GetImageRows()); img_cols.push_back(fr.GetImageCols());
+    }
+    for (const auto& v : kp) ptr.push_back(v.data());
+    moff.push_back(0); ioff.push_back(0);
+    for (const RelativePair& p : pairs) {
+      if (p.image_pair.first >= frames.size() || p.image_pair.second >= frames.size() || p.inlier_idx.size() != p.triangulated.size()) return false;
+      src.push_back((int)p.image_pair.first); tgt.push_back((int)p.image_pair.second);
+      for (const auto& m : p.matches) matches.push_back(pvlm_match{m.first, m.second, 0.0f});
+      moff.push_back((long long)matches.size());
+      for (size_t k = 0; k < p.inlier_idx.size(); ++k) { idx.push_back((int)p.inlier_idx[k]); tri.insert(tri.end(), p.triangulated[k].begin(), p.triangulated[k].end()); }
+      ioff.push_back((long long)idx.size());
+      R.insert(R.end(), p.R_21.begin(), p.R_21.end()); t.insert(t.end(), p.t_21.begin(), p.t_21.end());
+    }
+    matches.push_back(pvlm_match{0, 0, 0.0f}); idx.push_back(0); tri.resize(tri.size() + 3); R.resize(R.size() + 9); t.resize(t.size() + 3);   // never empty
+    return true;
+  }
+  void Store(std::vector<RelativePair>& pairs) const {
+    for (size_t p = 0; p < pairs.size(); ++p) {
+      std::copy(R.begin() + 9 * (std::ptrdiff_t)p, R.begin() + 9 * (std::ptrdiff_t)p + 9, pairs[p].R_21.begin());
+      std::copy(t.begin() + 3 * (std::ptrdiff_t)p, t.begin() + 3 * (std::ptrdiff_t)p + 3, pairs[p].t_21.begin());
+      for (size_t k = 0; k < pairs[p].triangulated.size(); ++k)
+        for (int c = 0; c < 3; ++c) pairs[p].triangulated[k][(size_t)c] = tri[3 * ((size_t)ioff[p] + k) + (size_t)c];
+    }
+  }
+};
+relpose_detail::TailPair ToTail(const RelativePair& p, size_t tag) {
+  relpose_detail::TailPair t;
+  t.image_pair = p.image_pair; t.tag = tag; t.points_with_depth = p.points_with_depth; t.upper_scale = p.upper_scale; t.lower_scale = p.lower_scale;
+  std::copy(p.R_21.begin(), p.R_21.end(), t.R); std::copy(p.t_21.begin(), p.t_21.end(), t.t);
+  for (const Vector3d& X : p.triangulated) t.tri.insert(t.tri.end(), X.begin(), X.end());
+  return t;
+}
+void FromTail(const relpose_detail::TailPair& t, RelativePair& p) {
+  std::copy(t.t, t.t + 3, p.t_21.begin());
+  for (size_t k = 0; k < p.triangulated.size(); ++k) p.triangulated[k] = {t.tri[3 * k], t.tri[3 * k + 1], t.tri[3 * k + 2]};
+  p.points_with_depth = t.points_with_depth; p.upper_scale = t.upper_scale; p.lower_scale = t.lower_scale;
+}
+std::vector<relpose_detail::DepthView> DepthViews(const std::vector<Frame>& frames, const DepthMaps& d) {
+  std::vector<relpose_detail::DepthView> v(frames.size());
+  for (size_t f = 0; f < frames.size() && f < d.maps.size(); ++f) {
+    if (d.maps[f].empty()) continue;
+    if (f >= d.rows.size() || f >= d.cols.size() || d.rows[f] <= 0 || d.cols[f] <= 0 || d.maps[f].size() != (size_t)d.rows[f] * (size_t)d.cols[f])
+      throw std::invalid_argument("DepthMaps: map " + std::to_string(f) + " is not rows x cols");
+    v[f].data = d.maps[f].data(); v[f].rows = d.rows[f]; v[f].cols = d.cols[f];
+  }
+  return v;
+}
+// :449-476 on the pairs the refinement leaves
+void FinishImagePairs(const std::vector<Frame>& frames, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair, std::set<size_t>& covered_frames, bool keep_no_scale) {
+  std::vector<relpose_detail::TailPair> tail;
+  for (size_t p = 0; p < good_pair.size(); ++p) tail.push_back(ToTail(good_pair[p], p));
+  std::vector<int> frame_rows;
+  for (const Frame& f : frames) frame_rows.push_back(f.GetImageRows());
+  relpose_detail::FinishPairs(frames.empty() ? 0 : frames[0].GetImageRows(), frames.empty() ? 0 : frames[0].GetImageCols(), frame_rows, DepthViews(frames, depth_maps), tail,
+                              covered_frames, keep_no_scale);
+  std::vector<RelativePair> out;
+  for (const relpose_detail::TailPair& t : tail) { out.push_back(good_pair[t.tag]); FromTail(t, out.back()); }
+  good_pair.swap(out);
+}
+}  // namespace
+
+bool RefineRelativePosesHost(const std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, int residual_type, std::vector<bool>* ok, const int num_threads) {
+  const int kind = RelposeKind(residual_type);
+  RelposeInputs in;
+  if (!in.Fill(frames, image_pairs)) return false;
+  std::vector<unsigned char> good(image_pairs.size() + 1);
+  if (relpose_detail::RefinePosesHost((int)frames.size(), in.ptr.data(), in.rows_kp.data(), in.img_rows.data(), in.img_cols.data(), (int)image_pairs.size(), in.src.data(),
+                                      in.tgt.data(), in.moff.data(), in.matches.data(), in.ioff.data(), in.idx.data(), in.R.data(), in.t.data(), in.tri.data(), kind, 50,
+                                      (size_t)std::max(num_threads, 1), good.data(), nullptr, nullptr)) return false;
+  in.Store(image_pairs);
+  if (ok) { ok->assign(image_pairs.size(), false); for (size_t p = 0; p < image_pairs.size(); ++p) (*ok)[p] = good[p] != 0; }
+  return true;
+}
+
+bool RefineRelativePoses(const std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, int residual_type, std::vector<bool>* ok) {
+  StageTimer stage_timer_("RefineRelativePoses");
+  const int kind = RelposeKind(residual_type);
+  RelposeInputs in;
+  if (!in.Fill(frames, image_pairs)) return false;
+  Engine& e = Engine::Default();
+  std::vector<unsigned char> good(image_pairs.size() + 1);
+  const pvlm_relpose_params prm{(pvlm_ba_kind)kind, 50};
+  const pvlm_status st = pvlm_refine_relative_poses(e.ctx(), (int)frames.size(), in.ptr.data(), in.rows_kp.data(), in.img_rows.data(), in.img_cols.data(), (int)image_pairs.size(),
+                                                    in.src.data(), in.tgt.data(), in.moff.data(), in.matches.data(), in.ioff.data(), in.idx.data(), in.R.data(), in.t.data(),
+                                                    in.tri.data(), &prm, good.data(), nullptr);
+  if (st == PVLM_ERR_ARG) return false;
+  e.Check(st, "pvlm_refine_relative_poses");
+  in.Store(image_pairs);
+  if (ok) { ok->assign(image_pairs.size(), false); for (size_t p = 0; p < image_pairs.size(); ++p) (*ok)[p] = good[p] != 0; }
+  return true;
+}
+
+bool SfMLocalBA(const Frame& frame1, const Frame& frame2, int residual_type, RelativePair& image_pair) {
+  std::vector<RelativePair> one{image_pair};
+  one[0].image_pair = {0, 1};
+  std::vector<bool> ok;
+  if (!RefineRelativePosesHost({frame1, frame2}, one, residual_type, &ok, 1)) return false;
+  one[0].image_pair = image_pair.image_pair;
+  image_pair = one[0];
+  return ok[0];
+}
+
+bool RefineRelativePose(const std::vector<Frame>& frames, RelativePair& image_pair) {
+  return SfMLocalBA(frames.at(image_pair.image_pair.first), frames.at(image_pair.image_pair.second), PIXEL_RESIDUAL, image_pair);
+}
+
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, RelativePair& image_pair) {
+  const std::vector<relpose_detail::DepthView> dv = DepthViews(frames, depth_maps);
+  relpose_detail::TailPair t = ToTail(image_pair, 0);
+  const bool ok = relpose_detail::SetScaleOne(frames.at(0).GetImageRows(), frames.at(0).GetImageCols(), frames.at(image_pair.image_pair.first).GetImageRows(),
+                                              dv.at(image_pair.image_pair.first), dv.at(image_pair.image_pair.second), t);
+  FromTail(t, image_pair);
+  return ok;
+}
+
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, std::vector<RelativePair>& image_pairs, const bool keep_no_scale) {
+  std::vector<relpose_detail::TailPair> tail;
+  for (size_t p = 0; p < image_pairs.size(); ++p) {
+    if (image_pairs[p].image_pair.first >= frames.size() || image_pairs[p].image_pair.second >= frames.size()) throw std::invalid_argument("SetTranslationScaleDepthMap: a pair names a frame that is not there");
+    tail.push_back(ToTail(image_pairs[p], p));
+  }
+  std::vector<int> frame_rows;
+  for (const Frame& f : frames) frame_rows.push_back(f.GetImageRows());
+  const bool any = relpose_detail::SetScaleList(frames.empty() ? 0 : frames[0].GetImageRows(), frames.empty() ? 0 : frames[0].GetImageCols(), frame_rows, DepthViews(frames, depth_maps),
+                                                tail, keep_no_scale);
+  std::vector<RelativePair> out;
+  for (const relpose_detail::TailPair& t : tail) { out.push_back(image_pairs[t.tag]); FromTail(t, out.back()); }
+  image_pairs.swap(out);
+  return any;
+}
+
+std::vector<RelativePair> LargestBiconnectedGraph(const std::vector<RelativePair>& pairs, std::set<size_t>& nodes) {
+  std::vector<std::pair<size_t, size_t>> edges;
+  for (const RelativePair& p : pairs) edges.push_back(p.image_pair);
+  nodes = relpose_detail::LargestEdgeBiconnected(edges);
+  std::vector<RelativePair> good;
+  for (const RelativePair& p : pairs) if (nodes.count(p.image_pair.first) > 0 && nodes.count(p.image_pair.second) > 0) good.push_back(p);
+  return good;
+}
+
+bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                          std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options) {
+  if (!FilterImagePairs(frames, image_pairs, good_pair, triangulation_num_threshold, options)) return false;
+  if (!RefineRelativePoses(frames, good_pair, PIXEL_RESIDUAL, nullptr)) return false;
+  FinishImagePairs(frames, depth_maps, good_pair, covered_frames, keep_no_scale);
+  return true;
+}
+
+bool FilterImagePairsFullHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                              std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options,
+                              const int num_threads) {
+  if (!FilterImagePairsHost(frames, image_pairs, good_pair, triangulation_num_threshold, options, num_threads)) return false;
+  if (!RefineRelativePosesHost(frames, good_pair, PIXEL_RESIDUAL, nullptr, num_threads)) return false;
+  FinishImagePairs(frames, depth_maps, good_pair, covered_frames, keep_no_scale);
   return true;
 }
 
