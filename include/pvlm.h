@@ -715,6 +715,31 @@ pvlm_status pvlm_image_to_cam_f32_dev(pvlm_ctx* ctx, int rows, int cols, int64_t
 pvlm_status pvlm_project_lidar_depth(pvlm_ctx* ctx, int rows, int cols, int64_t n, const float* xyz, const double* T_cl_rowmajor16,
                                      unsigned size, uint16_t* depth);
 
+/* ---- K37: LiDAR depth completion ---------------------------------------------------------------------------------------------------------
+ * DepthCompletion (util/DepthCompletion.cpp:154-316) for a batch of n_images equal-sized images (rows x cols, one after the other): the chain of masked dilations,
+ * close, medians, column scans, hole fills and the bilateral filter that csrc/pvlm_depthfill_core.h states stage by stage, with the OpenCV semantics it rests on and
+ * the deliberate divergence of the bilateral filter.  Exactly one input: sparse_u16 (depth * 256, upstream's CV_16U image; value / 256 is exact) or sparse_f32
+ * (metres; a value with a sign bit or a non-finite value is PVLM_ERR_ARG).  At least one output: dense_f32 (DepthCompletion's result) and / or dense_u16
+ * (rint(result * 256), half to even, saturated: what ComputeDepthImage stores).  max_depth must be finite and > 0.  The images are worked through in bounded
+ * batches of whole images; PVLM_DEPTHFILL_BATCH_IMAGES (read at every call) lowers the limit and changes no result.  Synchronous; PVLM_ERR_STATE inside a capture. */
+typedef struct pvlm_depthfill_stats {
+  long long images;        /* images completed */
+  long long batches;       /* device batches they were worked through in */
+  long long valid_in;      /* pixels with s0 > 0.1 (a depth in (0.1, max_depth]) over all inputs */
+  long long valid_out;     /* pixels > 0.1 over all results */
+  double splat_ms;         /* HIP-event time of the batches' splats, the clearing of their 64-bit images and the upload of the points included (pvlm_compute_depth_images; else 0) */
+  double fill_ms;          /* HIP-event time of the batches' three completion kernels */
+} pvlm_depthfill_stats;
+pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, int n_images, const uint16_t* sparse_u16_or_null, const float* sparse_f32_or_null, float max_depth,
+                                  float* dense_f32_or_null, uint16_t* dense_u16_or_null, pvlm_depthfill_stats* stats_or_null);
+/* The loop body of SfM::ComputeDepthImage (sfm/SfM.cpp:170-226) for all scans in one call: ProjectLidar2PanoramaDepth(cloud, rows, cols, T_cl, size) (the splat of
+ * pvlm_project_lidar_depth), DepthCompletion(depth, max_depth), x 256, uint16; nothing returns to the host in between.  rows x cols is the size of the depth
+ * image (upstream passes (image rows + 1) / 2 and (image cols + 1) / 2 and size 4).  Scan s is the points first_point[s] .. first_point[s + 1] of xyz (3 floats each,
+ * LiDAR frame; first_point ascending from 0, PVLM_ERR_ARG otherwise); T_cl (16 doubles, row-major) is the one calibration of all scans.  depth_u16: n_scans
+ * images.  A scan without points gives an all-zero image.  No visualisation, no file export. */
+pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl_rowmajor16,
+                                      unsigned size, float max_depth, uint16_t* depth_u16, pvlm_depthfill_stats* stats_or_null);
+
 /* MVS::InitDepthNormal (mvs/MVS.cpp:496-584; config 5 "LiDAR-seeded depth priors"): the depth image of
  * pvlm_project_lidar_depth (uint16, depth * 256; size 2 upstream, :512) seeds the depth map, every pixel without a LiDAR depth
  * gets a uniform random depth in [min_depth, max_depth], keep_lidar_constant != 0 marks the seeded pixels in depth_constant

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
     "pvlm_resset_plane_runs",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
+    "pvlm_depth_completion", "pvlm_compute_depth_images",
 ]
 
 
@@ -476,6 +477,46 @@ class Context:
         self._check(self.lib.pvlm_project_lidar_depth(self._h, C.c_int(rows), C.c_int(cols), C.c_int64(xyz.shape[0]), _p(xyz, C.c_float),
                                                       _p(T, C.c_double), C.c_uint(size), _p(out, C.c_uint16)), "pvlm_project_lidar_depth")
         return out
+
+    def depth_completion(self, sparse, max_depth, want_f32=True, want_u16=False):
+        """pvlm_depth_completion (K37): DepthCompletion (util/DepthCompletion.cpp:154-316) of one rows x cols image or a batch n x rows x cols.  sparse: uint16
+        (depth * 256) or float32 (metres; a negative or non-finite value is refused).  Returns (dense float32 or None, dense uint16 or None, stats dict), shaped as
+        the input."""
+        sparse = np.asarray(sparse)
+        if sparse.dtype not in (np.uint16, np.float32) or sparse.ndim not in (2, 3):
+            raise PvlmError("depth_completion: a uint16 or float32 image (rows x cols) or batch (n x rows x cols)")
+        if not (want_f32 or want_u16):
+            raise PvlmError("depth_completion: no output")
+        sparse = np.ascontiguousarray(sparse)
+        n = 1 if sparse.ndim == 2 else sparse.shape[0]
+        rows, cols = sparse.shape[-2:]
+        f32 = np.zeros(sparse.shape, np.float32) if want_f32 else None
+        u16 = np.zeros(sparse.shape, np.uint16) if want_u16 else None
+        st = DepthfillStats()
+        is16 = sparse.dtype == np.uint16
+        self._check(self.lib.pvlm_depth_completion(self._h, C.c_int(rows), C.c_int(cols), C.c_int(n), _p(sparse if is16 else None, C.c_uint16),
+                                                   _p(None if is16 else sparse, C.c_float), C.c_float(max_depth), _p(f32, C.c_float), _p(u16, C.c_uint16),
+                                                   C.byref(st)), "pvlm_depth_completion")
+        return f32, u16, _depthfill_stats(st)
+
+    def compute_depth_images(self, rows, cols, clouds, T_cl, size, max_depth):
+        """pvlm_compute_depth_images (K37): the loop body of SfM::ComputeDepthImage (sfm/SfM.cpp:170-226) for every cloud (n x 3 float32, LiDAR frame) in one call:
+        the splat of project_lidar_depth(rows, cols, cloud, T_cl, size), DepthCompletion, x 256, uint16.  Returns (n_scans x rows x cols uint16, stats dict)."""
+        clouds = [_f32(c).reshape(-1, 3) for c in clouds]
+        first = np.zeros(len(clouds) + 1, np.int64)
+        first[1:] = np.cumsum([len(c) for c in clouds])
+        xyz = np.ascontiguousarray(np.concatenate(clouds + [np.zeros((1, 3), np.float32)]))
+        return self.compute_depth_images_flat(rows, cols, first, xyz, T_cl, size, max_depth)
+
+    def compute_depth_images_flat(self, rows, cols, first_point, xyz, T_cl, size, max_depth):
+        """compute_depth_images on the call's own arrays: scan s is the points first_point[s] .. first_point[s + 1] of xyz."""
+        first = _i64(first_point); xyz = _f32(xyz).reshape(-1, 3); T = _f64(T_cl).reshape(16)
+        n = max(len(first) - 1, 0)
+        out = np.zeros((n, rows, cols), np.uint16)
+        st = DepthfillStats()
+        self._check(self.lib.pvlm_compute_depth_images(self._h, C.c_int(rows), C.c_int(cols), C.c_int(n), _p(first, C.c_longlong), _p(xyz, C.c_float), _p(T, C.c_double),
+                                                       C.c_uint(size), C.c_float(max_depth), _p(out, C.c_uint16), C.byref(st)), "pvlm_compute_depth_images")
+        return out, _depthfill_stats(st)
 
     def cam_lidar_votes_batch(self, rows, cols, lines_list, lidar_scans, T_cl_list):
         """One launch for many (image lines, LiDAR-local scan, T_cl) triples; returns the list of vote matrices."""
@@ -1384,6 +1425,14 @@ def match_pairs(ctx, descset, src, tgt, ratio, matches_threshold, flags=0, capac
     return dict(keep=keep, offsets=off, matches=out[:min(needed.value, cap)], needed=needed.value, overflow=rc == -5,
                 guard_intact=bool(np.all(g["query"] == -7) and np.all(g["train"] == -7) and np.all(g["distance"] == -7.0)),
                 stats=dict(queries=st.queries, fallback_queries=st.fallback_queries, batches=st.batches))
+
+
+class DepthfillStats(C.Structure):
+    _fields_ = [("images", C.c_longlong), ("batches", C.c_longlong), ("valid_in", C.c_longlong), ("valid_out", C.c_longlong), ("splat_ms", C.c_double), ("fill_ms", C.c_double)]
+
+
+def _depthfill_stats(st):
+    return dict(images=st.images, batches=st.batches, valid_in=st.valid_in, valid_out=st.valid_out, splat_ms=st.splat_ms, fill_ms=st.fill_ms)
 
 
 class VladStats(C.Structure):

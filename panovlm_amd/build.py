@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip")
 
 
 def _hipcc():
@@ -118,6 +118,8 @@ MATCH_DRIVER = os.path.join(HERE, "build", "pvlm_match_driver")
 ESSENTIAL_DRIVER = os.path.join(HERE, "build", "pvlm_essential_driver")
 VLAD_DRIVER = os.path.join(HERE, "build", "pvlm_vlad_driver")
 RELPOSE_DRIVER = os.path.join(HERE, "build", "pvlm_relpose_driver")
+DEPTHFILL_DRIVER = os.path.join(HERE, "build", "pvlm_depthfill_driver")
+DEPTHFILL_CHECK = os.path.join(HERE, "build", "depthfill_core_check")
 
 
 def build_host(force=False):
@@ -200,6 +202,17 @@ def build_host(force=False):
                                  os.path.getmtime(RELPOSE_DRIVER) < max(os.path.getmtime(rdrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", rdrv, "-o", RELPOSE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
+    # the depth-map driver (ComputeDepthImage into FilterImagePairsFull: K37) and the stand-alone check of the K37 core (no device; its own main)
+    ddrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_depthfill_driver.cpp")
+    if os.path.exists(ddrv) and (force or not os.path.exists(DEPTHFILL_DRIVER) or
+                                 os.path.getmtime(DEPTHFILL_DRIVER) < max(os.path.getmtime(ddrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", ddrv, "-o", DEPTHFILL_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    dchk = os.path.join(HERE, "..", "tests", "cpp", "depthfill_core_check.cpp")
+    core = os.path.join(HERE, "csrc", "pvlm_depthfill_core.h")
+    if os.path.exists(dchk) and (force or not os.path.exists(DEPTHFILL_CHECK) or
+                                 os.path.getmtime(DEPTHFILL_CHECK) < max(os.path.getmtime(dchk), os.path.getmtime(core))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", "-DDEPTHFILL_CHECK_MAIN", dchk, "-o", DEPTHFILL_CHECK])
     return HOST_LIB
 
 

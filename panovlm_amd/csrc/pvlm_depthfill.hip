@@ -1,0 +1,336 @@
+// K37: DepthCompletion (util/DepthCompletion.cpp:154-316) and the loop body of SfM::ComputeDepthImage (sfm/SfM.cpp:170-226) on the GPU.  The definition is
+// pvlm_depthfill_core.h; this file wraps its per-pixel functions in three tiled kernels, one per phase between the two column scans:
+//   k_fill_a  S0-S4  (reach 3 + 2 + 2 + 2 = 9)   input (uint16, fp32 or the splat's 64-bit image) -> s4, top 1
+//   k_fill_b  S5     (reach 4)                    s4, top 1 -> s5, top 2
+//   k_fill_c  S7a-u16 (reach 6 x 2 + 2 + 2 = 16)  s5, top 2 -> the dense fp32 and / or uint16 image
+// A workgroup of 256 lanes owns a kTileH x kTileW tile of one image (blockIdx.z) and loads it with the phase's reach as halo into LDS.  No pass is in place over its
+// neighbours: every stencil pass reads one of two LDS images and writes the other (a square is a row pass and a column pass), on a region that shrinks by the pass's
+// reach (region<HALO, MR, MC>: the tile grown by MR rows and MC columns), so that every tap a pass reads was computed by the pass before it.  The only in-place
+// update, the blend of a fill round, reads its own pixel alone.  A pixel outside the image holds, for the next reader, the value that never wins (0 for a maximum of
+// values >= +0, +inf for a minimum); the medians clamp and the bilateral reflects their coordinates, which stays inside the loaded region.
+// The column scans ride on the phases before them: a tile takes the minimum row of its valid pixels per column in LDS and sends one integer atomicMin per column
+// (integer minima: no order dependence).
+#include <cmath>
+#include <cstdlib>
+
+#include "pvlm_depth_launch.h"
+#include "pvlm_depthfill_core.h"
+#include "pvlm_internal.h"
+
+namespace {
+namespace df = pvlm_depthfill;
+
+constexpr int kTileH = 32;
+constexpr int kTileW = 64;
+constexpr int kThreads = 256;
+constexpr int kTopNone = 0x7f7f7f7f;                    // a column without a valid pixel (hipMemsetAsync of 0x7f); read as row 0
+constexpr size_t kBatchBytes = (size_t)1 << 30;         // device scratch of one batch of whole images
+
+template <int HALO> struct Buf { static constexpr int H = kTileH + 2 * HALO, W = kTileW + 2 * HALO, N = H * W; };
+
+// f(LDS index, image row, image column) for every position of the tile grown by MR rows and MC columns, then a barrier
+template <int HALO, int MR, int MC, class F> __device__ __forceinline__ void region(int r0, int c0, F f) {
+  static_assert(MR >= 0 && MC >= 0 && MR <= HALO && MC <= HALO, "a region lies inside the loaded tile");
+  constexpr int W = kTileW + 2 * MC, H = kTileH + 2 * MR;
+  for (int idx = threadIdx.x; idx < W * H; idx += kThreads) {
+    const int rr = idx / W, cc = idx - rr * W;
+    f((HALO - MR + rr) * Buf<HALO>::W + (HALO - MC + cc), r0 - MR + rr, c0 - MC + cc);
+  }
+  __syncthreads();
+}
+
+struct SrcU16 { const unsigned short* p; __device__ float operator()(size_t i) const { return df::from_u16(p[i]); } };
+struct SrcF32 { const float* p; __device__ float operator()(size_t i) const { return p[i]; } };
+struct SrcSplat { const unsigned long long* p; __device__ float operator()(size_t i) const { return df::from_u16((unsigned)(p[i] & 0xffffull)); } };
+
+// the tile's share of a column scan and of a pixel count: colmin[c] -> top, the lanes' counts -> *total
+__device__ __forceinline__ void tile_finish(int cols, int c0, const int* colmin, int* top_f, int* cnt, int my, unsigned long long* total) {
+  if (my) atomicAdd(cnt, my);
+  __syncthreads();
+  if (top_f && threadIdx.x < kTileW && colmin[threadIdx.x] != kTopNone && c0 + (int)threadIdx.x < cols) atomicMin(&top_f[c0 + threadIdx.x], colmin[threadIdx.x]);
+  if (total && threadIdx.x == 0 && *cnt) atomicAdd(total, (unsigned long long)*cnt);
+}
+
+template <class Src>
+__global__ __launch_bounds__(kThreads) void k_fill_a(int rows, int cols, Src src, float M, float* __restrict__ s4, int* __restrict__ top, unsigned long long* valid_in) {
+  constexpr int HALO = df::kReachA;
+  using B = Buf<HALO>;
+  __shared__ float A[B::N], Bf[B::N];
+  __shared__ int colmin[kTileW], cnt;
+  const int r0 = blockIdx.y * kTileH, c0 = blockIdx.x * kTileW;
+  const size_t base = (size_t)blockIdx.z * rows * cols;
+  const float inf = __builtin_inff();
+  if (threadIdx.x < kTileW) colmin[threadIdx.x] = kTopNone;
+  if (threadIdx.x == 0) cnt = 0;
+  auto in = [&](int r, int c) { return r >= 0 && r < rows && c >= 0 && c < cols; };
+  int my = 0;
+  region<HALO, HALO, HALO>(r0, c0, [&](int i, int r, int c) {                                        // S0
+    float v = 0.f;
+    if (in(r, c)) {
+      v = df::s0_of(src(base + (size_t)r * cols + c), M);
+      my += (v > df::kValid) && r >= r0 && r < r0 + kTileH && c >= c0 && c < c0 + kTileW;
+    }
+    A[i] = v;
+  });
+  region<HALO, 6, 6>(r0, c0, [&](int i, int r, int c) {                                              // S1, S2
+    Bf[i] = in(r, c) ? df::s2_pixel([&](int dr, int dc) { return A[i + dr * B::W + dc]; }, M) : 0.f;
+  });
+  region<HALO, 6, 4>(r0, c0, [&](int i, int r, int c) { A[i] = in(r, c) ? df::run_max<2>([&](int k) { return Bf[i + k]; }) : 0.f; });          // S3: dilate
+  region<HALO, 4, 4>(r0, c0, [&](int i, int r, int c) { Bf[i] = in(r, c) ? df::run_max<2>([&](int k) { return A[i + k * B::W]; }) : inf; });
+  region<HALO, 4, 2>(r0, c0, [&](int i, int r, int c) { A[i] = in(r, c) ? df::run_min<2>([&](int k) { return Bf[i + k]; }) : inf; });          //     erode
+  region<HALO, 2, 2>(r0, c0, [&](int i, int r, int c) { Bf[i] = in(r, c) ? df::run_min<2>([&](int k) { return A[i + k * B::W]; }) : 0.f; });
+  region<HALO, 0, 0>(r0, c0, [&](int i, int r, int c) {                                              // S4
+    if (!in(r, c)) return;
+    const float s3 = Bf[i];
+    float out = s3;
+    if (s3 > df::kValid)
+      out = df::median5([&](int dr, int dc) { return Bf[(df::clampi(r + dr, rows) - (r0 - HALO)) * B::W + (df::clampi(c + dc, cols) - (c0 - HALO))]; });
+    s4[base + (size_t)r * cols + c] = out;
+    if (out > df::kValid) atomicMin(&colmin[c - c0], r);
+  });
+  tile_finish(cols, c0, colmin, top + (size_t)blockIdx.z * cols, &cnt, my, valid_in);
+}
+
+__device__ __forceinline__ int top_row(int t) { return t == kTopNone ? 0 : t; }
+
+__global__ __launch_bounds__(kThreads) void k_fill_b(int rows, int cols, const float* __restrict__ s4, const int* __restrict__ top, float* __restrict__ s5,
+                                                     int* __restrict__ top2) {
+  constexpr int HALO = df::kReachB;
+  using B = Buf<HALO>;
+  __shared__ float A[B::N], Bf[B::N];
+  __shared__ int colmin[kTileW], cnt;
+  const int r0 = blockIdx.y * kTileH, c0 = blockIdx.x * kTileW;
+  const size_t base = (size_t)blockIdx.z * rows * cols;
+  if (threadIdx.x < kTileW) colmin[threadIdx.x] = kTopNone;
+  if (threadIdx.x == 0) cnt = 0;
+  auto in = [&](int r, int c) { return r >= 0 && r < rows && c >= 0 && c < cols; };
+  region<HALO, HALO, HALO>(r0, c0, [&](int i, int r, int c) { A[i] = in(r, c) ? s4[base + (size_t)r * cols + c] : 0.f; });
+  region<HALO, HALO, 0>(r0, c0, [&](int i, int r, int c) { Bf[i] = in(r, c) ? df::run_max<4>([&](int k) { return A[i + k]; }) : 0.f; });
+  region<HALO, 0, 0>(r0, c0, [&](int i, int r, int c) {                                              // S5
+    if (!in(r, c)) return;
+    float v = A[i];
+    if (!(v > df::kValid) && r >= top_row(top[(size_t)blockIdx.z * cols + c])) v = df::run_max<4>([&](int k) { return Bf[i + k * B::W]; });
+    s5[base + (size_t)r * cols + c] = v;
+    if (v > df::kValid) atomicMin(&colmin[c - c0], r);
+  });
+  tile_finish(cols, c0, colmin, top2 + (size_t)blockIdx.z * cols, &cnt, 0, nullptr);
+}
+
+// one fill round of S7a and the rounds after it: ROUND leaves the tile grown by kReachC - 2 (ROUND + 1) valid
+template <int ROUND, class In>
+__device__ __forceinline__ void fill_rounds(int r0, int c0, float* A, float* Bf, const int* tops, const In& in) {
+  constexpr int HALO = df::kReachC, REM = HALO - 2 * (ROUND + 1);
+  using B = Buf<HALO>;
+  region<HALO, REM + 2, REM>(r0, c0, [&](int i, int r, int c) { Bf[i] = in(r, c) ? df::run_max<2>([&](int k) { return A[i + k]; }) : 0.f; });
+  region<HALO, REM, REM>(r0, c0, [&](int i, int r, int c) {
+    if (in(r, c) && A[i] < df::kValid && r >= tops[c - (c0 - HALO)]) A[i] = df::run_max<2>([&](int k) { return Bf[i + k * B::W]; });   // its own pixel of A only
+  });
+  if constexpr (ROUND + 1 < df::kFillRounds) fill_rounds<ROUND + 1>(r0, c0, A, Bf, tops, in);
+}
+
+__global__ __launch_bounds__(kThreads) void k_fill_c(int rows, int cols, const float* __restrict__ s5, const int* __restrict__ top2, float M,
+                                                     float* __restrict__ dense, unsigned short* __restrict__ u16, unsigned long long* valid_out) {
+  constexpr int HALO = df::kReachC;
+  using B = Buf<HALO>;
+  static_assert(HALO == 2 * df::kFillRounds + 4, "six fills, a median and the bilateral");
+  __shared__ float A[B::N], Bf[B::N];
+  __shared__ int tops[B::W], cnt;
+  const int r0 = blockIdx.y * kTileH, c0 = blockIdx.x * kTileW;
+  const size_t base = (size_t)blockIdx.z * rows * cols;
+  if (threadIdx.x == 0) cnt = 0;
+  for (int k = threadIdx.x; k < B::W; k += kThreads) {
+    const int c = c0 - HALO + k;
+    tops[k] = (c >= 0 && c < cols) ? top_row(top2[(size_t)blockIdx.z * cols + c]) : 0;
+  }
+  auto in = [&](int r, int c) { return r >= 0 && r < rows && c >= 0 && c < cols; };
+  region<HALO, HALO, HALO>(r0, c0, [&](int i, int r, int c) { A[i] = in(r, c) ? s5[base + (size_t)r * cols + c] : 0.f; });
+  fill_rounds<0>(r0, c0, A, Bf, tops, in);                                                           // S7a
+  region<HALO, 2, 2>(r0, c0, [&](int i, int r, int c) {                                              // S7b
+    if (!in(r, c)) return;
+    float s7 = A[i];
+    if (s7 > df::kValid && r >= tops[c - (c0 - HALO)])
+      s7 = df::median5([&](int dr, int dc) { return A[(df::clampi(r + dr, rows) - (r0 - HALO)) * B::W + (df::clampi(c + dc, cols) - (c0 - HALO))]; });
+    Bf[i] = s7;
+  });
+  int my = 0;
+  region<HALO, 0, 0>(r0, c0, [&](int i, int r, int c) {                                              // S7c, S8, u16
+    if (!in(r, c)) return;
+    float s7 = Bf[i];
+    if (A[i] > df::kValid && r >= tops[c - (c0 - HALO)])
+      s7 = df::bilateral([&](int dy, int dx) { return Bf[(df::reflect101(r + dy, rows) - (r0 - HALO)) * B::W + (df::reflect101(c + dx, cols) - (c0 - HALO))]; });
+    const float out = df::invert(s7, M);
+    my += out > df::kValid;
+    if (dense) dense[base + (size_t)r * cols + c] = out;
+    if (u16) u16[base + (size_t)r * cols + c] = df::to_u16(out);
+  });
+  tile_finish(cols, c0, nullptr, nullptr, &cnt, my, valid_out);
+}
+
+pvlm_status launched(pvlm_ctx* ctx, const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return PVLM_OK;
+  PVLM_SET_ERR(ctx, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+  return PVLM_ERR_HIP;
+}
+
+// the images of one batch
+int batch_images(int n_images, size_t bytes_per_image) {
+  long long limit = (long long)std::max<size_t>(1, kBatchBytes / std::max<size_t>(1, bytes_per_image));
+  limit = std::min<long long>(limit, 65535);                                                          // gridDim.z
+  // PVLM_DEPTHFILL_BATCH_IMAGES (read at every call) lowers the image limit of a batch: how the tests run several batches on small inputs.  It changes no result.
+  if (const char* e = std::getenv("PVLM_DEPTHFILL_BATCH_IMAGES")) { const long long v = std::atoll(e); if (v > 0 && v < limit) limit = v; }
+  return (int)std::min<long long>(limit, n_images);
+}
+
+struct Work {                                            // the device images of one batch of nb images
+  float* x = nullptr; float* y = nullptr; int* top = nullptr; unsigned short* u16 = nullptr; unsigned long long* counts = nullptr;
+};
+
+// phases A, B, C of nb images on the stream: src -> (w.x | w.u16), the fp32 result in w.x when want_f32
+template <class Src>
+pvlm_status run_phases(pvlm_ctx* ctx, const char* who, int rows, int cols, int nb, Src src, float M, const Work& w, bool want_f32, bool want_u16) {
+  const dim3 grid((unsigned)((cols + kTileW - 1) / kTileW), (unsigned)((rows + kTileH - 1) / kTileH), (unsigned)nb);
+  if (hipMemsetAsync(w.top, 0x7f, 2 * (size_t)nb * cols * sizeof(int), ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "%s: memset failed", who); return PVLM_ERR_HIP; }
+  int* top2 = w.top + (size_t)nb * cols;
+  hipLaunchKernelGGL(k_fill_a<Src>, grid, dim3(kThreads), 0, ctx->stream, rows, cols, src, M, w.x, w.top, w.counts);
+  pvlm_status st = launched(ctx, who);
+  if (st) return st;
+  hipLaunchKernelGGL(k_fill_b, grid, dim3(kThreads), 0, ctx->stream, rows, cols, (const float*)w.x, (const int*)w.top, w.y, top2);
+  st = launched(ctx, who);
+  if (st) return st;
+  hipLaunchKernelGGL(k_fill_c, grid, dim3(kThreads), 0, ctx->stream, rows, cols, (const float*)w.y, (const int*)top2, M, want_f32 ? w.x : (float*)nullptr,
+                     want_u16 ? w.u16 : (unsigned short*)nullptr, w.counts + 1);
+  return launched(ctx, who);
+}
+
+pvlm_status alloc_work(pvlm_dev_scratch& tmp, size_t npix, int cols, int nb, bool want_u16, Work* w) {
+  pvlm_status st = tmp.alloc(&w->x, npix * nb);
+  if (!st) st = tmp.alloc(&w->y, npix * nb);
+  if (!st) st = tmp.alloc(&w->top, 2 * (size_t)nb * cols);
+  if (!st && want_u16) st = tmp.alloc(&w->u16, npix * nb);
+  if (!st) st = tmp.alloc(&w->counts, 2);
+  return st;
+}
+
+// the device time of a batch's stages for the statistics: three events on the context's stream, read after the batch's synchronisation
+struct StageClock {
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  bool on = false;
+  explicit StageClock(bool want) {
+    if (!want) return;
+    on = true;
+    for (hipEvent_t& x : e) if (hipEventCreate(&x) != hipSuccess) { x = nullptr; on = false; }
+  }
+  ~StageClock() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  StageClock(const StageClock&) = delete;
+  StageClock& operator=(const StageClock&) = delete;
+  void mark(pvlm_ctx* ctx, int k) { if (on) (void)hipEventRecord(e[k], ctx->stream); }
+  double ms(int a, int b) const { float t = 0.f; return on && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? (double)t : 0.0; }
+};
+
+pvlm_status enter(pvlm_ctx* ctx, const char* who) {
+  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
+  return PVLM_OK;
+}
+
+}  // namespace
+
+extern "C" pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, int n_images, const uint16_t* sparse_u16, const float* sparse_f32, float max_depth,
+                                             float* dense_f32, uint16_t* dense_u16, pvlm_depthfill_stats* stats) {
+  const char* who = "pvlm_depth_completion";
+  if (!ctx) return PVLM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || n_images < 0) { PVLM_SET_ERR(ctx, "%s: rows, cols or n_images", who); return PVLM_ERR_ARG; }
+  if ((sparse_u16 != nullptr) == (sparse_f32 != nullptr)) { PVLM_SET_ERR(ctx, "%s: exactly one of the two inputs", who); return PVLM_ERR_ARG; }
+  if (!dense_f32 && !dense_u16) { PVLM_SET_ERR(ctx, "%s: no output", who); return PVLM_ERR_ARG; }
+  if (!std::isfinite(max_depth) || !(max_depth > 0.f)) { PVLM_SET_ERR(ctx, "%s: max_depth must be finite and > 0", who); return PVLM_ERR_ARG; }
+  const size_t npix = (size_t)rows * cols;
+  if (sparse_f32)
+    for (size_t i = 0; i < npix * (size_t)n_images; ++i)
+      if (!df::input_ok(sparse_f32[i])) { PVLM_SET_ERR(ctx, "%s: value %zu of the fp32 input is negative or not finite", who, i); return PVLM_ERR_ARG; }
+  if (stats) *stats = pvlm_depthfill_stats{0, 0, 0, 0, 0.0, 0.0};
+  if (n_images == 0) return PVLM_OK;
+  pvlm_status st = enter(ctx, who);
+  if (st) return st;
+  const size_t in_bytes = sparse_u16 ? 2 : 4;
+  const int limit = batch_images(n_images, npix * (in_bytes + 8 + (dense_u16 ? 2 : 0)));
+  StageClock clock(stats != nullptr);
+  for (int k0 = 0; k0 < n_images && !st; k0 += limit) {
+    const int nb = std::min(limit, n_images - k0);
+    pvlm_dev_scratch tmp(ctx);
+    Work w;
+    unsigned short* d_in16 = nullptr; float* d_in32 = nullptr;
+    unsigned long long counts[2] = {0, 0};
+    st = alloc_work(tmp, npix, cols, nb, dense_u16 != nullptr, &w);
+    if (!st) st = sparse_u16 ? tmp.alloc(&d_in16, npix * nb) : tmp.alloc(&d_in32, npix * nb);
+    if (!st && hipMemsetAsync(w.counts, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "%s: memset failed", who); st = PVLM_ERR_HIP; }
+    if (!st) st = sparse_u16 ? pvlm_i_h2d_q(ctx, d_in16, sparse_u16 + npix * k0, npix * nb * 2) : pvlm_i_h2d_q(ctx, d_in32, sparse_f32 + npix * k0, npix * nb * 4);
+    clock.mark(ctx, 1);
+    if (!st) st = sparse_u16 ? run_phases(ctx, who, rows, cols, nb, SrcU16{d_in16}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr)
+                             : run_phases(ctx, who, rows, cols, nb, SrcF32{d_in32}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr);
+    clock.mark(ctx, 2);
+    if (!st && dense_f32) st = pvlm_i_d2h_q(ctx, dense_f32 + npix * k0, w.x, npix * nb * 4);
+    if (!st && dense_u16) st = pvlm_i_d2h_q(ctx, dense_u16 + npix * k0, w.u16, npix * nb * 2);
+    if (!st) st = pvlm_i_d2h_q(ctx, counts, w.counts, sizeof(counts));
+    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
+    if (!st && stats) { stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1]; stats->fill_ms += clock.ms(1, 2); }
+  }
+  return st;
+}
+
+extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl,
+                                                 unsigned size, float max_depth, uint16_t* depth_u16, pvlm_depthfill_stats* stats) {
+  const char* who = "pvlm_compute_depth_images";
+  if (!ctx) return PVLM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || n_scans < 0 || !T_cl || (n_scans > 0 && (!first_point || !depth_u16))) { PVLM_SET_ERR(ctx, "%s: null argument or size", who); return PVLM_ERR_ARG; }
+  if (!std::isfinite(max_depth) || !(max_depth > 0.f)) { PVLM_SET_ERR(ctx, "%s: max_depth must be finite and > 0", who); return PVLM_ERR_ARG; }
+  if (stats) *stats = pvlm_depthfill_stats{0, 0, 0, 0, 0.0, 0.0};
+  if (n_scans == 0) return PVLM_OK;
+  if (first_point[0] != 0) { PVLM_SET_ERR(ctx, "%s: first_point must start at 0", who); return PVLM_ERR_ARG; }
+  for (int s = 0; s < n_scans; ++s)
+    if (first_point[s + 1] < first_point[s]) { PVLM_SET_ERR(ctx, "%s: first_point is not ascending at scan %d", who, s); return PVLM_ERR_ARG; }
+  if (first_point[n_scans] > 0 && !xyz) { PVLM_SET_ERR(ctx, "%s: null argument", who); return PVLM_ERR_ARG; }
+  pvlm_status st = enter(ctx, who);
+  if (st) return st;
+  const size_t npix = (size_t)rows * cols;
+  const int limit = batch_images(n_scans, npix * (8 + 8 + 2));
+  StageClock clock(stats != nullptr);
+  pvlm_dev_scratch call_tmp(ctx);
+  double* d_T = nullptr;
+  st = call_tmp.alloc(&d_T, (size_t)16);
+  if (!st) st = pvlm_i_h2d_q(ctx, d_T, T_cl, 16 * sizeof(double));
+  for (int k0 = 0; k0 < n_scans && !st; k0 += limit) {
+    const int nb = std::min(limit, n_scans - k0);
+    const long long p0 = first_point[k0], np = first_point[k0 + nb] - p0;
+    pvlm_dev_scratch tmp(ctx);
+    Work w;
+    unsigned long long* d_img = nullptr; float* d_xyz = nullptr;
+    unsigned long long counts[2] = {0, 0};
+    st = alloc_work(tmp, npix, cols, nb, true, &w);
+    if (!st) st = tmp.alloc(&d_img, npix * nb);
+    if (!st) st = tmp.alloc(&d_xyz, 3 * (size_t)np);
+    clock.mark(ctx, 0);
+    if (!st && (hipMemsetAsync(w.counts, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess ||
+                hipMemsetAsync(d_img, 0, npix * nb * sizeof(unsigned long long), ctx->stream) != hipSuccess)) { PVLM_SET_ERR(ctx, "%s: memset failed", who); st = PVLM_ERR_HIP; }
+    if (!st && np > 0) st = pvlm_i_h2d_q(ctx, d_xyz, xyz + 3 * (size_t)p0, 3 * (size_t)np * sizeof(float));
+    for (int k = 0; k < nb && !st; ++k)
+      st = pvlm_depth_launch::splat(ctx, who, rows, cols, first_point[k0 + k + 1] - first_point[k0 + k], d_xyz + 3 * (size_t)(first_point[k0 + k] - p0), d_T, size,
+                                    d_img + npix * k);
+    clock.mark(ctx, 1);
+    if (!st) st = run_phases(ctx, who, rows, cols, nb, SrcSplat{d_img}, max_depth, w, false, true);
+    clock.mark(ctx, 2);
+    if (!st) st = pvlm_i_d2h_q(ctx, depth_u16 + npix * k0, w.u16, npix * nb * 2);
+    if (!st) st = pvlm_i_d2h_q(ctx, counts, w.counts, sizeof(counts));
+    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
+    if (!st && stats) {
+      stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1];
+      stats->splat_ms += clock.ms(0, 1); stats->fill_ms += clock.ms(1, 2);
+    }
+  }
+  if (st) (void)pvlm_i_sync(ctx);
+  return st;
+}
+
+// pvlm_preload: loads this file's code object at context set-up instead of at the first call (see pvlm_ba.hip)
+__global__ void k_preload_depthfill() {}
+void pvlm_i_preload_depthfill(hipStream_t s) { hipLaunchKernelGGL(k_preload_depthfill, dim3(1), dim3(1), 0, s); }

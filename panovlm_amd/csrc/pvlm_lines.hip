@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pvlm_depth_launch.h"
 #include "pvlm_internal.h"
 #include "pvlm_workers.h"
 #include "pvlm_exact_math.h"
@@ -584,6 +585,13 @@ static pvlm_status finish(pvlm_ctx* ctx, pvlm_status st) {
   return st ? st : s2;
 }
 
+pvlm_status pvlm_depth_launch::splat(pvlm_ctx* ctx, const char* who, int rows, int cols, long long n, const float* d_xyz, const double* d_T, unsigned size,
+                                     unsigned long long* d_img) {
+  if (n <= 0) return PVLM_OK;
+  hipLaunchKernelGGL(k_depth_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rows, cols, n, d_xyz, d_T, (int)(size / 2), d_img);
+  return hip_status(ctx, who, hipGetLastError());
+}
+
 // ---- host: K7 and the depth image -----------------------------------------------------------------------------------
 template <typename T, typename K>
 static pvlm_status run_map(pvlm_ctx* ctx, long long n, const T* in, int in_w, T* out, int out_w, K launch) {
@@ -641,10 +649,7 @@ pvlm_status pvlm_project_lidar_depth(pvlm_ctx* ctx, int rows, int cols, int64_t 
   if (!st) st = hip_status(ctx, "project_lidar_depth", hipMemsetAsync(d_img, 0, npix * sizeof(unsigned long long), ctx->stream));
   if (!st && n > 0) st = pvlm_i_h2d_q(ctx, d_xyz, xyz, (size_t)n * 3 * sizeof(float));
   if (!st) st = pvlm_i_h2d_q(ctx, d_T, T_cl, 16 * sizeof(double));
-  if (!st && n > 0) {
-    hipLaunchKernelGGL(k_depth_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rows, cols, (long long)n, d_xyz, d_T, (int)(size / 2), d_img);
-    st = hip_status(ctx, "project_lidar_depth", hipGetLastError());
-  }
+  if (!st) st = pvlm_depth_launch::splat(ctx, "project_lidar_depth", rows, cols, (long long)n, d_xyz, d_T, size, d_img);
   if (!st) {
     hipLaunchKernelGGL(k_depth_finish, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ctx->stream, (long long)npix, d_img, d_out);
     st = hip_status(ctx, "project_lidar_depth", hipGetLastError());

@@ -690,8 +690,22 @@ bool RefineRelativePoses(const std::vector<Frame>& frames, std::vector<RelativeP
 bool RefineRelativePosesHost(const std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, int residual_type = PIXEL_RESIDUAL, std::vector<bool>* ok = nullptr,
                              const int num_threads = 16);
 // The depth maps of the frames (upstream: frames[i].depth_map, a CV_16U image of depth x 256 read from a file): maps[f] is rows[f] x cols[f], row-major; an empty
-// vector means the frame has none.  DepthCompletion is the caller's business.
+// vector means the frame has none.  ComputeDepthImage / ComputeDepthImageHost below (K37) make them from the LiDAR scans.
 struct DepthMaps { std::vector<std::vector<uint16_t>> maps; std::vector<int> rows, cols; };
+// ---- K37: the depth maps (util/DepthCompletion.cpp:154-316, sfm/SfM.cpp:170-226) ---------------------------------------------------------------
+// DepthCompletion(sparse_depth, max_depth) on the whole-image host loop of csrc/pvlm_depthfill_core.h (the stages, the OpenCV semantics they rest on and the
+// deliberate divergence of the bilateral filter are stated there): image is rows x cols floats, row-major, metres; returns the dense image.  A negative or
+// non-finite value throws std::invalid_argument.  For a caller with one image; pvlm_depth_completion takes batches on the GPU.
+std::vector<float> DepthCompletion(const std::vector<float>& image, const int rows, const int cols, const float max_depth);
+// The loop of SfM::ComputeDepthImage over all frames in ONE pvlm_compute_depth_images call (K37): for frame i ProjectLidar2PanoramaDepth(clouds[i], rows, cols, T_cl,
+// 4), DepthCompletion(.., max_depth), x 256, CV_16U, with rows = (image_rows + 1) / 2 and cols = (image_cols + 1) / 2 when half_size (upstream's choice) and the image
+// size otherwise.  clouds[i] is the scan of frame i in the LiDAR frame, T_cl the one calibration.  Upstream's lidars.size() != frames.size() refusal:
+// std::invalid_argument.  No visualisation, no files.  The result is what FilterImagePairsFull takes.
+DepthMaps ComputeDepthImage(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows, const int image_cols,
+                            const float max_depth, const bool half_size = true);
+// the same on the host loop of the core, the frames spread over num_threads workers: the baseline tools/depthfill_bench.py times and the equality partner of the call
+DepthMaps ComputeDepthImageHost(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows, const int image_cols,
+                                const float max_depth, const bool half_size = true, const int num_threads = 16);
 // SfM::SetTranslationScaleDepthMap(eq, pair) (:487-603) operation by operation: the half-size test, round, IsInside, the 0.2 consistency test, two histogram passes
 // (the 1e-8 offset, the clamped bin index, the > 0.1 num_scale keep rule), the nth_element median fall-back.  It stays on the host on purpose.
 bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, RelativePair& image_pair);

@@ -12,6 +12,7 @@
 #include "pvlm_host_essential.hpp"
 #include "pvlm_host_vlad.hpp"
 #include "pvlm_host_relpose.hpp"
+#include "../csrc/pvlm_depthfill_core.h"
 
 namespace pvlm {
 
@@ -671,6 +672,62 @@ bool EstimateStructure(const std::vector<Frame>& frames, const std::vector<Match
 bool CameraLidarOptimizer::EstimateStructure(const std::vector<MatchPair>& image_pairs) {
   StageTimer stage_timer_("EstimateStructure");
   return structure_detail::EstimateStructureWith(DeviceKernels(), frames, image_pairs, structure);
+}
+
+// ================================================================================================
+// K37: DepthCompletion, ComputeDepthImage
+// ================================================================================================
+std::vector<float> DepthCompletion(const std::vector<float>& image, const int rows, const int cols, const float max_depth) {
+  if (rows <= 0 || cols <= 0 || image.size() != (size_t)rows * (size_t)cols) throw std::invalid_argument("DepthCompletion: the image is not rows x cols");
+  if (!std::isfinite(max_depth) || !(max_depth > 0.f)) throw std::invalid_argument("DepthCompletion: max_depth must be finite and > 0");
+  for (float v : image) if (!pvlm_depthfill::input_ok(v)) throw std::invalid_argument("DepthCompletion: a depth is negative or not finite");
+  std::vector<float> dense(image.size());
+  pvlm_depthfill::complete_host(rows, cols, image.data(), max_depth, dense.data(), nullptr);
+  return dense;
+}
+
+namespace {
+// the arrays of pvlm_compute_depth_images from the scans, and the result as DepthMaps
+struct DepthImageCall {
+  int rows, cols;
+  std::vector<long long> first; std::vector<float> xyz; std::vector<uint16_t> out;
+  DepthImageCall(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, int image_rows, int image_cols, float max_depth, bool half_size) {
+    if (clouds.size() != frames.size()) throw std::invalid_argument("ComputeDepthImage: lidars.size() != frames.size()");
+    if (image_rows <= 0 || image_cols <= 0 || !std::isfinite(max_depth) || !(max_depth > 0.f)) throw std::invalid_argument("ComputeDepthImage: image size or max_depth");
+    rows = half_size ? (image_rows + 1) / 2 : image_rows; cols = half_size ? (image_cols + 1) / 2 : image_cols;
+    first.push_back(0);
+    for (const PointCloud& c : clouds) {
+      for (const PointXYZI& p : c) { xyz.push_back(p.x); xyz.push_back(p.y); xyz.push_back(p.z); }
+      first.push_back((long long)(xyz.size() / 3));
+    }
+    xyz.resize(xyz.size() + 3);                                                // never empty
+    out.resize(clouds.size() * (size_t)rows * (size_t)cols + 1);
+  }
+  DepthMaps Maps() const {
+    DepthMaps d;
+    const size_t n = (size_t)rows * (size_t)cols;
+    for (size_t f = 0; f + 1 < first.size(); ++f) { d.maps.emplace_back(out.begin() + (std::ptrdiff_t)(f * n), out.begin() + (std::ptrdiff_t)((f + 1) * n)); d.rows.push_back(rows); d.cols.push_back(cols); }
+    return d;
+  }
+};
+}  // namespace
+
+DepthMaps ComputeDepthImage(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows, const int image_cols,
+                            const float max_depth, const bool half_size) {
+  StageTimer stage_timer_("ComputeDepthImage");
+  DepthImageCall call(frames, clouds, image_rows, image_cols, max_depth, half_size);
+  Engine& e = Engine::Default();
+  e.Check(pvlm_compute_depth_images(e.ctx(), call.rows, call.cols, (int)clouds.size(), call.first.data(), call.xyz.data(), T_cl.data(), 4u, max_depth, call.out.data(), nullptr),
+          "pvlm_compute_depth_images");
+  return call.Maps();
+}
+
+DepthMaps ComputeDepthImageHost(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows, const int image_cols,
+                                const float max_depth, const bool half_size, const int num_threads) {
+  DepthImageCall call(frames, clouds, image_rows, image_cols, max_depth, half_size);
+  pvlm_depthfill::depth_images_host(call.rows, call.cols, (int)clouds.size(), call.first.data(), call.xyz.data(), T_cl.data(), 4u, max_depth, call.out.data(),
+                                    (size_t)std::max(num_threads, 1));
+  return call.Maps();
 }
 
 }  // namespace pvlm
