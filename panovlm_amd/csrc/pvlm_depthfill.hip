@@ -166,50 +166,32 @@ __global__ __launch_bounds__(kThreads) void k_fill_c(int rows, int cols, const f
   tile_finish(cols, c0, nullptr, nullptr, &cnt, my, valid_out);
 }
 
-pvlm_status launched(pvlm_ctx* ctx, const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return PVLM_OK;
-  PVLM_SET_ERR(ctx, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-  return PVLM_ERR_HIP;
-}
-
 // the images of one batch
 int batch_images(int n_images, size_t bytes_per_image) {
   long long limit = (long long)std::max<size_t>(1, kBatchBytes / std::max<size_t>(1, bytes_per_image));
   limit = std::min<long long>(limit, 65535);                                                          // gridDim.z
-  // PVLM_DEPTHFILL_BATCH_IMAGES (read at every call) lowers the image limit of a batch: how the tests run several batches on small inputs.  It changes no result.
-  if (const char* e = std::getenv("PVLM_DEPTHFILL_BATCH_IMAGES")) { const long long v = std::atoll(e); if (v > 0 && v < limit) limit = v; }
-  return (int)std::min<long long>(limit, n_images);
+  return (int)std::min<long long>(pvlm_i_env_limit("PVLM_DEPTHFILL_BATCH_IMAGES", limit), n_images);
 }
 
-struct Work {                                            // the device images of one batch of nb images
-  float* x = nullptr; float* y = nullptr; int* top = nullptr; unsigned short* u16 = nullptr; unsigned long long* counts = nullptr;
+struct Work {                                            // the device images of one batch of nb images: scratch of the frame, the two counters zeroed
+  float* x; float* y; int* top; unsigned short* u16; unsigned long long* counts;
+  Work(pvlm_call& c, size_t npix, int cols, int nb, bool want_u16)
+      : x(c.alloc<float>(npix * nb)), y(c.alloc<float>(npix * nb)), top(c.alloc<int>(2 * (size_t)nb * cols)), u16(want_u16 ? c.alloc<unsigned short>(npix * nb) : nullptr),
+        counts(c.alloc<unsigned long long>(2)) {}
 };
 
 // phases A, B, C of nb images on the stream: src -> (w.x | w.u16), the fp32 result in w.x when want_f32
 template <class Src>
-pvlm_status run_phases(pvlm_ctx* ctx, const char* who, int rows, int cols, int nb, Src src, float M, const Work& w, bool want_f32, bool want_u16) {
+void run_phases(pvlm_call& c, int rows, int cols, int nb, Src src, float M, const Work& w, bool want_f32, bool want_u16) {
   const dim3 grid((unsigned)((cols + kTileW - 1) / kTileW), (unsigned)((rows + kTileH - 1) / kTileH), (unsigned)nb);
-  if (hipMemsetAsync(w.top, 0x7f, 2 * (size_t)nb * cols * sizeof(int), ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "%s: memset failed", who); return PVLM_ERR_HIP; }
+  c.memset(w.top, 0x7f, 2 * (size_t)nb * cols * sizeof(int));
   int* top2 = w.top + (size_t)nb * cols;
-  hipLaunchKernelGGL(k_fill_a<Src>, grid, dim3(kThreads), 0, ctx->stream, rows, cols, src, M, w.x, w.top, w.counts);
-  pvlm_status st = launched(ctx, who);
-  if (st) return st;
-  hipLaunchKernelGGL(k_fill_b, grid, dim3(kThreads), 0, ctx->stream, rows, cols, (const float*)w.x, (const int*)w.top, w.y, top2);
-  st = launched(ctx, who);
-  if (st) return st;
-  hipLaunchKernelGGL(k_fill_c, grid, dim3(kThreads), 0, ctx->stream, rows, cols, (const float*)w.y, (const int*)top2, M, want_f32 ? w.x : (float*)nullptr,
-                     want_u16 ? w.u16 : (unsigned short*)nullptr, w.counts + 1);
-  return launched(ctx, who);
-}
-
-pvlm_status alloc_work(pvlm_dev_scratch& tmp, size_t npix, int cols, int nb, bool want_u16, Work* w) {
-  pvlm_status st = tmp.alloc(&w->x, npix * nb);
-  if (!st) st = tmp.alloc(&w->y, npix * nb);
-  if (!st) st = tmp.alloc(&w->top, 2 * (size_t)nb * cols);
-  if (!st && want_u16) st = tmp.alloc(&w->u16, npix * nb);
-  if (!st) st = tmp.alloc(&w->counts, 2);
-  return st;
+  c.launch(k_fill_a<Src>, grid, dim3(kThreads), 0, rows, cols, src, M, w.x, w.top, w.counts);
+  c.check_launches();
+  c.launch(k_fill_b, grid, dim3(kThreads), 0, rows, cols, w.x, w.top, w.y, top2);
+  c.check_launches();
+  c.launch(k_fill_c, grid, dim3(kThreads), 0, rows, cols, w.y, top2, M, want_f32 ? w.x : nullptr, want_u16 ? w.u16 : nullptr, w.counts + 1);
+  c.check_launches();
 }
 
 // the device time of a batch's stages for the statistics: three events on the context's stream, read after the batch's synchronisation
@@ -228,12 +210,6 @@ struct StageClock {
   double ms(int a, int b) const { float t = 0.f; return on && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? (double)t : 0.0; }
 };
 
-pvlm_status enter(pvlm_ctx* ctx, const char* who) {
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
-  return PVLM_OK;
-}
-
 }  // namespace
 
 extern "C" pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, int n_images, const uint16_t* sparse_u16, const float* sparse_f32, float max_depth,
@@ -250,32 +226,29 @@ extern "C" pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, 
       if (!df::input_ok(sparse_f32[i])) { PVLM_SET_ERR(ctx, "%s: value %zu of the fp32 input is negative or not finite", who, i); return PVLM_ERR_ARG; }
   if (stats) *stats = pvlm_depthfill_stats{0, 0, 0, 0, 0.0, 0.0};
   if (n_images == 0) return PVLM_OK;
-  pvlm_status st = enter(ctx, who);
-  if (st) return st;
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const size_t in_bytes = sparse_u16 ? 2 : 4;
   const int limit = batch_images(n_images, npix * (in_bytes + 8 + (dense_u16 ? 2 : 0)));
   StageClock clock(stats != nullptr);
-  for (int k0 = 0; k0 < n_images && !st; k0 += limit) {
+  for (int k0 = 0; k0 < n_images && !c.st; k0 += limit) {
     const int nb = std::min(limit, n_images - k0);
-    pvlm_dev_scratch tmp(ctx);
-    Work w;
-    unsigned short* d_in16 = nullptr; float* d_in32 = nullptr;
+    pvlm_call::batch bs(c);                              // this batch's scratch
+    const Work w(c, npix, cols, nb, dense_u16 != nullptr);
     unsigned long long counts[2] = {0, 0};
-    st = alloc_work(tmp, npix, cols, nb, dense_u16 != nullptr, &w);
-    if (!st) st = sparse_u16 ? tmp.alloc(&d_in16, npix * nb) : tmp.alloc(&d_in32, npix * nb);
-    if (!st && hipMemsetAsync(w.counts, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "%s: memset failed", who); st = PVLM_ERR_HIP; }
-    if (!st) st = sparse_u16 ? pvlm_i_h2d_q(ctx, d_in16, sparse_u16 + npix * k0, npix * nb * 2) : pvlm_i_h2d_q(ctx, d_in32, sparse_f32 + npix * k0, npix * nb * 4);
+    c.memset(w.counts, 0, 2 * sizeof(unsigned long long));
+    unsigned short* d_in16 = sparse_u16 ? c.upload(sparse_u16 + npix * k0, npix * nb) : nullptr;
+    float* d_in32 = sparse_f32 ? c.upload(sparse_f32 + npix * k0, npix * nb) : nullptr;
     clock.mark(ctx, 1);
-    if (!st) st = sparse_u16 ? run_phases(ctx, who, rows, cols, nb, SrcU16{d_in16}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr)
-                             : run_phases(ctx, who, rows, cols, nb, SrcF32{d_in32}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr);
+    if (sparse_u16) run_phases(c, rows, cols, nb, SrcU16{d_in16}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr);
+    else run_phases(c, rows, cols, nb, SrcF32{d_in32}, max_depth, w, dense_f32 != nullptr, dense_u16 != nullptr);
     clock.mark(ctx, 2);
-    if (!st && dense_f32) st = pvlm_i_d2h_q(ctx, dense_f32 + npix * k0, w.x, npix * nb * 4);
-    if (!st && dense_u16) st = pvlm_i_d2h_q(ctx, dense_u16 + npix * k0, w.u16, npix * nb * 2);
-    if (!st) st = pvlm_i_d2h_q(ctx, counts, w.counts, sizeof(counts));
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    if (!st && stats) { stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1]; stats->fill_ms += clock.ms(1, 2); }
+    if (dense_f32) c.d2h(dense_f32 + npix * k0, w.x, npix * nb * 4);
+    if (dense_u16) c.d2h(dense_u16 + npix * k0, w.u16, npix * nb * 2);
+    c.d2h(counts, w.counts, sizeof(counts));
+    if (!c.sync() && stats) { stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1]; stats->fill_ms += clock.ms(1, 2); }
   }
-  return st;
+  return c.st;
 }
 
 extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl,
@@ -290,45 +263,38 @@ extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int co
   for (int s = 0; s < n_scans; ++s)
     if (first_point[s + 1] < first_point[s]) { PVLM_SET_ERR(ctx, "%s: first_point is not ascending at scan %d", who, s); return PVLM_ERR_ARG; }
   if (first_point[n_scans] > 0 && !xyz) { PVLM_SET_ERR(ctx, "%s: null argument", who); return PVLM_ERR_ARG; }
-  pvlm_status st = enter(ctx, who);
-  if (st) return st;
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const size_t npix = (size_t)rows * cols;
   const int limit = batch_images(n_scans, npix * (8 + 8 + 2));
   StageClock clock(stats != nullptr);
-  pvlm_dev_scratch call_tmp(ctx);
-  double* d_T = nullptr;
-  st = call_tmp.alloc(&d_T, (size_t)16);
-  if (!st) st = pvlm_i_h2d_q(ctx, d_T, T_cl, 16 * sizeof(double));
-  for (int k0 = 0; k0 < n_scans && !st; k0 += limit) {
+  double* d_T = c.upload(T_cl, (size_t)16);
+  for (int k0 = 0; k0 < n_scans && !c.st; k0 += limit) {
     const int nb = std::min(limit, n_scans - k0);
     const long long p0 = first_point[k0], np = first_point[k0 + nb] - p0;
-    pvlm_dev_scratch tmp(ctx);
-    Work w;
-    unsigned long long* d_img = nullptr; float* d_xyz = nullptr;
+    pvlm_call::batch bs(c);                              // this batch's scratch
+    const Work w(c, npix, cols, nb, true);
+    unsigned long long* d_img = c.alloc<unsigned long long>(npix * nb);
+    float* d_xyz = c.alloc<float>(3 * (size_t)np);
     unsigned long long counts[2] = {0, 0};
-    st = alloc_work(tmp, npix, cols, nb, true, &w);
-    if (!st) st = tmp.alloc(&d_img, npix * nb);
-    if (!st) st = tmp.alloc(&d_xyz, 3 * (size_t)np);
     clock.mark(ctx, 0);
-    if (!st && (hipMemsetAsync(w.counts, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess ||
-                hipMemsetAsync(d_img, 0, npix * nb * sizeof(unsigned long long), ctx->stream) != hipSuccess)) { PVLM_SET_ERR(ctx, "%s: memset failed", who); st = PVLM_ERR_HIP; }
-    if (!st && np > 0) st = pvlm_i_h2d_q(ctx, d_xyz, xyz + 3 * (size_t)p0, 3 * (size_t)np * sizeof(float));
-    for (int k = 0; k < nb && !st; ++k)
-      st = pvlm_depth_launch::splat(ctx, who, rows, cols, first_point[k0 + k + 1] - first_point[k0 + k], d_xyz + 3 * (size_t)(first_point[k0 + k] - p0), d_T, size,
-                                    d_img + npix * k);
+    c.memset(w.counts, 0, 2 * sizeof(unsigned long long));
+    c.memset(d_img, 0, npix * nb * sizeof(unsigned long long));
+    c.h2d(d_xyz, xyz + 3 * (size_t)p0, 3 * (size_t)np * sizeof(float));
+    for (int k = 0; k < nb && !c.st; ++k)                // the splat is pvlm_lines.hip's: it takes the context and reports a status
+      c.st = pvlm_depth_launch::splat(ctx, who, rows, cols, first_point[k0 + k + 1] - first_point[k0 + k], d_xyz + 3 * (size_t)(first_point[k0 + k] - p0), d_T, size,
+                                      d_img + npix * k);
     clock.mark(ctx, 1);
-    if (!st) st = run_phases(ctx, who, rows, cols, nb, SrcSplat{d_img}, max_depth, w, false, true);
+    run_phases(c, rows, cols, nb, SrcSplat{d_img}, max_depth, w, false, true);
     clock.mark(ctx, 2);
-    if (!st) st = pvlm_i_d2h_q(ctx, depth_u16 + npix * k0, w.u16, npix * nb * 2);
-    if (!st) st = pvlm_i_d2h_q(ctx, counts, w.counts, sizeof(counts));
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    if (!st && stats) {
+    c.d2h(depth_u16 + npix * k0, w.u16, npix * nb * 2);
+    c.d2h(counts, w.counts, sizeof(counts));
+    if (!c.sync() && stats) {
       stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1];
       stats->splat_ms += clock.ms(0, 1); stats->fill_ms += clock.ms(1, 2);
     }
   }
-  if (st) (void)pvlm_i_sync(ctx);
-  return st;
+  return c.st;
 }
 
 // pvlm_preload: loads this file's code object at context set-up instead of at the first call (see pvlm_ba.hip)

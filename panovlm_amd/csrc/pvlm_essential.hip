@@ -293,8 +293,7 @@ struct Batches { std::vector<int> first; };                 // first pair of eve
 // PVLM_ESSENTIAL_BATCH_PAIRS (read at every call) lowers the pair limit of a batch: how the tests run many batches on small inputs
 Batches make_batches(int n_pairs, const long long* off, int n_runs) {
   Batches b;
-  int pair_limit = std::max(1, kBatchChains / n_runs);
-  if (const char* e = std::getenv("PVLM_ESSENTIAL_BATCH_PAIRS")) { const int v = std::atoi(e); if (v > 0 && v < pair_limit) pair_limit = v; }
+  const int pair_limit = (int)pvlm_i_env_limit("PVLM_ESSENTIAL_BATCH_PAIRS", std::max(1, kBatchChains / n_runs));
   b.first.push_back(0);
   for (int p = 0; p < n_pairs;) {
     long long nm = 0; int k = p;
@@ -326,23 +325,19 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, bool raw, int n_frames, const fl
   static bool monotone = false;
   static const double cos_reject = es::angle_threshold(&monotone);
   if (!monotone) { PVLM_SET_ERR(ctx, "%s: this libm's acos is not monotone around 3 degrees", who); return PVLM_ERR_STATE; }
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const Batches bt = make_batches(n_pairs, off, n_runs);
-  pvlm_dev_scratch tmp(ctx);
-  hipStream_t S = ctx->stream;
   // the bearings of every frame, once
   std::vector<long long> row0((size_t)n_frames + 1, 0);
   for (int f = 0; f < n_frames; ++f) row0[(size_t)f + 1] = row0[(size_t)f] + rows[f];
-  float* d_bear = nullptr;
-  pvlm_status st = tmp.alloc(&d_bear, 3 * (size_t)row0[(size_t)n_frames]);
-  for (int f = 0; f < n_frames && !st; ++f)
-    if (rows[f] > 0) st = pvlm_i_h2d_q(ctx, d_bear + 3 * row0[(size_t)f], bearings[f], 3 * (size_t)rows[f] * sizeof(float));
-  if (st) { (void)pvlm_i_sync(ctx); return st; }
+  float* d_bear = c.alloc<float>(3 * (size_t)row0[(size_t)n_frames]);
+  for (int f = 0; f < n_frames; ++f) c.h2d(d_bear + 3 * row0[(size_t)f], bearings[f], 3 * (size_t)rows[f] * sizeof(float));
+  if (c.st) return c.st;
   std::map<int, std::vector<double>> tables;               // one table per distinct match count
   std::vector<PairDesc> pd; std::vector<TileDesc> tiles; std::vector<int> ns, h_iters, h_keep, h_cnt, h_lists; std::vector<long long> h_per; std::vector<double> h_tab, h_E, h_nfa;
   long long written = 0, total = 0;
-  for (size_t bi = 0; bi + 1 < bt.first.size() && !st; ++bi) {
+  for (size_t bi = 0; bi + 1 < bt.first.size() && !c.st; ++bi) {
     const int p0 = bt.first[bi], np = bt.first[bi + 1] - p0;
     const long long M = off[p0 + np] - off[p0];
     const size_t NC = (size_t)np * (size_t)n_runs;
@@ -371,93 +366,80 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, bool raw, int n_frames, const fl
     }
     make_tiles(ns.data(), np, pd.data(), tiles);
     const int nt = (int)tiles.size();
-    pvlm_dev_scratch bs(ctx);                                // this batch's scratch
-    PairDesc* d_pairs = nullptr; pvlm_match* d_m = nullptr; double* d_tab = nullptr; ChainRes* d_res = nullptr; int* d_iters = nullptr; unsigned* d_mask = nullptr;
-    double* d_fkey = nullptr; int* d_fidx = nullptr; int* d_fset = nullptr; double* d_E = nullptr; double* d_nfa = nullptr; int* d_cnt = nullptr; int* d_lists = nullptr;
-    TileDesc* d_tiles = nullptr; int* d_tcount = nullptr; long long* d_tbase = nullptr; long long* d_per = nullptr; int* d_win = nullptr; int* d_keep = nullptr;
-    double* d_R = nullptr; double* d_t = nullptr; int* d_oidx = nullptr; double* d_otri = nullptr;
-    st = bs.alloc(&d_pairs, (size_t)np);
-    if (!st) st = bs.alloc(&d_m, (size_t)M);
-    if (!st) st = bs.alloc(&d_tab, h_tab.size());
-    if (!st) st = bs.alloc(&d_iters, NC);
-    if (!st) st = bs.alloc(&d_fkey, (size_t)fkey);
-    if (!st) st = bs.alloc(&d_fidx, (size_t)fkey);
-    if (!st) st = bs.alloc(&d_fset, (size_t)fset);
-    if (!st && raw) { st = bs.alloc(&d_E, 9 * NC); if (!st) st = bs.alloc(&d_nfa, NC); if (!st) st = bs.alloc(&d_cnt, NC); if (!st) st = bs.alloc(&d_lists, (size_t)lists); }
-    if (!st && !raw) {
-      st = bs.alloc(&d_res, NC);
-      if (!st) st = bs.alloc(&d_mask, (size_t)words);
-      if (!st) st = bs.alloc(&d_tiles, (size_t)nt);
-      if (!st) st = bs.alloc(&d_tcount, (size_t)nt);
-      if (!st) st = bs.alloc(&d_tbase, (size_t)nt);
-      if (!st) st = bs.alloc(&d_per, (size_t)np + 1);
-      if (!st) st = bs.alloc(&d_win, (size_t)np);
-      if (!st) st = bs.alloc(&d_keep, (size_t)np);
-      if (!st) st = bs.alloc(&d_R, 9 * (size_t)np);
-      if (!st) st = bs.alloc(&d_t, 3 * (size_t)np);
-      if (!st) st = bs.alloc(&d_oidx, (size_t)M);
-      if (!st) st = bs.alloc(&d_otri, 3 * (size_t)M);
-    }
-    if (!st) st = pvlm_i_h2d_q(ctx, d_pairs, pd.data(), (size_t)np * sizeof(PairDesc));
-    if (!st && M > 0) st = pvlm_i_h2d_q(ctx, d_m, matches + off[p0], (size_t)M * sizeof(pvlm_match));
-    if (!st && !h_tab.empty()) st = pvlm_i_h2d_q(ctx, d_tab, h_tab.data(), h_tab.size() * sizeof(double));
-    if (!st && !raw && nt > 0) st = pvlm_i_h2d_q(ctx, d_tiles, tiles.data(), (size_t)nt * sizeof(TileDesc));
-    if (st) break;
+    pvlm_call::batch bs(c);                                  // this batch's scratch
+    PairDesc* d_pairs = c.upload(pd.data(), (size_t)np);
+    pvlm_match* d_m = c.upload(matches + off[p0], (size_t)M);
+    double* d_tab = c.upload(h_tab.data(), h_tab.size());
+    int* d_iters = c.alloc<int>(NC);
+    double* d_fkey = c.alloc<double>((size_t)fkey);
+    int* d_fidx = c.alloc<int>((size_t)fkey);
+    int* d_fset = c.alloc<int>((size_t)fset);
+    double* d_E = raw ? c.alloc<double>(9 * NC) : nullptr;                       // the raw entry's outputs
+    double* d_nfa = raw ? c.alloc<double>(NC) : nullptr;
+    int* d_cnt = raw ? c.alloc<int>(NC) : nullptr;
+    int* d_lists = raw ? c.alloc<int>((size_t)lists) : nullptr;
+    ChainRes* d_res = raw ? nullptr : c.alloc<ChainRes>(NC);                     // the filter entry's: the chains' results, the selection, the ordered compaction
+    unsigned* d_mask = raw ? nullptr : c.alloc<unsigned>((size_t)words);
+    TileDesc* d_tiles = raw ? nullptr : c.upload(tiles.data(), (size_t)nt);
+    int* d_tcount = raw ? nullptr : c.alloc<int>((size_t)nt);
+    long long* d_tbase = raw ? nullptr : c.alloc<long long>((size_t)nt);
+    long long* d_per = raw ? nullptr : c.alloc<long long>((size_t)np + 1);
+    int* d_win = raw ? nullptr : c.alloc<int>((size_t)np);
+    int* d_keep = raw ? nullptr : c.alloc<int>((size_t)np);
+    double* d_R = raw ? nullptr : c.alloc<double>(9 * (size_t)np);
+    double* d_t = raw ? nullptr : c.alloc<double>(3 * (size_t)np);
+    int* d_oidx = raw ? nullptr : c.alloc<int>((size_t)M);
+    double* d_otri = raw ? nullptr : c.alloc<double>(3 * (size_t)M);
     const int lp = pow2ceil(lds_n);
     const size_t lds_bytes = sizeof(double) * (size_t)(kHeadDoubles + lp) + sizeof(int) * (size_t)(lp + lds_n) + sizeof(float) * 6 * (size_t)lds_n;
-    hipLaunchKernelGGL(k_ess_chain, dim3((unsigned)NC), dim3(kChainThreads), lds_bytes, S, (const PairDesc*)d_pairs, (const pvlm_match*)d_m, (const double*)d_tab, n_runs, maxit,
-                       flags, prm->seed, cos_reject, prm->triangulation_num_threshold, lds_n, d_fkey, d_fidx, d_fset, d_mask, d_E, d_nfa, d_cnt, d_lists, d_iters, d_res);
+    c.launch(k_ess_chain, dim3((unsigned)NC), dim3(kChainThreads), lds_bytes, d_pairs, d_m, d_tab, n_runs, maxit, flags, prm->seed, cos_reject, prm->triangulation_num_threshold,
+             lds_n, d_fkey, d_fidx, d_fset, d_mask, d_E, d_nfa, d_cnt, d_lists, d_iters, d_res);
     if (!raw) {
-      hipLaunchKernelGGL(k_ess_select, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, S, (const ChainRes*)d_res, np, n_runs, d_win, d_keep, d_R, d_t);
-      if (nt > 0) hipLaunchKernelGGL(k_ess_count, dim3((unsigned)nt), dim3(kThreads), 0, S, (const PairDesc*)d_pairs, (const TileDesc*)d_tiles, (const pvlm_match*)d_m,
-                                     (const unsigned*)d_mask, (const int*)d_win, (const double*)d_R, (const double*)d_t, cos_reject, d_tcount);
-      hipLaunchKernelGGL(k_tile_scan<PairDesc>, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, nt, d_tbase, (const PairDesc*)d_pairs, np, d_per, d_per + 1);
-      if (nt > 0) hipLaunchKernelGGL(k_ess_scatter, dim3((unsigned)nt), dim3(kThreads), 0, S, (const PairDesc*)d_pairs, (const TileDesc*)d_tiles, (const pvlm_match*)d_m,
-                                     (const unsigned*)d_mask, (const int*)d_win, (const double*)d_R, (const double*)d_t, cos_reject, (const long long*)d_tbase, d_oidx, d_otri, M);
+      c.launch(k_ess_select, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, d_res, np, n_runs, d_win, d_keep, d_R, d_t);
+      if (nt > 0) c.launch(k_ess_count, dim3((unsigned)nt), dim3(kThreads), 0, d_pairs, d_tiles, d_m, d_mask, d_win, d_R, d_t, cos_reject, d_tcount);
+      c.launch(k_tile_scan<PairDesc>, dim3(1), dim3(kScanThreads), 0, d_tcount, nt, d_tbase, d_pairs, np, d_per, d_per + 1);
+      if (nt > 0) c.launch(k_ess_scatter, dim3((unsigned)nt), dim3(kThreads), 0, d_pairs, d_tiles, d_m, d_mask, d_win, d_R, d_t, cos_reject, d_tbase, d_oidx, d_otri, M);
     }
-    if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; break; }
+    c.check_launches();
     h_iters.resize(NC);
-    st = pvlm_i_d2h_q(ctx, h_iters.data(), d_iters, NC * sizeof(int));
+    c.d2h(h_iters.data(), d_iters, NC * sizeof(int));
     long long m_out = 0;
     if (raw) {
       h_cnt.resize(NC); h_lists.resize((size_t)std::max<long long>(lists, 1));
-      if (!st) st = pvlm_i_d2h_q(ctx, E + 9 * (size_t)p0 * n_runs, d_E, 9 * NC * sizeof(double));
-      if (!st) st = pvlm_i_d2h_q(ctx, nfa + (size_t)p0 * n_runs, d_nfa, NC * sizeof(double));
-      if (!st) st = pvlm_i_d2h_q(ctx, h_cnt.data(), d_cnt, NC * sizeof(int));
-      if (!st && lists > 0) st = pvlm_i_d2h_q(ctx, h_lists.data(), d_lists, (size_t)lists * sizeof(int));
-      { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-      if (st) break;
-      for (size_t c = 0; c < NC; ++c) {
-        const size_t gc = (size_t)p0 * n_runs + c;
-        const PairDesc& P = pd[c / (size_t)n_runs];
-        const int* src_list = h_lists.data() + P.list0 + (long long)(c % (size_t)n_runs) * P.n;
-        for (int i = 0; i < h_cnt[c]; ++i) { const long long at = out_offsets[gc] + i; if (at < capacity) out_idx[at] = src_list[i]; }
-        out_offsets[gc + 1] = out_offsets[gc] + h_cnt[c];
-        m_out += h_cnt[c];
+      c.d2h(E + 9 * (size_t)p0 * n_runs, d_E, 9 * NC * sizeof(double));
+      c.d2h(nfa + (size_t)p0 * n_runs, d_nfa, NC * sizeof(double));
+      c.d2h(h_cnt.data(), d_cnt, NC * sizeof(int));
+      c.d2h(h_lists.data(), d_lists, (size_t)lists * sizeof(int));
+      if (c.sync()) break;
+      for (size_t ch = 0; ch < NC; ++ch) {
+        const size_t gc = (size_t)p0 * n_runs + ch;
+        const PairDesc& P = pd[ch / (size_t)n_runs];
+        const int* src_list = h_lists.data() + P.list0 + (long long)(ch % (size_t)n_runs) * P.n;
+        for (int i = 0; i < h_cnt[ch]; ++i) { const long long at = out_offsets[gc] + i; if (at < capacity) out_idx[at] = src_list[i]; }
+        out_offsets[gc + 1] = out_offsets[gc] + h_cnt[ch];
+        m_out += h_cnt[ch];
       }
     } else {
       h_keep.resize((size_t)np); h_per.resize((size_t)np + 1);
-      if (!st) st = pvlm_i_d2h_q(ctx, h_keep.data(), d_keep, (size_t)np * sizeof(int));
-      if (!st) st = pvlm_i_d2h_q(ctx, h_per.data(), d_per, ((size_t)np + 1) * sizeof(long long));
-      if (!st) st = pvlm_i_d2h_q(ctx, R_21 + 9 * (size_t)p0, d_R, 9 * (size_t)np * sizeof(double));
-      if (!st) st = pvlm_i_d2h_q(ctx, t_21 + 3 * (size_t)p0, d_t, 3 * (size_t)np * sizeof(double));
-      { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-      if (st) break;
+      c.d2h(h_keep.data(), d_keep, (size_t)np * sizeof(int));
+      c.d2h(h_per.data(), d_per, ((size_t)np + 1) * sizeof(long long));
+      c.d2h(R_21 + 9 * (size_t)p0, d_R, 9 * (size_t)np * sizeof(double));
+      c.d2h(t_21 + 3 * (size_t)p0, d_t, 3 * (size_t)np * sizeof(double));
+      if (c.sync()) break;
       m_out = h_per[0];
       for (int k = 0; k < np; ++k) { keep[p0 + k] = (unsigned char)h_keep[(size_t)k]; out_offsets[p0 + k + 1] = out_offsets[p0 + k] + h_per[(size_t)k + 1]; }
       const long long fit = std::max<long long>(0, std::min(m_out, capacity - written));
       if (fit > 0) {
-        st = pvlm_i_d2h_q(ctx, out_idx + written, d_oidx, (size_t)fit * sizeof(int));
-        if (!st) st = pvlm_i_d2h_q(ctx, out_tri + 3 * written, d_otri, 3 * (size_t)fit * sizeof(double));
-        { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-        if (st) break;
+        c.d2h(out_idx + written, d_oidx, (size_t)fit * sizeof(int));
+        c.d2h(out_tri + 3 * written, d_otri, 3 * (size_t)fit * sizeof(double));
+        if (c.sync()) break;
         written += fit;
       }
     }
     total += m_out;
-    if (stats) for (size_t c = 0; c < NC; ++c) if (h_iters[c] > 0) stats->hypotheses += h_iters[c];
+    if (stats) for (size_t ch = 0; ch < NC; ++ch) if (h_iters[ch] > 0) stats->hypotheses += h_iters[ch];
   }
-  if (st) { (void)pvlm_i_sync(ctx); return st; }
+  if (c.st) return c.st;
   *needed = total;
   if (total > capacity) { PVLM_SET_ERR(ctx, "%s: %lld records, capacity %lld", who, total, capacity); return PVLM_ERR_CAPACITY; }
   return PVLM_OK;

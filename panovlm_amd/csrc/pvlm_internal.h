@@ -278,7 +278,7 @@ inline pvlm_status pvlm_i_alloc(pvlm_ctx* ctx, T** p, size_t count) {
 // smallest buffer go when the returned one is larger, and the returned one otherwise.  Nothing on the device may still use the buffer.
 void* pvlm_i_pinned_take(pvlm_ctx* ctx, size_t bytes, size_t* got);
 void pvlm_i_pinned_give(pvlm_ctx* ctx, void* p, size_t bytes);
-// the pinned buffer of one call: declare it before whatever synchronises the call's streams on the way out
+// the pinned buffer of one call, given back when it dies: by then the call has waited for every copy it queued into or out of the buffer
 struct pvlm_pinned_lease {
   pvlm_ctx* ctx; size_t bytes = 0; char* p;
   pvlm_pinned_lease(pvlm_ctx* c, size_t want) : ctx(c), p((char*)pvlm_i_pinned_take(c, want, &bytes)) {}
@@ -286,8 +286,8 @@ struct pvlm_pinned_lease {
   pvlm_pinned_lease(const pvlm_pinned_lease&) = delete;
   pvlm_pinned_lease& operator=(const pvlm_pinned_lease&) = delete;
 };
-// the device scratch of one call: from the context's pool, back to it on every exit path.  Declare it before whatever synchronises the call on the way out
-// (staged device-to-host copies have landed before the function returns; the blocks go back stream-ordered behind the call's launches).  A buffer that is
+// the device scratch of one call: from the context's pool, back to it on every exit path, stream-ordered behind the call's launches.  pvlm_call (pvlm_call.h)
+// holds one and waits for the call's queued work before the blocks go back; a function that uses it bare synchronises before it returns.  A buffer that is
 // released early on purpose, so that the pool can hand the block on, stays a plain pvlm_i_alloc / pvlm_i_free.
 struct pvlm_dev_scratch {
   pvlm_ctx* ctx; std::vector<const void*> ptrs;
@@ -342,3 +342,5 @@ pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs);
 pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows);
 int pvlm_i_ncols(int kind);
 int pvlm_i_stride(int kind);
+
+#include "pvlm_call.h"

@@ -300,8 +300,7 @@ struct Batches { std::vector<int> first; long long qcap = 0; int pcap = 0; };   
 // PVLM_MATCH_BATCH_QUERIES (read at every call) lowers the query limit of a batch: how the tests run many batches on small inputs
 Batches make_batches(const pvlm_descset* set, int n_pairs, const int* src) {
   Batches b;
-  long long limit = kBatchQueries;
-  if (const char* e = std::getenv("PVLM_MATCH_BATCH_QUERIES")) { const long long v = std::atoll(e); if (v > 0 && v < limit) limit = v; }
+  const long long limit = pvlm_i_env_limit("PVLM_MATCH_BATCH_QUERIES", kBatchQueries);
   b.first.push_back(0);
   for (int p = 0; p < n_pairs;) {
     long long nq = 0; int k = p;
@@ -322,34 +321,29 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
   if (n_pairs == 0) return PVLM_OK;
   for (int p = 0; p < n_pairs; ++p)
     if (src[p] < 0 || src[p] >= set->n_frames || tgt[p] < 0 || tgt[p] >= set->n_frames) { PVLM_SET_ERR(ctx, "%s: pair %d names a frame outside the set", who, p); return PVLM_ERR_ARG; }
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const bool exact = (flags & PVLM_FLAG_MATCH_EXACT) != 0;
   const Batches bt = make_batches(set, n_pairs, src);
   const size_t Q = (size_t)std::max<long long>(bt.qcap, 1), PB = (size_t)bt.pcap;
   const size_t TB = Q / kTile + PB + 1, QT = pvlm_match_launch::qtile_capacity(Q, PB);
   pvlm_pinned_lease lease(ctx, keep ? Q * sizeof(pvlm_match) : 1);
   if (!lease.p) { PVLM_SET_ERR(ctx, "%s: pinned memory unavailable", who); return PVLM_ERR_NOMEM; }
-  pvlm_dev_scratch tmp(ctx);
-  PairDesc* d_pairs = nullptr; QTile* d_qt = nullptr; TileDesc* d_tiles = nullptr; KnnRec* d_knn = nullptr; int2* d_fb = nullptr; int* d_cnt = nullptr;
-  int* d_tcount = nullptr; long long* d_tbase = nullptr; int* d_keep = nullptr; float* d_dmax = nullptr; long long* d_per = nullptr; pvlm_match* d_out = nullptr;
-  pvlm_status st = tmp.alloc(&d_pairs, PB);
-  if (!st) st = tmp.alloc(&d_knn, Q);
-  if (!st && !exact) st = tmp.alloc(&d_qt, QT);               // the screening path's query tiles, fallback list and its counter
-  if (!st && !exact) st = tmp.alloc(&d_fb, Q);
-  if (!st && !exact) st = tmp.alloc(&d_cnt, 2);
-  if (!st && keep) st = tmp.alloc(&d_tiles, TB);
-  if (!st && keep) st = tmp.alloc(&d_tcount, TB);
-  if (!st && keep) st = tmp.alloc(&d_tbase, TB);
-  if (!st && keep) st = tmp.alloc(&d_keep, PB);
-  if (!st && keep) st = tmp.alloc(&d_dmax, PB);
-  if (!st && keep) st = tmp.alloc(&d_per, PB + 1);
-  if (!st && keep) st = tmp.alloc(&d_out, Q);
-  if (st) return st;
-  hipStream_t S = ctx->stream;
+  PairDesc* d_pairs = c.alloc<PairDesc>(PB);
+  KnnRec* d_knn = c.alloc<KnnRec>(Q);
+  QTile* d_qt = exact ? nullptr : c.alloc<QTile>(QT);         // the screening path's query tiles, fallback list and its counter
+  int2* d_fb = exact ? nullptr : c.alloc<int2>(Q);
+  int* d_cnt = exact ? nullptr : c.alloc<int>(2);
+  TileDesc* d_tiles = keep ? c.alloc<TileDesc>(TB) : nullptr;
+  int* d_tcount = keep ? c.alloc<int>(TB) : nullptr;
+  long long* d_tbase = keep ? c.alloc<long long>(TB) : nullptr;
+  int* d_keep = keep ? c.alloc<int>(PB) : nullptr;
+  float* d_dmax = keep ? c.alloc<float>(PB) : nullptr;
+  long long* d_per = keep ? c.alloc<long long>(PB + 1) : nullptr;
+  pvlm_match* d_out = keep ? c.alloc<pvlm_match>(Q) : nullptr;
   std::vector<PairDesc> pd; std::vector<TileDesc> tiles; std::vector<int> n1s, h_keep; std::vector<long long> h_per; std::vector<KnnRec> h_knn;
   long long q_done = 0, written = 0, total = 0;
-  for (size_t bi = 0; bi + 1 < bt.first.size() && !st; ++bi) {
+  for (size_t bi = 0; bi + 1 < bt.first.size() && !c.st; ++bi) {
     const int p0 = bt.first[bi], np = bt.first[bi + 1] - p0;
     pd.assign((size_t)np, PairDesc()); n1s.assign((size_t)np, 0);
     long long nq = 0;
@@ -364,13 +358,11 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
     }
     make_tiles(n1s.data(), np, pd.data(), tiles);
     int fb = 0;
-    st = pvlm_match_launch::knn_batch(ctx, who, pd.data(), np, nq, exact, d_pairs, d_qt, d_knn, d_fb, d_cnt, &fb);
-    if (st) break;
+    pvlm_match_launch::knn_batch(c, pd.data(), np, nq, exact, d_pairs, d_qt, d_knn, d_fb, d_cnt, &fb);
     if (!keep) {                                              // knn2: indices and distances of every query
       h_knn.resize((size_t)nq);
-      if (nq > 0) st = pvlm_i_d2h_q(ctx, h_knn.data(), d_knn, (size_t)nq * sizeof(KnnRec));
-      { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-      if (st) break;
+      c.d2h(h_knn.data(), d_knn, (size_t)nq * sizeof(KnnRec));
+      if (c.sync()) break;
       for (long long i = 0; i < nq; ++i) {
         const KnnRec& k = h_knn[(size_t)i];
         idx[2 * (q_done + i)] = k.i0; idx[2 * (q_done + i) + 1] = k.i1;
@@ -378,26 +370,22 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
       }
     } else {
       const int nt = (int)tiles.size();
-      if (nt > 0) st = pvlm_i_h2d_q(ctx, d_tiles, tiles.data(), (size_t)nt * sizeof(TileDesc));
-      if (st) break;
-      hipLaunchKernelGGL(k_match_pair_stats, dim3((unsigned)np), dim3(256), 0, S, (const PairDesc*)d_pairs, (const KnnRec*)d_knn, ratio, threshold, d_keep, d_dmax);
-      if (nt > 0) hipLaunchKernelGGL(k_match_count, dim3((unsigned)nt), dim3(kThreads), 0, S, (const PairDesc*)d_pairs, (const TileDesc*)d_tiles, (const KnnRec*)d_knn, ratio,
-                                     (const int*)d_keep, (const float*)d_dmax, d_tcount);
-      hipLaunchKernelGGL(k_tile_scan<PairDesc>, dim3(1), dim3(kScanThreads), 0, S, (const int*)d_tcount, nt, d_tbase, (const PairDesc*)d_pairs, np, d_per, d_per + 1);
-      if (nt > 0) hipLaunchKernelGGL(k_match_scatter, dim3((unsigned)nt), dim3(kThreads), 0, S, (const PairDesc*)d_pairs, (const TileDesc*)d_tiles, (const KnnRec*)d_knn, ratio,
-                                     (const int*)d_keep, (const float*)d_dmax, (const long long*)d_tbase, d_out, (long long)Q);
-      if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; break; }
+      c.h2d(d_tiles, tiles.data(), (size_t)nt * sizeof(TileDesc));
+      c.launch(k_match_pair_stats, dim3((unsigned)np), dim3(256), 0, d_pairs, d_knn, ratio, threshold, d_keep, d_dmax);
+      if (nt > 0) c.launch(k_match_count, dim3((unsigned)nt), dim3(kThreads), 0, d_pairs, d_tiles, d_knn, ratio, d_keep, d_dmax, d_tcount);
+      c.launch(k_tile_scan<PairDesc>, dim3(1), dim3(kScanThreads), 0, d_tcount, nt, d_tbase, d_pairs, np, d_per, d_per + 1);
+      if (nt > 0) c.launch(k_match_scatter, dim3((unsigned)nt), dim3(kThreads), 0, d_pairs, d_tiles, d_knn, ratio, d_keep, d_dmax, d_tbase, d_out, (long long)Q);
+      c.check_launches();
       h_keep.resize((size_t)np); h_per.resize((size_t)np + 1);
-      st = pvlm_i_d2h_q(ctx, h_keep.data(), d_keep, (size_t)np * sizeof(int));
-      if (!st) st = pvlm_i_d2h_q(ctx, h_per.data(), d_per, ((size_t)np + 1) * sizeof(long long));
-      { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-      if (st) break;
+      c.d2h(h_keep.data(), d_keep, (size_t)np * sizeof(int));
+      c.d2h(h_per.data(), d_per, ((size_t)np + 1) * sizeof(long long));
+      if (c.sync()) break;
       const long long m = h_per[0];
       for (int k = 0; k < np; ++k) { keep[p0 + k] = (unsigned char)h_keep[(size_t)k]; match_offsets[p0 + k + 1] = match_offsets[p0 + k] + h_per[(size_t)k + 1]; }
       const long long fit = std::max<long long>(0, std::min(m, capacity - written));
-      if (fit > 0) {
-        if (hipMemcpyAsync(lease.p, d_out, (size_t)fit * sizeof(pvlm_match), hipMemcpyDeviceToHost, S) != hipSuccess || hipStreamSynchronize(S) != hipSuccess) {
-          PVLM_SET_ERR(ctx, "%s: download failed", who); st = PVLM_ERR_HIP; break;
+      if (fit > 0) {                                          // a direct copy into the pinned lease: the records bypass the staging arena
+        if (hipMemcpyAsync(lease.p, d_out, (size_t)fit * sizeof(pvlm_match), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+          PVLM_SET_ERR(ctx, "%s: download failed", who); c.st = PVLM_ERR_HIP; break;
         }
         std::memcpy(out + written, lease.p, (size_t)fit * sizeof(pvlm_match));
         written += fit;
@@ -407,7 +395,7 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
     q_done += nq;
     if (stats) { stats->queries += nq; stats->fallback_queries += exact ? nq : fb; stats->batches += 1; }
   }
-  if (st) { (void)pvlm_i_sync(ctx); return st; }              // also drops the staged copies that point into this frame (the fallback count)
+  if (c.st) return c.st;
   if (needed) *needed = total;
   if (keep && total > capacity) { PVLM_SET_ERR(ctx, "%s: %lld records, capacity %lld", who, total, capacity); return PVLM_ERR_CAPACITY; }
   return PVLM_OK;
@@ -417,36 +405,29 @@ pvlm_status run(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, int n_p
 
 size_t pvlm_match_launch::qtile_capacity(size_t queries, size_t pairs) { return queries / kScreenQ + pairs + 1; }
 
-pvlm_status pvlm_match_launch::knn_batch(pvlm_ctx* ctx, const char* who, const PairDesc* pd, int np, long long nq, bool exact, PairDesc* d_pairs, QTile* d_qt, KnnRec* d_knn,
-                                         int2* d_fb, int* d_cnt, int* fallback) {
-  hipStream_t S = ctx->stream;
+void pvlm_match_launch::knn_batch(pvlm_call& c, const PairDesc* pd, int np, long long nq, bool exact, PairDesc* d_pairs, QTile* d_qt, KnnRec* d_knn, int2* d_fb, int* d_cnt,
+                                  int* fallback) {
   *fallback = exact ? (int)nq : 0;
-  pvlm_status st = pvlm_i_h2d_q(ctx, d_pairs, pd, (size_t)np * sizeof(PairDesc));
-  if (!st && nq > 0) {
-    if (exact) {
-      hipLaunchKernelGGL(k_match_exact, dim3((unsigned)std::min<long long>((nq + 3) / 4, 8192)), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)nullptr,
-                         (const int*)nullptr, (int)nq, d_knn);
-    } else {
-      std::vector<QTile> qts;                                 // copied into the staging arena when the copy is queued
-      for (int k = 0; k < np; ++k) for (int q0 = 0; q0 < pd[k].n1; q0 += kScreenQ) qts.push_back(QTile{k, q0});
-      st = pvlm_i_h2d_q(ctx, d_qt, qts.data(), qts.size() * sizeof(QTile));
-      if (!st && hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), S) != hipSuccess) st = PVLM_ERR_HIP;
-      if (!st) {
-        hipLaunchKernelGGL(k_match_screen, dim3((unsigned)qts.size()), dim3(256), 0, S, (const PairDesc*)d_pairs, (const QTile*)d_qt, d_knn, d_fb, d_cnt);
-        hipLaunchKernelGGL(k_match_exact, dim3(2048), dim3(256), 0, S, (const PairDesc*)d_pairs, np, (const int2*)d_fb, (const int*)d_cnt, 0, d_knn);
-        st = pvlm_i_d2h_q(ctx, fallback, d_cnt, sizeof(int));
-      }
-    }
+  c.h2d(d_pairs, pd, (size_t)np * sizeof(PairDesc));
+  if (nq <= 0) return;
+  if (exact) {
+    c.launch(k_match_exact, dim3((unsigned)std::min<long long>((nq + 3) / 4, 8192)), dim3(256), 0, d_pairs, np, nullptr, nullptr, (int)nq, d_knn);
+  } else {
+    std::vector<QTile> qts;                                   // copied into the staging arena when the copy is queued
+    for (int k = 0; k < np; ++k) for (int q0 = 0; q0 < pd[k].n1; q0 += kScreenQ) qts.push_back(QTile{k, q0});
+    c.h2d(d_qt, qts.data(), qts.size() * sizeof(QTile));
+    c.memset(d_cnt, 0, 2 * sizeof(int));
+    c.launch(k_match_screen, dim3((unsigned)qts.size()), dim3(256), 0, d_pairs, d_qt, d_knn, d_fb, d_cnt);
+    c.launch(k_match_exact, dim3(2048), dim3(256), 0, d_pairs, np, d_fb, d_cnt, 0, d_knn);
+    c.d2h(fallback, d_cnt, sizeof(int));
   }
-  if (!st && hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; }
-  return st;
+  c.check_launches();
 }
 
-pvlm_status pvlm_match_launch::row_norms(pvlm_ctx* ctx, const char* who, const float* desc, long long n_rows, float* norm, int* bad) {
-  if (n_rows <= 0) return PVLM_OK;
-  hipLaunchKernelGGL(k_desc_norms, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, desc, n_rows, norm, bad);
-  if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); return PVLM_ERR_HIP; }
-  return PVLM_OK;
+void pvlm_match_launch::row_norms(pvlm_call& c, const float* desc, long long n_rows, float* norm, int* bad) {
+  if (n_rows <= 0) return;
+  c.launch(k_desc_norms, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, desc, n_rows, norm, bad);
+  c.check_launches();
 }
 
 extern "C" pvlm_status pvlm_descset_create(pvlm_ctx* ctx, int n_frames, const int* rows, int width, const float* const* descs, pvlm_descset** out) {
@@ -458,26 +439,23 @@ extern "C" pvlm_status pvlm_descset_create(pvlm_ctx* ctx, int n_frames, const in
     if (rows[f] < 0 || (rows[f] > 0 && !descs[f])) { PVLM_SET_ERR(ctx, "pvlm_descset_create: bad frame %d", f); return PVLM_ERR_ARG; }
     total += rows[f];
   }
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_descset_create inside a graph capture"); return PVLM_ERR_STATE; }
+  pvlm_call c(ctx, "pvlm_descset_create");
+  if (c.enter()) return c.st;
   pvlm_descset* s = new pvlm_descset();
   s->owner = ctx; s->n_frames = n_frames; s->rows.assign(rows, rows + n_frames); s->row0.assign((size_t)n_frames + 1, 0); s->nmax.assign((size_t)n_frames, 0.0f);
   for (int f = 0; f < n_frames; ++f) s->row0[(size_t)f + 1] = s->row0[(size_t)f] + rows[f];
-  int* d_bad = nullptr; int bad = 0;
+  int bad = 0;
   std::vector<float> norm((size_t)total);
-  pvlm_status st = pvlm_i_alloc(ctx, &s->d_desc, (size_t)total * kDim);
-  if (!st) st = pvlm_i_alloc(ctx, &s->d_norm, (size_t)total);
-  if (!st) st = pvlm_i_alloc(ctx, &d_bad, 1);
-  for (int f = 0; f < n_frames && !st; ++f)
-    if (rows[f] > 0) st = pvlm_i_h2d_q(ctx, s->d_desc + s->row0[(size_t)f] * kDim, descs[f], (size_t)rows[f] * kDim * sizeof(float));
-  if (!st && hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream) != hipSuccess) st = PVLM_ERR_HIP;
-  if (!st) st = pvlm_match_launch::row_norms(ctx, "pvlm_descset_create", s->d_desc, total, s->d_norm, d_bad);
-  if (!st && total > 0) st = pvlm_i_d2h_q(ctx, norm.data(), s->d_norm, (size_t)total * sizeof(float));
-  if (!st) st = pvlm_i_d2h_q(ctx, &bad, d_bad, sizeof(int));
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  pvlm_i_free(ctx, d_bad);
-  if (!st && bad) { PVLM_SET_ERR(ctx, "pvlm_descset_create: a descriptor value is not finite"); st = PVLM_ERR_ARG; }
-  if (st) { pvlm_descset_destroy(ctx, s); return st; }
+  c.st = pvlm_i_alloc(ctx, &s->d_desc, (size_t)total * kDim);          // the set's own blocks: they outlive the call, pvlm_descset_destroy frees them
+  if (!c.st) c.st = pvlm_i_alloc(ctx, &s->d_norm, (size_t)total);
+  int* d_bad = c.alloc<int>(1);
+  for (int f = 0; f < n_frames; ++f) c.h2d(s->d_desc + s->row0[(size_t)f] * kDim, descs[f], (size_t)rows[f] * kDim * sizeof(float));
+  c.memset(d_bad, 0, sizeof(int));
+  pvlm_match_launch::row_norms(c, s->d_desc, total, s->d_norm, d_bad);
+  c.d2h(norm.data(), s->d_norm, (size_t)total * sizeof(float));
+  c.d2h(&bad, d_bad, sizeof(int));
+  if (!c.sync() && bad) { PVLM_SET_ERR(ctx, "pvlm_descset_create: a descriptor value is not finite"); c.st = PVLM_ERR_ARG; }
+  if (c.st) { pvlm_descset_destroy(ctx, s); return c.st; }
   for (int f = 0; f < n_frames; ++f)
     for (long long i = s->row0[(size_t)f]; i < s->row0[(size_t)f + 1]; ++i) s->nmax[(size_t)f] = std::max(s->nmax[(size_t)f], norm[(size_t)i]);
   *out = s;

@@ -107,17 +107,14 @@ extern "C" pvlm_status pvlm_refine_relative_poses(pvlm_ctx* ctx, int n_frames, c
   if (!finite_all(R_21, 9 * (size_t)n_pairs) || !finite_all(t_21, 3 * (size_t)n_pairs) || !finite_all(triangulated, 3 * (size_t)total) || !finite_all(h_obs.data(), h_obs.size())) {
     PVLM_SET_ERR(ctx, "%s: a pose, a point or a keypoint is not finite", who); return PVLM_ERR_ARG;
   }
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
-  // PVLM_RELPOSE_BATCH_PAIRS (read at every call) lowers the pair limit of a batch: how the tests run several batches on a small list.  It changes no result.
-  int pair_limit = kBatchPairs;
-  if (const char* e = std::getenv("PVLM_RELPOSE_BATCH_PAIRS")) { const int v = std::atoi(e); if (v > 0 && v < pair_limit) pair_limit = v; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
+  const int pair_limit = (int)pvlm_i_env_limit("PVLM_RELPOSE_BATCH_PAIRS", kBatchPairs);
   rp::Options opt;
   opt.max_num_iterations = params->max_num_iterations;
   std::vector<PairDesc> pd;
   std::vector<rp::Summary> h_sum;
-  pvlm_status st = PVLM_OK;
-  for (int p0 = 0; p0 < n_pairs && !st;) {
+  for (int p0 = 0; p0 < n_pairs;) {
     int np = 0; long long pts = 0;
     while (p0 + np < n_pairs && np < pair_limit) {
       const long long ni = inlier_offsets[p0 + np + 1] - inlier_offsets[p0 + np];
@@ -131,38 +128,28 @@ extern "C" pvlm_status pvlm_refine_relative_poses(pvlm_ctx* ctx, int n_frames, c
       pd[(size_t)k] = PairDesc{inlier_offsets[p] - base, (int)(inlier_offsets[p + 1] - inlier_offsets[p]), kind, (double)img_rows[src[p]], (double)img_cols[src[p]],
                                (double)img_rows[tgt[p]], (double)img_cols[tgt[p]]};
     }
-    pvlm_dev_scratch bs(ctx);
-    PairDesc* d_pairs = nullptr; double* d_obs = nullptr; double* d_scr = nullptr; double* d_R = nullptr; double* d_t = nullptr; double* d_tri = nullptr;
-    unsigned char* d_ok = nullptr; rp::Summary* d_sum = nullptr;
-    st = bs.alloc(&d_pairs, (size_t)np);
-    if (!st) st = bs.alloc(&d_obs, 4 * (size_t)pts);
-    if (!st) st = bs.alloc(&d_scr, (size_t)rp::kScratchPerPoint * (size_t)pts);
-    if (!st) st = bs.alloc(&d_R, 9 * (size_t)np);
-    if (!st) st = bs.alloc(&d_t, 3 * (size_t)np);
-    if (!st) st = bs.alloc(&d_tri, 3 * (size_t)pts);
-    if (!st) st = bs.alloc(&d_ok, (size_t)np);
-    if (!st) st = bs.alloc(&d_sum, (size_t)np);
-    if (!st) st = pvlm_i_h2d_q(ctx, d_pairs, pd.data(), (size_t)np * sizeof(PairDesc));
-    if (!st && pts > 0) st = pvlm_i_h2d_q(ctx, d_obs, h_obs.data() + 4 * (size_t)base, 4 * (size_t)pts * sizeof(double));
-    if (!st && pts > 0) st = pvlm_i_h2d_q(ctx, d_tri, triangulated + 3 * (size_t)base, 3 * (size_t)pts * sizeof(double));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_R, R_21 + 9 * (size_t)p0, 9 * (size_t)np * sizeof(double));
-    if (!st) st = pvlm_i_h2d_q(ctx, d_t, t_21 + 3 * (size_t)p0, 3 * (size_t)np * sizeof(double));
-    if (st) break;
-    hipLaunchKernelGGL(k_relpose, dim3((unsigned)np), dim3(rp::kLanes), 0, ctx->stream, (const PairDesc*)d_pairs, np, (const double*)d_obs, d_scr, opt, d_R, d_t, d_tri, d_ok, d_sum);
-    if (hipGetLastError() != hipSuccess) { PVLM_SET_ERR(ctx, "%s: kernel launch failed", who); st = PVLM_ERR_HIP; break; }
+    pvlm_call::batch bs(c);                                  // this batch's scratch
+    PairDesc* d_pairs = c.upload(pd.data(), (size_t)np);
+    double* d_obs = c.upload(h_obs.data() + 4 * (size_t)base, 4 * (size_t)pts);
+    double* d_tri = c.upload(triangulated + 3 * (size_t)base, 3 * (size_t)pts);
+    double* d_R = c.upload(R_21 + 9 * (size_t)p0, 9 * (size_t)np);
+    double* d_t = c.upload(t_21 + 3 * (size_t)p0, 3 * (size_t)np);
+    double* d_scr = c.alloc<double>((size_t)rp::kScratchPerPoint * (size_t)pts);
+    unsigned char* d_ok = c.alloc<unsigned char>((size_t)np);
+    rp::Summary* d_sum = c.alloc<rp::Summary>((size_t)np);
+    c.launch(k_relpose, dim3((unsigned)np), dim3(rp::kLanes), 0, d_pairs, np, d_obs, d_scr, opt, d_R, d_t, d_tri, d_ok, d_sum);
+    c.check_launches();
     h_sum.resize((size_t)np);
-    st = pvlm_i_d2h_q(ctx, R_21 + 9 * (size_t)p0, d_R, 9 * (size_t)np * sizeof(double));
-    if (!st) st = pvlm_i_d2h_q(ctx, t_21 + 3 * (size_t)p0, d_t, 3 * (size_t)np * sizeof(double));
-    if (!st && pts > 0) st = pvlm_i_d2h_q(ctx, triangulated + 3 * (size_t)base, d_tri, 3 * (size_t)pts * sizeof(double));
-    if (!st) st = pvlm_i_d2h_q(ctx, ok + p0, d_ok, (size_t)np);
-    if (!st) st = pvlm_i_d2h_q(ctx, h_sum.data(), d_sum, (size_t)np * sizeof(rp::Summary));
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    if (st) break;
+    c.d2h(R_21 + 9 * (size_t)p0, d_R, 9 * (size_t)np * sizeof(double));
+    c.d2h(t_21 + 3 * (size_t)p0, d_t, 3 * (size_t)np * sizeof(double));
+    c.d2h(triangulated + 3 * (size_t)base, d_tri, 3 * (size_t)pts * sizeof(double));
+    c.d2h(ok + p0, d_ok, (size_t)np);
+    c.d2h(h_sum.data(), d_sum, (size_t)np * sizeof(rp::Summary));
+    if (c.sync()) break;
     if (summaries) std::memcpy(summaries + p0, h_sum.data(), (size_t)np * sizeof(rp::Summary));
     p0 += np;
   }
-  if (st) (void)pvlm_i_sync(ctx);
-  return st;
+  return c.st;
 }
 
 extern "C" int pvlm_relpose_workgroup_size(void) { return rp::kLanes; }

@@ -54,36 +54,23 @@ extern "C" pvlm_status pvlm_triangulate_tracks(pvlm_ctx* ctx, int rows, int cols
   if (keypoints_f32 && (rows <= 0 || cols <= 0)) return PVLM_ERR_ARG;
   if (n_tracks == 0) return PVLM_OK;
   if (!track_offsets || !points || !status || (n_frames > 0 && !T_cw_3x4)) return PVLM_ERR_ARG;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  pvlm_status st = check_tracks(ctx, "pvlm_triangulate_tracks", n_tracks, track_offsets, frame_ids, n_frames);
-  if (st) return st;
-  const int64_t n_obs = track_offsets[n_tracks];
+  pvlm_call c(ctx, "pvlm_triangulate_tracks");
+  if (c.enter() || (c.st = check_tracks(ctx, c.who, n_tracks, track_offsets, frame_ids, n_frames))) return c.st;
+  const size_t n_obs = (size_t)track_offsets[n_tracks];
   const int per = keypoints_f32 ? 2 : 3;                                  // floats per observation
-  pvlm_dev_scratch tmp(ctx);
-  long long* d_off = nullptr; int* d_fid = nullptr; float* d_obs = nullptr; double* d_T = nullptr; unsigned char* d_valid = nullptr;
-  double* d_X = nullptr; unsigned char* d_status = nullptr;
-  st = tmp.alloc(&d_off, (size_t)n_tracks + 1);
-  if (!st) st = tmp.alloc(&d_fid, (size_t)n_obs);
-  if (!st) st = tmp.alloc(&d_obs, (size_t)n_obs * per);
-  if (!st) st = tmp.alloc(&d_T, (size_t)n_frames * 12);
-  if (!st && frame_valid) st = tmp.alloc(&d_valid, (size_t)n_frames);
-  if (!st) st = tmp.alloc(&d_X, (size_t)n_tracks * 3);
-  if (!st) st = tmp.alloc(&d_status, (size_t)n_tracks);
-  if (!st) st = pvlm_i_h2d_q(ctx, d_off, track_offsets, ((size_t)n_tracks + 1) * sizeof(int64_t));
-  if (!st && n_obs) st = pvlm_i_h2d_q(ctx, d_fid, frame_ids, (size_t)n_obs * sizeof(int));
-  if (!st && n_obs) st = pvlm_i_h2d_q(ctx, d_obs, keypoints_f32 ? keypoints_f32 : bearings_f32, (size_t)n_obs * per * sizeof(float));
-  if (!st && n_frames) st = pvlm_i_h2d_q(ctx, d_T, T_cw_3x4, (size_t)n_frames * 12 * sizeof(double));
-  if (!st && frame_valid && n_frames) st = pvlm_i_h2d_q(ctx, d_valid, frame_valid, (size_t)n_frames);
-  if (!st) {
-    hipLaunchKernelGGL(k_triangulate_tracks, dim3((unsigned)((n_tracks + 63) / 64)), dim3(64), 0, ctx->stream, rows, cols, n_tracks, d_off, d_fid,
-                       keypoints_f32 ? d_obs : nullptr, bearings_f32 ? d_obs : nullptr, d_T, d_valid, d_X, d_status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_triangulate_tracks: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  if (!st) st = pvlm_i_d2h_q(ctx, points, d_X, (size_t)n_tracks * 3 * sizeof(double));
-  if (!st) st = pvlm_i_d2h_q(ctx, status, d_status, (size_t)n_tracks);
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  return st;
+  long long* d_off = c.upload(reinterpret_cast<const long long*>(track_offsets), (size_t)n_tracks + 1);
+  int* d_fid = c.upload(frame_ids, n_obs);
+  float* d_obs = c.upload(keypoints_f32 ? keypoints_f32 : bearings_f32, n_obs * per);
+  double* d_T = c.upload(T_cw_3x4, (size_t)n_frames * 12);
+  unsigned char* d_valid = frame_valid ? c.upload(frame_valid, (size_t)n_frames) : nullptr;
+  double* d_X = c.alloc<double>((size_t)n_tracks * 3);
+  unsigned char* d_status = c.alloc<unsigned char>((size_t)n_tracks);
+  c.launch(k_triangulate_tracks, dim3((unsigned)((n_tracks + 63) / 64)), dim3(64), 0, rows, cols, n_tracks, d_off, d_fid, keypoints_f32 ? d_obs : nullptr,
+           bearings_f32 ? d_obs : nullptr, d_T, d_valid, d_X, d_status);
+  c.check_launches();
+  c.d2h(points, d_X, (size_t)n_tracks * 3 * sizeof(double));
+  c.d2h(status, d_status, (size_t)n_tracks);
+  return c.sync();
 }
 
 extern "C" pvlm_status pvlm_filter_tracks_far(pvlm_ctx* ctx, int n_tracks, const int64_t* track_offsets, const int* frame_ids, const double* points,
@@ -91,32 +78,18 @@ extern "C" pvlm_status pvlm_filter_tracks_far(pvlm_ctx* ctx, int n_tracks, const
   if (!ctx || n_tracks < 0 || n_frames < 0) return PVLM_ERR_ARG;
   if (n_tracks == 0) return PVLM_OK;
   if (!track_offsets || !points || !keep || (n_frames > 0 && !t_wc)) return PVLM_ERR_ARG;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  pvlm_status st = check_tracks(ctx, "pvlm_filter_tracks_far", n_tracks, track_offsets, frame_ids, n_frames);
-  if (st) return st;
-  const int64_t n_obs = track_offsets[n_tracks];
-  pvlm_dev_scratch tmp(ctx);
-  long long* d_off = nullptr; int* d_fid = nullptr; double* d_X = nullptr; double* d_t = nullptr; unsigned char* d_valid = nullptr; unsigned char* d_keep = nullptr;
-  st = tmp.alloc(&d_off, (size_t)n_tracks + 1);
-  if (!st) st = tmp.alloc(&d_fid, (size_t)n_obs);
-  if (!st) st = tmp.alloc(&d_X, (size_t)n_tracks * 3);
-  if (!st) st = tmp.alloc(&d_t, (size_t)n_frames * 3);
-  if (!st && frame_valid) st = tmp.alloc(&d_valid, (size_t)n_frames);
-  if (!st) st = tmp.alloc(&d_keep, (size_t)n_tracks);
-  if (!st) st = pvlm_i_h2d_q(ctx, d_off, track_offsets, ((size_t)n_tracks + 1) * sizeof(int64_t));
-  if (!st && n_obs) st = pvlm_i_h2d_q(ctx, d_fid, frame_ids, (size_t)n_obs * sizeof(int));
-  if (!st) st = pvlm_i_h2d_q(ctx, d_X, points, (size_t)n_tracks * 3 * sizeof(double));
-  if (!st && n_frames) st = pvlm_i_h2d_q(ctx, d_t, t_wc, (size_t)n_frames * 3 * sizeof(double));
-  if (!st && frame_valid && n_frames) st = pvlm_i_h2d_q(ctx, d_valid, frame_valid, (size_t)n_frames);
-  if (!st) {
-    hipLaunchKernelGGL(k_filter_tracks_far, dim3((unsigned)((n_tracks + 63) / 64)), dim3(64), 0, ctx->stream, n_tracks, d_off, d_fid, d_X, d_t, d_valid, threshold,
-                       d_keep);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_filter_tracks_far: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  if (!st) st = pvlm_i_d2h_q(ctx, keep, d_keep, (size_t)n_tracks);
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  return st;
+  pvlm_call c(ctx, "pvlm_filter_tracks_far");
+  if (c.enter() || (c.st = check_tracks(ctx, c.who, n_tracks, track_offsets, frame_ids, n_frames))) return c.st;
+  long long* d_off = c.upload(reinterpret_cast<const long long*>(track_offsets), (size_t)n_tracks + 1);
+  int* d_fid = c.upload(frame_ids, (size_t)track_offsets[n_tracks]);
+  double* d_X = c.upload(points, (size_t)n_tracks * 3);
+  double* d_t = c.upload(t_wc, (size_t)n_frames * 3);
+  unsigned char* d_valid = frame_valid ? c.upload(frame_valid, (size_t)n_frames) : nullptr;
+  unsigned char* d_keep = c.alloc<unsigned char>((size_t)n_tracks);
+  c.launch(k_filter_tracks_far, dim3((unsigned)((n_tracks + 63) / 64)), dim3(64), 0, n_tracks, d_off, d_fid, d_X, d_t, d_valid, threshold, d_keep);
+  c.check_launches();
+  c.d2h(keep, d_keep, (size_t)n_tracks);
+  return c.sync();
 }
 
 // pvlm_preload: loads this file's code object at context set-up instead of at the first pvlm_triangulate_tracks (see pvlm_ba.hip)

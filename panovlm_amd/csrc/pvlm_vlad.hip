@@ -241,21 +241,9 @@ __global__ __launch_bounds__(256) void k_vlad_select(const double* __restrict__ 
   }
 }
 
-bool launch_ok(pvlm_ctx* ctx, const char* who) {
-  if (hipGetLastError() == hipSuccess) return true;
-  PVLM_SET_ERR(ctx, "%s: kernel launch failed", who);
-  return false;
-}
-
-// PVLM_VLAD_BATCH_ROWS (read at every call) lowers the row limit of a batch: how the tests cross batch boundaries on small inputs
-long long batch_limit() {
-  long long limit = kBatchRows;
-  if (const char* e = std::getenv("PVLM_VLAD_BATCH_ROWS")) { const long long v = std::atoll(e); if (v > 0 && v < limit) limit = v; }
-  return limit;
-}
 // `count` frames (list[k], or k itself without a list) cut into batches of whole frames: the first entry of every batch, and count behind the last
 std::vector<int> make_batches(const pvlm_descset* set, int count, const int* list, long long* qcap, int* fcap) {
-  const long long limit = batch_limit();
+  const long long limit = pvlm_i_env_limit("PVLM_VLAD_BATCH_ROWS", kBatchRows);
   std::vector<int> first(1, 0);
   *qcap = 0; *fcap = 0;
   for (int p = 0; p < count;) {
@@ -290,35 +278,31 @@ struct Scratch {
   PairDesc* d_pairs = nullptr; QTile* d_qt = nullptr; KnnRec* d_knn = nullptr; int2* d_fb = nullptr; int* d_cnt = nullptr;
   float* d_packed = nullptr; float* d_pnorm = nullptr; int* d_map = nullptr;
   GTile* d_tiles = nullptr; GSeg* d_segs = nullptr; int* d_hist = nullptr; int* d_start = nullptr; int* d_order = nullptr;
-  pvlm_status alloc(pvlm_dev_scratch& tmp, size_t Q, size_t F, size_t rows_grouped, size_t segs, int book, bool exact) {
-    pvlm_status st = tmp.alloc(&d_pairs, F);
-    if (!st) st = tmp.alloc(&d_knn, Q);
-    if (!st && !exact) st = tmp.alloc(&d_qt, pvlm_match_launch::qtile_capacity(Q, F));
-    if (!st && !exact) st = tmp.alloc(&d_fb, Q);
-    if (!st && !exact) st = tmp.alloc(&d_cnt, 2);
-    if (!st) st = tmp.alloc(&d_packed, (size_t)book * kDim);
-    if (!st) st = tmp.alloc(&d_pnorm, (size_t)book);
-    if (!st) st = tmp.alloc(&d_map, (size_t)book);
+  void alloc(pvlm_call& c, size_t Q, size_t F, size_t rows_grouped, size_t segs, int book, bool exact) {
+    d_pairs = c.alloc<PairDesc>(F);
+    d_knn = c.alloc<KnnRec>(Q);
+    if (!exact) { d_qt = c.alloc<QTile>(pvlm_match_launch::qtile_capacity(Q, F)); d_fb = c.alloc<int2>(Q); d_cnt = c.alloc<int>(2); }
+    d_packed = c.alloc<float>((size_t)book * kDim);
+    d_pnorm = c.alloc<float>((size_t)book);
+    d_map = c.alloc<int>((size_t)book);
     const size_t NT = rows_grouped / kGroupTile + segs + 1;
-    if (!st) st = tmp.alloc(&d_tiles, NT);
-    if (!st) st = tmp.alloc(&d_segs, segs);
-    if (!st) st = tmp.alloc(&d_hist, NT * (size_t)book);
-    if (!st) st = tmp.alloc(&d_start, segs * ((size_t)book + 1));
-    if (!st) st = tmp.alloc(&d_order, rows_grouped);
-    return st;
+    d_tiles = c.alloc<GTile>(NT);
+    d_segs = c.alloc<GSeg>(segs);
+    d_hist = c.alloc<int>(NT * (size_t)book);
+    d_start = c.alloc<int>(segs * ((size_t)book + 1));
+    d_order = c.alloc<int>(rows_grouped);
   }
 };
 
-pvlm_status upload_packed(pvlm_ctx* ctx, const PackedCentres& P, Scratch& S) {
-  pvlm_status st = pvlm_i_h2d_q(ctx, S.d_packed, P.rows.data(), P.rows.size() * sizeof(float));
-  if (!st) st = pvlm_i_h2d_q(ctx, S.d_pnorm, P.norm.data(), P.norm.size() * sizeof(float));
-  if (!st) st = pvlm_i_h2d_q(ctx, S.d_map, P.map.data(), P.map.size() * sizeof(int));
-  return st;
+void upload_packed(pvlm_call& c, const PackedCentres& P, Scratch& S) {
+  c.h2d(S.d_packed, P.rows.data(), P.rows.size() * sizeof(float));
+  c.h2d(S.d_pnorm, P.norm.data(), P.norm.size() * sizeof(float));
+  c.h2d(S.d_map, P.map.data(), P.map.size() * sizeof(int));
 }
 
 // queues the assignment of frames list[k0 .. k1) (or k0 .. k1 themselves) against the packed centres: assign[q] for the batch's rows in order
-pvlm_status assign_batch(pvlm_ctx* ctx, const char* who, const pvlm_descset* set, const int* list, int k0, int k1, const PackedCentres& P, Scratch& S, bool exact, int* d_assign,
-                         int* d_changed, long long* nq_out, int* fallback) {
+void assign_batch(pvlm_call& c, const pvlm_descset* set, const int* list, int k0, int k1, const PackedCentres& P, Scratch& S, bool exact, int* d_assign, int* d_changed,
+                  long long* nq_out, int* fallback) {
   std::vector<PairDesc> pd((size_t)(k1 - k0));
   long long nq = 0;
   for (int k = k0; k < k1; ++k) {
@@ -330,10 +314,10 @@ pvlm_status assign_batch(pvlm_ctx* ctx, const char* who, const pvlm_descset* set
     nq += D.n1;
   }
   *nq_out = nq;
-  pvlm_status st = pvlm_match_launch::knn_batch(ctx, who, pd.data(), k1 - k0, nq, exact, S.d_pairs, S.d_qt, S.d_knn, S.d_fb, S.d_cnt, fallback);
-  if (st || nq == 0) return st;
-  hipLaunchKernelGGL(k_vlad_take_assign, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, (const KnnRec*)S.d_knn, (const int*)S.d_map, (int)nq, d_assign, d_changed);
-  return launch_ok(ctx, who) ? PVLM_OK : PVLM_ERR_HIP;
+  pvlm_match_launch::knn_batch(c, pd.data(), k1 - k0, nq, exact, S.d_pairs, S.d_qt, S.d_knn, S.d_fb, S.d_cnt, fallback);
+  if (nq == 0) return;
+  c.launch(k_vlad_take_assign, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, S.d_knn, S.d_map, (int)nq, d_assign, d_changed);
+  c.check_launches();
 }
 
 // tiles and segments of `segs` runs of rows (n[s] rows each, one after the other from row 0)
@@ -349,19 +333,11 @@ void make_group(const std::vector<int>& n, std::vector<GTile>& tiles, std::vecto
 }
 
 // queues the stable grouping of key[] (tiles / segments already on the device) into S.d_order and S.d_start
-pvlm_status group_rows(pvlm_ctx* ctx, const char* who, const int* d_key, int n_tiles, int n_segs, int book, Scratch& S) {
-  hipStream_t st = ctx->stream;
-  if (n_tiles > 0) hipLaunchKernelGGL(k_group_hist, dim3((unsigned)n_tiles), dim3(256), 0, st, d_key, (const GTile*)S.d_tiles, book, S.d_hist);
-  hipLaunchKernelGGL(k_group_scan, dim3((unsigned)n_segs), dim3(256), 0, st, S.d_hist, (const GSeg*)S.d_segs, book, S.d_start);
-  if (n_tiles > 0) hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)n_tiles), dim3(256), 0, st, d_key, (const GTile*)S.d_tiles, (const int*)S.d_hist, (const GSeg*)S.d_segs,
-                                      (const int*)S.d_start, book, S.d_order);
-  return launch_ok(ctx, who) ? PVLM_OK : PVLM_ERR_HIP;
-}
-
-pvlm_status enter(pvlm_ctx* ctx, const char* who) {
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "%s inside a graph capture", who); return PVLM_ERR_STATE; }
-  return PVLM_OK;
+void group_rows(pvlm_call& c, const int* d_key, int n_tiles, int n_segs, int book, Scratch& S) {
+  if (n_tiles > 0) c.launch(k_group_hist, dim3((unsigned)n_tiles), dim3(256), 0, d_key, S.d_tiles, book, S.d_hist);
+  c.launch(k_group_scan, dim3((unsigned)n_segs), dim3(256), 0, S.d_hist, S.d_segs, book, S.d_start);
+  if (n_tiles > 0) c.launch(k_group_scatter, dim3((unsigned)n_tiles), dim3(256), 0, d_key, S.d_tiles, S.d_hist, S.d_segs, S.d_start, book, S.d_order);
+  c.check_launches();
 }
 
 }  // namespace
@@ -384,76 +360,66 @@ extern "C" pvlm_status pvlm_vlad_kmeans(pvlm_ctx* ctx, const pvlm_descset* set, 
   if (N >= (1ll << 31) - kGroupTile) { PVLM_SET_ERR(ctx, "%s: %lld training rows (below 2^31 are supported)", who, N); return PVLM_ERR_ARG; }
   for (int c = 0; c < book_size; ++c)
     if (init_rows[c] < 0 || init_rows[c] >= N) { PVLM_SET_ERR(ctx, "%s: init_rows[%d] is outside the training rows", who, c); return PVLM_ERR_ARG; }
-  { const pvlm_status e = enter(ctx, who); if (e) return e; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const bool exact = (flags & PVLM_FLAG_MATCH_EXACT) != 0;
   long long qcap = 0; int fcap = 0;
   const std::vector<int> first = make_batches(set, n_train, train_frames, &qcap, &fcap);
   const int n_batches = (int)first.size() - 1;
-  pvlm_dev_scratch tmp(ctx);
-  Scratch S;
-  long long* d_tstart = nullptr; long long* d_trow0 = nullptr; long long* d_src = nullptr; long long* d_init = nullptr;
-  float* d_code = nullptr; unsigned char* d_alive = nullptr; int* d_assign = nullptr; int* d_changed = nullptr; int* d_run0 = nullptr; double* d_runsum = nullptr;
   const size_t max_runs = (size_t)(N / kSumChunk) + (size_t)book_size;
-  pvlm_status st = S.alloc(tmp, (size_t)std::max<long long>(qcap, 1), (size_t)std::max(fcap, 1), (size_t)N, 1, book_size, exact);
-  if (!st) st = tmp.alloc(&d_tstart, (size_t)n_train + 1);
-  if (!st) st = tmp.alloc(&d_trow0, (size_t)n_train);
-  if (!st) st = tmp.alloc(&d_src, (size_t)N);
-  if (!st) st = tmp.alloc(&d_init, (size_t)book_size);
-  if (!st) st = tmp.alloc(&d_code, (size_t)book_size * kDim);
-  if (!st) st = tmp.alloc(&d_alive, (size_t)book_size);
-  if (!st) st = tmp.alloc(&d_assign, (size_t)N);
-  if (!st) st = tmp.alloc(&d_changed, 1);
-  if (!st) st = tmp.alloc(&d_run0, (size_t)book_size + 1);
-  if (!st) st = tmp.alloc(&d_runsum, max_runs * kDim);
-  if (st) return st;
-  hipStream_t Q = ctx->stream;
   std::vector<GTile> tiles; std::vector<GSeg> segs;
   make_group(std::vector<int>(1, (int)N), tiles, segs);
-  st = pvlm_i_h2d_q(ctx, d_tstart, tstart.data(), ((size_t)n_train + 1) * sizeof(long long));
-  if (!st) st = pvlm_i_h2d_q(ctx, d_trow0, trow0.data(), (size_t)n_train * sizeof(long long));
-  if (!st) st = pvlm_i_h2d_q(ctx, d_init, init_rows, (size_t)book_size * sizeof(long long));
-  if (!st) st = pvlm_i_h2d_q(ctx, S.d_tiles, tiles.data(), tiles.size() * sizeof(GTile));
-  if (!st) st = pvlm_i_h2d_q(ctx, S.d_segs, segs.data(), sizeof(GSeg));
-  if (!st && (hipMemsetAsync(d_assign, 0, (size_t)N * sizeof(int), Q) != hipSuccess || hipMemsetAsync(d_alive, 1, (size_t)book_size, Q) != hipSuccess)) st = PVLM_ERR_HIP;
-  if (!st) {
-    hipLaunchKernelGGL(k_vlad_train_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, Q, (const long long*)d_tstart, (const long long*)d_trow0, n_train, (int)N, d_src);
-    hipLaunchKernelGGL(k_vlad_gather, dim3((unsigned)book_size), dim3(128), 0, Q, (const float*)set->d_desc, (const long long*)d_src, (const long long*)d_init, d_code);
-    if (!launch_ok(ctx, who)) st = PVLM_ERR_HIP;
-  }
-  if (!st) st = pvlm_i_d2h_q(ctx, codebook, d_code, (size_t)book_size * kDim * sizeof(float));
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  if (st) return st;
+  Scratch S;
+  S.alloc(c, (size_t)std::max<long long>(qcap, 1), (size_t)std::max(fcap, 1), (size_t)N, 1, book_size, exact);
+  long long* d_tstart = c.alloc<long long>((size_t)n_train + 1);
+  long long* d_trow0 = c.alloc<long long>((size_t)n_train);
+  long long* d_src = c.alloc<long long>((size_t)N);
+  long long* d_init = c.alloc<long long>((size_t)book_size);
+  float* d_code = c.alloc<float>((size_t)book_size * kDim);
+  unsigned char* d_alive = c.alloc<unsigned char>((size_t)book_size);
+  int* d_assign = c.alloc<int>((size_t)N);
+  int* d_changed = c.alloc<int>(1);
+  int* d_run0 = c.alloc<int>((size_t)book_size + 1);
+  double* d_runsum = c.alloc<double>(max_runs * kDim);
+  if (c.st) return c.st;
+  c.h2d(d_tstart, tstart.data(), ((size_t)n_train + 1) * sizeof(long long));
+  c.h2d(d_trow0, trow0.data(), (size_t)n_train * sizeof(long long));
+  c.h2d(d_init, init_rows, (size_t)book_size * sizeof(long long));
+  c.h2d(S.d_tiles, tiles.data(), tiles.size() * sizeof(GTile));
+  c.h2d(S.d_segs, segs.data(), sizeof(GSeg));
+  c.memset(d_assign, 0, (size_t)N * sizeof(int));
+  c.memset(d_alive, 1, (size_t)book_size);
+  c.launch(k_vlad_train_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, d_tstart, d_trow0, n_train, (int)N, d_src);
+  c.launch(k_vlad_gather, dim3((unsigned)book_size), dim3(128), 0, set->d_desc, d_src, d_init, d_code);
+  c.check_launches();
+  c.d2h(codebook, d_code, (size_t)book_size * kDim * sizeof(float));
+  if (c.sync()) return c.st;
   std::memset(alive, 1, (size_t)book_size);
   PackedCentres P;
   std::vector<int> fbs((size_t)std::max(n_batches, 1), 0);
   int changed = 1, iter = 0;
   long long queries = 0, fallback = 0;
-  for (; iter < max_iterations && changed && !st; ++iter) {
+  for (; iter < max_iterations && changed; ++iter) {
     P.pack(codebook, alive, book_size);
-    st = upload_packed(ctx, P, S);
-    if (!st && hipMemsetAsync(d_changed, 0, sizeof(int), Q) != hipSuccess) st = PVLM_ERR_HIP;
-    for (int b = 0; b < n_batches && !st; ++b) {
+    upload_packed(c, P, S);
+    c.memset(d_changed, 0, sizeof(int));
+    for (int b = 0; b < n_batches && !c.st; ++b) {
       long long nq = 0;
-      st = assign_batch(ctx, who, set, train_frames, first[(size_t)b], first[(size_t)b + 1], P, S, exact, d_assign + tstart[(size_t)first[(size_t)b]], d_changed, &nq, &fbs[(size_t)b]);
+      assign_batch(c, set, train_frames, first[(size_t)b], first[(size_t)b + 1], P, S, exact, d_assign + tstart[(size_t)first[(size_t)b]], d_changed, &nq, &fbs[(size_t)b]);
       queries += nq;
     }
-    if (!st) st = group_rows(ctx, who, d_assign, (int)tiles.size(), 1, book_size, S);
-    if (!st) {
-      hipLaunchKernelGGL(k_vlad_run_prefix, dim3(1), dim3(1), 0, Q, (const int*)S.d_start, book_size, d_run0);
-      hipLaunchKernelGGL(k_vlad_run_sums, dim3((unsigned)max_runs), dim3(128), 0, Q, (const float*)set->d_desc, (const long long*)d_src, (const int*)S.d_order, (const int*)S.d_start,
-                         book_size, (const int*)d_run0, d_runsum);
-      hipLaunchKernelGGL(k_vlad_means, dim3((unsigned)book_size), dim3(128), 0, Q, (const double*)d_runsum, (const int*)d_run0, (const int*)S.d_start, d_code, d_alive);
-      if (!launch_ok(ctx, who)) st = PVLM_ERR_HIP;
-    }
-    if (!st) st = pvlm_i_d2h_q(ctx, codebook, d_code, (size_t)book_size * kDim * sizeof(float));
-    if (!st) st = pvlm_i_d2h_q(ctx, alive, d_alive, (size_t)book_size);
-    if (!st) st = pvlm_i_d2h_q(ctx, &changed, d_changed, sizeof(int));
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    if (st) break;
+    group_rows(c, d_assign, (int)tiles.size(), 1, book_size, S);
+    c.launch(k_vlad_run_prefix, dim3(1), dim3(1), 0, S.d_start, book_size, d_run0);
+    c.launch(k_vlad_run_sums, dim3((unsigned)max_runs), dim3(128), 0, set->d_desc, d_src, S.d_order, S.d_start, book_size, d_run0, d_runsum);
+    c.launch(k_vlad_means, dim3((unsigned)book_size), dim3(128), 0, d_runsum, d_run0, S.d_start, d_code, d_alive);
+    c.check_launches();
+    c.d2h(codebook, d_code, (size_t)book_size * kDim * sizeof(float));
+    c.d2h(alive, d_alive, (size_t)book_size);
+    c.d2h(&changed, d_changed, sizeof(int));
+    if (c.sync()) return c.st;
     for (int b = 0; b < n_batches; ++b) fallback += fbs[(size_t)b];
   }
-  if (!st && assign_or_null && N > 0) st = pvlm_i_d2h(ctx, assign_or_null, d_assign, (size_t)N * sizeof(int));
-  if (st) { (void)pvlm_i_sync(ctx); return st; }
+  if (assign_or_null) { c.d2h(assign_or_null, d_assign, (size_t)N * sizeof(int)); if (c.sync()) return c.st; }
   if (stats) {
     stats->queries = queries; stats->fallback_queries = fallback; stats->iterations = iter; stats->batches = n_batches;
     for (int c = 0; c < book_size; ++c) stats->dead_centres += alive[c] ? 0 : 1;
@@ -480,7 +446,8 @@ extern "C" pvlm_status pvlm_vlad_embed(pvlm_ctx* ctx, const pvlm_descset* set, i
     if (!alive_or_null || alive_or_null[c])
       for (int k = 0; k < kDim; ++k)
         if (!std::isfinite(codebook[(size_t)c * kDim + k])) { PVLM_SET_ERR(ctx, "%s: centre %d has a value that is not finite", who, c); return PVLM_ERR_ARG; }
-  { const pvlm_status e = enter(ctx, who); if (e) return e; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const bool exact = (flags & PVLM_FLAG_MATCH_EXACT) != 0;
   const int F = set->n_frames;
   const size_t D = (size_t)book_size * kDim;
@@ -491,49 +458,39 @@ extern "C" pvlm_status pvlm_vlad_embed(pvlm_ctx* ctx, const pvlm_descset* set, i
   const int n_batches = (int)first.size() - 1;
   pvlm_vladset* vs = new pvlm_vladset();
   vs->owner = ctx; vs->n_frames = F; vs->book_size = book_size;
-  pvlm_status st = pvlm_i_alloc(ctx, &vs->d_vlad, (size_t)F * D);
+  c.st = pvlm_i_alloc(ctx, &vs->d_vlad, (size_t)F * D);       // the set's own block: it outlives the call, pvlm_vladset_destroy frees it
   long long queries = 0, fallback = 0;
-  {
-    pvlm_dev_scratch tmp(ctx);
-    Scratch S;
-    float* d_code = nullptr; int* d_assign = nullptr; double* d_nrm = nullptr; double* d_bsum = nullptr;
-    const size_t Q = (size_t)std::max<long long>(qcap, 1), FB = (size_t)std::max(fcap, 1);
-    if (!st) st = S.alloc(tmp, Q, FB, Q, FB, book_size, exact);
-    if (!st) st = tmp.alloc(&d_code, D);
-    if (!st) st = tmp.alloc(&d_assign, Q);
-    if (!st) st = tmp.alloc(&d_nrm, Q);
-    if (!st) st = tmp.alloc(&d_bsum, FB * (size_t)book_size);
-    hipStream_t str = ctx->stream;
-    if (!st) st = pvlm_i_h2d_q(ctx, d_code, codebook, D * sizeof(float));
-    if (!st && P.count() > 0) st = upload_packed(ctx, P, S);
-    if (!st && P.count() == 0 && F > 0 && hipMemsetAsync(vs->d_vlad, 0, (size_t)F * D * sizeof(float), str) != hipSuccess) st = PVLM_ERR_HIP;
-    std::vector<int> fbs((size_t)std::max(n_batches, 1), 0), n; std::vector<GTile> tiles; std::vector<GSeg> segs;
-    for (int b = 0; b < n_batches && !st && P.count() > 0; ++b) {
-      const int f0 = first[(size_t)b], f1 = first[(size_t)b + 1], nf = f1 - f0;
-      long long nq = 0;
-      // the descriptor set keeps the frames one after the other, so the batch's rows are one range
-      const float* rows = set->d_desc + set->row0[(size_t)f0] * kDim;
-      if (hipMemsetAsync(d_assign, 0xff, Q * sizeof(int), str) != hipSuccess) { st = PVLM_ERR_HIP; break; }
-      st = assign_batch(ctx, who, set, nullptr, f0, f1, P, S, exact, d_assign, nullptr, &nq, &fbs[(size_t)b]);
-      if (st) break;
-      queries += nq;
-      n.assign(set->rows.begin() + f0, set->rows.begin() + f1);
-      make_group(n, tiles, segs);
-      if (!tiles.empty()) st = pvlm_i_h2d_q(ctx, S.d_tiles, tiles.data(), tiles.size() * sizeof(GTile));
-      if (!st) st = pvlm_i_h2d_q(ctx, S.d_segs, segs.data(), segs.size() * sizeof(GSeg));
-      if (!st) st = group_rows(ctx, who, d_assign, (int)tiles.size(), nf, book_size, S);
-      if (st) break;
-      if (normalization == 2 && nq > 0)
-        hipLaunchKernelGGL(k_vlad_res_norm, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, str, rows, (const int*)d_assign, (const float*)d_code, (int)nq, d_nrm);
-      hipLaunchKernelGGL(k_vlad_blocks, dim3((unsigned)book_size, (unsigned)nf), dim3(128), 0, str, rows, (const int*)S.d_order, (const int*)S.d_start, (const GSeg*)S.d_segs,
-                         (const float*)d_code, (const double*)d_nrm, normalization, book_size, vs->d_vlad + (size_t)f0 * D, d_bsum);
-      hipLaunchKernelGGL(k_vlad_finish, dim3((unsigned)nf), dim3(256), 0, str, vs->d_vlad + (size_t)f0 * D, (const double*)d_bsum, book_size);
-      if (!launch_ok(ctx, who)) st = PVLM_ERR_HIP;
-    }
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    for (int b = 0; b < n_batches; ++b) fallback += fbs[(size_t)b];
+  const size_t Q = (size_t)std::max<long long>(qcap, 1), FB = (size_t)std::max(fcap, 1);
+  Scratch S;
+  S.alloc(c, Q, FB, Q, FB, book_size, exact);
+  float* d_code = c.upload(codebook, D);
+  int* d_assign = c.alloc<int>(Q);
+  double* d_nrm = c.alloc<double>(Q);
+  double* d_bsum = c.alloc<double>(FB * (size_t)book_size);
+  if (P.count() > 0) upload_packed(c, P, S);
+  else c.memset(vs->d_vlad, 0, (size_t)F * D * sizeof(float));
+  std::vector<int> fbs((size_t)std::max(n_batches, 1), 0), n; std::vector<GTile> tiles; std::vector<GSeg> segs;
+  for (int b = 0; b < n_batches && !c.st && P.count() > 0; ++b) {
+    const int f0 = first[(size_t)b], f1 = first[(size_t)b + 1], nf = f1 - f0;
+    long long nq = 0;
+    // the descriptor set keeps the frames one after the other, so the batch's rows are one range
+    const float* rows = set->d_desc + set->row0[(size_t)f0] * kDim;
+    c.memset(d_assign, 0xff, Q * sizeof(int));
+    assign_batch(c, set, nullptr, f0, f1, P, S, exact, d_assign, nullptr, &nq, &fbs[(size_t)b]);
+    queries += nq;
+    n.assign(set->rows.begin() + f0, set->rows.begin() + f1);
+    make_group(n, tiles, segs);
+    c.h2d(S.d_tiles, tiles.data(), tiles.size() * sizeof(GTile));
+    c.h2d(S.d_segs, segs.data(), segs.size() * sizeof(GSeg));
+    group_rows(c, d_assign, (int)tiles.size(), nf, book_size, S);
+    if (normalization == 2 && nq > 0) c.launch(k_vlad_res_norm, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, rows, d_assign, d_code, (int)nq, d_nrm);
+    c.launch(k_vlad_blocks, dim3((unsigned)book_size, (unsigned)nf), dim3(128), 0, rows, S.d_order, S.d_start, S.d_segs, d_code, d_nrm, normalization, book_size,
+             vs->d_vlad + (size_t)f0 * D, d_bsum);
+    c.launch(k_vlad_finish, dim3((unsigned)nf), dim3(256), 0, vs->d_vlad + (size_t)f0 * D, d_bsum, book_size);
+    c.check_launches();
   }
-  if (st) { pvlm_vladset_destroy(ctx, vs); return st; }
+  if (c.sync()) { pvlm_vladset_destroy(ctx, vs); return c.st; }
+  for (int b = 0; b < n_batches; ++b) fallback += fbs[(size_t)b];
   if (stats) { stats->queries = queries; stats->fallback_queries = fallback; stats->batches = n_batches; stats->dead_centres = book_size - P.count(); }
   *out = vs;
   return PVLM_OK;
@@ -542,11 +499,11 @@ extern "C" pvlm_status pvlm_vlad_embed(pvlm_ctx* ctx, const pvlm_descset* set, i
 extern "C" pvlm_status pvlm_vladset_read(pvlm_ctx* ctx, const pvlm_vladset* vs, float* out) {
   if (!ctx || !vs || !out) return PVLM_ERR_ARG;
   if (vs->owner != ctx) { PVLM_SET_ERR(ctx, "pvlm_vladset_read: the set belongs to another context"); return PVLM_ERR_ARG; }
-  { const pvlm_status e = enter(ctx, "pvlm_vladset_read"); if (e) return e; }
+  pvlm_call c(ctx, "pvlm_vladset_read");
+  if (c.enter()) return c.st;
   if (vs->n_frames == 0) return PVLM_OK;
-  const pvlm_status st = pvlm_i_d2h(ctx, out, vs->d_vlad, (size_t)vs->n_frames * vs->book_size * kDim * sizeof(float));
-  const pvlm_status s2 = pvlm_i_sync(ctx);
-  return st ? st : s2;
+  c.d2h(out, vs->d_vlad, (size_t)vs->n_frames * vs->book_size * kDim * sizeof(float));
+  return c.sync();
 }
 
 extern "C" pvlm_status pvlm_vlad_neighbors(pvlm_ctx* ctx, const pvlm_vladset* vs, int neighbor_size, int* neighbors, double* sim_or_null) {
@@ -554,22 +511,19 @@ extern "C" pvlm_status pvlm_vlad_neighbors(pvlm_ctx* ctx, const pvlm_vladset* vs
   if (!ctx || !vs || !neighbors) return PVLM_ERR_ARG;
   if (vs->owner != ctx) { PVLM_SET_ERR(ctx, "%s: the set belongs to another context", who); return PVLM_ERR_ARG; }
   if (neighbor_size < 1) { PVLM_SET_ERR(ctx, "%s: neighbor_size < 1", who); return PVLM_ERR_ARG; }
-  { const pvlm_status e = enter(ctx, who); if (e) return e; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
   const int n = vs->n_frames, m = std::min(neighbor_size, n), D = vs->book_size * kDim;
   if (n == 0) return PVLM_OK;
-  pvlm_dev_scratch tmp(ctx);
-  double* d_sim = nullptr; int* d_nb = nullptr;
-  pvlm_status st = tmp.alloc(&d_sim, (size_t)n * n);
-  if (!st) st = tmp.alloc(&d_nb, (size_t)n * m);
-  if (st) return st;
+  double* d_sim = c.alloc<double>((size_t)n * n);
+  int* d_nb = c.alloc<int>((size_t)n * m);
   const unsigned T = (unsigned)((n + kSimTile - 1) / kSimTile);
-  hipLaunchKernelGGL(k_vlad_sim, dim3(T, T), dim3(256), 0, ctx->stream, (const float*)vs->d_vlad, n, D, d_sim);
-  hipLaunchKernelGGL(k_vlad_select, dim3((unsigned)n), dim3(256), 0, ctx->stream, (const double*)d_sim, n, m, d_nb);
-  if (!launch_ok(ctx, who)) st = PVLM_ERR_HIP;
-  if (!st) st = pvlm_i_d2h(ctx, neighbors, d_nb, (size_t)n * m * sizeof(int));
-  if (!st && sim_or_null) st = pvlm_i_d2h(ctx, sim_or_null, d_sim, (size_t)n * n * sizeof(double));
-  { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-  return st;
+  c.launch(k_vlad_sim, dim3(T, T), dim3(256), 0, vs->d_vlad, n, D, d_sim);
+  c.launch(k_vlad_select, dim3((unsigned)n), dim3(256), 0, d_sim, n, m, d_nb);
+  c.check_launches();
+  c.d2h(neighbors, d_nb, (size_t)n * m * sizeof(int));
+  if (sim_or_null) c.d2h(sim_or_null, d_sim, (size_t)n * n * sizeof(double));
+  return c.sync();
 }
 
 // pvlm_preload: loads this file's code object at context set-up instead of at the first call (see pvlm_ba.hip)
