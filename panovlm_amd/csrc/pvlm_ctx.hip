@@ -642,6 +642,9 @@ pvlm_status pvlm_i_resset_finalize(pvlm_ctx* ctx, pvlm_resset* rs) {
   if (const char* env = getenv("PVLM_WAVE_UNITS")) rs->wave_units = atoi(env) != 0;
   if (rs->wave_units) chunk = 2048;
   if (const char* env = getenv("PVLM_WAVE_CHUNK")) if (rs->wave_units && atoi(env) >= 128) chunk = atoi(env) / 128 * 128;
+  // ... and PVLM_FUSED_CHUNK the block form's: a multiple of 512 rows from 512 to 65 536 (a plane-run number is 16 bits), anything else is ignored.  Left alone
+  // the block form's row loop takes a second trip only in sets of more than 2.1 M rows; with it a test reaches the third with a few thousand.
+  if (const char* env = getenv("PVLM_FUSED_CHUNK")) { const int v = atoi(env); if (!rs->wave_units && v >= 512 && v <= 65536 && v % 512 == 0) chunk = v; }
   rs->chunk_rows = (int)chunk;
   std::vector<int> blk_pair, blk_chunk, pair_blk_start(P + 1, 0);
   std::vector<const double*> pair_cols(std::max(P, 1), nullptr);

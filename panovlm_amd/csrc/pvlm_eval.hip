@@ -327,7 +327,7 @@ __device__ __forceinline__ double wave_sum(double x) {
 
 // one residual block: evaluate, robustify, accumulate  S += rho' v v^T, gv += rho' v r, cost += rho/2
 template <int KIND, bool NORM, int NCOLS, int LOSS>
-__device__ __forceinline__ void accumulate_row(const double* rec, const double* T, double weight, double loss_a, double a2, double* acc) {
+__device__ __forceinline__ void accumulate_row(const double* rec, const double* T, double weight, double loss_a, double a2, double mh_a2, double* acc) {
   Wrench w;
   eval_wrench<KIND, NORM>(rec, T, weight, w);
   const double s = w.r * w.r;
@@ -338,7 +338,7 @@ __device__ __forceinline__ void accumulate_row(const double* rec, const double* 
     const bool out = s > a2;
     const double inv = fast_rcp(out ? rr : 1.0);
     rho1 = out ? fmax(std::numeric_limits<double>::min(), loss_a * inv) : 1.0;
-    half_rho = out ? fma(loss_a, rr, -0.5 * a2) : half_rho;
+    half_rho = out ? fma(loss_a, rr, mh_a2) : half_rho;   // mh_a2 = -0.5 * a2, computed once per kernel
   }
   const double vv[6] = {w.c[0], w.c[1], w.c[2], w.g[0], w.g[1], w.g[2]};
   int q = 0;
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   double acc[PVLM_PARTIAL];
 #pragma unroll
   for (int k = 0; k < PVLM_PARTIAL; ++k) acc[k] = 0.0;
-  const double a2 = loss_a * loss_a;
+  const double a2 = uniform_sgpr(loss_a * loss_a), mh_a2 = uniform_sgpr(-0.5 * a2);   // wave-uniform: a2 lives in a scalar pair; mh_a2 shares its fma with loss_a (one scalar operand per instruction) and the compiler may keep it in VGPRs
   // Each lane streams two consecutive rows per column with one 16-byte load.  The cheap (Meter)
   // functors are latency-bound: their next tile is prefetched into registers while the current one
   // is evaluated (+7 % on MI355X); the Angle functors are VALU-bound at 3 waves/SIMD and lose
@@ -410,35 +410,41 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   const double* tabb = nullptr;
   if (PR) { runb = pr.idx + pr.pair_idx0[p] + lo; tabb = pr.tab + 4 * pr.chunk_plane0[blockIdx.x]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
-  unsigned j = 2u * threadIdx.x;
+  // The loop runs on ONE register: o, the byte offset of the lane's two rows inside a column (8 * row).  It addresses the columns, the run word (at o / 4)
+  // and carries the bounds; a row counter beside it costs the registers that the run word below needs.
+  const unsigned span8 = 8u * span;
+  unsigned o = 16u * threadIdx.x;
   double2 nx[NS];
+  // PR: the run word's address depends on the row alone, and the addresses of the four table loads depend on the word.  It is fetched one trip ahead (one
+  // VGPR), so a trip issues its column loads, its table loads and the next word together and pays one memory round trip, not two in a row.  The next word's
+  // load has no branch around it — under an exec mask the wait-count merge puts a full wait in the middle of the table loads: the last trip re-reads its own
+  // word, which is in bounds.
   unsigned nx_runs = 0;
-  if (kPrefetch && j < span) {
+  if (PR && o < span8) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o >> 3);
+  if (kPrefetch && o < span8) {
 #pragma unroll
-    for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
-    if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
+    for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
   }
-  for (; j < span; j += 512) {
+  for (; o < span8; o += 4096) {     // 512 rows per trip
     double2 v[NS];
-    unsigned runs = 0;
+    const unsigned runs = nx_runs;
+    const unsigned o_next = o + 4096 < span8 ? o + 4096 : o;
     if (kPrefetch) {
 #pragma unroll
       for (int c = 0; c < NS; ++c) v[c] = nx[c];
-      runs = nx_runs;
-      if (j + 512 < span) {
+      if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o_next >> 3);
+      if (o + 4096 < span8) {
 #pragma unroll
-        for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * (j + 512)));
-        if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j + 512);
+        for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o + 4096));
       }
     } else {
 #ifdef PVLM_EXP_SKIP   // timing experiment only (wrong results): how does the rate respond to fewer bytes per evaluation?
 #pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NS - PVLM_EXP_SKIP ? c : 0] + j);
+      for (int c = 0; c < NS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NS - PVLM_EXP_SKIP ? c : 0] + (o >> 3));
 #else
 #pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
+      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
 #endif
-      if (PR) runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
     }
     double2 pl[2][2];              // PR: {a, b}, {c, d} of the lane's two rows (a pad row behind an odd last row names entry 0)
     if (PR) {
@@ -448,15 +454,16 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
         pl[h][0] = stream_load2<false>(at_byte(tabb, at));
         pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
       }
+      if (!kPrefetch) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o_next >> 3);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (j + h >= span) break;
+      if (o + 8u * h >= span8) break;
       double rec[NCOLS];
 #pragma unroll
       for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
       if (PR) { rec[3] = pl[h][0].x; rec[4] = pl[h][0].y; rec[5] = pl[h][1].x; rec[6] = pl[h][1].y; }
-      accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, acc);
+      accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, mh_a2, acc);
     }
   }
   __shared__ double red[4][PVLM_PARTIAL];
@@ -501,7 +508,7 @@ __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_w
   double acc[PVLM_PARTIAL];
 #pragma unroll
   for (int k = 0; k < PVLM_PARTIAL; ++k) acc[k] = 0.0;
-  const double a2 = loss_a * loss_a;
+  const double a2 = uniform_sgpr(loss_a * loss_a), mh_a2 = uniform_sgpr(-0.5 * a2);   // wave-uniform: a2 lives in a scalar pair; mh_a2 shares its fma with loss_a (one scalar operand per instruction) and the compiler may keep it in VGPRs
   const double* colb[NS];          // uniform column bases + one 32-bit row offset, as in k_eval_fused
 #pragma unroll
   for (int c = 0; c < NS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
@@ -509,19 +516,22 @@ __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_w
   const double* tabb = nullptr;
   if (PR) { runb = pr.idx + pr.pair_idx0[p] + lo; tabb = pr.tab + 4 * pr.chunk_plane0[unit]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
+  unsigned nx_runs = 0;            // PR: the run word one trip ahead, as in k_eval_fused
+  if (PR && 2u * lane < span) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, 2u * lane);
   for (unsigned j = 2u * lane; j < span; j += 128) {
     double2 v[NS];
 #pragma unroll
     for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], 8u * j));
     double2 pl[2][2];
     if (PR) {
-      const unsigned runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j);
+      const unsigned runs = nx_runs;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const unsigned at = 32u * (h ? runs >> 16 : runs & 0xffffu);
         pl[h][0] = stream_load2<false>(at_byte(tabb, at));
         pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
       }
+      nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, j + 128 < span ? j + 128 : j);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -530,7 +540,7 @@ __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_w
 #pragma unroll
       for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
       if (PR) { rec[3] = pl[h][0].x; rec[4] = pl[h][0].y; rec[5] = pl[h][1].x; rec[6] = pl[h][1].y; }
-      accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, acc);
+      accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, mh_a2, acc);
     }
   }
   // the 28 totals in one transposing butterfly (32 exchanges instead of 28 x 6): lanes 2k and 2k + 1 end with total k

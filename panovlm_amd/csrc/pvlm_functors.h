@@ -52,10 +52,31 @@ __device__ __forceinline__ double fma_sconst(double p, double u, double c) {
   return fma(p, u, c);
 #endif
 }
+// The FIRST step has two constants, p0 * u + c1.  With p0 as the "v" operand of fma_sconst it sits in a VGPR pair for the whole row loop; the constant bus
+// takes one scalar operand per instruction, so p0 is copied out of its scalar pair right in front of the fma and the pair of VGPRs is the step's result.
+__device__ __forceinline__ double fma_sconst2(double p0, double u, double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double d;
+  asm("v_mov_b64 %0, %1\n\tv_fma_f64 %0, %0, %2, %3" : "=&v"(d) : "s"(p0), "v"(u), "s"(c));
+  return d;
+#else
+  return fma(p0, u, c);
+#endif
+}
+// A wave-uniform double that the compiler cannot prove uniform (a product of kernel arguments is computed on the vector ALU: gfx9 has no scalar fp64) forced
+// into a scalar register pair, so a loop that only compares with it or adds it keeps no VGPRs for it.  The bits are the first active lane's, unchanged.
+__device__ __forceinline__ double uniform_sgpr(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+#else
+  return x;
+#endif
+}
 __device__ __forceinline__ double atan_small(double t) {
   const double u = t * t;
-  double p = 2.11272689568591313e-02;
-  p = fma_sconst(p, u, -4.34739031566048761e-02);
+  double p = fma_sconst2(2.11272689568591313e-02, u, -4.34739031566048761e-02);
   p = fma_sconst(p, u, 5.68812005923421543e-02);
   p = fma_sconst(p, u, -6.64019012732186553e-02);
   p = fma_sconst(p, u, 7.68994845277858746e-02);
