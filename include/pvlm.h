@@ -740,6 +740,47 @@ pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, int n_image
 pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl_rowmajor16,
                                       unsigned size, float max_depth, uint16_t* depth_u16, pvlm_depthfill_stats* stats_or_null);
 
+/* pvlm_depthset: the uint16 depth maps of a set of frames, resident on the device (upstream: frames[i].depth_map).  A frame without a map is "empty"
+ * (depth_map.empty()); frames may differ in size.  The memory comes from the context's pool: pvlm_mem_info counts it as in use and pvlm_trim leaves it alone, as
+ * for a pvlm_descset.  A set may be used only with the context that made it (PVLM_ERR_ARG otherwise).
+ * pvlm_depthset_compute: pvlm_compute_depth_images with the same arguments, checks and batches (PVLM_DEPTHFILL_BATCH_IMAGES included), the n_scans maps left in ONE
+ * device allocation of a new set; nothing returns to the host but the two counters of the statistics.
+ * pvlm_depthset_create: a set of n_frames empty frames.  pvlm_depthset_upload: frame `frame` becomes the rows x cols map depth_u16 (its own allocation; a map
+ * uploaded there before is released).  pvlm_depthset_info: the size of a frame's map, 0 x 0 for an empty frame.  pvlm_depthset_read: one map to the host
+ * (rows x cols of pvlm_depthset_info; an empty frame is PVLM_ERR_ARG).  Synchronous; PVLM_ERR_STATE inside a capture. */
+typedef struct pvlm_depthset pvlm_depthset;
+pvlm_status pvlm_depthset_compute(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl_rowmajor16,
+                                  unsigned size, float max_depth, pvlm_depthset** out, pvlm_depthfill_stats* stats_or_null);
+pvlm_status pvlm_depthset_create(pvlm_ctx* ctx, int n_frames, pvlm_depthset** out);
+pvlm_status pvlm_depthset_upload(pvlm_ctx* ctx, pvlm_depthset* set, int frame, int rows, int cols, const uint16_t* depth_u16);
+pvlm_status pvlm_depthset_info(const pvlm_depthset* set, int frame, int* rows, int* cols);
+pvlm_status pvlm_depthset_read(pvlm_ctx* ctx, const pvlm_depthset* set, int frame, uint16_t* depth_u16_out);
+void pvlm_depthset_destroy(pvlm_ctx* ctx, pvlm_depthset* set);
+
+/* ---- K39: the translation scale of every pair from the resident depth maps ---------------------------------------------------------------------
+ * SfM::SetTranslationScaleDepthMap(eq, pair) (sfm/SfM.cpp:487-603) for n_pairs pairs in one call, as csrc/pvlm_scale_core.h states it: bit for bit what the host
+ * step computes (fp64, no contraction, the mean added in list order).  eq_rows x eq_cols: the one Equirectangular of all frames; frame_rows[f]: the image rows of
+ * frame f (the half-size test d1.rows == (rows + 1) / 2); pair p is (src[p], tgt[p]) with the points point_offsets[p] .. point_offsets[p + 1] of triangulated (3
+ * doubles each, in the first camera's frame), R_21 (9, row-major) and t_21 (3).  A scaled pair: ok = 1, t_21 and its points multiplied by the scale,
+ * points_with_depth, upper_scale and lower_scale set (0, 0 for the median fall-back).  An unscaled pair (an empty map, or fewer than 10 scales): ok = 0, t_21, the
+ * points, upper_scale and lower_scale untouched, points_with_depth = 0 when both maps were there and untouched otherwise.  A pair's result does not depend on the
+ * other pairs, the batch or the run.  PVLM_ERR_ARG with no output touched: a frame index outside the set, offsets that do not ascend from 0, a pose or point that is
+ * not finite, eq_rows or eq_cols <= 0.  The list is worked through in batches bounded in pairs and points; PVLM_SCALE_BATCH_PAIRS (read at every call) lowers the
+ * pair limit and changes no result.  Synchronous; PVLM_ERR_STATE inside a capture. */
+typedef struct pvlm_scale_stats {
+  long long pairs_mean;      /* pairs scaled by the mean of the kept scales */
+  long long pairs_median;    /* pairs scaled by the median fall-back */
+  long long pairs_unscaled;  /* pairs left as they were */
+  long long points_tested;   /* points of the pairs whose two maps were there */
+  long long points_scaled;   /* points that gave a consistent scale pair */
+  long long batches;
+} pvlm_scale_stats;
+pvlm_status pvlm_set_translation_scales(pvlm_ctx* ctx, const pvlm_depthset* set, int eq_rows, int eq_cols, const int* frame_rows /* n_frames of the set */, int n_pairs,
+                                        const int* src, const int* tgt, const long long* point_offsets /* n_pairs + 1 */, const double* R_21, double* t_21 /* in/out */,
+                                        double* triangulated /* in/out */, unsigned char* ok, int* points_with_depth /* in/out */, double* upper_scale /* in/out */,
+                                        double* lower_scale /* in/out */, pvlm_scale_stats* stats_or_null);
+int pvlm_scale_workgroup_size(void);
+
 /* MVS::InitDepthNormal (mvs/MVS.cpp:496-584; config 5 "LiDAR-seeded depth priors"): the depth image of
  * pvlm_project_lidar_depth (uint16, depth * 256; size 2 upstream, :512) seeds the depth map, every pixel without a LiDAR depth
  * gets a uniform random depth in [min_depth, max_depth], keep_lidar_constant != 0 marks the seeded pixels in depth_constant

@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "pvlm_resset_plane_runs",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
+    "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
+    "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
 ]
 
 
@@ -1499,6 +1501,116 @@ def vlad_neighbors(ctx, vladset, neighbor_size, want_sim=False):
     sim = np.zeros((n, n), np.float64) if want_sim else None
     ctx._check(ctx.lib.pvlm_vlad_neighbors(ctx._h, vladset._h, C.c_int(neighbor_size), _p(nb, C.c_int), None if sim is None else _p(sim, C.c_double)), "pvlm_vlad_neighbors")
     return nb, sim
+
+
+class DepthSet:
+    """pvlm_depthset (K37 / K39): the uint16 depth maps of a set of frames, resident on the device.  compute / compute_flat make one from LiDAR scans
+    (pvlm_depthset_compute: what Context.compute_depth_images computes, left on the device); create makes one of empty frames for upload."""
+
+    def __init__(self, ctx, handle, n_frames, stats=None):
+        self.ctx, self._h, self.n_frames, self.stats = ctx, handle, n_frames, stats
+
+    @classmethod
+    def compute(cls, ctx, rows, cols, clouds, T_cl, size, max_depth):
+        clouds = [_f32(c).reshape(-1, 3) for c in clouds]
+        first = np.zeros(len(clouds) + 1, np.int64)
+        first[1:] = np.cumsum([len(c) for c in clouds])
+        xyz = np.ascontiguousarray(np.concatenate(clouds + [np.zeros((1, 3), np.float32)]))
+        return cls.compute_flat(ctx, rows, cols, first, xyz, T_cl, size, max_depth)
+
+    @classmethod
+    def compute_flat(cls, ctx, rows, cols, first_point, xyz, T_cl, size, max_depth):
+        first = _i64(first_point); xyz = _f32(xyz).reshape(-1, 3); T = _f64(T_cl).reshape(16)
+        n = max(len(first) - 1, 0)
+        h = C.c_void_p(); st = DepthfillStats()
+        ctx._check(ctx.lib.pvlm_depthset_compute(ctx._h, C.c_int(rows), C.c_int(cols), C.c_int(n), _p(first, C.c_longlong), _p(xyz, C.c_float), _p(T, C.c_double),
+                                                 C.c_uint(size), C.c_float(max_depth), C.byref(h), C.byref(st)), "pvlm_depthset_compute")
+        return cls(ctx, h, n, _depthfill_stats(st))
+
+    @classmethod
+    def create(cls, ctx, n_frames):
+        h = C.c_void_p()
+        ctx._check(ctx.lib.pvlm_depthset_create(ctx._h, C.c_int(n_frames), C.byref(h)), "pvlm_depthset_create")
+        return cls(ctx, h, n_frames)
+
+    def _live(self, what):
+        if not self._h or not self.ctx._h:
+            raise PvlmError(what + ": the depth set was closed")
+
+    def upload(self, frame, depth_u16):
+        self._live("DepthSet.upload")
+        d = np.ascontiguousarray(depth_u16, np.uint16)
+        if d.ndim != 2:
+            raise PvlmError("DepthSet.upload: a rows x cols uint16 map")
+        self.ctx._check(self.ctx.lib.pvlm_depthset_upload(self.ctx._h, self._h, C.c_int(frame), C.c_int(d.shape[0]), C.c_int(d.shape[1]), _p(d, C.c_uint16)),
+                        "pvlm_depthset_upload")
+
+    def info(self, frame):
+        """(rows, cols) of the frame's map; (0, 0) for an empty frame"""
+        self._live("DepthSet.info")
+        r = C.c_int(0); c = C.c_int(0)
+        self.ctx._check(self.ctx.lib.pvlm_depthset_info(self._h, C.c_int(frame), C.byref(r), C.byref(c)), "pvlm_depthset_info")
+        return r.value, c.value
+
+    def read(self, frame):
+        self._live("DepthSet.read")
+        rows, cols = self.info(frame)
+        out = np.zeros((rows, cols), np.uint16)
+        if rows and cols:
+            self.ctx._check(self.ctx.lib.pvlm_depthset_read(self.ctx._h, self._h, C.c_int(frame), _p(out, C.c_uint16)), "pvlm_depthset_read")
+        return out
+
+    def close(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.pvlm_depthset_destroy(self.ctx._h, self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ScaleStats(C.Structure):
+    _fields_ = [("pairs_mean", C.c_longlong), ("pairs_median", C.c_longlong), ("pairs_unscaled", C.c_longlong), ("points_tested", C.c_longlong),
+                ("points_scaled", C.c_longlong), ("batches", C.c_longlong)]
+
+
+def scale_workgroup_size():
+    """pvlm_scale_workgroup_size (K39): the lanes of the workgroup that scales one pair."""
+    return int(load_library().pvlm_scale_workgroup_size())
+
+
+def set_translation_scales(ctx, depthset, eq_rows, eq_cols, frame_rows, src, tgt, point_offsets, R_21, t_21, triangulated, points_with_depth=None, upper_scale=None,
+                           lower_scale=None, check=True):
+    """pvlm_set_translation_scales (K39): SfM::SetTranslationScaleDepthMap(eq, pair) for every pair on the maps of a DepthSet.  points_with_depth / upper_scale /
+    lower_scale: what the pairs hold before the call (default 0, -1, -1: util/MatchPair.h's constructors).  The inputs are not modified.  Returns a dict: t_21
+    (pairs x 3), triangulated (points x 3), ok (uint8), points_with_depth (int32), upper_scale, lower_scale, stats, rc.  An argument the library refuses raises
+    PvlmError; with check=False the dict comes back with its rc (the outputs then hold the inputs)."""
+    if not depthset._h:
+        raise PvlmError("set_translation_scales: the depth set was closed")
+    fr = _i32(frame_rows); src = _i32(src); tgt = _i32(tgt); off = _i64(point_offsets)
+    npairs = len(src); npts = int(np.asarray(triangulated).size // 3)
+    R = np.zeros((npairs + 1, 3, 3)); R[:npairs] = np.asarray(R_21, np.float64).reshape(npairs, 3, 3)
+    t = np.zeros((npairs + 1, 3)); t[:npairs] = np.asarray(t_21, np.float64).reshape(npairs, 3)
+    tri = np.zeros((npts + 1, 3)); tri[:npts] = np.asarray(triangulated, np.float64).reshape(npts, 3)
+    ok = np.full(npairs + 1, 0xA5, np.uint8)
+    pwd = np.zeros(npairs + 1, np.int32); up = np.full(npairs + 1, -1.0); lo = np.full(npairs + 1, -1.0)
+    if points_with_depth is not None:
+        pwd[:npairs] = points_with_depth
+    if upper_scale is not None:
+        up[:npairs] = upper_scale
+    if lower_scale is not None:
+        lo[:npairs] = lower_scale
+    st = ScaleStats()
+    rc = ctx.lib.pvlm_set_translation_scales(ctx._h, depthset._h, C.c_int(eq_rows), C.c_int(eq_cols), _p(fr, C.c_int), C.c_int(npairs), _p(src, C.c_int), _p(tgt, C.c_int),
+                                             _p(off, C.c_longlong), _p(R, C.c_double), _p(t, C.c_double), _p(tri, C.c_double), _p(ok, C.c_ubyte), _p(pwd, C.c_int),
+                                             _p(up, C.c_double), _p(lo, C.c_double), C.byref(st))
+    if check:
+        ctx._check(rc, "pvlm_set_translation_scales")
+    return dict(t_21=t[:npairs], triangulated=tri[:npts], ok=ok[:npairs], points_with_depth=pwd[:npairs], upper_scale=up[:npairs], lower_scale=lo[:npairs],
+                stats={k: getattr(st, k) for k, _ in ScaleStats._fields_}, rc=int(rc))
 
 
 class EssentialParams(C.Structure):

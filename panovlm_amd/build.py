@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip")
 
 
 def _hipcc():
@@ -120,6 +120,7 @@ VLAD_DRIVER = os.path.join(HERE, "build", "pvlm_vlad_driver")
 RELPOSE_DRIVER = os.path.join(HERE, "build", "pvlm_relpose_driver")
 DEPTHFILL_DRIVER = os.path.join(HERE, "build", "pvlm_depthfill_driver")
 DEPTHFILL_CHECK = os.path.join(HERE, "build", "depthfill_core_check")
+SCALE_DRIVER = os.path.join(HERE, "build", "pvlm_scale_driver")
 
 
 def build_host(force=False):
@@ -213,6 +214,12 @@ def build_host(force=False):
     if os.path.exists(dchk) and (force or not os.path.exists(DEPTHFILL_CHECK) or
                                  os.path.getmtime(DEPTHFILL_CHECK) < max(os.path.getmtime(dchk), os.path.getmtime(core))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", "-DDEPTHFILL_CHECK_MAIN", dchk, "-o", DEPTHFILL_CHECK])
+    # the scale driver (ComputeDepthImage + FilterImagePairsFull against ComputeDepthImageResident + the resident overload: K39)
+    cdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_scale_driver.cpp")
+    if os.path.exists(cdrv) and (force or not os.path.exists(SCALE_DRIVER) or
+                                 os.path.getmtime(SCALE_DRIVER) < max(os.path.getmtime(cdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", cdrv, "-o", SCALE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
     return HOST_LIB
 
 

@@ -15,6 +15,7 @@
 
 #include "pvlm_depth_launch.h"
 #include "pvlm_depthfill_core.h"
+#include "pvlm_depthset.h"
 #include "pvlm_internal.h"
 
 namespace {
@@ -251,18 +252,12 @@ extern "C" pvlm_status pvlm_depth_completion(pvlm_ctx* ctx, int rows, int cols, 
   return c.st;
 }
 
-extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl,
-                                                 unsigned size, float max_depth, uint16_t* depth_u16, pvlm_depthfill_stats* stats) {
-  const char* who = "pvlm_compute_depth_images";
-  if (!ctx) return PVLM_ERR_ARG;
-  if (rows <= 0 || cols <= 0 || n_scans < 0 || !T_cl || (n_scans > 0 && (!first_point || !depth_u16))) { PVLM_SET_ERR(ctx, "%s: null argument or size", who); return PVLM_ERR_ARG; }
-  if (!std::isfinite(max_depth) || !(max_depth > 0.f)) { PVLM_SET_ERR(ctx, "%s: max_depth must be finite and > 0", who); return PVLM_ERR_ARG; }
-  if (stats) *stats = pvlm_depthfill_stats{0, 0, 0, 0, 0.0, 0.0};
-  if (n_scans == 0) return PVLM_OK;
-  if (first_point[0] != 0) { PVLM_SET_ERR(ctx, "%s: first_point must start at 0", who); return PVLM_ERR_ARG; }
-  for (int s = 0; s < n_scans; ++s)
-    if (first_point[s + 1] < first_point[s]) { PVLM_SET_ERR(ctx, "%s: first_point is not ascending at scan %d", who, s); return PVLM_ERR_ARG; }
-  if (first_point[n_scans] > 0 && !xyz) { PVLM_SET_ERR(ctx, "%s: null argument", who); return PVLM_ERR_ARG; }
+namespace {
+// The body of pvlm_compute_depth_images and pvlm_depthset_compute: the checks, the batches and the stream order are one; the destination of k_fill_c's uint16
+// images is the parameter.  host_out: each batch's images land in a batch scratch and are downloaded behind its kernels.  dev_out (n_scans images of device memory
+// that outlives the call): k_fill_c writes there and nothing but the two counters returns.  Exactly one of the two, unless n_scans is 0.
+pvlm_status depth_images(pvlm_ctx* ctx, const char* who, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl, unsigned size,
+                         float max_depth, uint16_t* host_out, unsigned short* dev_out, pvlm_depthfill_stats* stats) {
   pvlm_call c(ctx, who);
   if (c.enter()) return c.st;
   const size_t npix = (size_t)rows * cols;
@@ -273,7 +268,8 @@ extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int co
     const int nb = std::min(limit, n_scans - k0);
     const long long p0 = first_point[k0], np = first_point[k0 + nb] - p0;
     pvlm_call::batch bs(c);                              // this batch's scratch
-    const Work w(c, npix, cols, nb, true);
+    Work w(c, npix, cols, nb, host_out != nullptr);
+    if (dev_out) w.u16 = dev_out + npix * k0;
     unsigned long long* d_img = c.alloc<unsigned long long>(npix * nb);
     float* d_xyz = c.alloc<float>(3 * (size_t)np);
     unsigned long long counts[2] = {0, 0};
@@ -287,7 +283,7 @@ extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int co
     clock.mark(ctx, 1);
     run_phases(c, rows, cols, nb, SrcSplat{d_img}, max_depth, w, false, true);
     clock.mark(ctx, 2);
-    c.d2h(depth_u16 + npix * k0, w.u16, npix * nb * 2);
+    if (host_out) c.d2h(host_out + npix * k0, w.u16, npix * nb * 2);
     c.d2h(counts, w.counts, sizeof(counts));
     if (!c.sync() && stats) {
       stats->images += nb; stats->batches += 1; stats->valid_in += (long long)counts[0]; stats->valid_out += (long long)counts[1];
@@ -295,6 +291,114 @@ extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int co
     }
   }
   return c.st;
+}
+
+// the argument checks of the two entries; *run = 0 when there is nothing to do
+pvlm_status depth_images_args(pvlm_ctx* ctx, const char* who, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl, float max_depth,
+                              bool have_dst, pvlm_depthfill_stats* stats, int* run) {
+  *run = 0;
+  if (!ctx) return PVLM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || n_scans < 0 || !T_cl || (n_scans > 0 && (!first_point || !have_dst))) { PVLM_SET_ERR(ctx, "%s: null argument or size", who); return PVLM_ERR_ARG; }
+  if (!std::isfinite(max_depth) || !(max_depth > 0.f)) { PVLM_SET_ERR(ctx, "%s: max_depth must be finite and > 0", who); return PVLM_ERR_ARG; }
+  if (stats) *stats = pvlm_depthfill_stats{0, 0, 0, 0, 0.0, 0.0};
+  if (n_scans == 0) return PVLM_OK;
+  if (first_point[0] != 0) { PVLM_SET_ERR(ctx, "%s: first_point must start at 0", who); return PVLM_ERR_ARG; }
+  for (int s = 0; s < n_scans; ++s)
+    if (first_point[s + 1] < first_point[s]) { PVLM_SET_ERR(ctx, "%s: first_point is not ascending at scan %d", who, s); return PVLM_ERR_ARG; }
+  if (first_point[n_scans] > 0 && !xyz) { PVLM_SET_ERR(ctx, "%s: null argument", who); return PVLM_ERR_ARG; }
+  *run = 1;
+  return PVLM_OK;
+}
+
+bool set_usable(pvlm_ctx* ctx, const pvlm_depthset* set, const char* who) {
+  if (!set) { PVLM_SET_ERR(ctx, "%s: null set", who); return false; }
+  if (set->owner != ctx) { PVLM_SET_ERR(ctx, "%s: the set belongs to another context", who); return false; }
+  return true;
+}
+}  // namespace
+
+extern "C" pvlm_status pvlm_compute_depth_images(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl,
+                                                 unsigned size, float max_depth, uint16_t* depth_u16, pvlm_depthfill_stats* stats) {
+  const char* who = "pvlm_compute_depth_images";
+  int run = 0;
+  const pvlm_status st = depth_images_args(ctx, who, rows, cols, n_scans, first_point, xyz, T_cl, max_depth, depth_u16 != nullptr, stats, &run);
+  if (st || !run) return st;
+  return depth_images(ctx, who, rows, cols, n_scans, first_point, xyz, T_cl, size, max_depth, depth_u16, nullptr, stats);
+}
+
+// ---- pvlm_depthset: the maps stay where k_fill_c writes them ------------------------------------------------------------------------------------
+extern "C" pvlm_status pvlm_depthset_create(pvlm_ctx* ctx, int n_frames, pvlm_depthset** out) {
+  if (!ctx) return PVLM_ERR_ARG;
+  if (n_frames < 0 || !out) { PVLM_SET_ERR(ctx, "pvlm_depthset_create: n_frames or null argument"); return PVLM_ERR_ARG; }
+  pvlm_depthset* s = new pvlm_depthset();
+  s->owner = ctx; s->n_frames = n_frames;
+  s->rows.assign((size_t)n_frames, 0); s->cols.assign((size_t)n_frames, 0); s->d_map.assign((size_t)n_frames, nullptr); s->d_own.assign((size_t)n_frames, nullptr);
+  *out = s;
+  return PVLM_OK;
+}
+
+extern "C" void pvlm_depthset_destroy(pvlm_ctx* ctx, pvlm_depthset* set) {
+  if (!ctx || !set || set->owner != ctx) return;
+  for (unsigned short* p : set->d_own) pvlm_i_free(ctx, p);
+  pvlm_i_free(ctx, set->d_block);
+  delete set;
+}
+
+extern "C" pvlm_status pvlm_depthset_compute(pvlm_ctx* ctx, int rows, int cols, int n_scans, const long long* first_point, const float* xyz, const double* T_cl,
+                                             unsigned size, float max_depth, pvlm_depthset** out, pvlm_depthfill_stats* stats) {
+  const char* who = "pvlm_depthset_compute";
+  int run = 0;
+  pvlm_status st = depth_images_args(ctx, who, rows, cols, n_scans, first_point, xyz, T_cl, max_depth, out != nullptr, stats, &run);
+  if (st) return st;
+  if (!out) { PVLM_SET_ERR(ctx, "%s: null argument or size", who); return PVLM_ERR_ARG; }
+  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  pvlm_depthset* s = nullptr;
+  if ((st = pvlm_depthset_create(ctx, n_scans, &s))) return st;
+  if (run) {
+    const size_t npix = (size_t)rows * cols;
+    st = pvlm_i_alloc(ctx, &s->d_block, npix * (size_t)n_scans);           // the set's own block: it outlives the call, pvlm_depthset_destroy frees it
+    if (!st) st = depth_images(ctx, who, rows, cols, n_scans, first_point, xyz, T_cl, size, max_depth, nullptr, s->d_block, stats);
+    if (st) { pvlm_depthset_destroy(ctx, s); return st; }
+    for (int f = 0; f < n_scans; ++f) { s->rows[(size_t)f] = rows; s->cols[(size_t)f] = cols; s->d_map[(size_t)f] = s->d_block + npix * (size_t)f; }
+  }
+  *out = s;
+  return PVLM_OK;
+}
+
+extern "C" pvlm_status pvlm_depthset_upload(pvlm_ctx* ctx, pvlm_depthset* set, int frame, int rows, int cols, const uint16_t* depth_u16) {
+  const char* who = "pvlm_depthset_upload";
+  if (!ctx) return PVLM_ERR_ARG;
+  if (!set_usable(ctx, set, who)) return PVLM_ERR_ARG;
+  if (frame < 0 || frame >= set->n_frames || rows <= 0 || cols <= 0 || !depth_u16) { PVLM_SET_ERR(ctx, "%s: frame, size or null argument", who); return PVLM_ERR_ARG; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
+  const size_t npix = (size_t)rows * cols;
+  unsigned short* d = nullptr;
+  if ((c.st = pvlm_i_alloc(ctx, &d, npix))) return c.st;                    // the frame's own block: it outlives the call
+  c.h2d(d, depth_u16, npix * sizeof(unsigned short));
+  if (c.sync()) { pvlm_i_free(ctx, d); return c.st; }
+  pvlm_i_free(ctx, set->d_own[(size_t)frame]);                             // a map uploaded before (a map inside d_block stays with the block)
+  set->d_own[(size_t)frame] = d; set->d_map[(size_t)frame] = d; set->rows[(size_t)frame] = rows; set->cols[(size_t)frame] = cols;
+  return PVLM_OK;
+}
+
+extern "C" pvlm_status pvlm_depthset_info(const pvlm_depthset* set, int frame, int* rows, int* cols) {
+  if (!set || frame < 0 || frame >= set->n_frames || !rows || !cols) return PVLM_ERR_ARG;
+  *rows = set->d_map[(size_t)frame] ? set->rows[(size_t)frame] : 0;
+  *cols = set->d_map[(size_t)frame] ? set->cols[(size_t)frame] : 0;
+  return PVLM_OK;
+}
+
+extern "C" pvlm_status pvlm_depthset_read(pvlm_ctx* ctx, const pvlm_depthset* set, int frame, uint16_t* depth_u16) {
+  const char* who = "pvlm_depthset_read";
+  if (!ctx) return PVLM_ERR_ARG;
+  if (!set_usable(ctx, set, who)) return PVLM_ERR_ARG;
+  if (frame < 0 || frame >= set->n_frames || !depth_u16) { PVLM_SET_ERR(ctx, "%s: frame or null argument", who); return PVLM_ERR_ARG; }
+  if (!set->d_map[(size_t)frame]) { PVLM_SET_ERR(ctx, "%s: frame %d has no map", who, frame); return PVLM_ERR_ARG; }
+  pvlm_call c(ctx, who);
+  if (c.enter()) return c.st;
+  c.d2h(depth_u16, set->d_map[(size_t)frame], (size_t)set->rows[(size_t)frame] * (size_t)set->cols[(size_t)frame] * sizeof(unsigned short));
+  return c.sync();
 }
 
 // pvlm_preload: loads this file's code object at context set-up instead of at the first call (see pvlm_ba.hip)

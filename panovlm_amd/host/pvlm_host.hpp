@@ -707,7 +707,7 @@ DepthMaps ComputeDepthImage(const std::vector<Frame>& frames, const std::vector<
 DepthMaps ComputeDepthImageHost(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows, const int image_cols,
                                 const float max_depth, const bool half_size = true, const int num_threads = 16);
 // SfM::SetTranslationScaleDepthMap(eq, pair) (:487-603) operation by operation: the half-size test, round, IsInside, the 0.2 consistency test, two histogram passes
-// (the 1e-8 offset, the clamped bin index, the > 0.1 num_scale keep rule), the nth_element median fall-back.  It stays on the host on purpose.
+// (the 1e-8 offset, the clamped bin index, the > 0.1 num_scale keep rule), the nth_element median fall-back.  The host route: right for maps that exist only as files and are read once; maps made by K37 take the DeviceDepthMaps route below.
 bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DepthMaps& depth_maps, RelativePair& image_pair);
 // the list form (:605-679): the frames are visited from the one with the fewest pairs on, the pairs that touch a frame in list order; a pair without a scale stays
 // only when keep_no_scale.  Returns whether any pair is left.
@@ -724,6 +724,40 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
 bool FilterImagePairsFullHost(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
                               std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale,
                               const EssentialOptions& options = EssentialOptions(), const int num_threads = 16);
+
+// ---- K39: the depth maps kept on the device, the scales set there --------------------------------------------------------------------------------------------
+// The owner of a pvlm_depthset of the engine's context: the maps of all frames where K37 writes them (ComputeDepthImageResident) or where UploadDepthMaps puts
+// them.  Movable, not copyable.  Destroy it on the thread that owns the engine.
+class DeviceDepthMaps {
+ public:
+  DeviceDepthMaps() = default;
+  explicit DeviceDepthMaps(pvlm_depthset* set, size_t n_frames) : set_(set), n_frames_(n_frames) {}
+  ~DeviceDepthMaps();
+  DeviceDepthMaps(DeviceDepthMaps&& o) noexcept : set_(o.set_), n_frames_(o.n_frames_) { o.set_ = nullptr; o.n_frames_ = 0; }
+  DeviceDepthMaps& operator=(DeviceDepthMaps&& o) noexcept;
+  DeviceDepthMaps(const DeviceDepthMaps&) = delete;
+  DeviceDepthMaps& operator=(const DeviceDepthMaps&) = delete;
+  pvlm_depthset* set() const { return set_; }
+  size_t size() const { return n_frames_; }
+  // rows and cols of a frame's map; 0 x 0: the frame has none
+  std::pair<int, int> Info(size_t frame) const;
+ private:
+  pvlm_depthset* set_ = nullptr;
+  size_t n_frames_ = 0;
+};
+// ComputeDepthImage with the maps left on the device (pvlm_depthset_compute): nothing of them crosses to the host
+DeviceDepthMaps ComputeDepthImageResident(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows,
+                                          const int image_cols, const float max_depth, const bool half_size = true);
+// host maps (read from files) to the device, one allocation per frame; an empty vector stays an empty frame
+DeviceDepthMaps UploadDepthMaps(const DepthMaps& depth_maps);
+// one map back (what a caller needs to write upstream's depth file of the frame); an empty vector for an empty frame
+std::vector<uint16_t> ReadDepthMap(const DeviceDepthMaps& depth_maps, size_t frame, int* rows = nullptr, int* cols = nullptr);
+// the list form of SetTranslationScaleDepthMap on resident maps: ONE pvlm_set_translation_scales call (K39) on the distinct pairs of the list, then upstream's
+// visiting order (as above) with the call's results in place of the per-pair step.  The same list, bit for bit, as the DepthMaps overload gives on the same maps.
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DeviceDepthMaps& depth_maps, std::vector<RelativePair>& image_pairs, const bool keep_no_scale);
+// FilterImagePairsFull on resident maps: K34, K36, K39, then LargestBiconnectedGraph and the sort on the host
+bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DeviceDepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                          std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options = EssentialOptions());
 
 // ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------
 // base/common.h's FrameMatchMethod and sfm/VLAD.h's normalisation types

@@ -220,6 +220,31 @@ inline bool SetScaleList(int eq_rows, int eq_cols, const std::vector<int>& frame
   return pairs.size() > 0;
 }
 
+// SetScaleList's visiting order with the per-pair step as a parameter: step(pair) -> scaled.  What the resident route runs with the results of ONE
+// pvlm_set_translation_scales call in place of SetScaleOne (host/pvlm_host_sfm.cpp).
+template <class Step>
+inline bool SetScaleListWith(size_t n_frames, std::vector<TailPair>& pairs, bool keep_no_scale, Step&& step) {
+  const size_t nf = n_frames;
+  std::vector<size_t> ref_count(nf, 0);
+  for (const TailPair& p : pairs) { ref_count[p.image_pair.first]++; ref_count[p.image_pair.second]++; }
+  const size_t start = nf ? (size_t)(std::min_element(ref_count.begin(), ref_count.end()) - ref_count.begin()) : 0;
+  std::vector<size_t> order;
+  for (size_t i = start; i < nf; ++i) order.push_back(i);
+  for (size_t i = 0; i < start; ++i) order.push_back(i);
+  std::vector<TailPair> good;
+  std::set<std::pair<size_t, size_t>> processed;
+  for (size_t idx1 : order)
+    for (TailPair& p : pairs) {
+      if (processed.count(p.image_pair) > 0) continue;
+      if (p.image_pair.first != idx1 && p.image_pair.second != idx1) continue;
+      const bool valid = step(p) || keep_no_scale;
+      processed.insert(p.image_pair);
+      if (valid) good.push_back(p);
+    }
+  good.swap(pairs);
+  return pairs.size() > 0;
+}
+
 // PoseGraph::KeepLargestEdgeBiconnected (sfm/PoseGraph.cpp:63-133) without lemon: the distinct (first, second) pairs are the edges (as SfM::LargestBiconnectedGraph
 // builds its std::set; (a, b) and (b, a) are two parallel edges), the bridges are found by one depth-first search and removed, and of the connected components that
 // remain (single nodes included) the one with the most nodes is returned.  Deliberate divergence: among components of equal size the one that holds the lowest frame

@@ -691,7 +691,7 @@ namespace {
 struct DepthImageCall {
   int rows, cols;
   std::vector<long long> first; std::vector<float> xyz; std::vector<uint16_t> out;
-  DepthImageCall(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, int image_rows, int image_cols, float max_depth, bool half_size) {
+  DepthImageCall(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, int image_rows, int image_cols, float max_depth, bool half_size, bool host_maps = true) {
     if (clouds.size() != frames.size()) throw std::invalid_argument("ComputeDepthImage: lidars.size() != frames.size()");
     if (image_rows <= 0 || image_cols <= 0 || !std::isfinite(max_depth) || !(max_depth > 0.f)) throw std::invalid_argument("ComputeDepthImage: image size or max_depth");
     rows = half_size ? (image_rows + 1) / 2 : image_rows; cols = half_size ? (image_cols + 1) / 2 : image_cols;
@@ -701,7 +701,7 @@ struct DepthImageCall {
       first.push_back((long long)(xyz.size() / 3));
     }
     xyz.resize(xyz.size() + 3);                                                // never empty
-    out.resize(clouds.size() * (size_t)rows * (size_t)cols + 1);
+    if (host_maps) out.resize(clouds.size() * (size_t)rows * (size_t)cols + 1);
   }
   DepthMaps Maps() const {
     DepthMaps d;
@@ -728,6 +728,110 @@ DepthMaps ComputeDepthImageHost(const std::vector<Frame>& frames, const std::vec
   pvlm_depthfill::depth_images_host(call.rows, call.cols, (int)clouds.size(), call.first.data(), call.xyz.data(), T_cl.data(), 4u, max_depth, call.out.data(),
                                     (size_t)std::max(num_threads, 1));
   return call.Maps();
+}
+
+// ================================================================================================
+// K39: resident depth maps, SetTranslationScaleDepthMap on the device
+// ================================================================================================
+DeviceDepthMaps::~DeviceDepthMaps() { if (set_) pvlm_depthset_destroy(Engine::Default().ctx(), set_); }
+DeviceDepthMaps& DeviceDepthMaps::operator=(DeviceDepthMaps&& o) noexcept {
+  if (this != &o) { if (set_) pvlm_depthset_destroy(Engine::Default().ctx(), set_); set_ = o.set_; n_frames_ = o.n_frames_; o.set_ = nullptr; o.n_frames_ = 0; }
+  return *this;
+}
+std::pair<int, int> DeviceDepthMaps::Info(size_t frame) const {
+  int r = 0, c = 0;
+  if (!set_ || frame >= n_frames_ || pvlm_depthset_info(set_, (int)frame, &r, &c) != PVLM_OK) throw std::invalid_argument("DeviceDepthMaps: frame " + std::to_string(frame) + " is not there");
+  return {r, c};
+}
+
+DeviceDepthMaps ComputeDepthImageResident(const std::vector<Frame>& frames, const std::vector<PointCloud>& clouds, const Matrix4d& T_cl, const int image_rows,
+                                          const int image_cols, const float max_depth, const bool half_size) {
+  StageTimer stage_timer_("ComputeDepthImageResident");
+  DepthImageCall call(frames, clouds, image_rows, image_cols, max_depth, half_size, false);
+  Engine& e = Engine::Default();
+  pvlm_depthset* set = nullptr;
+  e.Check(pvlm_depthset_compute(e.ctx(), call.rows, call.cols, (int)clouds.size(), call.first.data(), call.xyz.data(), T_cl.data(), 4u, max_depth, &set, nullptr),
+          "pvlm_depthset_compute");
+  return DeviceDepthMaps(set, clouds.size());
+}
+
+DeviceDepthMaps UploadDepthMaps(const DepthMaps& d) {
+  Engine& e = Engine::Default();
+  pvlm_depthset* set = nullptr;
+  e.Check(pvlm_depthset_create(e.ctx(), (int)d.maps.size(), &set), "pvlm_depthset_create");
+  DeviceDepthMaps out(set, d.maps.size());
+  for (size_t f = 0; f < d.maps.size(); ++f) {
+    if (d.maps[f].empty()) continue;
+    if (f >= d.rows.size() || f >= d.cols.size() || d.rows[f] <= 0 || d.cols[f] <= 0 || d.maps[f].size() != (size_t)d.rows[f] * (size_t)d.cols[f])
+      throw std::invalid_argument("DepthMaps: map " + std::to_string(f) + " is not rows x cols");
+    e.Check(pvlm_depthset_upload(e.ctx(), set, (int)f, d.rows[f], d.cols[f], d.maps[f].data()), "pvlm_depthset_upload");
+  }
+  return out;
+}
+
+std::vector<uint16_t> ReadDepthMap(const DeviceDepthMaps& depth_maps, size_t frame, int* rows, int* cols) {
+  const std::pair<int, int> rc = depth_maps.Info(frame);
+  if (rows) *rows = rc.first;
+  if (cols) *cols = rc.second;
+  std::vector<uint16_t> out((size_t)rc.first * (size_t)rc.second);
+  if (out.empty()) return out;
+  Engine& e = Engine::Default();
+  e.Check(pvlm_depthset_read(e.ctx(), depth_maps.set(), (int)frame, out.data()), "pvlm_depthset_read");
+  return out;
+}
+
+bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DeviceDepthMaps& depth_maps, std::vector<RelativePair>& image_pairs, const bool keep_no_scale) {
+  StageTimer stage_timer_("SetTranslationScale");
+  if (!depth_maps.set() || depth_maps.size() < frames.size()) throw std::invalid_argument("SetTranslationScaleDepthMap: the depth set holds fewer frames than the list");
+  std::vector<relpose_detail::TailPair> tail;
+  // the arrays of ONE call over the distinct pairs: the first of equal image_pairs is the one upstream's order reaches
+  std::map<std::pair<size_t, size_t>, size_t> slot_of;
+  std::vector<size_t> slot(image_pairs.size(), (size_t)-1);
+  std::vector<int> src, tgt, pwd; std::vector<long long> off{0}; std::vector<double> R, t, tri, up, lo;
+  for (size_t p = 0; p < image_pairs.size(); ++p) {
+    const RelativePair& rp = image_pairs[p];
+    if (rp.image_pair.first >= frames.size() || rp.image_pair.second >= frames.size()) throw std::invalid_argument("SetTranslationScaleDepthMap: a pair names a frame that is not there");
+    tail.push_back(ToTail(rp, p));
+    if (!slot_of.emplace(rp.image_pair, src.size()).second) continue;
+    slot[p] = src.size();
+    src.push_back((int)rp.image_pair.first); tgt.push_back((int)rp.image_pair.second);
+    const relpose_detail::TailPair& tp = tail.back();
+    R.insert(R.end(), tp.R, tp.R + 9); t.insert(t.end(), tp.t, tp.t + 3); tri.insert(tri.end(), tp.tri.begin(), tp.tri.end());
+    off.push_back((long long)(tri.size() / 3));
+    pwd.push_back(tp.points_with_depth); up.push_back(tp.upper_scale); lo.push_back(tp.lower_scale);
+  }
+  std::vector<int> frame_rows((size_t)depth_maps.size(), 0);
+  for (size_t f = 0; f < frames.size(); ++f) frame_rows[f] = frames[f].GetImageRows();
+  const size_t n = src.size();
+  std::vector<unsigned char> ok(n + 1, 0);
+  R.resize(R.size() + 9); t.resize(t.size() + 3); tri.resize(tri.size() + 3); pwd.push_back(0); up.push_back(0); lo.push_back(0); src.push_back(0); tgt.push_back(0);   // never empty
+  if (n > 0) {
+    Engine& e = Engine::Default();
+    e.Check(pvlm_set_translation_scales(e.ctx(), depth_maps.set(), frames[0].GetImageRows(), frames[0].GetImageCols(), frame_rows.data(), (int)n, src.data(), tgt.data(),
+                                        off.data(), R.data(), t.data(), tri.data(), ok.data(), pwd.data(), up.data(), lo.data(), nullptr),
+            "pvlm_set_translation_scales");
+  }
+  const bool any = relpose_detail::SetScaleListWith(frames.size(), tail, keep_no_scale, [&](relpose_detail::TailPair& tp) {
+    const size_t k = slot[tp.tag];                       // the first of its image_pair: the only one the order reaches
+    std::copy(t.begin() + 3 * (std::ptrdiff_t)k, t.begin() + 3 * (std::ptrdiff_t)k + 3, tp.t);
+    std::copy(tri.begin() + 3 * (std::ptrdiff_t)off[k], tri.begin() + 3 * (std::ptrdiff_t)off[k + 1], tp.tri.begin());
+    tp.points_with_depth = pwd[k]; tp.upper_scale = up[k]; tp.lower_scale = lo[k];
+    return ok[k] != 0;
+  });
+  std::vector<RelativePair> out;
+  for (const relpose_detail::TailPair& tp : tail) { out.push_back(image_pairs[tp.tag]); FromTail(tp, out.back()); }
+  image_pairs.swap(out);
+  return any;
+}
+
+bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DeviceDepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
+                          std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options) {
+  if (!FilterImagePairs(frames, image_pairs, good_pair, triangulation_num_threshold, options)) return false;
+  if (!RefineRelativePoses(frames, good_pair, PIXEL_RESIDUAL, nullptr)) return false;
+  SetTranslationScaleDepthMap(frames, depth_maps, good_pair, keep_no_scale);
+  good_pair = LargestBiconnectedGraph(good_pair, covered_frames);
+  relpose_detail::SortAsWritten(good_pair, [](const RelativePair& a, const RelativePair& b) { return relpose_detail::PairLessAsWritten(a.image_pair, b.image_pair); });
+  return true;
 }
 
 }  // namespace pvlm
