@@ -135,6 +135,15 @@ pvlm_status pvlm_resset_info(const pvlm_resset* rs, int64_t* n, int* n_pairs, in
  * (pvlm_eval_pair_blocks*, pvlm_neq_accumulate*) then reads instead of the four plane columns.  *in_use: 1 when the set was given the table
  * (by its mean run length, or PVLM_PLANE_RUNS=0/1); *runs: the runs counted (0 when the set was never counted).  Results do not depend on it. */
 pvlm_status pvlm_resset_plane_runs(const pvlm_resset* rs, int* in_use, int64_t* runs);
+/* Point-to-plane sets made by pvlm_assoc_point2plane that took the plane-run table in the block form, with at most 65 536 queries per neighbour scan: the
+ * fused evaluation reads a row's point (columns 0..2) from ONE table per distinct neighbour scan of the call, through the row's 16-bit query number, and
+ * visits its work list in an order that brings the readers of a table slice together (PVLM_POINT_TABLE=0/1, PVLM_DISPATCH_ORDER=0/1).  The tables are a snapshot
+ * owned by the set.  *in_use: 1 when the set has the form; *tables: its tables; *positions: the grid of the fused kernel (work-list entries + padding;
+ * the number of work-list entries when the order is the identity).  Results do not depend on any of it. */
+pvlm_status pvlm_resset_point_table(const pvlm_resset* rs, int* in_use, int* tables, int* positions);
+/* Debug read of that form, shaped like pvlm_assoc_point2plane_debug: per residual block in compact order the stored query number (qnum, n entries) and the
+ * entry of its neighbour's table under that number (points, n x 3 doubles).  Either may be NULL.  PVLM_ERR_STATE when the set does not have the form. */
+pvlm_status pvlm_resset_point_table_debug(pvlm_ctx* ctx, const pvlm_resset* rs, uint16_t* qnum, double* points);
 /* Copies the segment table / rows back (rows in the upload layout); any pointer may be NULL. */
 pvlm_status pvlm_resset_download(pvlm_ctx* ctx, const pvlm_resset* rs, int64_t* pair_offsets, int* pair_ref,
                                  int* pair_nei, double* rows);

@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "pvlm_descset_create", "pvlm_descset_destroy", "pvlm_match_knn2", "pvlm_match_pairs",
     "pvlm_essential_acransac", "pvlm_filter_image_pairs",
     "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
-    "pvlm_resset_plane_runs",
+    "pvlm_resset_plane_runs", "pvlm_resset_point_table", "pvlm_resset_point_table_debug",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
@@ -752,6 +752,19 @@ class ResidualSet:
         u, r = C.c_int(0), C.c_int64(0)
         self.ctx._check(self.ctx.lib.pvlm_resset_plane_runs(self._h, C.byref(u), C.byref(r)), "pvlm_resset_plane_runs")
         return dict(in_use=bool(u.value), runs=int(r.value))
+
+    def point_table(self):
+        """Sets of the association: whether the fused evaluation reads the point from the per-neighbour table, the tables, and the fused kernel's grid."""
+        u, t, g = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.ctx._check(self.ctx.lib.pvlm_resset_point_table(self._h, C.byref(u), C.byref(t), C.byref(g)), "pvlm_resset_point_table")
+        return dict(in_use=bool(u.value), tables=int(t.value), positions=int(g.value))
+
+    def point_table_debug(self):
+        """Per residual block (compact order): the stored 16-bit query number and the table entry (3 doubles) it names."""
+        q = np.empty(max(self.n, 1), np.uint16); pts = np.empty((max(self.n, 1), 3), np.float64)
+        self.ctx._check(self.ctx.lib.pvlm_resset_point_table_debug(self.ctx._h, self._h, _p(q, C.c_uint16), _p(pts, C.c_double)),
+                        "pvlm_resset_point_table_debug")
+        return q[:self.n], pts[:self.n]
 
     def set_pose_ids(self, pair_ref, pair_nei):
         """Renumbers the segments' poses (one pose table for every set of a problem)."""

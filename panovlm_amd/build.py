@@ -121,6 +121,7 @@ RELPOSE_DRIVER = os.path.join(HERE, "build", "pvlm_relpose_driver")
 DEPTHFILL_DRIVER = os.path.join(HERE, "build", "pvlm_depthfill_driver")
 DEPTHFILL_CHECK = os.path.join(HERE, "build", "depthfill_core_check")
 SCALE_DRIVER = os.path.join(HERE, "build", "pvlm_scale_driver")
+DISPATCH_ORDER_CHECK = os.path.join(HERE, "build", "dispatch_order_check")
 
 
 def build_host(force=False):
@@ -214,6 +215,12 @@ def build_host(force=False):
     if os.path.exists(dchk) and (force or not os.path.exists(DEPTHFILL_CHECK) or
                                  os.path.getmtime(DEPTHFILL_CHECK) < max(os.path.getmtime(dchk), os.path.getmtime(core))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", "-DDEPTHFILL_CHECK_MAIN", dchk, "-o", DEPTHFILL_CHECK])
+    # the stand-alone check of the dispatch order of the fused kernel on a point table (csrc/pvlm_dispatch_core.h; no device; its own main)
+    ochk = os.path.join(HERE, "..", "tests", "cpp", "dispatch_order_driver.cpp")
+    ocore = os.path.join(HERE, "csrc", "pvlm_dispatch_core.h")
+    if os.path.exists(ochk) and (force or not os.path.exists(DISPATCH_ORDER_CHECK) or
+                                 os.path.getmtime(DISPATCH_ORDER_CHECK) < max(os.path.getmtime(ochk), os.path.getmtime(ocore))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-DDISPATCH_ORDER_MAIN", ochk, "-o", DISPATCH_ORDER_CHECK])
     # the scale driver (ComputeDepthImage + FilterImagePairsFull against ComputeDepthImageResident + the resident overload: K39)
     cdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_scale_driver.cpp")
     if os.path.exists(cdrv) and (force or not os.path.exists(SCALE_DRIVER) or

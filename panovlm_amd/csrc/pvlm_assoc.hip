@@ -16,6 +16,7 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <unordered_map>
 
 #include "pvlm_internal.h"
 #include "pvlm_workers.h"
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PVLM_K2_WAV
 template <bool EXACT, int SUB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXACT ? PVLM_K3_WAVES : PVLM_K3F_WAVES, 8))) void k_fit_pairs(const PairDesc* __restrict__ pairs, double plane_tol, const int* __restrict__ nn_tmp, long long tmp_rows,
                                                    double* __restrict__ cols, long long n_dev, unsigned long long* __restrict__ chain, int* __restrict__ pair_count,
-                                                   int* __restrict__ ticket, int* __restrict__ qidx_out, int* __restrict__ nn_out, int chunks_x, int total) {
+                                                   int* __restrict__ ticket, int* __restrict__ qidx_out, int* __restrict__ nn_out, uint16_t* __restrict__ q16_out, int chunks_x, int total) {
   constexpr int PVLM_K3_CHUNK = 256 * SUB;
   static_assert(SUB == 1 || SUB == 2, "the sub-chunk loop below keeps its per-pass results in slots 0 and SUB - 1");
   __shared__ int s_vid, s_vid2;
@@ -348,6 +349,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXACT ? PVL
         for (int c = 0; c < 3; ++c) cols[(size_t)c * n_dev + d] = pl[c];
 #pragma unroll
         for (int c = 0; c < 4; ++c) cols[(size_t)(3 + c) * n_dev + d] = s_rec[prev_buf][u][c][threadIdx.x];
+        if (q16_out) q16_out[d] = (uint16_t)q;     // the row's query number for the point table (pvlm_resset::point_table): asked for only when every nq <= 65 536
         if (qidx_out) {
           qidx_out[d] = q;
 #pragma unroll
@@ -498,6 +500,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXACT ? PVL
 // A sparse column block made dense: the accepted rows of every pair copied into a block that holds only them (segment p: rows [dst[p], dst[p] + count[p])).
 // With raw scans as targets 94 % of the queries are rejected: the block of a batch reserves a row per QUERY (the ordered placement needs no sizing round trip)
 // and would keep sixteen times the memory it uses for as long as the residual set lives.
+// The point table of a residual set (pvlm_resset::point_table): for every distinct neighbour scan of the call, the local point of each of its queries — what
+// `place` writes into columns 0..2 of a row, through the same world2local on the same R_wl / t_wl and float cloud (this file is compiled without contraction:
+// the same bits).  Three columns of PVLM_POINT_TAB_STRIDE doubles per neighbour; entries behind nq are never read.
+struct PointTabDesc { const float* q_xyz; int nq; int pad; double Rn[9], tn[3]; };
+__global__ __launch_bounds__(256) void k_point_table(const PointTabDesc* __restrict__ descs, double* __restrict__ tab) {
+  const PointTabDesc& d = descs[blockIdx.y];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= d.nq) return;
+  double pl[3];
+  world2local(d.Rn, d.tn, (double)d.q_xyz[3 * q], (double)d.q_xyz[3 * q + 1], (double)d.q_xyz[3 * q + 2], pl);
+  double* t = tab + (size_t)blockIdx.y * 3 * PVLM_POINT_TAB_STRIDE;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) t[(size_t)c * PVLM_POINT_TAB_STRIDE + q] = pl[c];
+}
+
 struct CompactSeg { long long src, dst; int count, pad; };
 __global__ __launch_bounds__(256) void k_compact_block(const CompactSeg* __restrict__ segs, const double* __restrict__ src, long long src_rows, double* __restrict__ dst, long long dst_rows) {
   const CompactSeg sg = segs[blockIdx.y];
@@ -1243,6 +1260,43 @@ pvlm_status pvlm_knn(pvlm_ctx* ctx, const pvlm_scan* scan, int which, const floa
   return st;
 }
 
+}  // extern "C"
+// One table per distinct neighbour handle of the call (rs->d_point_tab, rs->h_pair_tab), queued behind the batches.  No memory: the set goes on without
+// (rs->d_point_tab stays null), which is not an error.
+static pvlm_status build_point_tables(pvlm_ctx* ctx, pvlm_resset* rs, int n_pairs, pvlm_scan* const* nei) {
+  std::vector<PointTabDesc> td;
+  std::unordered_map<const pvlm_scan*, int> seen;
+  rs->h_pair_tab.assign((size_t)n_pairs, 0);
+  for (int p = 0; p < n_pairs; ++p) {
+    auto it = seen.find(nei[p]);
+    if (it == seen.end()) {
+      it = seen.emplace(nei[p], (int)td.size()).first;
+      PointTabDesc d;
+      d.q_xyz = nei[p]->flat.d_xyz; d.nq = nei[p]->flat.n; d.pad = 0;
+      std::memcpy(d.Rn, nei[p]->R_wl, 72); std::memcpy(d.tn, nei[p]->t_wl, 24);
+      td.push_back(d);
+    }
+    rs->h_pair_tab[(size_t)p] = it->second;
+  }
+  const std::string kept_err = ctx->err;
+  PointTabDesc* d_td = nullptr;
+  if (pvlm_i_alloc(ctx, &rs->d_point_tab, td.size() * 3 * (size_t)PVLM_POINT_TAB_STRIDE) || pvlm_i_alloc(ctx, &d_td, td.size())) {
+    pvlm_i_free(ctx, rs->d_point_tab); rs->d_point_tab = nullptr; pvlm_i_free(ctx, d_td);
+    ctx->err = kept_err;
+    return PVLM_OK;
+  }
+  rs->n_point_tabs = (int)td.size();
+  pvlm_status st = pvlm_i_h2d_q(ctx, d_td, td.data(), td.size() * sizeof(PointTabDesc));
+  for (size_t t0 = 0; t0 < td.size() && !st; t0 += 32768) {
+    const unsigned ny = (unsigned)std::min<size_t>(32768, td.size() - t0);
+    hipLaunchKernelGGL(k_point_table, dim3(PVLM_POINT_TAB_STRIDE / 256, ny), dim3(256), 0, ctx->stream, (const PointTabDesc*)d_td + t0,
+                       rs->d_point_tab + t0 * 3 * (size_t)PVLM_POINT_TAB_STRIDE);
+    if (hipGetLastError() != hipSuccess) st = PVLM_ERR_HIP;
+  }
+  pvlm_i_free(ctx, d_td);                        // stream-ordered: reused only by work queued behind the kernel
+  return st;
+}
+extern "C" {
 // The call is a two-slot software pipeline over batches of pairs (<= PVLM_ASSOC_BATCH_ROWS query rows, 16 M by
 // default = 1.6 GB of scratch per slot, whatever the size of the pair list):
 //   issue(b):  K2 + K3 of batch b into slot b & 1, accept counts -> pinned host memory, event
@@ -1273,6 +1327,11 @@ pvlm_status pvlm_assoc_point2plane(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const*
   rs->h_seg_start.assign(n_pairs + 1, 0);
   rs->h_pair_block.assign(n_pairs, 0);
 
+  // the point table (pvlm_resset::point_table): K3 leaves the 16-bit query number of every row, one table per distinct neighbour is built behind the last batch.
+  // Whether the evaluation uses them is decided when the set is finalised; PVLM_POINT_TABLE=0 does not even make them.
+  bool want_pt = n_pairs > 0;
+  if (const char* env = getenv("PVLM_POINT_TABLE")) want_pt = want_pt && atoi(env) != 0;
+  for (int p = 0; p < n_pairs && want_pt; ++p) if (nei[p]->flat.n > PVLM_POINT_TAB_STRIDE) want_pt = false;
   std::vector<PairDesc> descs(n_pairs);
   for (int p = 0; p < n_pairs; ++p) {
     PairDesc& d = descs[p];
@@ -1339,6 +1398,11 @@ pvlm_status pvlm_assoc_point2plane(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const*
       if ((sa = pvlm_i_alloc(ctx, &d_n, (size_t)R * 10))) return sa;
       rs->d_nn.push_back(d_n);
     }
+    uint16_t* d_q16 = nullptr;
+    if (want_pt) {
+      if (pvlm_i_alloc(ctx, &d_q16, (size_t)R)) { want_pt = false; d_q16 = nullptr; ctx->err.clear(); }      // no memory: the set keeps the three columns as its only form
+      else { rs->d_q16.resize(rs->col_blocks.size(), nullptr); rs->d_q16.back() = d_q16; }
+    }
     std::memcpy(ws.h_desc[s], &descs[b.p0], (size_t)nb * sizeof(PairDesc));
     PVLM_HIP(ctx, hipMemcpyAsync(ws.d_desc[s], ws.h_desc[s], (size_t)nb * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
     const PairDesc* d_desc = static_cast<const PairDesc*>(ws.d_desc[s]);
@@ -1359,10 +1423,10 @@ pvlm_status pvlm_assoc_point2plane(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const*
       static const int k3f_blocks = [] { const char* e = getenv("PVLM_K3F_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 256 * PVLM_K3F_WAVES; }();   // the fast kernel: PVLM_K3F_WAVES workgroups per CU
       if (batch_exact)
         hipLaunchKernelGGL((k_fit_pairs<true, PVLM_K3_SUB>), dim3((unsigned)std::min<long long>(total, k3_blocks)), dim3(256), 0, ctx->stream, d_desc, plane_tolerance, ws.d_nn[s], ws.rows, d_block, R, d_chain,
-                           d_count, d_ticket, d_q, d_n, chunks_x, (int)total);
+                           d_count, d_ticket, d_q, d_n, d_q16, chunks_x, (int)total);
       else
         hipLaunchKernelGGL((k_fit_pairs<false, PVLM_K3F_SUB>), dim3((unsigned)std::min<long long>(total, k3f_blocks)), dim3(256), 0, ctx->stream, d_desc, plane_tolerance, ws.d_nn[s], ws.rows, d_block, R, d_chain,
-                           d_count, d_ticket, d_q, d_n, chunks_x, (int)total);
+                           d_count, d_ticket, d_q, d_n, d_q16, chunks_x, (int)total);
       PVLM_HIP(ctx, hipGetLastError());
     }
     PVLM_HIP(ctx, hipMemcpyAsync(ws.h_count[s], d_count, ((size_t)nb + 2) * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));   // per-pair totals, the ticket, the exact fits
@@ -1405,6 +1469,7 @@ pvlm_status pvlm_assoc_point2plane(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const*
       PVLM_HIP(ctx, hipGetLastError());
       pvlm_i_free(ctx, rs->col_blocks[(size_t)bi]); pvlm_i_free(ctx, d_segs);     // stream-ordered: reused only by work queued after the copy
       rs->col_blocks[(size_t)bi] = d_new; rs->block_rows[(size_t)bi] = R2; rs->n_dev += R2 - R;
+      want_pt = false;                               // the query numbers are not carried through the copy: such a set keeps today's form
     }
     return PVLM_OK;
   };
@@ -1420,6 +1485,8 @@ pvlm_status pvlm_assoc_point2plane(pvlm_ctx* ctx, int n_pairs, pvlm_scan* const*
   }
   if (!st && finished < B) st = finish(B - 1);
   rs->assoc_exact_kernel_batches = batch_exact && !exact_fit ? B - 1 : (exact_fit ? B : 0);
+  if (!st && want_pt) st = build_point_tables(ctx, rs, n_pairs, nei);
+  if (!want_pt || st) { for (uint16_t* b : rs->d_q16) pvlm_i_free(ctx, b); rs->d_q16.clear(); }
   if (!st) {
     rs->n = rs->h_out_start[n_pairs];
     st = pvlm_i_resset_finalize(ctx, rs);   // uploads the segment table + work list; the call's one full synchronisation

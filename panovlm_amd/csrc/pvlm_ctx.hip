@@ -607,6 +607,43 @@ pvlm_status pvlm_resset_plane_runs(const pvlm_resset* rs, int* in_use, int64_t* 
   return PVLM_OK;
 }
 
+pvlm_status pvlm_resset_point_table(const pvlm_resset* rs, int* in_use, int* tables, int* positions) {
+  if (!rs) return PVLM_ERR_ARG;
+  if (in_use) *in_use = rs->point_table ? 1 : 0;
+  if (tables) *tables = rs->point_table ? rs->n_point_tabs : 0;
+  if (positions) *positions = rs->point_table ? rs->n_positions : rs->n_blocks;
+  return PVLM_OK;
+}
+
+pvlm_status pvlm_resset_point_table_debug(pvlm_ctx* ctx, const pvlm_resset* rs, uint16_t* qnum, double* points) {
+  if (!ctx || !rs) return PVLM_ERR_ARG;
+  if (!rs->point_table) { PVLM_SET_ERR(ctx, "the set does not read its points from a table (pvlm_resset_point_table)"); return PVLM_ERR_STATE; }
+  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
+  pvlm_status st = PVLM_OK;
+  std::vector<uint16_t> words;
+  std::vector<double> tab((size_t)3 * PVLM_POINT_TAB_STRIDE);
+  int have = -1;
+  int64_t idx0 = 0;                                  // first row of the pair in d_plane_idx (pvlm_i_plane_runs_build: padded segments in pair order)
+  for (int p = 0; p < rs->n_pairs && !st; ++p) {
+    const int64_t o = rs->h_out_start[(size_t)p], m = rs->h_out_start[(size_t)p + 1] - o, padded = pvlm_i_seg_rows(m);
+    if (m > 0) {
+      words.resize((size_t)padded * 2);
+      st = pvlm_i_d2h(ctx, words.data(), rs->d_plane_idx + 2 * idx0, words.size() * sizeof(uint16_t));
+      if (!st && points && have != rs->h_pair_tab[(size_t)p]) {
+        have = rs->h_pair_tab[(size_t)p];
+        st = pvlm_i_d2h(ctx, tab.data(), rs->d_point_tab + (size_t)have * 3 * PVLM_POINT_TAB_STRIDE, tab.size() * sizeof(double));
+      }
+      for (int64_t j = 0; j < m && !st; ++j) {
+        const uint16_t q = words[(size_t)(4 * (j >> 1) + 2 + (j & 1))];
+        if (qnum) qnum[o + j] = q;
+        if (points) for (int c = 0; c < 3; ++c) points[(o + j) * 3 + c] = tab[(size_t)c * PVLM_POINT_TAB_STRIDE + q];
+      }
+    }
+    idx0 += padded;
+  }
+  return st;
+}
+
 }  // extern "C"
 
 pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs) {
@@ -620,6 +657,8 @@ pvlm_status pvlm_i_resset_free(pvlm_ctx* ctx, pvlm_resset* rs) {
   pvlm_i_free(ctx, rs->d_nei); pvlm_i_free(ctx, rs->d_blk_pair); pvlm_i_free(ctx, rs->d_blk_chunk); pvlm_i_free(ctx, rs->d_pair_blk_start);
   pvlm_i_free(ctx, rs->d_pair_tab); pvlm_i_free(ctx, rs->d_partials); pvlm_i_free(ctx, rs->d_pair_blocks); pvlm_i_free(ctx, rs->d_stage);
   pvlm_i_free(ctx, rs->d_plane_idx); pvlm_i_free(ctx, rs->d_plane_tab); pvlm_i_free(ctx, rs->d_chunk_plane0); pvlm_i_free(ctx, rs->d_pair_idx0);
+  for (uint16_t* b : rs->d_q16) pvlm_i_free(ctx, b);
+  pvlm_i_free(ctx, rs->d_point_tab); pvlm_i_free(ctx, rs->d_pair_ptab); pvlm_i_free(ctx, rs->d_order);
   delete rs;
   return PVLM_OK;
 }

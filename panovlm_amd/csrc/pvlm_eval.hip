@@ -7,6 +7,7 @@
 // are read through wave-uniform (scalar) loads.  Algorithmic HBM traffic per evaluation in fused
 // mode = 8*ncols bytes; materialise mode adds 8 + 96 B of stores.  Point-to-plane (7 columns, 56 B): a set whose planes repeat from row to row is read as
 // 24 B of point + a 2-byte run number per row + one 32-byte table entry per run of equal planes (pvlm_plane_args below): 26 + 32 / L bytes at mean run length L.
+// A set of the association on that form takes the point itself from one table per neighbour scan through a 2-byte query number (pvlm_resset::point_table).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -55,6 +56,9 @@ struct pvlm_plane_args {
   const int64_t* pair_idx0;
   const int64_t* chunk_plane0;   // per work-list entry: first table entry of the chunk
   const double* tab;             // {a, b, c, d} per run
+  // the point table (pvlm_resset::point_table, k_eval_fused<..., PT = true> only): idx then holds four words per PAIR of rows {run, run, query, query}
+  const double* const* pair_ptab;   // per pair: the table of its neighbour scan, 3 columns of PVLM_POINT_TAB_STRIDE doubles
+  const int* order;                 // grid position -> work-list slot, -1 = padding; nullptr = identity (pvlm_dispatch_core.h)
 };
 template <bool NT>
 __device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`: low and high half
@@ -65,6 +69,29 @@ __device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsig
 #endif
   ptr q = (ptr)(reinterpret_cast<const char*>(base) + 2u * row);
   return NT ? __builtin_nontemporal_load(q) : *q;
+}
+// The point-table form: the run numbers and the query numbers of the lane's two rows in ONE 8-byte load (x: runs, y: queries; low half = the even row), streamed
+// like the run word; and a point coordinate out of the neighbour's table — an ordinary load: the table is read by every pair of the neighbour and is meant to
+// stay in the cache.
+template <bool NT>
+__device__ __forceinline__ uint2 stream_load_words(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`
+  typedef unsigned pvlm_u2 __attribute__((ext_vector_type(2)));
+#if PVLM_GLOBAL_LOADS
+  typedef const __attribute__((address_space(1))) pvlm_u2* ptr;
+#else
+  typedef const pvlm_u2* ptr;
+#endif
+  ptr q = (ptr)(reinterpret_cast<const char*>(base) + 4u * row);
+  const pvlm_u2 v = NT ? __builtin_nontemporal_load(q) : *q;
+  return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ double table_load(const double* base, unsigned bytes) {
+#if PVLM_GLOBAL_LOADS
+  typedef const __attribute__((address_space(1))) double* ptr;
+#else
+  typedef const double* ptr;
+#endif
+  return *(ptr)(reinterpret_cast<const char*>(base) + bytes);
 }
 // ... and the stores of the materialising kernels (r, the 1 x 12 rows, the wrench rows).  Non-temporal STORES were measured and lose:
 // k_eval_materialise 4.80 TB/s against 5.04 TB/s with ordinary stores (profiles/r2_ab_eval_loads.txt) — off.
@@ -374,7 +401,7 @@ __device__ __forceinline__ double wave_transpose_sum(const double (&a)[N], int l
   return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
+template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR, bool PT>
 __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUSED_WAVES)) void k_eval_fused(const double* const* __restrict__ pair_cols,
                                                     const int64_t* __restrict__ pair_stride,
                                                     const int64_t* __restrict__ out_start,
@@ -382,12 +409,16 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
                                                     int chunk_rows, const double* __restrict__ pair_tab, double weight,
                                                     double loss_a, double* __restrict__ partials, pvlm_plane_args pr) {
   static_assert(!PR || NCOLS == 7, "plane runs: the 7-column kinds only");
+  static_assert(!PT || PR, "the point table: on top of the plane runs only");
+  // PT: the grid visits the work list in the order of pr.order (slots that read the same table slice together on one XCD); everything below is per SLOT
+  const int slot = (PT && pr.order) ? pr.order[blockIdx.x] : (int)blockIdx.x;
+  if (PT && slot < 0) return;     // padding position
   constexpr int NS = PR ? 3 : NCOLS;                // columns streamed row by row (PR: the point; the plane comes from the run table)
-  const int p = blk_pair[blockIdx.x];
+  const int p = blk_pair[slot];
   const double* __restrict__ cols = pair_cols[p];   // first row of the pair's segment, column 0
   const int64_t n_dev = pair_stride[p];             // column stride of the pair's block
   const int64_t len = out_start[p + 1] - out_start[p];
-  const int64_t lo = (int64_t)blk_chunk[blockIdx.x] * chunk_rows;
+  const int64_t lo = (int64_t)blk_chunk[slot] * chunk_rows;
   const int64_t hi = min(len, lo + (int64_t)chunk_rows);
   double T[15];
 #pragma unroll
@@ -400,15 +431,16 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   // functors are latency-bound: their next tile is prefetched into registers while the current one
   // is evaluated (+7 % on MI355X); the Angle functors are VALU-bound at 3 waves/SIMD and lose
   // occupancy to the extra 28 VGPRs, so they load in place.
-  constexpr bool kPrefetch = PVLM_PREFETCH >= 0 ? (PVLM_PREFETCH != 0) : (KIND == PVLM_POINT2PLANE_METER || KIND == PVLM_POINT2LINE_METER);
+  // (PT: the point's address comes out of the prefetched word — there is nothing to prefetch it with a trip ahead; in place for every kind)
+  constexpr bool kPrefetch = !PT && (PVLM_PREFETCH >= 0 ? (PVLM_PREFETCH != 0) : (KIND == PVLM_POINT2PLANE_METER || KIND == PVLM_POINT2LINE_METER));
   // addresses = a wave-uniform column base (scalar registers) + one 32-bit row offset shared by the columns: the loads take the
   // saddr + voffset form and an iteration advances ONE register instead of a 64-bit pointer per column
   const double* colb[NS];
 #pragma unroll
-  for (int c = 0; c < NS; ++c) colb[c] = cols + (size_t)c * n_dev + lo;
+  for (int c = 0; c < NS; ++c) colb[c] = PT ? pr.pair_ptab[p] + (size_t)c * PVLM_POINT_TAB_STRIDE : cols + (size_t)c * n_dev + lo;   // PT: column c of the neighbour's table, indexed by the query number
   const uint16_t* runb = nullptr;  // PR: run numbers of the chunk's rows, and the chunk's first table entry — wave-uniform bases like colb
   const double* tabb = nullptr;
-  if (PR) { runb = pr.idx + pr.pair_idx0[p] + lo; tabb = pr.tab + 4 * pr.chunk_plane0[blockIdx.x]; }
+  if (PR) { runb = pr.idx + (PT ? 2 : 1) * (pr.pair_idx0[p] + lo); tabb = pr.tab + 4 * pr.chunk_plane0[slot]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
   // The loop runs on ONE register: o, the byte offset of the lane's two rows inside a column (8 * row).  It addresses the columns, the run word (at o / 4)
   // and carries the bounds; a row counter beside it costs the registers that the run word below needs.
@@ -419,20 +451,25 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   // VGPR), so a trip issues its column loads, its table loads and the next word together and pays one memory round trip, not two in a row.  The next word's
   // load has no branch around it — under an exec mask the wait-count merge puts a full wait in the middle of the table loads: the last trip re-reads its own
   // word, which is in bounds.
-  unsigned nx_runs = 0;
-  if (PR && o < span8) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o >> 3);
+  // PT: the word pair {runs, queries}; the six point loads depend on it exactly as the four table loads do — still one round trip per trip.
+  unsigned nx_runs = 0, nx_qs = 0;
+  auto load_words = [&](unsigned row) {
+    if (PT) { const uint2 w = stream_load_words<PVLM_NT_LOADS != 0>(runb, row); nx_runs = w.x; nx_qs = w.y; }
+    else nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, row);
+  };
+  if (PR && o < span8) load_words(o >> 3);
   if (kPrefetch && o < span8) {
 #pragma unroll
     for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
   }
   for (; o < span8; o += 4096) {     // 512 rows per trip
     double2 v[NS];
-    const unsigned runs = nx_runs;
+    const unsigned runs = nx_runs, qs = nx_qs;
     const unsigned o_next = o + 4096 < span8 ? o + 4096 : o;
     if (kPrefetch) {
 #pragma unroll
       for (int c = 0; c < NS; ++c) v[c] = nx[c];
-      if (PR) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o_next >> 3);
+      if (PR) load_words(o_next >> 3);
       if (o + 4096 < span8) {
 #pragma unroll
         for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o + 4096));
@@ -442,8 +479,14 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
 #pragma unroll
       for (int c = 0; c < NS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NS - PVLM_EXP_SKIP ? c : 0] + (o >> 3));
 #else
+      if (PT) {
+        const unsigned q0 = 8u * (qs & 0xffffu), q1 = 8u * (qs >> 16);
 #pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
+        for (int c = 0; c < NS; ++c) v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
+      } else {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
+      }
 #endif
     }
     double2 pl[2][2];              // PR: {a, b}, {c, d} of the lane's two rows (a pad row behind an odd last row names entry 0)
@@ -454,7 +497,7 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
         pl[h][0] = stream_load2<false>(at_byte(tabb, at));
         pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
       }
-      if (!kPrefetch) nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, o_next >> 3);
+      if (!kPrefetch) load_words(o_next >> 3);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -474,7 +517,7 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   }
   __syncthreads();
   if (threadIdx.x < PVLM_PARTIAL)
-    partials[(size_t)blockIdx.x * PVLM_PARTIAL + threadIdx.x] =
+    partials[(size_t)slot * PVLM_PARTIAL + threadIdx.x] =
         ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
@@ -711,13 +754,16 @@ static void launch_wrench(pvlm_ctx* ctx, const pvlm_resset* rs, double* d_w, int
 
 template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
 static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
-  const pvlm_plane_args pr = {rs->d_plane_idx, rs->d_pair_idx0, rs->d_chunk_plane0, rs->d_plane_tab};
+  const pvlm_plane_args pr = {rs->d_plane_idx, rs->d_pair_idx0, rs->d_chunk_plane0, rs->d_plane_tab, rs->d_pair_ptab, rs->d_order};
   if (rs->wave_units)            // many short segments: one wave per (pair, chunk)
     hipLaunchKernelGGL((k_eval_fused_wave<KIND, NORM, NCOLS, LOSS, PR>), dim3((unsigned)((rs->n_blocks + 3) / 4)), dim3(256), 0, ctx->stream, rs->d_pair_cols,
                        rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a,
                        rs->d_partials, pr);
+  else if (PR && rs->point_table)  // the point from the neighbour's table, the grid in the set's dispatch order (pvlm_i_plane_runs_build chose both)
+    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>), dim3(rs->n_positions), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
+                       rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
   else
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
+    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
                        rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
 }
 template <int KIND, bool NORM, int NCOLS>

@@ -22,6 +22,7 @@
 #define PVLM_PAIR_TAB 33
 // Fused partial: [S upper triangle (21) | gv (6) | cost (1)]
 #define PVLM_PARTIAL 28
+#define PVLM_POINT_TAB_STRIDE 65536   // entries per column of a neighbour's point table (pvlm_resset::d_point_tab): a query number is 16 bits
 
 // Device memory of a context comes from a caching sub-allocator: hipMalloc maps pages at 40-70 ms per GB on MI355X
 // (tools/micro/alloc_cost.hip: 16 GB 0.64 s, 48 GB 1.9-3.5 s), which made the association call 27x slower than
@@ -165,6 +166,18 @@ struct pvlm_resset {
   double* d_plane_tab = nullptr;        // n_plane_runs x {a, b, c, d}
   int64_t* d_chunk_plane0 = nullptr;    // n_blocks: first table entry of the work-list entry
   int64_t* d_pair_idx0 = nullptr;       // n_pairs: first element of the pair in d_plane_idx (a multiple of 16)
+  // Point table (sets made by the association, plane-run form, block form, every neighbour <= 65 536 queries): the local point of query q of a neighbour scan
+  // — columns 0..2 of every row that q has in any pair with that neighbour — is kept ONCE per distinct neighbour (d_point_tab: 3 columns of
+  // PVLM_POINT_TAB_STRIDE doubles per neighbour, a snapshot taken by the association), and a row names its query with 16 bits.  d_plane_idx then holds, per
+  // pair of rows, four 16-bit words {run(2k), run(2k+1), query(2k), query(2k+1)}: one 8-byte load per lane of k_eval_fused.  The three columns stay.
+  bool point_table = false;             // k_eval_fused takes the point from d_point_tab
+  std::vector<uint16_t*> d_q16;         // per column block, while the set is being made: query number of every row (freed by the finalize pass)
+  std::vector<int> h_pair_tab;          // n_pairs: the pair's neighbour among the distinct neighbours of the call
+  int n_point_tabs = 0;
+  double* d_point_tab = nullptr;        // n_point_tabs x 3 x PVLM_POINT_TAB_STRIDE
+  const double** d_pair_ptab = nullptr; // n_pairs: the table of the pair's neighbour
+  int* d_order = nullptr;               // grid position -> work-list slot, -1 = padding (pvlm_dispatch_core.h); nullptr = identity
+  int n_positions = 0;                  // grid of k_eval_fused on the point table
   int* d_blk_pair = nullptr;
   int* d_blk_chunk = nullptr;
   int* d_pair_blk_start = nullptr;  // n_pairs+1

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "pvlm_compact.h"
+#include "pvlm_dispatch_core.h"
 #include "pvlm_internal.h"
 
 // The plane of a point-to-plane row is fitted to the query's 10 nearest targets; neighbouring queries of a ring very often have the same ten, and then
@@ -52,9 +53,13 @@ __global__ __launch_bounds__(pvlm_compact::kThreads) void k_plane_run_write(cons
                                                                             const int64_t* __restrict__ out_start, const int* __restrict__ blk_pair,
                                                                             const int* __restrict__ blk_chunk, int chunk_rows,
                                                                             const int64_t* __restrict__ chunk_plane0, const int64_t* __restrict__ pair_idx0,
-                                                                            uint16_t* __restrict__ plane_idx, double* __restrict__ plane_tab) {
+                                                                            uint16_t* __restrict__ plane_idx, double* __restrict__ plane_tab,
+                                                                            const uint16_t* const* __restrict__ pair_q16) {
   const PlaneChunk c = plane_chunk(pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows);
-  uint16_t* idx = plane_idx + pair_idx0[c.p];                                                   // indexed by the row inside the pair
+  // pair_q16 (the point table, pvlm_resset::point_table): the pair's query numbers go in beside the run numbers, four 16-bit words per PAIR of rows
+  // {run(2k), run(2k+1), query(2k), query(2k+1)}; without it one word per row
+  const uint16_t* q16 = pair_q16 ? pair_q16[c.p] : nullptr;
+  uint16_t* idx = plane_idx + (q16 ? 2 : 1) * pair_idx0[c.p];                                    // indexed by the row inside the pair
   ulonglong2* tab = reinterpret_cast<ulonglong2*>(plane_tab) + 2 * chunk_plane0[blockIdx.x];    // two 16-byte halves per entry
   __shared__ int wave_runs[pvlm_compact::kWaves];
   const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
@@ -72,7 +77,8 @@ __global__ __launch_bounds__(pvlm_compact::kThreads) void k_plane_run_write(cons
     for (int k = 0; k < pvlm_compact::kWaves; ++k) { const int t = wave_runs[k]; before += k < wv ? t : 0; all += t; }
     if (j < c.hi) {
       const int run = before + upto - 1;                       // >= 0: the chunk's first row starts a run; < chunk_rows <= 65536 (pvlm_i_plane_runs_build)
-      idx[j] = (uint16_t)run;
+      if (q16) { const int64_t e = 4 * (j >> 1) + (j & 1); idx[e] = (uint16_t)run; idx[e + 2] = q16[j]; }
+      else idx[j] = (uint16_t)run;
       if (starts) { tab[2 * run] = make_ulonglong2(w[0], w[1]); tab[2 * run + 1] = make_ulonglong2(w[2], w[3]); }
     }
     carry += all;
@@ -91,8 +97,9 @@ static const double kPlaneRunsMinMean = 1.25;
 // Counts the runs, decides (PVLM_PLANE_RUNS=0/1 forces the choice, like PVLM_WAVE_UNITS: A/B runs and the tests) and builds d_plane_idx / d_plane_tab /
 // d_chunk_plane0 / d_pair_idx0.  Called by pvlm_i_resset_finalize behind its queued copies of the work list.  A set that cannot have its table (no memory)
 // keeps the 7-column path: only a failure of the stream itself is an error.
-pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows) {
+static pvlm_status plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows) {
   rs->plane_runs = false;
+  rs->point_table = false;
   if (rs->ncols != 7 || rs->n_blocks == 0 || rs->chunk_rows > 65536) return PVLM_OK;     // a run number is 16 bits (PVLM_WAVE_CHUNK can ask for longer chunks)
   int force = -1;
   if (const char* env = getenv("PVLM_PLANE_RUNS")) force = atoi(env) != 0;
@@ -101,6 +108,7 @@ pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padd
   std::string kept_err = ctx->err;
   auto give_up = [&]() {                      // the set keeps the 7-column path
     pvlm_i_free(ctx, rs->d_plane_idx); pvlm_i_free(ctx, rs->d_plane_tab); pvlm_i_free(ctx, rs->d_chunk_plane0); pvlm_i_free(ctx, rs->d_pair_idx0);
+    pvlm_i_free(ctx, rs->d_pair_ptab); rs->d_pair_ptab = nullptr;
     rs->d_plane_idx = nullptr; rs->d_plane_tab = nullptr; rs->d_chunk_plane0 = nullptr; rs->d_pair_idx0 = nullptr;
     ctx->err = kept_err;
     return PVLM_OK;
@@ -129,17 +137,65 @@ pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padd
   std::vector<int64_t> pair_idx0((size_t)P);
   int64_t o = 0;
   for (int p = 0; p < P; ++p) { pair_idx0[(size_t)p] = o; o += pvlm_i_seg_rows(rs->h_out_start[(size_t)p + 1] - rs->h_out_start[(size_t)p]); }
-  if (pvlm_i_alloc(ctx, &rs->d_pair_idx0, (size_t)P) || pvlm_i_alloc(ctx, &rs->d_plane_idx, (size_t)padded_rows) ||
+  // The point table: a set of the association (tables and query numbers are there), block form.  PVLM_POINT_TABLE=1 cannot force it onto a set that lacks
+  // them (uploaded, compacted, a neighbour of more than 65 536 queries) or onto the wave form; =0 kept the association from making them.
+  bool pt = rs->d_point_tab != nullptr && !rs->wave_units && rs->d_q16.size() == rs->col_blocks.size();
+  const uint16_t** d_pair_q16 = nullptr;
+  if (pt && (scratch.alloc(&d_pair_q16, (size_t)P) || pvlm_i_alloc(ctx, &rs->d_pair_ptab, (size_t)P))) { pt = false; ctx->err = kept_err; }
+  if (pvlm_i_alloc(ctx, &rs->d_pair_idx0, (size_t)P) || pvlm_i_alloc(ctx, &rs->d_plane_idx, (size_t)padded_rows * (pt ? 2 : 1)) ||
       pvlm_i_alloc(ctx, &rs->d_plane_tab, (size_t)total * 4))
     return give_up();
+  std::vector<const uint16_t*> pair_q16;
+  std::vector<const double*> pair_ptab;
+  if (pt) {
+    pair_q16.resize((size_t)P); pair_ptab.resize((size_t)P);
+    for (int p = 0; p < P; ++p) {
+      pair_q16[(size_t)p] = rs->d_q16[(size_t)rs->h_pair_block[(size_t)p]] + rs->h_seg_start[(size_t)p];
+      pair_ptab[(size_t)p] = rs->d_point_tab + (size_t)rs->h_pair_tab[(size_t)p] * 3 * PVLM_POINT_TAB_STRIDE;
+    }
+    if ((st = pvlm_i_h2d_q(ctx, d_pair_q16, pair_q16.data(), (size_t)P * sizeof(uint16_t*)))) return st;
+    if ((st = pvlm_i_h2d_q(ctx, rs->d_pair_ptab, pair_ptab.data(), (size_t)P * sizeof(double*)))) return st;
+  }
   if ((st = pvlm_i_h2d_q(ctx, rs->d_pair_idx0, pair_idx0.data(), (size_t)P * sizeof(int64_t)))) return st;
   // a lane of the fused kernels loads the run numbers of its TWO rows at once: the pad row behind an odd last row must name an entry that exists (0)
-  PVLM_HIP(ctx, hipMemsetAsync(rs->d_plane_idx, 0, (size_t)padded_rows * sizeof(uint16_t), ctx->stream));
+  // (and query 0: every table has the entry's memory, whatever it holds — the pad row is loaded, never evaluated)
+  PVLM_HIP(ctx, hipMemsetAsync(rs->d_plane_idx, 0, (size_t)padded_rows * (pt ? 2 : 1) * sizeof(uint16_t), ctx->stream));
   hipLaunchKernelGGL(k_plane_run_write, dim3(nb), dim3(pvlm_compact::kThreads), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
-                     rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_chunk_plane0, rs->d_pair_idx0, rs->d_plane_idx, rs->d_plane_tab);
+                     rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_chunk_plane0, rs->d_pair_idx0, rs->d_plane_idx, rs->d_plane_tab,
+                     (const uint16_t* const*)d_pair_q16);
   PVLM_HIP(ctx, hipGetLastError());
   if ((st = pvlm_i_sync(ctx))) return st;           // pair_idx0 goes out of scope
   rs->plane_runs = true;
+  rs->point_table = pt;
   mark("table built");
   return PVLM_OK;
+}
+
+// The order in which the grid of k_eval_fused visits the work list of a set on the point table (pvlm_dispatch_core.h); PVLM_DISPATCH_ORDER=0: the identity
+// (no table).  Speed only: without memory for it the set runs in work-list order.
+static pvlm_status dispatch_order_build(pvlm_ctx* ctx, pvlm_resset* rs) {
+  rs->n_positions = rs->n_blocks;
+  if (const char* env = getenv("PVLM_DISPATCH_ORDER")) if (atoi(env) == 0) return PVLM_OK;
+  std::vector<int64_t> key((size_t)rs->n_blocks);
+  for (int p = 0; p < rs->n_pairs; ++p)
+    for (int b = rs->h_pair_blk_start[(size_t)p]; b < rs->h_pair_blk_start[(size_t)p + 1]; ++b)
+      key[(size_t)b] = pvlm_dispatch::group_key(rs->h_pair_tab[(size_t)p], b - rs->h_pair_blk_start[(size_t)p]);
+  std::vector<int> pos;
+  pvlm_dispatch::build_order(rs->n_blocks, key.data(), pos);
+  const std::string kept_err = ctx->err;
+  if (pvlm_i_alloc(ctx, &rs->d_order, pos.size())) { rs->d_order = nullptr; ctx->err = kept_err; return PVLM_OK; }
+  pvlm_status st = pvlm_i_h2d_q(ctx, rs->d_order, pos.data(), pos.size() * sizeof(int));
+  if (!st) st = pvlm_i_sync(ctx);                    // pos goes out of scope
+  if (!st) rs->n_positions = (int)pos.size();
+  return st;
+}
+
+pvlm_status pvlm_i_plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows) {
+  pvlm_status st = plane_runs_build(ctx, rs, padded_rows);
+  // what only the making of the set needed: the per-block query numbers (now beside the run numbers) and, for a set that does not take the form, the tables
+  for (uint16_t* b : rs->d_q16) pvlm_i_free(ctx, b);
+  rs->d_q16.clear();
+  if (!rs->point_table) { pvlm_i_free(ctx, rs->d_point_tab); rs->d_point_tab = nullptr; rs->n_point_tabs = 0; }
+  if (!st && rs->point_table) st = dispatch_order_build(ctx, rs);
+  return st;
 }
