@@ -19,6 +19,7 @@
 #include <unordered_map>
 
 #include "pvlm_internal.h"
+#include "pvlm_layout.h"
 #include "pvlm_workers.h"
 #include "pvlm_assoc_core.h"
 
@@ -655,32 +656,32 @@ struct GridJob { CloudPlan* plan; const float* d_xyz; const float* d_tag; };
 static pvlm_status grids_build(pvlm_ctx* ctx, const std::vector<GridJob>& jobs, char** out_slab) {
   *out_slab = nullptr;
   const int n_grids = (int)jobs.size();
-  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  auto place = [&](size_t& off, size_t& cursor, size_t bytes) { off = cursor; cursor = align(cursor + bytes); };
   if (n_grids == 0) {
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "scan upload: device error"); return PVLM_ERR_HIP; }
     return PVLM_OK;
   }
   size_t n_blocks = 0, n_small = 0;
   for (const GridJob& j : jobs) { n_blocks += ((size_t)j.plan->n + 255) / 256; n_small += j.plan->T <= GRID_SCAN_MAX; }
-  size_t slab = 0, scratch = 0, o_desc = 0, o_blocks = 0, o_small = 0;
-  place(o_desc, slab, (size_t)n_grids * sizeof(GridDesc));
-  place(o_blocks, slab, std::max<size_t>(n_blocks, 1) * sizeof(GridBlock));
-  place(o_small, slab, std::max<size_t>(n_small, 1) * sizeof(int));
-  const size_t tables_bytes = slab, o_count0 = slab;
-  for (const GridJob& j : jobs) place(j.plan->o_count, slab, (size_t)j.plan->T * 4);
-  const size_t count_bytes = slab - o_count0, o_keys0 = slab;
-  for (const GridJob& j : jobs) if (!j.plan->dense) place(j.plan->o_keys, slab, (size_t)j.plan->T * 8);
-  const size_t keys_bytes = slab - o_keys0;
+  // add(0): the walk's cursor rounded up to the next region's start (a group of regions is copied or cleared as one span, padding included)
+  pvlm_layout slab_l, scratch_l;
+  const size_t o_desc = slab_l.add((size_t)n_grids * sizeof(GridDesc));
+  const size_t o_blocks = slab_l.add(std::max<size_t>(n_blocks, 1) * sizeof(GridBlock));
+  const size_t o_small = slab_l.add(std::max<size_t>(n_small, 1) * sizeof(int));
+  const size_t tables_bytes = slab_l.add(0), o_count0 = tables_bytes;
+  for (const GridJob& j : jobs) j.plan->o_count = slab_l.add((size_t)j.plan->T * 4);
+  const size_t o_keys0 = slab_l.add(0), count_bytes = o_keys0 - o_count0;
+  for (const GridJob& j : jobs) if (!j.plan->dense) j.plan->o_keys = slab_l.add((size_t)j.plan->T * 8);
+  const size_t keys_bytes = slab_l.add(0) - o_keys0;
   for (const GridJob& j : jobs) {
     CloudPlan& c = *j.plan;
-    place(c.o_start, slab, (size_t)c.T * 4);
-    place(c.o_sorted, slab, ((size_t)c.n + 1) * 16);          // + 1: the search may read (never use) one record past a run
-    if (j.d_tag) place(c.o_pt4, slab, (size_t)c.n * 16);
+    c.o_start = slab_l.add((size_t)c.T * 4);
+    c.o_sorted = slab_l.add(((size_t)c.n + 1) * 16);          // + 1: the search may read (never use) one record past a run
+    if (j.d_tag) c.o_pt4 = slab_l.add((size_t)c.n * 16);
   }
-  for (const GridJob& j : jobs) place(j.plan->s_cursor, scratch, (size_t)j.plan->T * 4);
-  const size_t cursor_bytes = scratch;
-  for (const GridJob& j : jobs) place(j.plan->s_slot, scratch, (size_t)j.plan->n * 4);
+  for (const GridJob& j : jobs) j.plan->s_cursor = scratch_l.add((size_t)j.plan->T * 4);
+  const size_t cursor_bytes = scratch_l.add(0);
+  for (const GridJob& j : jobs) j.plan->s_slot = scratch_l.add((size_t)j.plan->n * 4);
+  const size_t slab = slab_l.add(0), scratch = scratch_l.add(0);
   // pinned mirror of the tables (grow-only; idle here: every build ends with a synchronisation)
   if (ctx->grid_bytes < tables_bytes) {
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { PVLM_SET_ERR(ctx, "voxel-grid build: device error"); return PVLM_ERR_HIP; }
@@ -918,21 +919,19 @@ static pvlm_status scan_upload_batch_impl(pvlm_ctx* ctx, int n_scans, const pvlm
   pvlm_i_trace("scan_upload_batch: plan (bbox, host tables)");
   // ---- 2. layout.  Points slab (lives as long as the scans; pvlm_scan_transform_batch re-poses it in place): the uploaded arrays.  The voxel
   //         grids go into a slab of their own (grids_build), replaced whenever the clouds are re-posed.
-  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  size_t up = 0;
-  auto place = [&](size_t& off, size_t& cursor, size_t bytes) { off = cursor; cursor = align(cursor + bytes); };
+  pvlm_layout up;
   auto each_cloud = [&](auto&& f) { for (ScanPlan& P : plan) { f(P.flat); f(P.less); f(P.corner); } };
   each_cloud([&](CloudPlan& c) {
     if (c.n <= 0) return;
-    place(c.o_xyz, up, (size_t)c.n * 12);
-    if (c.tag) place(c.o_tag, up, (size_t)c.n * 4);
+    c.o_xyz = up.add((size_t)c.n * 12);
+    if (c.tag) c.o_tag = up.add((size_t)c.n * 4);
   });
   for (int k = 0; k < n_scans; ++k) {
     ScanPlan& P = plan[(size_t)k];
-    if (!scans[(size_t)k]->h_p2s_off.empty()) { place(P.o_p2s_off, up, scans[(size_t)k]->h_p2s_off.size() * 4); place(P.o_p2s_ids, up, std::max<size_t>(P.n_p2s_ids, 1) * 4); }
-    if (!scans[(size_t)k]->h_seg_pt_off.empty()) place(P.o_seg_xyz, up, std::max<size_t>(P.n_seg_pts, 1) * 12);
+    if (!scans[(size_t)k]->h_p2s_off.empty()) { P.o_p2s_off = up.add(scans[(size_t)k]->h_p2s_off.size() * 4); P.o_p2s_ids = up.add(std::max<size_t>(P.n_p2s_ids, 1) * 4); }
+    if (!scans[(size_t)k]->h_seg_pt_off.empty()) P.o_seg_xyz = up.add(std::max<size_t>(P.n_seg_pts, 1) * 12);
   }
-  const size_t up_bytes = up;
+  const size_t up_bytes = up.add(0);      // the slab ends on a 256-byte boundary, like every region in it
   // ---- 3. allocate: the slab from the pool, the staging mirror of the uploaded arrays (pinned, grow-only)
   char* d_slab = nullptr;
   if ((st = pvlm_i_alloc_bytes(ctx, (void**)&d_slab, std::max<size_t>(up_bytes, 256)))) return fail(st);
@@ -940,7 +939,7 @@ static pvlm_status scan_upload_batch_impl(pvlm_ctx* ctx, int n_scans, const pvlm
   // staging window: the whole front when it fits, else PVLM_UPLOAD_STAGE_MB (default 64) at a time
   size_t window = (size_t)64 << 20;
   if (const char* env = getenv("PVLM_UPLOAD_STAGE_MB")) if (atof(env) > 0) window = (size_t)(atof(env) * 1048576.0);
-  window = align(std::max<size_t>(window, 4096));
+  window = pvlm_layout{std::max<size_t>(window, 4096)}.add(0);
   const size_t need = std::min(up_bytes, window);
   if (ctx->up_bytes < need) {
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(PVLM_ERR_HIP);
@@ -977,7 +976,7 @@ static pvlm_status scan_upload_batch_impl(pvlm_ctx* ctx, int n_scans, const pvlm
   // the next one (staging at ~14 GB/s of host copy bandwidth and the link at ~55 GB/s used to take turns: 15 + 8 ms of a Floor-sized upload)
   size_t piece = (size_t)8 << 20;
   if (const char* env = getenv("PVLM_UPLOAD_PIECE_MB")) if (atof(env) > 0) piece = (size_t)(atof(env) * 1048576.0);
-  piece = align(std::max<size_t>(piece, 4096));
+  piece = pvlm_layout{std::max<size_t>(piece, 4096)}.add(0);
   for (size_t lo = 0; lo < up_bytes && e == hipSuccess; lo += ctx->up_bytes) {
     const size_t hi = std::min(up_bytes, lo + ctx->up_bytes);
     if (lo > 0) e = hipStreamSynchronize(ctx->stream);            // the window is refilled: the previous copies must have left it

@@ -1,4 +1,4 @@
-// The frame of one host-side call of the SfM stages (K31-K37); included by pvlm_internal.h.  An entry point declares one pvlm_call, enters, and does its device
+// The frame of one host-side call of the SfM stages (K31-K37) and of the ring batches (K16-K24); included by pvlm_internal.h.  An entry point declares one pvlm_call, enters, and does its device
 // work through it: scratch, queued copies, memsets and launches all stop at the first error, which `st` keeps.  The frame owns the rule that used to be an
 // instruction to every caller: scratch and staged copies never outlive the call.  Its destructor waits for whatever is still queued (an error path that left
 // before its sync), DROPS the staged device-to-host copies instead of landing them (their targets are locals of the returning function, some destroyed already),
@@ -36,6 +36,13 @@ struct pvlm_call {
   // copies through the staging arena: an upload has left src when it returns, a download reaches dst at the next sync()
   void h2d(void* dst, const void* src, size_t bytes) { if (!st && bytes) { queued = true; st = pvlm_i_h2d_q(ctx, dst, src, bytes); } }
   void d2h(void* dst, const void* src, size_t bytes) { if (!st && bytes) { queued = true; st = pvlm_i_d2h_q(ctx, dst, src, bytes); } }
+  // a large copy that does not go through the arena: its host side is pinned memory the caller owns, `s` the context's stream or a second one the caller drains
+  void copy_pinned(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (st || !bytes) return;
+    queued = true;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, s);
+    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "%s: copy failed: %s", who, hipGetErrorString(e)); st = e == hipErrorOutOfMemory ? PVLM_ERR_NOMEM : PVLM_ERR_HIP; }
+  }
   void memset(void* dst, int value, size_t bytes) {
     if (st || !bytes) return;
     queued = true;

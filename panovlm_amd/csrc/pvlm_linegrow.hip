@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pvlm_internal.h"
+#include "pvlm_layout.h"
 #include "pvlm_linegrow_core.h"
 
 using namespace pvlm_linegrow;
@@ -48,8 +49,6 @@ struct LdsLists {
   __device__ unsigned short& m(int k) { return m_[k * THREADS]; }
   __device__ unsigned short& o(int k) { return o_[k * THREADS]; }
 };
-
-struct SegRecord { int scan, order, task, count, mem_off, pad; double coeff[6]; };      // order: position of the segment in the scan's walk
 
 constexpr int kMaxScanPoints = 8192;   // `visited` flags of a scan in LDS (a byte each); a larger edge cloud is left to the host
 constexpr int kLdsPoints = 2048;       // edge points of a scan kept in LDS (32 KB as float4); a larger scan reads them from global memory
@@ -145,18 +144,16 @@ struct pvlm_line_grow {
   std::vector<double> coeffs;                 // 6 per segment
   double kernel_ms = 0;                       // k_edge_knn + k_line_grow_walk (HIP events)
   long long tasks_run = 0;
-  // between pvlm_line_grow_begin and pvlm_line_grow_finish: the device blocks of the batch in flight
+  // between pvlm_line_grow_begin and pvlm_line_grow_finish: the device blocks of the batch in flight and the layouts of the two pinned buffers
   bool pending = false;
-  float4* d_xyz = nullptr; int* d_pt_scan = nullptr; GrowScan* d_scans = nullptr; int* d_nn_idx = nullptr; float* d_nn_sqd = nullptr;
-  SegRecord* d_segs = nullptr; int* d_members = nullptr; int* d_counters = nullptr; int* d_status = nullptr;
+  enum { kXyz, kPtScan, kScans, kNnIdx, kNnSqd, kSegs, kMembers, kCounters, kStatus, kBlocks };
+  void* d[kBlocks] = {};
+  pvlm_grow_in_layout in{}; pvlm_grow_out_layout res{};
   int seg_cap = 0, mem_cap = 0;
 };
 
 static void grow_release(pvlm_ctx* ctx, pvlm_line_grow* G) {
-  pvlm_i_free(ctx, G->d_xyz); pvlm_i_free(ctx, G->d_pt_scan); pvlm_i_free(ctx, G->d_scans); pvlm_i_free(ctx, G->d_nn_idx); pvlm_i_free(ctx, G->d_nn_sqd);
-  pvlm_i_free(ctx, G->d_segs); pvlm_i_free(ctx, G->d_members); pvlm_i_free(ctx, G->d_counters); pvlm_i_free(ctx, G->d_status);
-  G->d_xyz = nullptr; G->d_pt_scan = nullptr; G->d_scans = nullptr; G->d_nn_idx = nullptr; G->d_nn_sqd = nullptr; G->d_segs = nullptr; G->d_members = nullptr;
-  G->d_counters = nullptr; G->d_status = nullptr;
+  for (void*& p : G->d) { pvlm_i_free(ctx, p); p = nullptr; }
 }
 // a grow-only pinned buffer of the context
 static bool grow_pinned(void** buf, size_t* have, size_t need) {
@@ -199,17 +196,18 @@ pvlm_status pvlm_line_grow_begin(pvlm_ctx* ctx, int n_scans, const pvlm_edge_clo
       for (int k = 0; k < 3 && ok; ++k) ok = hipEventCreate(&ctx->grow_ev[k]) == hipSuccess;
       if (!ok) { (void)hipGetLastError(); delete G; PVLM_SET_ERR(ctx, "pvlm_line_grow_begin: no stream / events"); return PVLM_ERR_HIP; }
     }
-    // pinned input: [xyz (float4) | point -> scan | scan table]; pinned output: [counters (4) | statuses | segments | members]
-    const size_t o_pt = n_points * 16, o_sc = o_pt + n_points * 4, in_bytes = o_sc + (size_t)n_scans * sizeof(GrowScan);
     // a kept segment belongs to one of the six tasks of a start point: at most 6 n segments, sized for one per point (more: PVLM_ERR_REFUSED, the caller grows on
     // the host); the member pool for 16 members per edge point (a walk keeps ~0.3 segments of ~16 members per edge point)
     G->seg_cap = (int)std::min<size_t>(n_points + 1024, (size_t)1 << 28); G->mem_cap = (int)std::min<size_t>(n_points * 16 + 4096, (size_t)1 << 30);
-    const size_t out_bytes = 16 + (size_t)n_scans * 4 + (size_t)G->seg_cap * sizeof(SegRecord) + (size_t)G->mem_cap * 4;
-    if (!grow_pinned(&ctx->h_grow_in, &ctx->grow_in_bytes, in_bytes) || !grow_pinned(&ctx->h_grow_out, &ctx->grow_out_bytes, out_bytes)) {
+    // the two pinned buffers (pvlm_layout.h); finish reads the same layouts
+    G->in = pvlm_grow_in_layout_of(n_points, (size_t)n_scans, sizeof(GrowScan));
+    G->res = pvlm_grow_out_layout_of((size_t)n_scans, (size_t)G->seg_cap, sizeof(SegRecord), (size_t)G->mem_cap);
+    if (!grow_pinned(&ctx->h_grow_in, &ctx->grow_in_bytes, G->in.bytes) || !grow_pinned(&ctx->h_grow_out, &ctx->grow_out_bytes, G->res.bytes)) {
       delete G; PVLM_SET_ERR(ctx, "pvlm_line_grow_begin: pinned staging unavailable"); return PVLM_ERR_NOMEM;
     }
     char* hin = static_cast<char*>(ctx->h_grow_in);
-    float* xyz = reinterpret_cast<float*>(hin); int* pt_scan = reinterpret_cast<int*>(hin + o_pt); GrowScan* scans = reinterpret_cast<GrowScan*>(hin + o_sc);
+    float* xyz = reinterpret_cast<float*>(hin + G->in.xyz); int* pt_scan = reinterpret_cast<int*>(hin + G->in.pt_scan);
+    GrowScan* scans = reinterpret_cast<GrowScan*>(hin + G->in.scans);
     size_t at = 0; int n_max = 0;
     for (int s = 0; s < n_scans; ++s) {
       const int n = clouds[s].n;
@@ -224,32 +222,29 @@ pvlm_status pvlm_line_grow_begin(pvlm_ctx* ctx, int n_scans, const pvlm_edge_clo
       at += (size_t)n;
     }
     static const Turn turn = turn_thresholds();
-    pvlm_status st = pvlm_i_alloc(ctx, &G->d_xyz, n_points);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_pt_scan, n_points);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_scans, (size_t)n_scans);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_nn_idx, n_points * kK);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_nn_sqd, n_points * kK);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_segs, (size_t)G->seg_cap);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_members, (size_t)G->mem_cap);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_counters, 4);
-    if (!st) st = pvlm_i_alloc(ctx, &G->d_status, (size_t)n_scans);
+    const size_t block_bytes[pvlm_line_grow::kBlocks] = {n_points * 16, n_points * 4, (size_t)n_scans * sizeof(GrowScan), n_points * kK * 4, n_points * kK * 4,
+                                                         (size_t)G->seg_cap * sizeof(SegRecord), (size_t)G->mem_cap * 4, 16, (size_t)n_scans * 4};
+    pvlm_status st = PVLM_OK;
+    for (int k = 0; k < pvlm_line_grow::kBlocks && !st; ++k) st = pvlm_i_alloc_bytes(ctx, &G->d[k], block_bytes[k]);
     if (st) { grow_release(ctx, G); delete G; return st; }
+    const float4* d_xyz = (const float4*)G->d[G->kXyz]; const int* d_pt_scan = (const int*)G->d[G->kPtScan]; const GrowScan* d_scans = (const GrowScan*)G->d[G->kScans];
+    int* d_nn_idx = (int*)G->d[G->kNnIdx]; float* d_nn_sqd = (float*)G->d[G->kNnSqd]; SegRecord* d_segs = (SegRecord*)G->d[G->kSegs];
+    int* d_members = (int*)G->d[G->kMembers]; int* d_counters = (int*)G->d[G->kCounters]; int* d_status = (int*)G->d[G->kStatus];
     hipStream_t gs = ctx->grow_stream;
     hipError_t e = hipEventRecord(ctx->grow_ev[0], ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(gs, ctx->grow_ev[0], 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(G->d_xyz, xyz, n_points * 16, hipMemcpyHostToDevice, gs);
-    if (e == hipSuccess) e = hipMemcpyAsync(G->d_pt_scan, pt_scan, n_points * 4, hipMemcpyHostToDevice, gs);
-    if (e == hipSuccess) e = hipMemcpyAsync(G->d_scans, scans, (size_t)n_scans * sizeof(GrowScan), hipMemcpyHostToDevice, gs);
-    if (e == hipSuccess) e = hipMemsetAsync(G->d_counters, 0, 4 * sizeof(int), gs);
-    if (e == hipSuccess) e = hipMemsetAsync(G->d_status, 0, (size_t)n_scans * sizeof(int), gs);
+    if (e == hipSuccess) e = hipMemcpyAsync(G->d[G->kXyz], xyz, block_bytes[G->kXyz], hipMemcpyHostToDevice, gs);
+    if (e == hipSuccess) e = hipMemcpyAsync(G->d[G->kPtScan], pt_scan, block_bytes[G->kPtScan], hipMemcpyHostToDevice, gs);
+    if (e == hipSuccess) e = hipMemcpyAsync(G->d[G->kScans], scans, block_bytes[G->kScans], hipMemcpyHostToDevice, gs);
+    if (e == hipSuccess) e = hipMemsetAsync(d_counters, 0, block_bytes[G->kCounters], gs);
+    if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, block_bytes[G->kStatus], gs);
     if (e == hipSuccess) {
       hipEventRecord(ctx->grow_ev[1], gs);
-      hipLaunchKernelGGL(k_edge_knn, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, gs, (const GrowScan*)G->d_scans, (const int*)G->d_pt_scan, (int)n_points,
-                         (const float4*)G->d_xyz, G->d_nn_idx, G->d_nn_sqd);
+      hipLaunchKernelGGL(k_edge_knn, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, gs, d_scans, d_pt_scan, (int)n_points, d_xyz, d_nn_idx, d_nn_sqd);
       static const int waves = [] { const char* v = getenv("PVLM_K27_WAVES"); const int k = v ? atoi(v) : 0; return k == 1 || k == 2 || k == 4 ? k : 2; }();
       const bool in_lds = n_max <= kLdsPoints;
-#define PVLM_K27_LAUNCH(W, L) hipLaunchKernelGGL((k_line_grow_walk<W, L>), dim3((unsigned)n_scans), dim3(W * 64), 0, gs, (const GrowScan*)G->d_scans, (const float4*)G->d_xyz, \
-                                                 (const int*)G->d_nn_idx, (const float*)G->d_nn_sqd, turn, G->d_segs, G->seg_cap, G->d_members, G->mem_cap, G->d_counters, G->d_status)
+#define PVLM_K27_LAUNCH(W, L) hipLaunchKernelGGL((k_line_grow_walk<W, L>), dim3((unsigned)n_scans), dim3(W * 64), 0, gs, d_scans, d_xyz, (const int*)d_nn_idx, \
+                                                 (const float*)d_nn_sqd, turn, d_segs, G->seg_cap, d_members, G->mem_cap, d_counters, d_status)
       if (waves == 1) { if (in_lds) PVLM_K27_LAUNCH(1, true); else PVLM_K27_LAUNCH(1, false); }
       else if (waves == 2) { if (in_lds) PVLM_K27_LAUNCH(2, true); else PVLM_K27_LAUNCH(2, false); }
       else { if (in_lds) PVLM_K27_LAUNCH(4, true); else PVLM_K27_LAUNCH(4, false); }
@@ -258,8 +253,8 @@ pvlm_status pvlm_line_grow_begin(pvlm_ctx* ctx, int n_scans, const pvlm_edge_clo
       e = hipGetLastError();
     }
     char* hout = static_cast<char*>(ctx->h_grow_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(hout, G->d_counters, 16, hipMemcpyDeviceToHost, gs);
-    if (e == hipSuccess) e = hipMemcpyAsync(hout + 16, G->d_status, (size_t)n_scans * 4, hipMemcpyDeviceToHost, gs);
+    if (e == hipSuccess) e = hipMemcpyAsync(hout + G->res.counters, d_counters, block_bytes[G->kCounters], hipMemcpyDeviceToHost, gs);
+    if (e == hipSuccess) e = hipMemcpyAsync(hout + G->res.status, d_status, block_bytes[G->kStatus], hipMemcpyDeviceToHost, gs);
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(gs);
       PVLM_SET_ERR(ctx, "pvlm_line_grow_begin: %s", hipGetErrorString(e));
@@ -288,19 +283,20 @@ pvlm_status pvlm_line_grow_finish(pvlm_ctx* ctx, pvlm_line_grow* G) {
   if (hipStreamSynchronize(gs) != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_line_grow_finish: device error"); (void)hipGetLastError(); return done(PVLM_ERR_HIP); }
   const char* hout = static_cast<const char*>(ctx->h_grow_out);
   int counters[4];
-  std::memcpy(counters, hout, sizeof counters);
-  std::memcpy(G->status.data(), hout + 16, (size_t)G->n_scans * 4);
+  std::memcpy(counters, hout + G->res.counters, sizeof counters);
+  std::memcpy(G->status.data(), hout + G->res.status, (size_t)G->n_scans * 4);
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, ctx->grow_ev[1], ctx->grow_ev[2]) == hipSuccess) G->kernel_ms = ms; else (void)hipGetLastError();
   G->tasks_run = counters[3];
   if (counters[2]) { PVLM_SET_ERR(ctx, "pvlm_line_grow_finish: segment pool exhausted (%d segments, %d members)", counters[0], counters[1]); return done(PVLM_ERR_REFUSED); }
   try {
     const size_t n_seg = (size_t)counters[0], n_mem = (size_t)counters[1];
-    const SegRecord* segs = reinterpret_cast<const SegRecord*>(hout + 16 + (((size_t)G->n_scans * 4 + 7) & ~(size_t)7));
-    const int* pool = reinterpret_cast<const int*>(reinterpret_cast<const char*>(segs) + n_seg * sizeof(SegRecord));
+    // counters[2] == 0: n_seg <= seg_cap and n_mem <= mem_cap, the capacities the layout was sized for
+    const SegRecord* segs = reinterpret_cast<const SegRecord*>(hout + G->res.segs);
+    const int* pool = reinterpret_cast<const int*>(hout + G->res.members);
     if (n_seg > 0) {
-      hipError_t e = hipMemcpyAsync(const_cast<SegRecord*>(segs), G->d_segs, n_seg * sizeof(SegRecord), hipMemcpyDeviceToHost, gs);
-      if (e == hipSuccess && n_mem > 0) e = hipMemcpyAsync(const_cast<int*>(pool), G->d_members, n_mem * sizeof(int), hipMemcpyDeviceToHost, gs);
+      hipError_t e = hipMemcpyAsync(const_cast<SegRecord*>(segs), G->d[G->kSegs], n_seg * sizeof(SegRecord), hipMemcpyDeviceToHost, gs);
+      if (e == hipSuccess && n_mem > 0) e = hipMemcpyAsync(const_cast<int*>(pool), G->d[G->kMembers], n_mem * sizeof(int), hipMemcpyDeviceToHost, gs);
       if (e == hipSuccess) e = hipStreamSynchronize(gs);
       if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_line_grow_finish: %s", hipGetErrorString(e)); return done(PVLM_ERR_HIP); }
     }

@@ -32,6 +32,9 @@ enum Status { kNone = 0, kSegment = 1, kOverflow = 2, kUndecided = 3 };
 
 struct Turn { double sure_true, sure_false; };     // turn > 1 degree  <=>  cosine <= sure_true;   not  <=>  cosine > sure_false;   between: undecided
 
+// a kept segment as K27 writes it; order: position of the segment in the scan's walk
+struct SegRecord { int scan, order, task, count, mem_off, pad; double coeff[6]; };
+
 // edge cloud of one scan: xyz with a stride (pcl::PointXYZI records: 4), its neighbour table (k = min(5, n) entries per point, ascending (d2, index))
 struct Cloud {
   const float* xyz; int stride; int n; int k;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "pvlm_internal.h"
+#include "pvlm_layout.h"
 #include "pvlm_workers.h"
 #include "pvlm_ring_core.h"
 #include "pvlm_ring_picks.h"
@@ -505,8 +506,287 @@ struct pvlm_ring_batch {
 
 extern "C" pvlm_status pvlm_ring_batch_destroy(pvlm_ctx* ctx, pvlm_ring_batch* b);
 
-static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, const pvlm_raw_scan* raw_scans, int n_rings, int horizon, int segment, long long total,
+// The device arrays of one call — scratch of the call's frame, listed by the stage that fills them (what a batch keeps is a member of pvlm_ring_batch) — with the
+// layout of the pinned buffer, the nine timing events and the stream the result arrays go down on.
+struct RingArrays {
+  float4* raw; PointRec* rec; int* listed; int* counter; PtBlock* blocks; int* winner;                                  // upload, K16
+  int2* colpos; int* ring_count; int2* status; int* source;                                                            // K17, K18
+  unsigned char* edges; EdgeQuery* queries; int* parent; int* root; int* comp_size; unsigned long long* row_mask;      // K19, K20
+  int* source2; int* ring_col2; float* range2; int* ring_count2; int* counts;                                          // K21
+  float* curv; int* half; int* order; unsigned char* sector; int4* ties;                                               // K22, K23
+  unsigned char* state; int* corner; int* flat; int2* vspan; float4* voxels; unsigned char* ring_host;                 // K24
+  size_t n_blocks, n_sectors, n_ring_slots, voxel_cap;
+  pvlm_ring_layout lay; hipEvent_t* ev; hipStream_t second;
+};
+constexpr int kQueryCap = 1 << 16;
+constexpr hipMemcpyKind kDown = hipMemcpyDeviceToHost;
+
+// what the host's own libm says about raw point `at` of the batch (std::atan2 / std::atan on the same floats); returns the point's scan
+static int exact_of(const pvlm_ring_batch* B, const pvlm_raw_scan* raw_scans, long long at, PointPatch* pp) {
+  int s = 0;
+  for (int hi = B->n_scans - 1; s < hi;) { const int mid = (s + hi + 1) / 2; if (B->scans[(size_t)mid].pt0 <= at) s = mid; else hi = mid - 1; }
+  const RingScan& sc = B->scans[(size_t)s];
+  const float* p = raw_scans[s].xyzi + (size_t)(at - sc.pt0) * raw_scans[s].stride_floats;
+  const float q = -p[1] / std::sqrt(p[0] * p[0] + p[2] * p[2]);
+  pp->slot = sc.slot0 + chunk_slot((int)(at - sc.pt0), chunk_of(sc.n, kColumnThreads), kColumnThreads);
+  pp->az = std::atan2(p[0], p[2]); pp->ring = q == q ? ring_of_atan(std::atan(q), B->rings) : -1;
+  return s;
+}
+
+// One round of host decisions going back to the device: the list goes up as scratch, the patch kernel runs, the stream is drained (the stage behind it reads the
+// patched words, and the list's block goes back to the pool here).
+template <class P, class T> static pvlm_status patch_round(pvlm_call& call, void (*kernel)(int, const P*, T*), const std::vector<P>& list, T* target) {
+  if (list.empty()) return call.st;
+  pvlm_call::batch round(call);
+  call.launch(kernel, dim3((unsigned)((list.size() + 255) / 256)), dim3(256), 0, (int)list.size(), call.upload(list.data(), list.size()), target);
+  call.check_launches();
+  return call.sync();
+}
+
+// ---- pinned buffer, staging copy, upload, K16 + the host's libm for the listed points
+static pvlm_status ring_classify(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A, const pvlm_raw_scan* raw_scans, const std::vector<PtBlock>& blocks) {
+  pvlm_ctx* ctx = call.ctx;
+  const int n_scans = B->n_scans;
+  const size_t NP = (size_t)B->total_points, NC = (size_t)B->total_cells;
+  // device memory: everything from the context's pool; the batch's own arrays stay until pvlm_ring_batch_destroy, the scratch goes back with the frame
+  auto keep = [&](auto** p, size_t count) { if (!call.st) call.st = pvlm_i_alloc(ctx, p, count); };
+  keep(&B->d_scans, (size_t)n_scans); keep(&B->d_cloud_scan, NP); keep(&B->d_rc, NP); keep(&B->d_range_image, NC);
+  keep(&B->d_image_to_point, NC); keep(&B->d_cloud2, NP); keep(&B->d_image_to_point2, NC);
+  A.raw = call.alloc<float4>(NP); A.rec = call.alloc<PointRec>((size_t)B->total_slots); A.listed = call.alloc<int>(NP); A.counter = call.alloc<int>(8); A.winner = call.alloc<int>(NC);
+  if (call.st) return call.st;
+  pvlm_i_trace("ring: device memory");
+  // pinned buffer: raw points on the way up (16 B / point), the result arrays and the sector flags on the way down; with K24 + states, the per-ring lists and
+  // the centroids.  K24: one centroid per four points is the batch's budget (a Room scan needs one per ten); rings beyond it go to the host like any undecided ring
+  A.voxel_cap = NP / 4 + 64;
+  const pvlm_ring_layout& L = A.lay = pvlm_ring_layout_of(NP, (size_t)n_scans, (size_t)B->rings, B->picks != 0, 1 + kCornerSlots, 1 + kFlatSlots, A.voxel_cap);
+  char* h = B->h_results = (char*)pvlm_i_pinned_take(ctx, L.bytes, &B->results_bytes);
+  if (!h) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %zu bytes of pinned memory unavailable", L.bytes); return call.st = PVLM_ERR_NOMEM; }
+  auto at = [h](auto*& p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(h + off); };
+  at(B->h_source, L.source); at(B->h_ring_col, L.ring_col); at(B->h_curvature, L.curvature); at(B->h_half, L.half); at(B->h_range, L.range); at(B->h_order, L.order);
+  at(B->h_sector_host, L.sector);
+  if (B->picks) { at(B->h_state, L.state); at(B->h_corner, L.corner); at(B->h_flat, L.flat); at(B->h_voxel_span, L.voxel_span); at(B->h_ring_host, L.ring_host); at(B->h_voxels, L.voxels); }
+  pvlm_i_trace("ring: pinned buffer");
+  {   // staging copy, scan-parallel (a scan's points are contiguous when stride_floats == 4)
+    float4* hp = (float4*)h;
+    std::atomic<int> next{0};
+    std::atomic<long long> bad{-1};
+    auto work = [&]() {
+      for (int s = next++; s < n_scans; s = next++) {
+        const pvlm_raw_scan& r = raw_scans[s];
+        float4* d = hp + B->scans[(size_t)s].pt0;
+        if (r.stride_floats == 4) std::memcpy(d, r.xyzi, (size_t)r.n * 16);
+        else for (int i = 0; i < r.n; ++i) { const float* p = r.xyzi + (size_t)i * r.stride_floats; d[i] = make_float4(p[0], p[1], p[2], p[3]); }
+        for (int i = 0; i < r.n; ++i)
+          if (!std::isfinite(d[i].x) || !std::isfinite(d[i].y) || !std::isfinite(d[i].z)) { bad = B->scans[(size_t)s].pt0 + i; break; }
+      }
+    };
+    const size_t n_threads = std::max<size_t>(1, std::min<size_t>({pvlm_thread_cap(), (size_t)n_scans / 32 + 1, (size_t)std::max(1u, std::thread::hardware_concurrency())}));
+    pvlm_run_workers(n_threads, work);
+    if (bad >= 0) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: non-finite coordinate (point %lld of the batch)", (long long)bad); return call.st = PVLM_ERR_REFUSED; }
+  }
+  pvlm_i_trace("ring: staging copy");
+  (void)hipEventRecord(A.ev[0], ctx->stream);
+  call.copy_pinned(A.raw, h, NP * 16, hipMemcpyHostToDevice, ctx->stream);
+  call.h2d(B->d_scans, B->scans.data(), (size_t)n_scans * sizeof(RingScan));
+  A.blocks = call.upload(blocks.data(), blocks.size());
+  call.memset(A.counter, 0, 8 * sizeof(int)); call.memset(A.winner, 0xFF, NC * sizeof(int));
+  call.memset(B->d_range_image, 0, NC * sizeof(float)); call.memset(B->d_image_to_point, 0xFF, NC * sizeof(int));
+  (void)hipEventRecord(A.ev[1], ctx->stream);
+  call.launch(k_ring_classify, dim3((unsigned)A.n_blocks), dim3(256), 0, B->d_scans, A.blocks, B->rings, B->horizon, A.raw, A.rec, A.counter, A.listed);
+  int n_listed = 0;
+  call.d2h(&n_listed, A.counter, sizeof(int));
+  if (call.sync()) return call.st;      // also: the staging buffer is free again
+  if (n_listed > 0) {
+    std::vector<int> listed((size_t)n_listed);
+    call.d2h(listed.data(), A.listed, listed.size() * sizeof(int));
+    if (call.sync()) return call.st;
+    std::vector<PointPatch> patches(listed.size());
+    for (size_t k = 0; k < listed.size(); ++k) B->resolved_points[(size_t)exact_of(B, raw_scans, listed[k], &patches[k])]++;
+    if (patch_round(call, k_ring_patch, patches, A.rec)) return call.st;
+  }
+  pvlm_i_trace("ring: upload + K16 + listed points");
+  (void)hipEventRecord(A.ev[2], ctx->stream);
+  return call.st;
+}
+
+// ---- K17; a scan whose +z crossing stays undecided gets the host's azimuths for the points of that comparison and is replayed
+static pvlm_status ring_columns(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A, const pvlm_raw_scan* raw_scans) {
+  const int n_scans = B->n_scans, n_rings = B->rings;
+  A.colpos = call.alloc<int2>((size_t)B->total_slots); A.ring_count = call.alloc<int>((size_t)n_scans * kMaxRings); A.status = call.alloc<int2>((size_t)n_scans);
+  std::vector<int2> status((size_t)n_scans, make_int2(-1, -1));
+  auto run = [&](size_t n, const int* d_todo) {
+    call.launch(k_ring_columns, dim3((unsigned)n), dim3(1024), 0, B->d_scans, d_todo, n_rings, B->horizon, A.rec, A.colpos, A.ring_count, A.status);
+    call.d2h(status.data(), A.status, (size_t)n_scans * sizeof(int2));
+    return call.sync();
+  };
+  if (run((size_t)n_scans, nullptr)) return call.st;
+  for (int round = 0;; ++round) {
+    std::vector<int> again;
+    for (int s = 0; s < n_scans; ++s) if (status[(size_t)s].x >= 0) again.push_back(s);
+    if (again.empty()) break;
+    std::vector<PointPatch> patches;
+    for (int s : again) {
+      const RingScan& sc = B->scans[(size_t)s];
+      B->replayed[(size_t)s]++;
+      const int at = status[(size_t)s].x, last = status[(size_t)s].y;
+      // after 64 rounds (never seen): the whole scan from the host libm, which cannot be undecided
+      const int lo = round < 64 ? at : 0, hi = round < 64 ? std::min(sc.n, at + n_rings + 1) : sc.n;
+      PointPatch pp;
+      if (round < 64 && last >= 0) { exact_of(B, raw_scans, sc.pt0 + last, &pp); patches.push_back(pp); }
+      for (int i = lo; i < hi; ++i) { exact_of(B, raw_scans, sc.pt0 + i, &pp); patches.push_back(pp); }
+    }
+    if (patch_round(call, k_ring_patch, patches, A.rec)) return call.st;
+    pvlm_call::batch replay(call);
+    if (run(again.size(), call.upload(again.data(), again.size()))) return call.st;
+  }
+  pvlm_i_trace("ring: K17");
+  (void)hipEventRecord(A.ev[3], call.ctx->stream);
+  return call.st;
+}
+
+// ---- K18
+static pvlm_status ring_scatter(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A) {
+  A.source = call.alloc<int>((size_t)B->total_points);
+  call.launch(k_ring_scatter, dim3((unsigned)A.n_blocks), dim3(256), 0, B->d_scans, A.blocks, B->horizon, A.raw, A.rec, A.colpos, A.ring_count, B->d_cloud_scan, A.source, B->d_rc, A.winner);
+  call.launch(k_ring_cells, dim3((unsigned)A.n_blocks), dim3(256), 0, B->d_scans, A.blocks, B->horizon, A.raw, A.rec, A.colpos, A.ring_count, A.winner, B->d_range_image, B->d_image_to_point);
+  (void)hipEventRecord(A.ev[4], call.ctx->stream);
+  return call.st;
+}
+
+// ---- K19 / K20: segmentation, with the host's libm for the undecided edges; K21
+static pvlm_status ring_segment(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A) {
+  pvlm_ctx* ctx = call.ctx;
+  const int n_scans = B->n_scans, n_rings = B->rings, horizon = B->horizon, cells = n_rings * horizon;
+  const size_t NP = (size_t)B->total_points, NC = (size_t)B->total_cells;
+  const dim3 cell_grid((unsigned)((cells + 255) / 256), (unsigned)n_scans);
+  A.root = call.alloc<int>(NC); A.comp_size = call.alloc<int>(NC); A.row_mask = call.alloc<unsigned long long>(NC);
+  if (B->segment) {
+    A.edges = call.alloc<unsigned char>(NC + 4); A.queries = call.alloc<EdgeQuery>((size_t)kQueryCap); A.parent = call.alloc<int>(NC);
+    // the constants of :1459-1462 and their sin / cos (:1510), float libm of the host
+    const float alpha_x = 0.2 / 180.0 * M_PI, alpha_y = 2.0 / 180.0 * M_PI, theta = 20.0 / 180.0 * M_PI;
+    const float sin_x = std::sin(alpha_x), cos_x = std::cos(alpha_x), sin_y = std::sin(alpha_y), cos_y = std::cos(alpha_y);
+    call.launch(k_seg_edges, cell_grid, dim3(256), 0, B->d_scans, n_rings, horizon, B->d_range_image, sin_x, cos_x, sin_y, cos_y, theta, A.edges, A.counter + 1, A.queries, kQueryCap);
+    int n_queries = 0;
+    call.d2h(&n_queries, A.counter + 1, sizeof(int));
+    if (call.sync()) return call.st;
+    if (n_queries > kQueryCap) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %d undecided segmentation edges (capacity %d)", n_queries, kQueryCap); return call.st = PVLM_ERR_REFUSED; }
+    if (n_queries > 0) {
+      std::vector<EdgeQuery> q((size_t)n_queries);
+      call.d2h(q.data(), A.queries, q.size() * sizeof(EdgeQuery));
+      if (call.sync()) return call.st;
+      std::vector<EdgePatch> ep;
+      for (const EdgeQuery& e : q) {
+        B->resolved_edges[(size_t)(e.cell / cells)]++;
+        if (std::atan2(e.y, e.x) > theta) ep.push_back(EdgePatch{e.cell, e.bit});
+      }
+      if (patch_round(call, k_seg_patch, ep, A.edges)) return call.st;
+    }
+    (void)hipEventRecord(A.ev[5], ctx->stream);
+    call.launch(k_seg_init, dim3((unsigned)n_rings, (unsigned)n_scans), dim3(256), 0, B->d_scans, horizon, A.edges, A.parent, A.comp_size, A.row_mask, B->d_image_to_point2);
+    call.launch(k_seg_union, cell_grid, dim3(256), 0, B->d_scans, n_rings, horizon, A.edges, A.parent);
+    call.launch(k_seg_stats, cell_grid, dim3(256), 0, B->d_scans, n_rings, horizon, A.parent, A.root, A.comp_size, A.row_mask);
+  } else {
+    call.memset(B->d_image_to_point2, 0xFF, NC * sizeof(int));
+    (void)hipEventRecord(A.ev[5], ctx->stream);
+  }
+  (void)hipEventRecord(A.ev[6], ctx->stream);
+  A.source2 = call.alloc<int>(NP); A.ring_col2 = call.alloc<int>(NP); A.range2 = call.alloc<float>(NP);
+  A.ring_count2 = call.alloc<int>((size_t)n_scans * kMaxRings); A.counts = call.alloc<int>((size_t)n_scans * 2);
+  call.launch(k_seg_compact, dim3((unsigned)n_scans), dim3(1024), 0, B->d_scans, n_rings, horizon, B->segment, A.ring_count, B->d_cloud_scan, A.source, B->d_rc, B->d_range_image,
+              A.root, A.comp_size, A.row_mask, B->d_cloud2, A.source2, A.ring_col2, A.range2, B->d_image_to_point2, A.ring_count2, A.counts);
+  return call.st;
+}
+
+// ---- K22 - K24: curvature, sector orders, picks; the finished per-point arrays start down the link beside K23 / K24
+static pvlm_status ring_curvature_picks(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A) {
+  pvlm_ctx* ctx = call.ctx;
+  const int n_scans = B->n_scans, n_rings = B->rings;
+  const size_t NP = (size_t)B->total_points;
+  hipStream_t S = ctx->stream;
+  A.curv = call.alloc<float>(NP); A.half = call.alloc<int>(NP); A.order = call.alloc<int>(NP);
+  A.sector = call.alloc<unsigned char>(A.n_sectors); A.ties = call.alloc<int4>(2 * A.n_sectors);
+  if (B->picks) {
+    A.state = call.alloc<unsigned char>(NP); A.corner = call.alloc<int>(A.n_ring_slots * (1 + kCornerSlots)); A.flat = call.alloc<int>(A.n_ring_slots * (1 + kFlatSlots));
+    A.vspan = call.alloc<int2>(A.n_ring_slots); A.voxels = call.alloc<float4>(A.voxel_cap); A.ring_host = call.alloc<unsigned char>(A.n_ring_slots);
+  }
+  call.launch(k_curvature, dim3((unsigned)A.n_blocks), dim3(256), 0, B->d_scans, A.blocks, A.ring_count2, A.counts, B->d_cloud2, A.range2, A.curv, A.half, A.order);
+  if (call.check_launches()) return call.st;       // a rejected launch must fail the batch: the arrays below would be copied down uninitialised (the caller's host path takes over)
+  // the five per-point arrays are final here: they go down the link on a second stream while K23 / K24 run (20 of the 27 B per point)
+  char* h = B->h_results;
+  const pvlm_ring_layout& L = A.lay;
+  if (!ctx->aux_stream && hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->aux_stream = nullptr; }
+  if (ctx->aux_stream && hipEventRecord(A.ev[8], S) == hipSuccess && hipStreamWaitEvent(ctx->aux_stream, A.ev[8], 0) == hipSuccess) A.second = ctx->aux_stream;
+  call.copy_pinned(h + L.source, A.source2, NP * 4, kDown, A.second); call.copy_pinned(h + L.ring_col, A.ring_col2, NP * 4, kDown, A.second);
+  if (!B->lazy_arrays) {
+    call.copy_pinned(h + L.curvature, A.curv, NP * 4, kDown, A.second); call.copy_pinned(h + L.half, A.half, NP * 4, kDown, A.second);
+    call.copy_pinned(h + L.range, A.range2, NP * 4, kDown, A.second);
+  }
+  call.launch(k_sector_sort, dim3((unsigned)(n_rings * 6), (unsigned)n_scans), dim3(256), 0, B->d_scans, n_rings, A.ring_count2, A.counts, A.curv, stdsort_selfcheck() ? 1 : 0, A.order,
+              A.sector, A.counter + 2, A.ties, (int)A.n_sectors);
+  const unsigned waves = 256u * 16u;                                     // persistent: every wave walks the list with a grid stride
+  call.launch(k_sector_ties<kTieSmall>, dim3(waves), dim3(64), 0, B->d_scans, A.ties, A.counter + 2, A.curv, A.order, A.sector);
+  call.launch(k_sector_ties<kSectorMax>, dim3(waves / 4), dim3(64), 0, B->d_scans, A.ties + A.n_sectors, A.counter + 3, A.curv, A.order, A.sector);
+  if (call.check_launches()) return call.st;       // K23: sector orders / flags of a launch that did not run are pool garbage
+  if (B->picks) {
+    const int ring_cap = std::min(B->horizon, 4096);                       // a ring holds one point per column; longer rings are refused by the kernel (-> host)
+    PickArrays P;
+    P.scans = B->d_scans; P.ring_count2 = A.ring_count2; P.counts = A.counts; P.cloud2 = B->d_cloud2; P.range2 = A.range2; P.curvature = A.curv; P.half_window = A.half;
+    P.order = A.order; P.sector_host = A.sector; P.state = A.state; P.corner = A.corner; P.flat = A.flat; P.voxel_span = A.vspan; P.voxels = A.voxels;
+    P.voxel_counter = A.counter + 4; P.voxel_cap = (int)A.voxel_cap; P.ring_host = A.ring_host;
+    call.launch(k_ring_picks, dim3((unsigned)n_rings, (unsigned)n_scans), dim3(64), pick_lds_bytes(ring_cap), P, n_rings, ring_cap, B->max_curvature, B->angle_threshold);
+    if (call.check_launches()) return call.st;     // K24 (dynamic LDS up to ~56 KB): ring_host / pick lists of a rejected launch must not reach AssemblePicks
+  }
+  (void)hipEventRecord(A.ev[7], S);
+  return call.st;
+}
+
+// ---- results: what K23 / K24 finished goes down on the main stream, the small tables through the frame
+static pvlm_status ring_results(pvlm_call& call, pvlm_ring_batch* B, RingArrays& A) {
+  const int n_scans = B->n_scans, n_rings = B->rings;
+  const size_t NP = (size_t)B->total_points, slots = A.n_ring_slots;
+  hipStream_t S = call.ctx->stream;
+  char* h = B->h_results;
+  const pvlm_ring_layout& L = A.lay;
+  if (!B->lazy_arrays) { call.copy_pinned(h + L.order, A.order, NP * 4, kDown, S); call.copy_pinned(h + L.sector, A.sector, A.n_sectors, kDown, S); }
+  int n_voxels = 0;
+  if (B->picks) {
+    call.copy_pinned(h + L.state, A.state, NP, kDown, S); call.copy_pinned(h + L.corner, A.corner, slots * (1 + kCornerSlots) * 4, kDown, S);
+    call.copy_pinned(h + L.flat, A.flat, slots * (1 + kFlatSlots) * 4, kDown, S); call.copy_pinned(h + L.voxel_span, A.vspan, slots * 8, kDown, S);
+    call.copy_pinned(h + L.ring_host, A.ring_host, slots, kDown, S);
+    call.d2h(&n_voxels, A.counter + 4, sizeof(int));
+  }
+  call.d2h(B->counts.data(), A.counts, (size_t)n_scans * 2 * sizeof(int));
+  call.d2h(B->ring_count.data(), A.ring_count, (size_t)n_scans * kMaxRings * sizeof(int));
+  call.d2h(B->ring_count2.data(), A.ring_count2, (size_t)n_scans * kMaxRings * sizeof(int));
+  if (B->picks) {                                                  // the centroids: as many as the rings reserved (rings that overflowed the budget are flagged)
+    if (call.sync()) return call.st;
+    B->n_voxels = (int)std::min<size_t>((size_t)std::max(n_voxels, 0), A.voxel_cap);
+    call.copy_pinned(h + L.voxels, A.voxels, (size_t)B->n_voxels * 16, kDown, S);
+    // the ring flags are on the host (the synchronisation above): the five per-point arrays — 16 of the 27 B per point of round 5's download — come down only
+    // for the scans with a ring K24 left to the host (incidence angle at the libm threshold, a sector with ties beyond the kernel's bounds: 0-6 % of the scans)
+    for (int sc = 0; sc < n_scans && B->lazy_arrays; ++sc) {
+      bool undecided = false;
+      for (int q = 0; q < n_rings && !undecided; ++q) undecided = B->h_ring_host[(size_t)sc * n_rings + q] != 0;
+      if (!undecided) continue;
+      const size_t p0 = (size_t)B->scans[(size_t)sc].pt0, np = (size_t)B->scans[(size_t)sc].n, f0 = (size_t)sc * n_rings * 6;
+      call.copy_pinned(h + L.curvature + p0 * 4, A.curv + p0, np * 4, kDown, S); call.copy_pinned(h + L.half + p0 * 4, A.half + p0, np * 4, kDown, S);
+      call.copy_pinned(h + L.range + p0 * 4, A.range2 + p0, np * 4, kDown, S); call.copy_pinned(h + L.order + p0 * 4, A.order + p0, np * 4, kDown, S);
+      call.copy_pinned(h + L.sector + f0, A.sector + f0, (size_t)n_rings * 6, kDown, S);
+      B->has_arrays[(size_t)sc] = 1;
+    }
+  }
+  if (call.st) return call.st;
+  PVLM_HIP(call.ctx, hipStreamSynchronize(A.second));
+  (void)hipEventRecord(A.ev[8], S);
+  if (call.sync()) return call.st;
+  pvlm_i_trace("ring: segmentation, curvature, download");
+  for (int k = 0; k < 8; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, A.ev[k], A.ev[k + 1]) == hipSuccess) B->ms[k] = ms; }
+  return PVLM_OK;
+}
+
+static pvlm_status ring_run(pvlm_call& call, pvlm_ring_batch* B, int n_scans, const pvlm_raw_scan* raw_scans, int n_rings, int horizon, int segment, long long total,
                             int picks, float max_curvature, float angle_threshold) {
+  pvlm_ctx* ctx = call.ctx;
   B->picks = picks ? 1 : 0; B->max_curvature = max_curvature; B->angle_threshold = angle_threshold;
   B->ctx = ctx; B->n_scans = n_scans; B->rings = n_rings; B->horizon = horizon; B->segment = (segment & 1) ? 1 : 0;
   B->lazy_arrays = picks != 0 && (segment & 2) == 0;       // bit 1 of `segment`: always deliver the per-point arrays (parity tests, traces)
@@ -529,281 +809,16 @@ static pvlm_status ring_run(pvlm_ctx* ctx, pvlm_ring_batch* B, int n_scans, cons
     }
   }
   if (n_scans == 0 || total == 0) return PVLM_OK;
-  // ---- device memory: everything from the context's pool; the scratch goes back at the end of the call
-  pvlm_dev_scratch tmp(ctx);
-  const size_t NP = (size_t)total, NC = (size_t)B->total_cells, NS = (size_t)B->total_slots;
-  float4* d_raw = nullptr; PointRec* d_rec = nullptr; int* d_listed = nullptr; int* d_counter = nullptr;
-  int2* d_colpos = nullptr; int* d_ring_count = nullptr; int2* d_status = nullptr; PtBlock* d_blocks = nullptr; int* d_source = nullptr; int* d_winner = nullptr;
-  unsigned char* d_edges = nullptr; EdgeQuery* d_queries = nullptr; int* d_parent = nullptr; int* d_root = nullptr; int* d_comp_size = nullptr;
-  unsigned long long* d_row_mask = nullptr; int* d_source2 = nullptr; int* d_ring_col2 = nullptr; float* d_range2 = nullptr; int* d_ring_count2 = nullptr;
-  int* d_counts = nullptr; float* d_curv = nullptr; int* d_half = nullptr; int* d_order = nullptr; unsigned char* d_sector = nullptr; int4* d_ties = nullptr;
-  const size_t n_sectors = (size_t)n_scans * n_rings * 6;
-  const int query_cap = 1 << 16;
-  pvlm_status st = PVLM_OK;
-#define RING_GET(ptr, count) if (!st) st = tmp.alloc(&ptr, count)
-#define RING_KEEP(ptr, count) if (!st) st = pvlm_i_alloc(ctx, &ptr, count)
-  RING_KEEP(B->d_scans, (size_t)n_scans); RING_KEEP(B->d_cloud_scan, NP); RING_KEEP(B->d_rc, NP); RING_KEEP(B->d_range_image, NC);
-  RING_KEEP(B->d_image_to_point, NC); RING_KEEP(B->d_cloud2, NP); RING_KEEP(B->d_image_to_point2, NC);
-  RING_GET(d_raw, NP); RING_GET(d_rec, NS); RING_GET(d_listed, NP); RING_GET(d_counter, 8);
-  RING_GET(d_colpos, NS); RING_GET(d_ring_count, (size_t)n_scans * kMaxRings); RING_GET(d_status, (size_t)n_scans); RING_GET(d_blocks, blocks.size());
-  RING_GET(d_source, NP); RING_GET(d_winner, NC); RING_GET(d_edges, NC + 4); RING_GET(d_queries, (size_t)query_cap); RING_GET(d_parent, NC);
-  RING_GET(d_root, NC); RING_GET(d_comp_size, NC); RING_GET(d_row_mask, NC); RING_GET(d_source2, NP); RING_GET(d_ring_col2, NP); RING_GET(d_range2, NP);
-  RING_GET(d_ring_count2, (size_t)n_scans * kMaxRings); RING_GET(d_counts, (size_t)n_scans * 2); RING_GET(d_curv, NP); RING_GET(d_half, NP);
-  RING_GET(d_order, NP); RING_GET(d_sector, n_sectors); RING_GET(d_ties, 2 * n_sectors);
-  // K24: one centroid per four points is the batch's budget (a Room scan needs one per ten); rings beyond it go to the host like any undecided ring
-  const size_t n_ring_slots = (size_t)n_scans * n_rings, voxel_cap = NP / 4 + 64;
-  unsigned char* d_state = nullptr; int* d_corner = nullptr; int* d_flat = nullptr; int2* d_vspan = nullptr; float4* d_voxels = nullptr; unsigned char* d_ring_host = nullptr;
-  if (picks) {
-    RING_GET(d_state, NP); RING_GET(d_corner, n_ring_slots * (1 + kCornerSlots)); RING_GET(d_flat, n_ring_slots * (1 + kFlatSlots)); RING_GET(d_vspan, n_ring_slots);
-    RING_GET(d_voxels, voxel_cap); RING_GET(d_ring_host, n_ring_slots);
-  }
-#undef RING_GET
-#undef RING_KEEP
-  if (st) return (st);
-  pvlm_i_trace("ring: device memory");
-  // ---- pinned buffer: raw points on the way up (16 B / point), the six result arrays (24 B / point) and the sector flags on the way down
-  // with K24: + states (1 B / point), the per-ring lists and the centroids (16 B each, voxel_cap of them at most)
-  const size_t picks_fixed = picks ? NP + n_ring_slots * ((1 + kCornerSlots) * 4 + (1 + kFlatSlots) * 4 + 8 + 1) + 64 : 0;
-  const size_t pinned = NP * 24 + n_sectors + 256 + picks_fixed + (picks ? voxel_cap * 16 : 0);
-  B->h_results = (char*)pvlm_i_pinned_take(ctx, pinned, &B->results_bytes);
-  if (!B->h_results) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %zu bytes of pinned memory unavailable", pinned); return (PVLM_ERR_NOMEM); }
-  pvlm_i_trace("ring: pinned buffer");
-  hipStream_t S = ctx->stream;
-  hipEvent_t ev[9];
-  for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) { PVLM_SET_ERR(ctx, "hipEventCreate failed"); return (PVLM_ERR_HIP); }
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 9; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
-  {   // staging copy, scan-parallel (a scan's points are contiguous when stride_floats == 4)
-    float4* h = (float4*)B->h_results;
-    std::atomic<int> next{0};
-    std::atomic<long long> bad{-1};
-    auto work = [&]() {
-      for (int s = next++; s < n_scans; s = next++) {
-        const pvlm_raw_scan& r = raw_scans[s];
-        float4* d = h + B->scans[(size_t)s].pt0;
-        if (r.stride_floats == 4) std::memcpy(d, r.xyzi, (size_t)r.n * 16);
-        else for (int i = 0; i < r.n; ++i) { const float* p = r.xyzi + (size_t)i * r.stride_floats; d[i] = make_float4(p[0], p[1], p[2], p[3]); }
-        for (int i = 0; i < r.n; ++i)
-          if (!std::isfinite(d[i].x) || !std::isfinite(d[i].y) || !std::isfinite(d[i].z)) { bad = B->scans[(size_t)s].pt0 + i; break; }
-      }
-    };
-    const size_t n_threads = std::max<size_t>(1, std::min<size_t>({pvlm_thread_cap(), (size_t)n_scans / 32 + 1, (size_t)std::max(1u, std::thread::hardware_concurrency())}));
-    pvlm_run_workers(n_threads, work);
-    if (bad >= 0) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: non-finite coordinate (point %lld of the batch)", (long long)bad); return PVLM_ERR_REFUSED; }
-  }
-  pvlm_i_trace("ring: staging copy");
-  (void)hipEventRecord(ev[0], S);
-  PVLM_HIP(ctx, hipMemcpyAsync(d_raw, B->h_results, NP * 16, hipMemcpyHostToDevice, S));
-  PVLM_HIP(ctx, hipMemcpyAsync(B->d_scans, B->scans.data(), (size_t)n_scans * sizeof(RingScan), hipMemcpyHostToDevice, S));
-  PVLM_HIP(ctx, hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(PtBlock), hipMemcpyHostToDevice, S));
-  PVLM_HIP(ctx, hipMemsetAsync(d_counter, 0, 8 * sizeof(int), S));
-  PVLM_HIP(ctx, hipMemsetAsync(d_winner, 0xFF, NC * sizeof(int), S));
-  PVLM_HIP(ctx, hipMemsetAsync(B->d_range_image, 0, NC * sizeof(float), S));
-  PVLM_HIP(ctx, hipMemsetAsync(B->d_image_to_point, 0xFF, NC * sizeof(int), S));
-  (void)hipEventRecord(ev[1], S);
-  // ---- K16 + the host's libm for the listed points
-  hipLaunchKernelGGL(k_ring_classify, dim3((unsigned)blocks.size()), dim3(256), 0, S, B->d_scans, d_blocks, n_rings, horizon, d_raw, d_rec, d_counter, d_listed);
-  int h_counter[4] = {0, 0, 0, 0};
-  PVLM_HIP(ctx, hipMemcpyAsync(h_counter, d_counter, sizeof(int), hipMemcpyDeviceToHost, S));
-  PVLM_HIP(ctx, hipStreamSynchronize(S));      // also: the staging buffer is free again
-  auto scan_of = [&](long long at) { int lo = 0, hi = n_scans - 1; while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (B->scans[(size_t)mid].pt0 <= at) lo = mid; else hi = mid - 1; } return lo; };
-  auto exact_of = [&](long long at, PointPatch* pp) {
-    const int s = scan_of(at);
-    const pvlm_raw_scan& r = raw_scans[s];
-    const float* p = r.xyzi + (size_t)(at - B->scans[(size_t)s].pt0) * r.stride_floats;
-    const float q = -p[1] / std::sqrt(p[0] * p[0] + p[2] * p[2]);
-    const RingScan& sc = B->scans[(size_t)s];
-    pp->slot = sc.slot0 + chunk_slot((int)(at - sc.pt0), chunk_of(sc.n, kColumnThreads), kColumnThreads);
-    pp->az = std::atan2(p[0], p[2]); pp->ring = q == q ? ring_of_atan(std::atan(q), n_rings) : -1;
-    return s;
-  };
-  std::vector<PointPatch> patches;
-  PointPatch* d_patch = nullptr;
-  auto send_patches = [&]() -> pvlm_status {
-    if (patches.empty()) return PVLM_OK;
-    pvlm_i_free(ctx, d_patch); d_patch = nullptr;
-    pvlm_status s2 = pvlm_i_alloc(ctx, &d_patch, patches.size());
-    if (s2) return s2;
-    PVLM_HIP(ctx, hipMemcpyAsync(d_patch, patches.data(), patches.size() * sizeof(PointPatch), hipMemcpyHostToDevice, S));
-    hipLaunchKernelGGL(k_ring_patch, dim3((unsigned)((patches.size() + 255) / 256)), dim3(256), 0, S, (int)patches.size(), d_patch, d_rec);
-    PVLM_HIP(ctx, hipStreamSynchronize(S));     // `patches` is pageable
-    return PVLM_OK;
-  };
-  if (h_counter[0] > 0) {
-    std::vector<int> listed((size_t)h_counter[0]);
-    PVLM_HIP(ctx, hipMemcpy(listed.data(), d_listed, listed.size() * sizeof(int), hipMemcpyDeviceToHost));
-    patches.resize(listed.size());
-    for (size_t k = 0; k < listed.size(); ++k) B->resolved_points[(size_t)exact_of(listed[k], &patches[k])]++;
-    if ((st = send_patches())) { pvlm_i_free(ctx, d_patch); return (st); }
-  }
-  pvlm_i_trace("ring: upload + K16 + listed points");
-  (void)hipEventRecord(ev[2], S);
-  // ---- K17; a scan whose +z crossing stays undecided gets the host's azimuths for the points of that comparison and is replayed
-  hipLaunchKernelGGL(k_ring_columns, dim3((unsigned)n_scans), dim3(1024), 0, S, B->d_scans, (const int*)nullptr, n_rings, horizon, d_rec, d_colpos,
-                     d_ring_count, d_status);
-  std::vector<int2> status((size_t)n_scans, make_int2(-1, -1));
-  PVLM_HIP(ctx, hipMemcpyAsync(status.data(), d_status, (size_t)n_scans * sizeof(int2), hipMemcpyDeviceToHost, S));
-  PVLM_HIP(ctx, hipStreamSynchronize(S));
-  for (int round = 0;; ++round) {
-    std::vector<int> again;
-    for (int s = 0; s < n_scans; ++s) if (status[(size_t)s].x >= 0) again.push_back(s);
-    if (again.empty()) break;
-    patches.clear();
-    for (int s : again) {
-      const RingScan& sc = B->scans[(size_t)s];
-      B->replayed[(size_t)s]++;
-      const int at = status[(size_t)s].x, last = status[(size_t)s].y;
-      // after 64 rounds (never seen): the whole scan from the host libm, which cannot be undecided
-      const int lo = round < 64 ? at : 0, hi = round < 64 ? std::min(sc.n, at + n_rings + 1) : sc.n;
-      PointPatch pp;
-      if (round < 64 && last >= 0) { exact_of(sc.pt0 + last, &pp); patches.push_back(pp); }
-      for (int i = lo; i < hi; ++i) { exact_of(sc.pt0 + i, &pp); patches.push_back(pp); }
-    }
-    if ((st = send_patches())) { pvlm_i_free(ctx, d_patch); return (st); }
-    int* d_again = nullptr;
-    if ((st = pvlm_i_alloc(ctx, &d_again, again.size()))) { pvlm_i_free(ctx, d_patch); return (st); }
-    hipError_t e = hipMemcpyAsync(d_again, again.data(), again.size() * sizeof(int), hipMemcpyHostToDevice, S);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_ring_columns, dim3((unsigned)again.size()), dim3(1024), 0, S, B->d_scans, (const int*)d_again, n_rings, horizon, d_rec, d_colpos,
-                         d_ring_count, d_status);
-      e = hipMemcpyAsync(status.data(), d_status, (size_t)n_scans * sizeof(int2), hipMemcpyDeviceToHost, S);
-      if (e == hipSuccess) e = hipStreamSynchronize(S);
-    }
-    pvlm_i_free(ctx, d_again);
-    if (e != hipSuccess) { pvlm_i_free(ctx, d_patch); PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: replay failed: %s", hipGetErrorString(e)); return (PVLM_ERR_HIP); }
-  }
-  pvlm_i_free(ctx, d_patch); d_patch = nullptr;
-  pvlm_i_trace("ring: K17");
-  (void)hipEventRecord(ev[3], S);
-  // ---- K18
-  hipLaunchKernelGGL(k_ring_scatter, dim3((unsigned)blocks.size()), dim3(256), 0, S, B->d_scans, d_blocks, horizon, d_raw, d_rec, d_colpos, d_ring_count, B->d_cloud_scan, d_source,
-                     B->d_rc, d_winner);
-  hipLaunchKernelGGL(k_ring_cells, dim3((unsigned)blocks.size()), dim3(256), 0, S, B->d_scans, d_blocks, horizon, d_raw, d_rec, d_colpos, d_ring_count, d_winner, B->d_range_image,
-                     B->d_image_to_point);
-  (void)hipEventRecord(ev[4], S);
-  // ---- K19 / K20: segmentation
-  const dim3 cell_grid((unsigned)((cells + 255) / 256), (unsigned)n_scans);
-  if (B->segment) {
-    // the constants of :1459-1462 and their sin / cos (:1510), float libm of the host
-    const float alpha_x = 0.2 / 180.0 * M_PI, alpha_y = 2.0 / 180.0 * M_PI, theta = 20.0 / 180.0 * M_PI;
-    const float sin_x = std::sin(alpha_x), cos_x = std::cos(alpha_x), sin_y = std::sin(alpha_y), cos_y = std::cos(alpha_y);
-    hipLaunchKernelGGL(k_seg_edges, cell_grid, dim3(256), 0, S, B->d_scans, n_rings, horizon, B->d_range_image, sin_x, cos_x, sin_y, cos_y, theta, d_edges, d_counter + 1, d_queries, query_cap);
-    PVLM_HIP(ctx, hipMemcpyAsync(h_counter + 1, d_counter + 1, sizeof(int), hipMemcpyDeviceToHost, S));
-    PVLM_HIP(ctx, hipStreamSynchronize(S));
-    if (h_counter[1] > query_cap) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: %d undecided segmentation edges (capacity %d)", h_counter[1], query_cap); return (PVLM_ERR_REFUSED); }
-    if (h_counter[1] > 0) {
-      std::vector<EdgeQuery> q((size_t)h_counter[1]);
-      PVLM_HIP(ctx, hipMemcpy(q.data(), d_queries, q.size() * sizeof(EdgeQuery), hipMemcpyDeviceToHost));
-      std::vector<EdgePatch> ep;
-      for (const EdgeQuery& e : q) {
-        B->resolved_edges[(size_t)(e.cell / cells)]++;
-        if (std::atan2(e.y, e.x) > theta) ep.push_back(EdgePatch{e.cell, e.bit});
-      }
-      if (!ep.empty()) {
-        EdgePatch* d_ep = nullptr;
-        if ((st = pvlm_i_alloc(ctx, &d_ep, ep.size()))) return (st);
-        hipError_t e = hipMemcpyAsync(d_ep, ep.data(), ep.size() * sizeof(EdgePatch), hipMemcpyHostToDevice, S);
-        if (e == hipSuccess) { hipLaunchKernelGGL(k_seg_patch, dim3((unsigned)((ep.size() + 255) / 256)), dim3(256), 0, S, (int)ep.size(), d_ep, d_edges); e = hipStreamSynchronize(S); }
-        pvlm_i_free(ctx, d_ep);
-        if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: edge patch failed: %s", hipGetErrorString(e)); return (PVLM_ERR_HIP); }
-      }
-    }
-    (void)hipEventRecord(ev[5], S);
-    hipLaunchKernelGGL(k_seg_init, dim3((unsigned)n_rings, (unsigned)n_scans), dim3(256), 0, S, B->d_scans, horizon, d_edges, d_parent, d_comp_size, d_row_mask, B->d_image_to_point2);
-    hipLaunchKernelGGL(k_seg_union, cell_grid, dim3(256), 0, S, B->d_scans, n_rings, horizon, d_edges, d_parent);
-    hipLaunchKernelGGL(k_seg_stats, cell_grid, dim3(256), 0, S, B->d_scans, n_rings, horizon, d_parent, d_root, d_comp_size, d_row_mask);
-  } else {
-    PVLM_HIP(ctx, hipMemsetAsync(B->d_image_to_point2, 0xFF, NC * sizeof(int), S));
-    (void)hipEventRecord(ev[5], S);
-  }
-  (void)hipEventRecord(ev[6], S);
-  // ---- K21 / K22
-  hipLaunchKernelGGL(k_seg_compact, dim3((unsigned)n_scans), dim3(1024), 0, S, B->d_scans, n_rings, horizon, B->segment, d_ring_count, B->d_cloud_scan, d_source, B->d_rc,
-                     B->d_range_image, d_root, d_comp_size, d_row_mask, B->d_cloud2, d_source2, d_ring_col2, d_range2, B->d_image_to_point2, d_ring_count2, d_counts);
-  hipLaunchKernelGGL(k_curvature, dim3((unsigned)blocks.size()), dim3(256), 0, S, B->d_scans, d_blocks, d_ring_count2, d_counts, B->d_cloud2, d_range2, d_curv, d_half, d_order);
-  PVLM_HIP(ctx, hipGetLastError());       // a rejected launch must fail the batch: the arrays below would be copied down uninitialised (the caller's host path takes over)
-  // the five per-point arrays are final here: they go down the link on a second stream while K23 / K24 run (20 of the 27 B per point)
-  char* h = B->h_results;
-  hipStream_t S2 = S;
-  if (!ctx->aux_stream && hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->aux_stream = nullptr; }
-  if (ctx->aux_stream && hipEventRecord(ev[8], S) == hipSuccess && hipStreamWaitEvent(ctx->aux_stream, ev[8], 0) == hipSuccess) S2 = ctx->aux_stream;
-  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{S2};        // before the scratch goes back to the pool, on every exit path
-  PVLM_HIP(ctx, hipMemcpyAsync(h, d_source2, NP * 4, hipMemcpyDeviceToHost, S2));
-  PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 4, d_ring_col2, NP * 4, hipMemcpyDeviceToHost, S2));
-  if (!B->lazy_arrays) {
-    PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 8, d_curv, NP * 4, hipMemcpyDeviceToHost, S2));
-    PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 12, d_half, NP * 4, hipMemcpyDeviceToHost, S2));
-    PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 16, d_range2, NP * 4, hipMemcpyDeviceToHost, S2));
-  }
-  hipLaunchKernelGGL(k_sector_sort, dim3((unsigned)(n_rings * 6), (unsigned)n_scans), dim3(256), 0, S, B->d_scans, n_rings, d_ring_count2, d_counts, d_curv, stdsort_selfcheck() ? 1 : 0, d_order, d_sector, d_counter + 2, d_ties, (int)n_sectors);
-  {
-    const unsigned waves = 256u * 16u;                                     // persistent: every wave walks the list with a grid stride
-    hipLaunchKernelGGL(k_sector_ties<kTieSmall>, dim3(waves), dim3(64), 0, S, B->d_scans, d_ties, d_counter + 2, d_curv, d_order, d_sector);
-    hipLaunchKernelGGL(k_sector_ties<kSectorMax>, dim3(waves / 4), dim3(64), 0, S, B->d_scans, d_ties + n_sectors, d_counter + 3, d_curv, d_order, d_sector);
-    PVLM_HIP(ctx, hipGetLastError());     // K23: sector orders / flags of a launch that did not run are pool garbage
-  }
-  int ring_cap = 0;
-  if (picks) {
-    ring_cap = std::min(horizon, 4096);                       // a ring holds one point per column; longer rings are refused by the kernel (-> host)
-    PickArrays A;
-    A.scans = B->d_scans; A.ring_count2 = d_ring_count2; A.counts = d_counts; A.cloud2 = B->d_cloud2; A.range2 = d_range2; A.curvature = d_curv; A.half_window = d_half;
-    A.order = d_order; A.sector_host = d_sector; A.state = d_state; A.corner = d_corner; A.flat = d_flat; A.voxel_span = d_vspan; A.voxels = d_voxels;
-    A.voxel_counter = d_counter + 4; A.voxel_cap = (int)voxel_cap; A.ring_host = d_ring_host;
-    const size_t lds = pick_lds_bytes(ring_cap);
-    hipLaunchKernelGGL(k_ring_picks, dim3((unsigned)n_rings, (unsigned)n_scans), dim3(64), lds, S, A, n_rings, ring_cap, max_curvature, angle_threshold);
-    PVLM_HIP(ctx, hipGetLastError());     // K24 (dynamic LDS up to ~56 KB): ring_host / pick lists of a rejected launch must not reach AssemblePicks
-  }
-  (void)hipEventRecord(ev[7], S);
-  // ---- results
-  B->h_source = (const int*)h; B->h_ring_col = (const int*)(h + NP * 4); B->h_curvature = (const float*)(h + NP * 8); B->h_half = (const int*)(h + NP * 12);
-  B->h_range = (const float*)(h + NP * 16); B->h_order = (const int*)(h + NP * 20); B->h_sector_host = (const unsigned char*)(h + NP * 24);
-  if (!B->lazy_arrays) {
-    PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 20, d_order, NP * 4, hipMemcpyDeviceToHost, S));
-    PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 24, d_sector, n_sectors, hipMemcpyDeviceToHost, S));
-  }
-  char* hp = h + NP * 24 + ((n_sectors + 63) / 64) * 64;       // K24's results behind the sector flags
-  int h_voxel_count = 0;
-  if (picks) {
-    char* q = hp;
-    B->h_state = (const unsigned char*)q; PVLM_HIP(ctx, hipMemcpyAsync(q, d_state, NP, hipMemcpyDeviceToHost, S)); q += (NP + 63) / 64 * 64;
-    B->h_corner = (const int*)q; PVLM_HIP(ctx, hipMemcpyAsync(q, d_corner, n_ring_slots * (1 + kCornerSlots) * 4, hipMemcpyDeviceToHost, S)); q += n_ring_slots * (1 + kCornerSlots) * 4;
-    B->h_flat = (const int*)q; PVLM_HIP(ctx, hipMemcpyAsync(q, d_flat, n_ring_slots * (1 + kFlatSlots) * 4, hipMemcpyDeviceToHost, S)); q += n_ring_slots * (1 + kFlatSlots) * 4;
-    B->h_voxel_span = (const int*)q; PVLM_HIP(ctx, hipMemcpyAsync(q, d_vspan, n_ring_slots * 8, hipMemcpyDeviceToHost, S)); q += n_ring_slots * 8;
-    B->h_ring_host = (const unsigned char*)q; PVLM_HIP(ctx, hipMemcpyAsync(q, d_ring_host, n_ring_slots, hipMemcpyDeviceToHost, S)); q += (n_ring_slots + 63) / 64 * 64;
-    B->h_voxels = (const float*)q;
-    PVLM_HIP(ctx, hipMemcpyAsync(&h_voxel_count, d_counter + 4, sizeof(int), hipMemcpyDeviceToHost, S));
-  }
-  PVLM_HIP(ctx, hipMemcpyAsync(B->counts.data(), d_counts, (size_t)n_scans * 2 * sizeof(int), hipMemcpyDeviceToHost, S));
-  PVLM_HIP(ctx, hipMemcpyAsync(B->ring_count.data(), d_ring_count, (size_t)n_scans * kMaxRings * sizeof(int), hipMemcpyDeviceToHost, S));
-  PVLM_HIP(ctx, hipMemcpyAsync(B->ring_count2.data(), d_ring_count2, (size_t)n_scans * kMaxRings * sizeof(int), hipMemcpyDeviceToHost, S));
-  if (picks) {                                                  // the centroids: as many as the rings reserved (rings that overflowed the budget are flagged)
-    PVLM_HIP(ctx, hipStreamSynchronize(S));
-    B->n_voxels = (int)std::min<size_t>((size_t)std::max(h_voxel_count, 0), voxel_cap);
-    if (B->n_voxels > 0) PVLM_HIP(ctx, hipMemcpyAsync(const_cast<float*>(B->h_voxels), d_voxels, (size_t)B->n_voxels * 16, hipMemcpyDeviceToHost, S));
-    if (B->lazy_arrays) {
-      // the ring flags are on the host (the synchronisation above): the five per-point arrays — 16 of the 27 B per point of round 5's download — come down only
-      // for the scans with a ring K24 left to the host (incidence angle at the libm threshold, a sector with ties beyond the kernel's bounds: 0-6 % of the scans)
-      for (int sc = 0; sc < n_scans; ++sc) {
-        bool undecided = false;
-        for (int q = 0; q < n_rings && !undecided; ++q) undecided = B->h_ring_host[(size_t)sc * n_rings + q] != 0;
-        if (!undecided) continue;
-        const size_t p0 = (size_t)B->scans[(size_t)sc].pt0, np = (size_t)B->scans[(size_t)sc].n;
-        if (np) {
-          PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 8 + p0 * 4, d_curv + p0, np * 4, hipMemcpyDeviceToHost, S));
-          PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 12 + p0 * 4, d_half + p0, np * 4, hipMemcpyDeviceToHost, S));
-          PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 16 + p0 * 4, d_range2 + p0, np * 4, hipMemcpyDeviceToHost, S));
-          PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 20 + p0 * 4, d_order + p0, np * 4, hipMemcpyDeviceToHost, S));
-        }
-        PVLM_HIP(ctx, hipMemcpyAsync(h + NP * 24 + (size_t)sc * n_rings * 6, d_sector + (size_t)sc * n_rings * 6, (size_t)n_rings * 6, hipMemcpyDeviceToHost, S));
-        B->has_arrays[(size_t)sc] = 1;
-      }
-    }
-  }
-  PVLM_HIP(ctx, hipStreamSynchronize(S2));
-  (void)hipEventRecord(ev[8], S);
-  PVLM_HIP(ctx, hipStreamSynchronize(S));
-  pvlm_i_trace("ring: segmentation, curvature, download");
-  for (int k = 0; k < 8; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) B->ms[k] = ms; }
-  return PVLM_OK;
+  // the events' guard stands before the first hipEventCreate: a failed creation leaves nothing behind
+  struct Events { hipEvent_t e[9] = {}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;
+  for (hipEvent_t& e : events.e) if (hipEventCreate(&e) != hipSuccess) { e = nullptr; PVLM_SET_ERR(ctx, "hipEventCreate failed"); return PVLM_ERR_HIP; }
+  RingArrays A{};
+  A.n_blocks = blocks.size(); A.n_sectors = (size_t)n_scans * n_rings * 6; A.n_ring_slots = (size_t)n_scans * n_rings; A.ev = events.e; A.second = ctx->stream;
+  // Drains the second stream on every exit path.  It stands behind the caller's frame and dies before it: its copies read scratch that the frame returns.
+  struct Drain { RingArrays& a; ~Drain() { (void)hipStreamSynchronize(a.second); } } drain{A};
+  if (ring_classify(call, B, A, raw_scans, blocks) || ring_columns(call, B, A, raw_scans) || ring_scatter(call, B, A) || ring_segment(call, B, A) || ring_curvature_picks(call, B, A))
+    return call.st;
+  return ring_results(call, B, A);
 }
 
 extern "C" {
@@ -845,13 +860,13 @@ static pvlm_status ring_extract(pvlm_ctx* ctx, int n_scans, const pvlm_raw_scan*
     total += raw_scans[s].n;
   }
   if (total >= (1ll << 31) || (long long)n_scans * n_rings * horizon >= (1ll << 31)) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: batch too large (split it)"); return PVLM_ERR_ARG; }
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  if (ctx->capturing) { PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch inside a graph capture"); return PVLM_ERR_STATE; }
+  pvlm_call call(ctx, "pvlm_ring_extract_batch");
+  if (call.enter()) return call.st;
   pvlm_ring_batch* B = new (std::nothrow) pvlm_ring_batch();
   if (!B) return PVLM_ERR_NOMEM;
   pvlm_status st = PVLM_ERR_HIP;
   try {
-    st = ring_run(ctx, B, n_scans, raw_scans, n_rings, horizon, segment, total, picks, max_curvature, angle_threshold);
+    st = ring_run(call, B, n_scans, raw_scans, n_rings, horizon, segment, total, picks, max_curvature, angle_threshold);
   } catch (const std::bad_alloc&) {
     PVLM_SET_ERR(ctx, "pvlm_ring_extract_batch: out of host memory");
     st = PVLM_ERR_NOMEM;
@@ -891,21 +906,16 @@ pvlm_status pvlm_ring_batch_scan(const pvlm_ring_batch* b, int scan, pvlm_ring_r
 
 pvlm_status pvlm_ring_debug_sort(pvlm_ctx* ctx, const unsigned* keys, int n, int* order) {
   if (!ctx || !keys || !order || n < 1 || n > 4096) return PVLM_ERR_ARG;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  unsigned* d_keys = nullptr; int* d_order = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_keys, (size_t)n);
-  if (!st) st = pvlm_i_alloc(ctx, &d_order, (size_t)n + 1);
-  if (st) { pvlm_i_free(ctx, d_keys); return st; }
-  hipError_t e = hipMemcpyAsync(d_keys, keys, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
+  pvlm_call call(ctx, "pvlm_ring_debug_sort");
+  if (call.enter()) return call.st;
+  const unsigned* d_keys = call.upload(keys, (size_t)n);
+  int* d_order = call.alloc<int>((size_t)n + 1);
+  call.launch(k_debug_sort, dim3(1), dim3(64), 0, d_keys, n, d_order, d_order + n);
+  call.check_launches();
   int sane = 0;
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_sort, dim3(1), dim3(64), 0, ctx->stream, d_keys, n, d_order, d_order + n);
-    e = hipMemcpyAsync(order, d_order, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&sane, d_order + n, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  pvlm_i_free(ctx, d_keys); pvlm_i_free(ctx, d_order);
-  if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_ring_debug_sort: %s", hipGetErrorString(e)); return PVLM_ERR_HIP; }
+  call.d2h(order, d_order, (size_t)n * 4);
+  call.d2h(&sane, d_order + n, 4);
+  if (call.sync()) return call.st;
   if (!sane) { PVLM_SET_ERR(ctx, "pvlm_ring_debug_sort: the sort refused the keys"); return PVLM_ERR_STATE; }
   return PVLM_OK;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pvlm_internal.h"
+#include "pvlm_layout.h"
 #include "pvlm_workers.h"
 #include "pvlm_undistort_core.h"
 
@@ -50,12 +51,12 @@ extern "C" pvlm_status pvlm_undistort_batch(pvlm_ctx* ctx, int n_scans, const pv
       pt0 += scans[s].n;
     }
     // pinned staging: the ring batches' pool (the same scans pass through both in one EstimatePose / UndistortLidars / EstimatePose sequence)
-    const size_t bytes = (size_t)total * 16 + (size_t)n_scans * sizeof(SweepDesc) + 256;
-    pvlm_pinned_lease lease(ctx, bytes);
+    const pvlm_undistort_layout L = pvlm_undistort_layout_of((size_t)total, (size_t)n_scans, sizeof(SweepDesc));
+    pvlm_pinned_lease lease(ctx, L.bytes);
     char* h = lease.p;
-    if (!h) { PVLM_SET_ERR(ctx, "pvlm_undistort_batch: %zu bytes of pinned memory unavailable", bytes); return PVLM_ERR_NOMEM; }
-    float4* hp = (float4*)h;
-    SweepDesc* hd = (SweepDesc*)(h + (((size_t)total * 16 + 255) & ~(size_t)255));
+    if (!h) { PVLM_SET_ERR(ctx, "pvlm_undistort_batch: %zu bytes of pinned memory unavailable", L.bytes); return PVLM_ERR_NOMEM; }
+    float4* hp = (float4*)(h + L.points);
+    SweepDesc* hd = (SweepDesc*)(h + L.desc);
     std::memcpy(hd, desc.data(), (size_t)n_scans * sizeof(SweepDesc));
     auto each_scan = [&](auto&& body) {
       const size_t n_threads = std::min(pvlm_i_threads_max(), (size_t)n_scans / 16 + 1);

@@ -19,16 +19,44 @@ CASES = [
     dict(k=12, scale=0.05, cols=600),
     dict(k=13, start_deg=0.0, jitter=0.0, skew=0.0),          # azimuths at +-0: the + 2 pi of :445-446 sits on the interval
     dict(k=14, n_scans=32), dict(k=15, n_scans=64, cols=360),
+    dict(k=6, cols=360, clutter=30, edge_cols=(7, 63, 147)),  # three horizontal edges of ring 0 whose angle sits on the 20-degree threshold: the host's atan2 decides
 ]
+
+_EDGE_CASES = {}
+
+
+def _on_the_edge_threshold(raw, n_scans, horizon, cols):
+    """The scan with the point behind cell (0, c + 1) moved along its ray, for every c of `cols`, to the range at which the segmentation angle between the cells
+    (0, c) and (0, c + 1) — atan2(near sin ax, far - near cos ax), sensors/Velodyne.cpp:1500-1512 — equals the threshold: far / near = cos ax + sin ax / tan theta.
+    No float within a few ulps of that atan2 is certainly above or below theta, so the device lists the edge for the host's libm."""
+    from oracle import oracle as orc
+    orc.build()
+    before = orc.ScanFeatures(raw, n_scans=n_scans, horizon=horizon, extract=False)
+    R, cloud, cell_point = before.range_image, before.cloud_scan, before.image_to_point_idx
+    ax, theta = np.float32(np.deg2rad(0.2)), np.float32(np.deg2rad(20.0))          # float angles, float sin / cos: the constants the stage itself uses
+    f = float(np.cos(ax)) + float(np.sin(ax)) / float(np.tan(theta))
+    raw = raw.copy()
+    for c in cols:
+        assert R[0, c] > 0 and R[0, c + 1] > 0
+        behind = np.flatnonzero((raw[:, :3] == cloud[cell_point[0, c + 1], :3]).all(axis=1))
+        assert len(behind) == 1
+        raw[behind[0], :3] *= np.float32(R[0, c] * f / R[0, c + 1])
+    return raw
 
 
 def raw_of(case):
     c = dict(case)
     k = c.pop("k"); scale = c.pop("scale", None)
     seg = c.pop("segment", True); n_scans = c.pop("n_scans", 16)
+    edge_cols = c.pop("edge_cols", None)
     raw = sy.raw_vlp16_scan(k, **c)
     if scale:
         raw = raw.copy(); raw[:, :3] *= np.float32(scale)
+    if edge_cols:                                              # built once: the construction runs the oracle
+        key = case_id(case)
+        if key not in _EDGE_CASES:
+            _EDGE_CASES[key] = _on_the_edge_threshold(raw, n_scans, c.get("cols", 1800), edge_cols)
+        raw = _EDGE_CASES[key]
     return raw, n_scans, c.get("cols", 1800), seg
 
 

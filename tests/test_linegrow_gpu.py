@@ -70,8 +70,8 @@ def test_batch_of_edge_clouds_equals_the_cpu_walk(chk):
     got = ctx.line_grow_batch(clouds)
     assert len(got) == len(clouds) and got[0]["tasks_run"] > 0 and got[0]["kernel_ms"] > 0
     n_seg = 0
-    for g, c in zip(got, clouds):
-        want = cpu_walk(chk, c)
+    wants = [cpu_walk(chk, c) for c in clouds]
+    for g, want in zip(got, wants):
         same(g, want)
         n_seg += 0 if want["status"] else len(want["seg_task"])
     assert n_seg > 60 and got[8]["status"] == 2 and got[7]["status"] == 0 and len(got[7]["seg_task"]) >= 2
@@ -79,6 +79,13 @@ def test_batch_of_edge_clouds_equals_the_cpu_walk(chk):
     again = ctx.line_grow_batch(clouds[:4], two_halves=True)
     for g, h in zip(again, got[:4]):
         same(g, h)
+    # an odd number of clouds: the segment records behind the statuses start on a multiple of 8 bytes that the statuses do not end on
+    for odd in ([7], [0, 7, 1]):
+        for two_halves in (False, True):
+            res = ctx.line_grow_batch([clouds[k] for k in odd], two_halves=two_halves)
+            assert len(res) == len(odd)
+            for g, k in zip(res, odd):
+                same(g, wants[k])
 
 
 def test_large_edge_cloud_takes_the_points_from_global_memory(chk):

@@ -33,18 +33,25 @@ def test_batch_matches_oracle(ctx, oracle, key):
     members = _groups()[key]
     extra = [members[0][1][:0], members[0][1][:1], members[0][1][:40]]                     # an empty, a one-point and a 40-point scan ride along
     batch = pv.RingBatch(ctx, [raw for _, raw in members] + extra, n_rings=n_scans, horizon=horizon, segment=segment)
-    listed = 0
+    listed = replayed = 0
     for k, (case, raw) in enumerate(members):
         g = batch.arrays(k)
         rc.assert_matches_oracle(oracle, raw, n_scans, horizon, segment, g)
         assert np.array_equal(g["cloud_kept"][:, :3], raw[g["source"], :3])               # `source` indexes the raw scan
         assert np.array_equal(g["ring_col"] >> 16, g["rc_kept"][:, 0]) and np.array_equal(g["ring_col"] & 0xFFFF, g["rc_kept"][:, 1])
-        listed += g["resolved_points"]
+        listed += g["resolved_points"]; replayed += g["replayed"]
         print("%s: %d points, %d decided by the host libm, %d edges, %d replays, %d of %d sectors left to the host's std::sort" %
               (rc.case_id(case), len(raw), g["resolved_points"], g["resolved_edges"], g["replayed"], int(g["sector_host"].sum()), 6 * n_scans))
         assert int(g["sector_host"].sum()) == 0                                            # no NaN curvature, no sector beyond 2048 points in these cases
+        if "edge_cols" in case:
+            assert g["resolved_edges"] >= 1                                                # the edge-patch round: EdgeQuery -> host atan2 -> k_seg_patch
     for k, raw in enumerate(extra):
         rc.assert_matches_oracle(oracle, raw, n_scans, horizon, segment, batch.arrays(len(members) + k))
+    # the other two patch rounds on the device (the host-compiled twin: k4 lists 10 points and k13 lists 16, k10 is replayed once)
+    if key == (16, 1800, True):
+        assert listed > 0
+    if key == (16, 4096, True):
+        assert replayed > 0
     print("stage ms:", {k: round(v, 3) for k, v in batch.timing().items()})
     batch.close()
 
@@ -62,14 +69,23 @@ def test_batch_equals_scan_by_scan(ctx):
     together.close()
 
 
-def test_errors(ctx):
+def test_errors(ctx, oracle):
     raw = rc.raw_of(rc.CASES[0])[0]
     with pytest.raises(pv.PvlmError):
         pv.RingBatch(ctx, [raw], n_rings=8)                                                  # no ring table (:386-390)
     bad = raw.copy(); bad[7, 1] = np.nan
+    in_use = ctx.mem_info()["in_use"]
     with pytest.raises(pv.PvlmError):
         pv.RingBatch(ctx, [raw, bad])
+    assert ctx.mem_info()["in_use"] == in_use                                                # the refused call gave back its scratch and the batch's arrays
     pv.RingBatch(ctx, []).close()
+    # and the context still computes: the 16 x 360 case alone
+    case = rc.CASES[5]
+    small, n_scans, horizon, segment = rc.raw_of(case)
+    assert (n_scans, horizon) == (16, 360)
+    batch = pv.RingBatch(ctx, [small], n_rings=n_scans, horizon=horizon, segment=segment)
+    rc.assert_matches_oracle(oracle, small, n_scans, horizon, segment, batch.arrays(0))
+    batch.close()
 
 
 @pytest.mark.parametrize("key", sorted(_groups().keys()), ids=lambda k: "rings%d-cols%d-seg%d" % k)
