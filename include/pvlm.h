@@ -790,6 +790,70 @@ pvlm_status pvlm_set_translation_scales(pvlm_ctx* ctx, const pvlm_depthset* set,
                                         double* lower_scale /* in/out */, pvlm_scale_stats* stats_or_null);
 int pvlm_scale_workgroup_size(void);
 
+/* ---- K41: SIFT keypoints and (Root)SIFT descriptors (util/SIFT.cpp:10-128 behind Frame::ExtractKeyPoints / ComputeDescriptor, sensors/Frame.cpp:110-121) ----
+ * The definition (csrc/pvlm_sift_core.h) is this library's own statement of cv::xfeatures2d::SIFT as upstream calls it; there is no OpenCV build to pin it against.
+ * [recalled] create(nfeatures): 3 layers per octave, contrast threshold 0.04, edge threshold 10, sigma 1.6, first octave -1; the float build (sift_wt = float,
+ *   fixed-point scale 1).  [recalled] cvRound is round-half-to-even; that is every "rint" below.
+ * Base image: grey -> float; doubled by bilinear interpolation at (d + 0.5) / 2 - 0.5 with a replicated border (weights exactly 0.25 / 0.75); blurred with
+ *   sigma sqrt(max(1.6^2 - 1^2, 0.01)) [recalled].  Octaves: round(log2(min(base w, base h)) - 2) + 1 [recalled], evaluated in integers.
+ * Layers: layer i >= 1 is layer i - 1 blurred with sqrt((1.6 k^i)^2 - (1.6 k^(i-1))^2), k = 2^(1/3); 6 Gaussian and 5 difference layers per octave; the next
+ *   octave is layer 3 at every second pixel (2y, 2x) ([recalled] upstream: resize INTER_NEAREST to (w / 2, h / 2), the same pixels for even sizes).
+ * Blur: separable, rows then columns; taps = floor(8 sigma + 1.5) | 1 [recalled]; coefficients exp(-x^2 / 2 sigma^2) normalised in double on the host and rounded
+ *   to float once; reflect-101 folded as often as needed; s = s + c[k] * tap for k ascending from s = 0, multiply and add unfused.
+ * Extrema: strictly inside a 5-pixel border, |v| > floor(0.5 * 0.04 / 3 * 255) = 1, >= all 26 neighbours (v > 0) or <= all 26 (v < 0) [recalled].
+ * Refinement [recalled adjustLocalExtrema]: at most 5 Newton steps of the 3-D quadratic fit with derivative scales 1/255 * (0.5, 1, 0.25); the 3 x 3 system by
+ *   cofactors in float; an offset component of 0.5 or more moves by rint(offset); leaving layers 1..3 or the border, 5 moves, a zero determinant or an offset of
+ *   1e6 or more rejects; contrast |D + 0.5 g.x| / 255-scaled * 3 >= 0.04; edge tr^2 * 10 < 11^2 det, det > 0.  Record: x = (c + xc) 2^o, y = (r + xr) 2^o,
+ *   size = 1.6 * 2^((layer + xi) / 3) * 2^o * 2, response = |contrast|, octave word = o + (layer << 8) + (rint((xi + 0.5) * 255) << 16).
+ * Orientation [recalled calcOrientationHist]: 36 bins, radius rint(3 * 1.5 * scale), weight exp(-(i^2 + j^2) / (2 (1.5 scale)^2)), pixels with a missing neighbour
+ *   skipped, [1 4 6 4 1] / 16 smoothing, every local peak >= 0.8 of the maximum with parabolic interpolation, angle = 360 - 10 * bin (360 -> 0).
+ * Selection, in this order: duplicates (equal x, y, size, angle; the first in order stays), retainBest(nfeatures) (everything with response >= the nfeatures-th
+ *   largest: ties keep more than n), coordinates and size * 0.5 and the octave byte - 1 (first octave -1), then the mask: dropped where
+ *   mask(rint y, rint x) == 0, the indices clamped into the image.
+ * Descriptor [recalled calcSIFTDescriptor]: on the keypoint's own Gaussian layer, 4 x 4 x 8 bins, histogram width 3 * size / 2, radius
+ *   rint(width * sqrt 2 * 5 / 2) capped at the layer's diagonal, weight exp(-(r^2 + c^2) / 8) in bin units, trilinear; clamp at 0.2 of the norm, * 512 / norm,
+ *   rint saturated to 0..255, stored as float.  RootSIFT (PVLM_FLAG_SIFT_ROOT, util/SIFT.cpp:10-21): per row v / L1, square root, * 512.
+ * Deliberate divergences:
+ *   - exp, atan2, sin / cos, 2^x and sqrt are this library's deterministic ones (K37's exp_neg, a polynomial atan2, Taylor sin / cos, IEEE sqrt), not OpenCV's
+ *     hal::fastAtan2 / exp32f tables; histogram sums have one fixed order (sample j of a window belongs to lane j % 64, lanes added in ascending order).
+ *   - keypoints come out in one defined order: octave, layer, row, column of the detection, then ascending histogram bin; the selection is a stable filter of
+ *     that order (upstream: TLS-parallel row strips and nth_element).
+ *   - an all-zero row under RootSIFT stays zero (upstream divides by 0); an image with a side below 8 pixels is PVLM_ERR_ARG; the pyramid is built once for
+ *     detect and compute (upstream builds it twice with identical values).
+ *   - the refinement rejects an offset component of 1e6 or more in magnitude (or a NaN) where upstream rejects above INT_MAX / 3: the bound within which the
+ *     half-to-even rounding used here is exact; either is far outside any offset that could move to a pixel of the image.
+ *   - the next octave takes the pixels (2y, 2x) of layer 3; for odd sizes upstream's INTER_NEAREST resize picks other columns.
+ * pvlm_sift_extract: n_images grey images of rows x cols (uint8, row-major), an optional mask of the same size, nfeatures > 0.  Image i's keypoints are
+ *   keypoints[kp_offsets[i] .. kp_offsets[i + 1]) and their descriptors the same rows of `descriptors` (128 floats each): Frame's layout, what pvlm_descset_create
+ *   takes.  *needed = kp_offsets[n_images]; when it exceeds capacity the call returns PVLM_ERR_CAPACITY with kp_offsets and *needed set and nothing past
+ *   capacity written.  A call that fails for capacity has done all the work but the descriptors: size the first call by n_images * nfeatures plus some room
+ *   for ties at the nfeatures-th response and repeat only on PVLM_ERR_CAPACITY (pvlm::ReadImages and the Python binding do).  descriptors == NULL asks for the
+ *   keypoints alone: the descriptor kernel is not run.  One image is in flight at a time; its layers come from the context's pool.  The selection runs on the host between the orientation and
+ *   the descriptor kernels.  A result does not depend on the other images of the batch.  Synchronous; PVLM_ERR_STATE inside a capture.
+ * pvlm_sift_pyramid_debug: one image; the 6 Gaussian and 5 difference layers of `octave` (octave_rows x octave_cols floats each; either may be NULL), that
+ *   octave's refined candidates and the whole image's keypoints before the selection, both with the capacity protocol above. */
+#define PVLM_FLAG_SIFT_ROOT 0x1000u
+typedef struct pvlm_sift_keypoint { float x, y, size, angle, response; int octave; } pvlm_sift_keypoint;
+typedef struct pvlm_sift_candidate {
+  int octave, layer, r, c;          /* the refined position in its octave's pixels */
+  float x, y, size, response;       /* before the first octave's 0.5 */
+  int word, det_layer, det_r, det_c; /* the octave word; where the extremum was detected */
+} pvlm_sift_candidate;
+typedef struct pvlm_sift_stats {
+  long long images, octaves;
+  long long candidates;            /* refined extrema */
+  long long keypoints_detected;    /* with their orientations, before the selection */
+  long long keypoints;             /* returned */
+  double part_ms[6];               /* device time by HIP events: (a) doubling + first blur, (b) layer blurs + differences, (c) decimation, (d) extrema +
+                                      refinement, (e) orientation, (f) descriptors */
+} pvlm_sift_stats;
+pvlm_status pvlm_sift_extract(pvlm_ctx* ctx, int n_images, int rows, int cols, const unsigned char* const* images, const unsigned char* mask_or_null, int nfeatures,
+                              unsigned flags, long long* kp_offsets /* n_images + 1 */, pvlm_sift_keypoint* keypoints, float* descriptors /* 128 per keypoint */,
+                              long long capacity, long long* needed, pvlm_sift_stats* stats_or_null);
+pvlm_status pvlm_sift_pyramid_debug(pvlm_ctx* ctx, int rows, int cols, const unsigned char* image, int octave, int* n_octaves, int* octave_rows, int* octave_cols,
+                                    float* gauss_or_null /* 6 layers */, float* dog_or_null /* 5 layers */, pvlm_sift_candidate* candidates, long long candidate_capacity,
+                                    long long* candidates_needed, pvlm_sift_keypoint* keypoints, long long keypoint_capacity, long long* keypoints_needed);
+
 /* MVS::InitDepthNormal (mvs/MVS.cpp:496-584; config 5 "LiDAR-seeded depth priors"): the depth image of
  * pvlm_project_lidar_depth (uint16, depth * 256; size 2 upstream, :512) seeds the depth map, every pixel without a LiDAR depth
  * gets a uniform random depth in [min_depth, max_depth], keep_lidar_constant != 0 marks the seeded pixels in depth_constant

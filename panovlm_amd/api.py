@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
+    "pvlm_sift_extract", "pvlm_sift_pyramid_debug",
 ]
 
 
@@ -1841,3 +1842,84 @@ class RingBatch:
                     curvature=res["curvature"], half_window=res["half_window"], range=res["range"], source=res["source"], ring_col=res["ring_col"],
                     resolved_points=res["resolved_points"], resolved_edges=res["resolved_edges"], replayed=res["replayed"], sorted=res["sorted"],
                     sector_host=res["sector_host"])
+
+
+# ---- K41: SIFT keypoints and (Root)SIFT descriptors ----
+FLAG_SIFT_ROOT = 0x1000
+SIFT_KEYPOINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])
+SIFT_CANDIDATE_DTYPE = np.dtype([("octave", np.int32), ("layer", np.int32), ("r", np.int32), ("c", np.int32), ("x", np.float32), ("y", np.float32), ("size", np.float32),
+                                 ("response", np.float32), ("word", np.int32), ("det_layer", np.int32), ("det_r", np.int32), ("det_c", np.int32)])
+SIFT_GUARD = 4       # sentinel records sift_extract keeps behind the capacity it passes on
+SIFT_TIE_ROOM, SIFT_GUESS_PER_IMAGE = 64, 1 << 15      # how sift_extract sizes a call whose capacity the caller left open
+
+
+class SiftStats(C.Structure):
+    _fields_ = [("images", C.c_longlong), ("octaves", C.c_longlong), ("candidates", C.c_longlong), ("keypoints_detected", C.c_longlong), ("keypoints", C.c_longlong),
+                ("part_ms", C.c_double * 6)]
+
+
+def _sift_images(images):
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    shapes = set(im.shape for im in imgs)
+    if len(shapes) > 1 or any(im.ndim != 2 for im in imgs):
+        raise PvlmError("pvlm_sift_extract: the images of a batch must be two-dimensional and of one size")
+    return imgs
+
+
+def sift_extract(ctx, images, nfeatures, mask=None, flags=0, capacity=None):
+    """pvlm_sift_extract (K41): SIFT keypoints and 128-float descriptors (RootSIFT with FLAG_SIFT_ROOT) of a batch of equal-sized uint8 grey images.  Returns a dict:
+    offsets (int64, images + 1), keypoints (SIFT_KEYPOINT_DTYPE), descriptors (n x 128 float32), needed, overflow, guard_intact, stats, calls.  A call that fails
+    for capacity has done all the work but the descriptors, so capacity None sizes ONE call by min(nfeatures, SIFT_GUESS_PER_IMAGE) + SIFT_TIE_ROOM keypoints per image
+    and repeats it with the reported count only when more come back (calls == 2: more ties at the threshold than the room, or an nfeatures above the guess)."""
+    imgs = _sift_images(images)
+    rows, cols = imgs[0].shape if imgs else (8, 8)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    if m is not None and m.shape != (rows, cols):
+        raise PvlmError("pvlm_sift_extract: the mask must have the images' size")
+    ptrs = (C.POINTER(C.c_ubyte) * max(len(imgs), 1))(*[_p(im, C.c_ubyte) for im in imgs])
+    off = np.zeros(len(imgs) + 1, np.int64)
+
+    def call(cap):
+        kp = np.zeros(cap + SIFT_GUARD, SIFT_KEYPOINT_DTYPE); kp["octave"] = -7; kp["x"] = -7.0
+        desc = np.full((cap + SIFT_GUARD, 128), -7.0, np.float32)
+        needed = C.c_longlong(0); st = SiftStats()
+        rc = ctx.lib.pvlm_sift_extract(ctx._h, C.c_int(len(imgs)), C.c_int(rows), C.c_int(cols), ptrs, _p(m, C.c_ubyte), C.c_int(nfeatures), C.c_uint(flags),
+                                       _p(off, C.c_longlong), kp.ctypes.data_as(C.c_void_p), _p(desc, C.c_float), C.c_longlong(cap), C.byref(needed), C.byref(st))
+        return rc, kp, desc, needed.value, st
+
+    cap = int(capacity) if capacity is not None else len(imgs) * (min(max(int(nfeatures), 0), SIFT_GUESS_PER_IMAGE) + SIFT_TIE_ROOM)
+    rc, kp, desc, needed, st = call(cap)
+    calls = 1
+    if capacity is None and rc == ERR_CAPACITY:
+        cap = needed
+        rc, kp, desc, needed, st = call(cap)
+        calls = 2
+    if rc != ERR_CAPACITY:
+        ctx._check(rc, "pvlm_sift_extract")
+    n = min(needed, cap)
+    return dict(offsets=off.copy(), keypoints=kp[:n], descriptors=desc[:n], needed=needed, overflow=rc == ERR_CAPACITY, calls=calls,
+                guard_intact=bool(np.all(kp["octave"][cap:] == -7) and np.all(kp["x"][cap:] == -7.0) and np.all(desc[cap:] == -7.0)),
+                stats=dict(images=st.images, octaves=st.octaves, candidates=st.candidates, keypoints_detected=st.keypoints_detected, keypoints=st.keypoints,
+                           part_ms=dict(zip("abcdef", (float(v) for v in st.part_ms)))))
+
+
+def sift_pyramid_debug(ctx, image, octave):
+    """pvlm_sift_pyramid_debug (K41): the Gaussian (6 x R x C) and difference (5 x R x C) layers of one octave, that octave's refined candidates
+    (SIFT_CANDIDATE_DTYPE) and the image's keypoints before the selection.  Returns a dict with n_octaves, gauss, dog, candidates, keypoints."""
+    im = np.ascontiguousarray(image, np.uint8)
+    if im.ndim != 2:
+        raise PvlmError("pvlm_sift_pyramid_debug: a two-dimensional image")
+    rows, cols = im.shape
+    n_oct, orows, ocols = C.c_int(0), C.c_int(0), C.c_int(0)
+    nc, nk = C.c_longlong(0), C.c_longlong(0)
+    # sizing call: no layers, no records
+    rc = ctx.lib.pvlm_sift_pyramid_debug(ctx._h, C.c_int(rows), C.c_int(cols), _p(im, C.c_ubyte), C.c_int(octave), C.byref(n_oct), C.byref(orows), C.byref(ocols), None, None,
+                                         None, C.c_longlong(0), C.byref(nc), None, C.c_longlong(0), C.byref(nk))
+    if rc != ERR_CAPACITY:
+        ctx._check(rc, "pvlm_sift_pyramid_debug")
+    gauss = np.zeros((6, orows.value, ocols.value), np.float32); dog = np.zeros((5, orows.value, ocols.value), np.float32)
+    cands = np.zeros(max(nc.value, 1), SIFT_CANDIDATE_DTYPE); kps = np.zeros(max(nk.value, 1), SIFT_KEYPOINT_DTYPE)
+    ctx._check(ctx.lib.pvlm_sift_pyramid_debug(ctx._h, C.c_int(rows), C.c_int(cols), _p(im, C.c_ubyte), C.c_int(octave), C.byref(n_oct), C.byref(orows), C.byref(ocols),
+                                               _p(gauss, C.c_float), _p(dog, C.c_float), cands.ctypes.data_as(C.c_void_p), C.c_longlong(len(cands)), C.byref(nc),
+                                               kps.ctypes.data_as(C.c_void_p), C.c_longlong(len(kps)), C.byref(nk)), "pvlm_sift_pyramid_debug")
+    return dict(n_octaves=n_oct.value, gauss=gauss, dog=dog, candidates=cands[:nc.value], keypoints=kps[:nk.value])

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip")
 
 
 def _hipcc():
@@ -122,6 +122,7 @@ DEPTHFILL_DRIVER = os.path.join(HERE, "build", "pvlm_depthfill_driver")
 DEPTHFILL_CHECK = os.path.join(HERE, "build", "depthfill_core_check")
 SCALE_DRIVER = os.path.join(HERE, "build", "pvlm_scale_driver")
 DISPATCH_ORDER_CHECK = os.path.join(HERE, "build", "dispatch_order_check")
+SIFT_DRIVER = os.path.join(HERE, "build", "pvlm_sift_driver")
 
 
 def build_host(force=False):
@@ -226,6 +227,12 @@ def build_host(force=False):
     if os.path.exists(cdrv) and (force or not os.path.exists(SCALE_DRIVER) or
                                  os.path.getmtime(SCALE_DRIVER) < max(os.path.getmtime(cdrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", cdrv, "-o", SCALE_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    # the feature driver (ReadImages into InitImagePairs and MatchImagePairs: K41)
+    xdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_sift_driver.cpp")
+    if os.path.exists(xdrv) and (force or not os.path.exists(SIFT_DRIVER) or
+                                 os.path.getmtime(SIFT_DRIVER) < max(os.path.getmtime(xdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", xdrv, "-o", SIFT_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     return HOST_LIB
 

@@ -344,6 +344,7 @@ void pvlm_i_preload_vlad(hipStream_t s);
 void pvlm_i_preload_relpose(hipStream_t s);
 void pvlm_i_preload_depthfill(hipStream_t s);
 void pvlm_i_preload_scale(hipStream_t s);
+void pvlm_i_preload_sift(hipStream_t s);
 void pvlm_i_preload_texture(hipStream_t s);
 void pvlm_i_preload_mvs(hipStream_t s);
 void pvlm_i_preload_ring(hipStream_t s);

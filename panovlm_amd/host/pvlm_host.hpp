@@ -586,6 +586,15 @@ std::vector<uint16_t> ProjectLidar2PanoramaDepth(const PointCloud& cloud, const 
 // ---- joint_optimization/CameraLidarOptimizer.h (mapping mode) --------------------------------------------------
 // sensors/Frame.h contract as far as the path needs it: image size, pose T_wc, the detected image lines
 // (image_lines_all[frame].GetLines()).
+// cv::Mat of type CV_8UC1 as far as the feature path reads it (the grey image of a frame, a mask): rows x cols bytes, row-major; no pixels = an empty Mat
+struct GrayImage {
+  int rows = 0, cols = 0;
+  std::vector<unsigned char> pixels;
+  bool empty() const { return pixels.empty(); }
+};
+// cv::KeyPoint as SIFT fills it (pt.x, pt.y, size, angle, response, octave): the record of pvlm_sift_keypoint (K41)
+struct KeyPoint { float x, y, size, angle, response; int octave; };
+
 struct Frame {
   int id = 0, rows = 2880, cols = 5760;
   Matrix3d R_wc{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
@@ -594,6 +603,15 @@ struct Frame {
   std::vector<std::array<float, 4>> lines;
   std::vector<std::array<float, 2>> keypoints;   // GetKeyPoints()[k].pt (SIFT keypoints, pixels)
   std::vector<float> descriptor;                 // GetDescriptor(): rows x 128 floats, row-major, row k the SIFT descriptor of keypoints[k] (K33)
+  std::vector<KeyPoint> keypoints_all;           // the full records behind `keypoints` (sensors/Frame.h: keypoints_all), filled by ExtractKeyPoints / ReadImages (K41)
+  GrayImage img_gray;                            // LoadImageGray's result; ReadImages releases it as upstream does
+  std::vector<float> sift_rows;                  // the plain descriptor rows of keypoints_all as ExtractKeyPoints' device call returned them (ComputeDescriptor's source)
+  // sensors/Frame.cpp:110-121.  ExtractKeyPoints: ExtractSIFTQuadtree(img_gray, keypoints_all, 0, num_keypoints, mask) as ONE pvlm_sift_extract call that also
+  // brings the plain descriptor rows (the pyramid exists only inside that call), `keypoints` set beside it.  ComputeDescriptor: those rows, RootSIFT applied on
+  // request -- bit for bit ComputeSIFTDescriptor(img_gray, keypoints_all, descriptor, root_sift), which it falls back to (host compile) only when keypoints_all did
+  // not come from ExtractKeyPoints alone.  One image per call: SfM's loop is ReadImages below.
+  bool ExtractKeyPoints(int num_keypoints, const GrayImage& mask);
+  bool ComputeDescriptor(bool root_sift);
   bool IsPoseValid() const { return pose_valid; }
   int GetImageRows() const { return rows; }
   int GetImageCols() const { return cols; }
@@ -640,6 +658,33 @@ std::vector<DMatch> MatchSIFT(const std::vector<float>& descriptor1, const std::
 bool MatchImagePairs(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold);
 // the same on the host compile of the core, the pairs spread over num_threads workers: the baseline tools/match_bench.py times
 bool MatchImagePairsHost(const std::vector<Frame>& frames, std::vector<MatchPair>& image_pairs, const float ratio, const int matches_threshold, const int num_threads = 16);
+
+// ---- K41: SIFT keypoints and descriptors (util/SIFT.cpp:10-128, sensors/Frame.cpp:110-121, sfm/SfM.cpp:15-42) ---------------------------------------------------
+// The definition is pvlm.h's K41 (csrc/pvlm_sift_core.h), with its divergences from OpenCV's SIFT.  A mask is an image of the same size or empty.
+// ExtractSIFT (util/SIFT.cpp:22-30): detect(img_gray, keypoints, mask) of SIFT::create(num_sift), one pvlm_sift_extract call without descriptors; false for num_sift <= 0, a side below 8
+// pixels, a mask of another size, or no keypoint.
+bool ExtractSIFT(const GrayImage& img_gray, std::vector<KeyPoint>& keypoints, const int num_sift = 8096, const GrayImage& mask = GrayImage());
+// ExtractSIFTQuadtree (:82-118) at tree_depth 0, what Frame::ExtractKeyPoints calls: one cell, the whole image, i.e. ExtractSIFT appended to `keypoints`; any other
+// depth returns false and leaves `keypoints` untouched.  The default depth is therefore 0 here, not upstream's 1: a caller who relies on defaults gets the served case.
+bool ExtractSIFTQuadtree(const GrayImage& img_gray, std::vector<KeyPoint>& keypoints, const int tree_depth = 0, const int num_sift = 8096, const GrayImage& mask = GrayImage());
+// ComputeSIFTDescriptor (:120-128): the descriptors of ARBITRARY given keypoints, rows x 128 floats.  The C ABI computes descriptors only together with the detection
+// (the pyramid lives inside that call), so this one-image call runs the host compile of the core (the pyramid, then every keypoint on the worker pool): about 2 s for
+// a 5760 x 2880 panorama on 16 threads, bit-identical to the device's rows.  It is NOT on the path of ReadImages or of Frame::ExtractKeyPoints + ComputeDescriptor,
+// which take their rows from the device call; it serves a caller with keypoints of its own.  Open: a compute-only entry point.
+bool ComputeSIFTDescriptor(const GrayImage& img_gray, std::vector<KeyPoint>& keypoints, std::vector<float>& descriptor, const bool root_sift = false);
+// RootSIFT (:10-21) on rows x 128 floats: per row L1-normalise, square root, x 512 (upstream's order of operations); a zero row stays zero.
+void RootSIFT(std::vector<float>& descriptor);
+// detect + compute of one image on the host compile of the core, on num_threads workers: the baseline tools/sift_bench.py times, and the fallback without a device
+bool ExtractSIFTHost(const GrayImage& img_gray, const GrayImage& mask, const int num_sift, const bool root_sift, std::vector<KeyPoint>& keypoints,
+                     std::vector<float>& descriptor, const int num_threads = 16);
+// Fills `image` with the grey image of frame `frame` (frames[frame].rows x cols); false = no image.
+using GrayImageProvider = std::function<bool(size_t frame, GrayImage& image)>;
+// SfM::ReadImages (sfm/SfM.cpp:15-42) for frames that exist already (id, rows, cols): in id order, images_per_call frames at a time, the images asked of the
+// provider, ONE pvlm_sift_extract call per group (ExtractKeyPoints and ComputeDescriptor of every frame of the group; its buffers sized by num_sift per image plus
+// room for ties, a second call only if more keypoints tie at the threshold than that room), keypoints_all / keypoints / descriptor filled, the images released.  False (frames untouched) when an image is missing or of another size than the first, or num_sift <= 0.
+bool ReadImages(std::vector<Frame>& frames, GrayImageProvider images, const GrayImage& mask, const int num_sift, const bool root_sift, const int images_per_call = 8);
+// the pvlm_sift_extract calls the functions above have made in this process (what the driver counts)
+long SiftDeviceCalls();
 
 // ---- K34: relative poses from the matches (sfm/SfM.cpp:298-480, base/EssentialMatrix.cpp, base/ACRansac_NFA.cpp) ---------------------------------
 // base/Serialization.h's MatchPair as FilterImagePairs leaves it, up to and not including RefineRelativePose
