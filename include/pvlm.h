@@ -482,6 +482,39 @@ pvlm_status pvlm_refine_relative_poses(pvlm_ctx* ctx, int n_frames, const float*
                                        pvlm_relpose_summary* summaries_or_null);
 int pvlm_relpose_workgroup_size(void);
 
+/* ---- K42: translation averaging (SfM::EstimateGlobalTranslation sfm/SfM.cpp:1047; TranslationAveragingDLT / L2 / SoftL1 sfm/TranslationAveraging.cpp:31-204) ---- *
+ * The definition (csrc/pvlm_transavg_core.h).  Unknowns: the translation t_cw of every camera (origin_idx constant and zero) and one private scale per pair.
+ * Pair p: r = t[second] - R_21 t[first] - s_p d_p, d_p = t_21 / |t_21| (base/CostFunction.h:51-83), under SoftLOneLoss(loss_a) on |r|^2 (no loss when loss_a < 0,
+ * :184-185); per scale one ScaleFactor block (CostFunction.h:119-144): scales[p] != 1 (as written, :101) gives the bounds upper_scale_ratio * s0 and
+ * lower_scale_ratio * s0 and the parameter bounds [0.5 s0, 3 s0]; otherwise ScaleFactor(2, 1) and no parameter bounds.  R_21 is row-major.
+ * Per LM iteration the scales are eliminated (a 1 x 1 pivot per pair), the reduced 3 x 3 camera blocks are gathered per camera over a CSR of its incident pairs
+ * and the camera system goes through the solver behind pvlm_spd_solve_blocks; the scale steps are back-substituted, the candidate scales CLAMPED onto their
+ * parameter bounds and the step quality taken against the model at the clamped step.  The trust-region policy is ceres_like::Solve's (Solver::Options' defaults).
+ * Every sum has one order (per camera: its pairs in list order over pvlm_transavg_group_size() lanes and a fixed butterfly; the scalars: a fixed tree over the
+ * pairs), so a call is bit-reproducible from run to run — for a pair list that names no camera pair more than twice (the solver adds repeated blocks atomically).
+ * Write-back (:160-166): summary->final_cost; weight[i] = (|t2 - R_21 t1 - scales[i] t_21| + 1e-2)^-0.5, t_21 not normalised, as line 165 is written.
+ * Deliberate divergences: the functor's `weight` member is never applied upstream and is not applied here (weight is only written); R_21 is used directly instead
+ * of through an angle-axis vector (as K36); Ceres' own treatment of parameter bounds (projection plus a line search) is replaced by the clamp without a line search;
+ * no pairs: nothing is changed, termination 6; the three 3 F vectors of an iteration (gather, right-hand side, camera step) pass through the host, the per-pair
+ * state stays on the device.
+ * pvlm_transavg_dlt: the least-squares solution of the stacked t_j - R_ji t_i = t_ji by its normal equations with camera 0 fixed at zero (upstream: SparseQR on a
+ * system that is rank-deficient by the gauge t_i = R_i c, so it returns SOME basic solution; every caller runs SetToOrigin afterwards, which cancels the gauge).
+ * info: 0, or k > 0 when the system is not positive definite (a pair graph that is not connected); the output is then untouched.
+ * summary: initial and final cost, accepted and rejected steps, termination on K36's numbering (6: no pairs).
+ * PVLM_ERR_ARG, with no output touched: a NULL, a camera index out of range, first == second, an input that is not finite, t_21 of zero length, origin_idx out of
+ * range, translations[origin_idx] not zero (upstream asserts), max_num_iterations < 0.
+ * pvlm_transavg_group_size: the lanes that share one camera's gather (the tests place the degrees of a hub camera around it).  The environment variable
+ * PVLM_TRANSAVG_MAX_BLOCKS (read at every call) lowers the grid of the per-pair kernels; it changes no result, the tests use it to make them stride.  With
+ * PVLM_TRANSAVG_PROFILE set, pvlm_transavg_solve prints one line on stderr: the wall clock of the call split into kernels, camera solves and host. */
+typedef struct pvlm_transavg_params { double loss_a /* 0.01 */, upper_scale_ratio, lower_scale_ratio; int max_num_iterations /* 50 */; } pvlm_transavg_params;
+typedef struct pvlm_transavg_summary { double initial_cost, final_cost; int successful_steps, unsuccessful_steps, termination; } pvlm_transavg_summary;
+pvlm_status pvlm_transavg_dlt(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21 /* n_pairs * 9 */,
+                              const double* t_21 /* n_pairs * 3 */, double* translations_out /* n_cameras * 3 */, int* info);
+pvlm_status pvlm_transavg_solve(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21, const double* t_21,
+                                double* scales /* in/out, n_pairs */, int origin_idx, double* translations /* in/out, 3 per camera */,
+                                double* weight /* in/out, n_pairs */, const pvlm_transavg_params* params, pvlm_transavg_summary* summary);
+int pvlm_transavg_group_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
     "pvlm_resset_plane_runs", "pvlm_resset_point_table", "pvlm_resset_point_table_debug",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
+    "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1733,6 +1734,61 @@ def refine_relative_poses(ctx, keypoints, img_rows, img_cols, src, tgt, match_of
     intact = bool(np.all(R[npairs:] == -7.0) and np.all(t[npairs:] == -7.0) and np.all(tri[nin:] == -7.0) and np.all(ok[npairs:] == 0xA5) and
                   np.all(sm["termination"][npairs:] == -7))
     return dict(R_21=R[:npairs], t_21=t[:npairs], triangulated=tri[:nin], ok=ok[:npairs], summaries=sm[:npairs], guard_intact=intact, rc=int(rc))
+
+
+class TransavgParams(C.Structure):
+    _fields_ = [("loss_a", C.c_double), ("upper_scale_ratio", C.c_double), ("lower_scale_ratio", C.c_double), ("max_num_iterations", C.c_int)]
+
+
+class TransavgSummary(C.Structure):
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("successful_steps", C.c_int), ("unsuccessful_steps", C.c_int), ("termination", C.c_int)]
+
+
+TRANSAVG_TERMINATIONS = ("max iterations", "function tolerance", "gradient tolerance", "parameter tolerance", "trust region collapsed", "initial cost not finite",
+                         "no pairs")
+TRANSAVG_GUARD = 8     # sentinel records the two wrappers keep behind every output
+
+
+def transavg_group_size():
+    """pvlm_transavg_group_size (K42): the lanes that share one camera's gather."""
+    return int(load_library().pvlm_transavg_group_size())
+
+
+def transavg_dlt(ctx, n_cameras, first, second, R_21, t_21, check=True):
+    """pvlm_transavg_dlt (K42): TranslationAveragingDLT with camera 0 fixed at zero.  Returns a dict: translations (cameras x 3; -7 everywhere when the library wrote
+    nothing), info (0, or k > 0: not positive definite), guard_intact, rc.  An argument the library refuses raises PvlmError; with check=False the dict comes back
+    with its rc."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRANSAVG_GUARD
+    R = _f64(np.asarray(R_21, np.float64).reshape(P, 9)); t21 = _f64(np.asarray(t_21, np.float64).reshape(P, 3))
+    out = np.full((n_cameras + G, 3), -7.0); info = C.c_int(-7)
+    rc = ctx.lib.pvlm_transavg_dlt(ctx._h, C.c_int(n_cameras), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R, C.c_double), _p(t21, C.c_double),
+                                   _p(out, C.c_double), C.byref(info))
+    if check:
+        ctx._check(rc, "pvlm_transavg_dlt")
+    return dict(translations=out[:n_cameras], info=int(info.value), guard_intact=bool(np.all(out[n_cameras:] == -7.0)), rc=int(rc))
+
+
+def transavg_solve(ctx, first, second, R_21, t_21, scales, origin_idx, translations, weight=None, loss_a=0.01, upper_scale_ratio=1.3, lower_scale_ratio=1.0,
+                   max_num_iterations=50, check=True):
+    """pvlm_transavg_solve (K42): TranslationAveragingL2 under SoftLOneLoss(loss_a) (no loss when loss_a < 0).  The inputs are not modified.  Returns a dict:
+    translations (cameras x 3), scales, weight (pairs), initial_cost, final_cost, successful_steps (accepted), unsuccessful_steps, termination
+    (TRANSAVG_TERMINATIONS), guard_intact (the TRANSAVG_GUARD sentinel records kept behind each output were not written), rc.  An argument the library refuses
+    raises PvlmError; with check=False the dict comes back with its rc (the outputs then hold the inputs: the library touches nothing it refuses)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRANSAVG_GUARD
+    R = _f64(np.asarray(R_21, np.float64).reshape(P, 9)); t21 = _f64(np.asarray(t_21, np.float64).reshape(P, 3))
+    t_in = np.asarray(translations, np.float64).reshape(-1, 3); F = len(t_in)
+    t = np.full((F + G, 3), -7.0); t[:F] = t_in
+    s = np.full(P + G, -7.0); s[:P] = np.asarray(scales, np.float64).reshape(P)
+    w = np.full(P + G, -7.0); w[:P] = 1.0 if weight is None else np.asarray(weight, np.float64).reshape(P)
+    prm = TransavgParams(loss_a, upper_scale_ratio, lower_scale_ratio, max_num_iterations)
+    sm = TransavgSummary(-7.0, -7.0, -7, -7, -7)
+    rc = ctx.lib.pvlm_transavg_solve(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R, C.c_double), _p(t21, C.c_double), _p(s, C.c_double),
+                                     C.c_int(origin_idx), _p(t, C.c_double), _p(w, C.c_double), C.byref(prm), C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_transavg_solve")
+    intact = bool(np.all(t[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0))
+    return dict(translations=t[:F], scales=s[:P], weight=w[:P], initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
+                unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
 
 
 def device_sort(ctx, keys):

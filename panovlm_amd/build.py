@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip")
 
 
 def _hipcc():
@@ -123,6 +123,9 @@ DEPTHFILL_CHECK = os.path.join(HERE, "build", "depthfill_core_check")
 SCALE_DRIVER = os.path.join(HERE, "build", "pvlm_scale_driver")
 DISPATCH_ORDER_CHECK = os.path.join(HERE, "build", "dispatch_order_check")
 SIFT_DRIVER = os.path.join(HERE, "build", "pvlm_sift_driver")
+TRANSAVG_DRIVER = os.path.join(HERE, "build", "pvlm_transavg_driver")
+TRANSAVG_CHECK = os.path.join(HERE, "build", "libtransavg_check.so")
+TRANSAVG_CHECK_MAIN = os.path.join(HERE, "build", "transavg_check_main")
 
 
 def build_host(force=False):
@@ -234,7 +237,31 @@ def build_host(force=False):
                                  os.path.getmtime(SIFT_DRIVER) < max(os.path.getmtime(xdrv), os.path.getmtime(HOST_LIB))):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", xdrv, "-o", SIFT_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
+    # the translation-averaging driver (EstimateGlobalTranslation, TranslationAveragingL2IRLS on the host compile or through the device: K42) and the host compile
+    # of the K42 core for the tests
+    gdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_transavg_driver.cpp")
+    if os.path.exists(gdrv) and (force or not os.path.exists(TRANSAVG_DRIVER) or
+                                 os.path.getmtime(TRANSAVG_DRIVER) < max(os.path.getmtime(gdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", gdrv, "-o", TRANSAVG_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    build_transavg_check()
     return HOST_LIB
+
+
+def build_transavg_check(main=False, sanitize=False):
+    """The host compile of the K42 core (csrc/pvlm_transavg_core.h behind tests/cpp/transavg_core_check.cpp; no device, -ffp-contract=off as the device build of
+    pvlm_transavg.hip): build/libtransavg_check.so for the tests, or with main=True the stand-alone program of the same file (sanitize: the host sanitizers)."""
+    chk = os.path.join(HERE, "..", "tests", "cpp", "transavg_core_check.cpp")
+    core = os.path.join(HERE, "csrc", "pvlm_transavg_core.h")
+    backend = os.path.join(HERE, "host", "pvlm_host_transavg.hpp")
+    out = TRANSAVG_CHECK_MAIN if main else TRANSAVG_CHECK
+    if not os.path.exists(chk):
+        return None
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(chk), os.path.getmtime(core), os.path.getmtime(backend)):
+        mode = ["-O1", "-g", "-DTRANSAVG_CHECK_MAIN"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off"] + mode + [chk, "-o", out])
+    return out
 
 
 if __name__ == "__main__":

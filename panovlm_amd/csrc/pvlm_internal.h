@@ -331,6 +331,9 @@ pvlm_status pvlm_i_h2d(pvlm_ctx* ctx, void* dst, const void* src, size_t bytes);
 pvlm_status pvlm_i_d2h(pvlm_ctx* ctx, void* dst, const void* src, size_t bytes);
 void pvlm_i_assoc_ws_free(pvlm_ctx* ctx);
 void pvlm_i_spd_plan_release(pvlm_ctx* ctx);
+// pvlm_spd_solve_blocks for a caller inside the library; blocks_on_device: `blocks` is a device pointer read in place (csrc/pvlm_linalg.hip)
+pvlm_status pvlm_i_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int* row_idx, const int* col_idx, const int* mirror, const double* blocks,
+                                    bool blocks_on_device, const double* scale, const double* diag_add, double* rhs, int* info_out);
 void pvlm_i_preload_assoc(hipStream_t s);
 void pvlm_i_preload_ba(hipStream_t s);
 void pvlm_i_preload_eval(hipStream_t s);
@@ -342,6 +345,7 @@ void pvlm_i_preload_match(hipStream_t s);
 void pvlm_i_preload_essential(hipStream_t s);
 void pvlm_i_preload_vlad(hipStream_t s);
 void pvlm_i_preload_relpose(hipStream_t s);
+void pvlm_i_preload_transavg(hipStream_t s);
 void pvlm_i_preload_depthfill(hipStream_t s);
 void pvlm_i_preload_scale(hipStream_t s);
 void pvlm_i_preload_sift(hipStream_t s);

@@ -1524,6 +1524,15 @@ extern "C" {
 // also adds the transposed block to the other triangle; a block of one pose with itself is given in full, mirror = 0.
 pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int* row_idx, const int* col_idx, const int* mirror, const double* blocks,
                                   const double* scale, const double* diag_add, double* rhs, int* info_out) {
+  return pvlm_i_spd_solve_blocks(ctx, n, n_blocks, row_idx, col_idx, mirror, blocks, false, scale, diag_add, rhs, info_out);
+}
+
+}  // extern "C"
+
+// The same solve for a caller inside the library whose block VALUES already sit on the device (blocks_on_device: `blocks` is a device pointer that stays valid and
+// unchanged until the call returns; the copy through the pinned arena is skipped and the scatter reads it in place).  Everything else is the caller's host memory.
+pvlm_status pvlm_i_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int* row_idx, const int* col_idx, const int* mirror, const double* blocks,
+                                    bool blocks_on_device, const double* scale, const double* diag_add, double* rhs, int* info_out) {
   if (!ctx || n < 0 || n_blocks < 0 || !info_out || (n > 0 && (!scale || !diag_add || !rhs)) || (n_blocks > 0 && (!row_idx || !col_idx || !mirror || !blocks)))
     return PVLM_ERR_ARG;
   *info_out = 0;
@@ -1600,12 +1609,13 @@ pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int*
   if (plan->levels) n = plan->n_pad;                     // from here on the device works on the padded system
   SpdTileLists lists{plan->d_row_tiles, plan->d_pairs, plan->row_off.data(), plan->pair_off.data()};
   const size_t linv_count = (size_t)((n + PVLM_CHOL_NB - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
-  const size_t need = pad256((size_t)n * n * 8) + pad256((size_t)n_blocks * 36 * 8) + 3 * pad256((size_t)n_blocks * 6 * 4) + 4 * pad256((size_t)n * 8) +
+  const size_t staged_blocks = blocks_on_device ? 0 : (size_t)n_blocks * 36;          // values the caller holds on the device are read where they are
+  const size_t need = pad256((size_t)n * n * 8) + pad256(staged_blocks * 8) + 3 * pad256((size_t)n_blocks * 6 * 4) + 4 * pad256((size_t)n * 8) +
                       pad256(linv_count * 8) + 256;
   pvlm_status st = ws_reserve(ctx, need);
   if (st) return st;
   WsCarver ws{static_cast<char*>(ctx->d_ws)};
-  double* d_M = ws.take<double>((size_t)n * n); double* d_blocks = ws.take<double>((size_t)n_blocks * 36);
+  double* d_M = ws.take<double>((size_t)n * n); double* d_blocks = ws.take<double>(staged_blocks);
   int* d_row = ws.take<int>((size_t)n_blocks * 6); int* d_col = ws.take<int>((size_t)n_blocks * 6); int* d_mir = ws.take<int>((size_t)n_blocks * 6);
   double* d_scale = ws.take<double>(n); double* d_diag = ws.take<double>(n); double* d_rhs = ws.take<double>(n);
   double* d_y = ws.take<double>(n); double* d_Linv = ws.take<double>(linv_count);
@@ -1617,7 +1627,8 @@ pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int*
     else e = hipMemsetAsync(d_M, 0, (size_t)n * n * sizeof(double), s);
     // through the pinned arena (1.3 MB of blocks at Room scale, once per LM step: a pageable copy locks the caller's pages)
     if (e == hipSuccess && n_blocks) {
-      st = pvlm_i_h2d_q(ctx, d_blocks, blocks, (size_t)n_blocks * 36 * sizeof(double));
+      if (blocks_on_device) d_blocks = const_cast<double*>(blocks);
+      else st = pvlm_i_h2d_q(ctx, d_blocks, blocks, (size_t)n_blocks * 36 * sizeof(double));
       if (plan->sparse && !plan->idx_on_device && !st) {
         // the (permuted) index lists of this structure stay on the device with the plan: later solves send the values only
         st = pvlm_i_alloc(ctx, &plan->d_idx_rows, (size_t)n_blocks * 6);
@@ -1685,7 +1696,7 @@ pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int*
       // redone with them — same inputs (the caller's right-hand side has not been touched yet), a deterministic result again.
       ctx->spd_one_launch = 0; ctx->spd_fallbacks += 1;
       fprintf(stderr, "pvlm_spd_solve_blocks: redone with the level launches; this context keeps them (pvlm_spd_one_launch)\n");
-      return pvlm_spd_solve_blocks(ctx, n_user, n_blocks, user_rows, user_cols, mirror, blocks, user_scale, user_diag, rhs, info_out);
+      return pvlm_i_spd_solve_blocks(ctx, n_user, n_blocks, user_rows, user_cols, mirror, blocks, blocks_on_device, user_scale, user_diag, rhs, info_out);
     }
     pvlm_i_trace("spd solve: factorised and solved");
     if (!st && plan->sparse) for (int i = 0; i < n_user; ++i) rhs[i] = prhs[(size_t)plan->new_of_old[(size_t)i]];
@@ -1695,6 +1706,8 @@ pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int*
   }
   return st;
 }
+
+extern "C" {
 
 // Starts the host half of the plan for this structure on a thread of its own and returns at once; the next pvlm_spd_solve_blocks with EXACTLY these lists takes it
 // (any other structure: the prefetch is dropped and the plan made as before).  The lists are copied.  No device work here.

@@ -804,6 +804,49 @@ bool SetTranslationScaleDepthMap(const std::vector<Frame>& frames, const DeviceD
 bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<MatchPair>& image_pairs, const DeviceDepthMaps& depth_maps, std::vector<RelativePair>& good_pair,
                           std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options = EssentialOptions());
 
+// ---- K42: translation averaging (sfm/TranslationAveraging.cpp:31-204, :419-481; sfm/SfM.cpp:908-934, :1047-1344, :1385-1421) ----------------------------------
+// sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built; L1 (the LP), CHORDAL, BATA and LUD are not: EstimateGlobalTranslation returns false with upstream's "not supported".
+enum TranslationAveragingMethod { TRANSLATION_AVERAGING_SOFTL1 = 1, TRANSLATION_AVERAGING_L1 = 2, TRANSLATION_AVERAGING_CHORDAL = 3, TRANSLATION_AVERAGING_L2IRLS = 4,
+                                  TRANSLATION_AVERAGING_BATA = 5, TRANSLATION_AVERAGING_LUD = 6 };
+// what base/Config.h holds for the stage, and what upstream draws from srand(time): the start translations are uniform [-1, 1] from splitmix64 on `seed` (K34's
+// answer to std::random_device).  host = true runs every solve through the host compile of csrc/pvlm_transavg_core.h (pvlm_host_transavg.hpp; no device).
+// message: where the text of upstream's LOG(ERROR) goes when the call returns false.
+struct TranslationOptions {
+  bool use_all_pairs_ta = true, init_translation_DLT = true, init_translation_GPS = false;
+  std::string gps_path;
+  int num_iteration_L2IRLS = 10;
+  float upper_scale_ratio = 1.3f, lower_scale_ratio = 0.9f;
+  unsigned long long seed = 0;
+  bool host = false;
+  std::string* message = nullptr;
+};
+// TranslationAveragingDLT (:31-84) through pvlm_transavg_dlt: the normal equations with camera 0 fixed at zero.  Upstream's SparseQR returns SOME basic solution of a
+// system that is rank-deficient by the gauge t_i = R_i c; every caller runs SetToOrigin afterwards, which cancels the difference.  false: a pair names a camera
+// past global_translations (upstream writes out of range), or the system is not positive definite (a pair graph that is not connected).
+bool TranslationAveragingDLT(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const bool host = false);
+// TranslationAveragingL2 (:87-169) through pvlm_transavg_solve (see pvlm.h for the definition and its divergences).  loss_a stands for the ceres::LossFunction*:
+// SoftLOneLoss(loss_a), none when negative.  `weight` is read by nobody upstream (the functor never applies it) and is only written.  false: the summary is not usable.
+bool TranslationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, std::vector<double>& scales, const size_t origin_idx,
+                            std::vector<double>& weight, double& costs, const double loss_a, const float upper_scale_ratio, const float lower_scale_ratio, const bool host = false);
+// :171-204
+bool TranslationAveragingSoftL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const double l1_loss_threshold,
+                                const float upper_scale_ratio, const float lower_scale_ratio, const bool host = false);
+// :419-481: at most num_iteration solves; stops when the cost moved by less than 5 % or is below 10 (as written, :443); after a solve that did not stop, the pairs whose
+// scale went negative are dropped from image_pairs.  iterations_run: the solves done.
+bool TranslationAveragingL2IRLS(std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const int num_iteration,
+                                const float upper_scale_ratio, const float lower_scale_ratio, const bool host = false, int* iterations_run = nullptr);
+// SfM::ReIndex (sfm/SfM.cpp:908-934): the frame ids of a pair list onto 0 .. n - 1 in ascending order
+void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward);
+// SfM::SetToOrigin (:1385-1421) without the structure: every valid pose into the frame of frames[frame_idx] (the first valid frame when that one has no pose).
+// A pose is valid as sensors/Frame.cpp:203-208 writes it (finite translation, rotation not zero); pose_valid is kept equal to that.
+bool SetToOrigin(std::vector<Frame>& frames, size_t frame_idx);
+// SfM::EstimateGlobalTranslation (:1047-1344), operation by operation: the frames with a rotation, the scaled / unscaled split, LargestBiconnectedGraph, both
+// re-indexings, the DLT start with its SetToOrigin, the solve, t_wc = -R_wc t_cw, the final filter of the pairs.  frames[i].R_wc holds the global rotations (all zero:
+// none); image_pairs is replaced by the pairs with a global pose.  Divergences: the random start (TranslationOptions::seed); :1183 hands the DLT ALL pairs under the
+// global indices with an output sized by the scaled component — followed as written whenever every index fits, refused with a message when one does not (upstream
+// writes out of range); GPS is not supported.
+bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const TranslationOptions& options = TranslationOptions());
+
 // ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------
 // base/common.h's FrameMatchMethod and sfm/VLAD.h's normalisation types
 enum FrameMatchMethod { EXHAUSTIVE = 1, CONTIGUOUS = 2, VLAD = 4, GPS = 8, GPS_VLAD = 16 };

@@ -3,7 +3,8 @@
 // SfM::GlobalBundleAdjustment (sfm/SfM.cpp:1362-1383), MVS::RefineCameraPose (mvs/MVS.cpp:383-428) and
 // CameraLidarOptimizer::GlobalBundleAdjustment (joint_optimization/CameraLidarOptimizer.cpp:732-740); and what builds the structure they refine —
 // TriangulateTracks / FilterTracksToFar (sfm/Structure.cpp:8-119), CameraLidarOptimizer::EstimateStructure (:720-729), MVS::EstimateStructure
-// (mvs/MVS.cpp:44-59).
+// (mvs/MVS.cpp:44-59); and the step between the relative and the global poses — EstimateGlobalTranslation with TranslationAveragingDLT / L2 / SoftL1 / L2IRLS, ReIndex,
+// SetToOrigin (sfm/SfM.cpp:1047-1344, sfm/TranslationAveraging.cpp; K42).
 // Host logic only; the reprojection blocks are solved and the tracks are triangulated and tested by libpvlm.so on the GPU (K9 / K31 / K32).
 #include "pvlm_host_internal.hpp"
 #include "pvlm_host_structure.hpp"
@@ -13,6 +14,7 @@
 #include "pvlm_host_vlad.hpp"
 #include "pvlm_host_relpose.hpp"
 #include "../csrc/pvlm_depthfill_core.h"
+#include "pvlm_host_transavg.hpp"
 
 namespace pvlm {
 
@@ -831,6 +833,229 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
   SetTranslationScaleDepthMap(frames, depth_maps, good_pair, keep_no_scale);
   good_pair = LargestBiconnectedGraph(good_pair, covered_frames);
   relpose_detail::SortAsWritten(good_pair, [](const RelativePair& a, const RelativePair& b) { return relpose_detail::PairLessAsWritten(a.image_pair, b.image_pair); });
+  return true;
+}
+
+// ================================================================================================
+// K42: translation averaging — TranslationAveragingDLT / L2 / SoftL1 / L2IRLS (sfm/TranslationAveraging.cpp), ReIndex, SetToOrigin, EstimateGlobalTranslation
+// ================================================================================================
+namespace {
+// the arrays of pvlm_transavg_* from a pair list; false: a pair names a camera past n_cameras
+struct TransavgInputs {
+  std::vector<int> first, second; std::vector<double> R, t;
+  bool Fill(const std::vector<RelativePair>& pairs, size_t n_cameras) {
+    for (const RelativePair& p : pairs) {
+      if (p.image_pair.first >= n_cameras || p.image_pair.second >= n_cameras) return false;
+      first.push_back((int)p.image_pair.first); second.push_back((int)p.image_pair.second);
+      R.insert(R.end(), p.R_21.begin(), p.R_21.end()); t.insert(t.end(), p.t_21.begin(), p.t_21.end());
+    }
+    first.push_back(0); second.push_back(0); R.resize(R.size() + 9); t.resize(t.size() + 3);   // never empty
+    return true;
+  }
+};
+bool RotationIsZero(const Frame& f) { for (double v : f.R_wc) if (v != 0.0) return false; return true; }
+// sensors/Frame.cpp:203-208 on the numbers themselves: the translation finite and the rotation not zero
+bool PoseValidAsWritten(const Frame& f) { return std::isfinite(f.t_wc[0]) && std::isfinite(f.t_wc[1]) && std::isfinite(f.t_wc[2]) && !RotationIsZero(f); }
+void SetTranslationOf(Frame& f, const Vector3d& t_wc) { f.t_wc = t_wc; f.pose_valid = PoseValidAsWritten(f); }
+Vector3d MinusRt(const Matrix3d& R, const Vector3d& t) {       // -R t
+  return {-(R[0] * t[0] + R[1] * t[1] + R[2] * t[2]), -(R[3] * t[0] + R[4] * t[1] + R[5] * t[2]), -(R[6] * t[0] + R[7] * t[1] + R[8] * t[2])};
+}
+bool Say(const TranslationOptions& o, const char* m) { if (o.message) *o.message = m; return false; }
+}  // namespace
+
+bool TranslationAveragingDLT(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const bool host) {
+  TransavgInputs in;
+  if (!in.Fill(image_pairs, global_translations.size())) return false;      // upstream writes past the matrix here (sfm/SfM.cpp:1183 is the caller that can do it)
+  const int F = (int)global_translations.size(), P = (int)image_pairs.size();
+  std::vector<double> out(3 * (size_t)F + 3, 0.0);
+  int info = 0;
+  if (host) { if (transavg_detail::DltHost(F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), out.data(), &info)) return false; }
+  else { Engine& e = Engine::Default(); e.Check(pvlm_transavg_dlt(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), out.data(), &info), "pvlm_transavg_dlt"); }
+  if (info != 0) return false;
+  for (int c = 0; c < F; ++c) global_translations[(size_t)c] = {out[3 * (size_t)c], out[3 * (size_t)c + 1], out[3 * (size_t)c + 2]};
+  return true;
+}
+
+bool TranslationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, std::vector<double>& scales, const size_t origin_idx,
+                            std::vector<double>& weight, double& costs, const double loss_a, const float upper_scale_ratio, const float lower_scale_ratio, const bool host) {
+  TransavgInputs in;
+  const int F = (int)global_translations.size(), P = (int)image_pairs.size();
+  if (!in.Fill(image_pairs, global_translations.size()) || scales.size() != image_pairs.size() || weight.size() != image_pairs.size()) return false;
+  std::vector<double> x(3 * (size_t)F + 3, 0.0), s(scales), w(weight);
+  for (int c = 0; c < F; ++c) for (int k = 0; k < 3; ++k) x[3 * (size_t)c + k] = global_translations[(size_t)c][(size_t)k];
+  s.push_back(0.0); w.push_back(0.0);
+  pvlm_transavg_summary sum{0, 0, 0, 0, 0};
+  if (host) {
+    pvlm_transavg::Summary hs;
+    if (transavg_detail::SolveHost(F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), s.data(), (int)origin_idx, x.data(), w.data(), loss_a, upper_scale_ratio,
+                                   lower_scale_ratio, 50, &hs)) return false;
+    sum.initial_cost = hs.initial_cost; sum.final_cost = hs.final_cost; sum.termination = hs.termination;
+  } else {
+    Engine& e = Engine::Default();
+    const pvlm_transavg_params prm{loss_a, upper_scale_ratio, lower_scale_ratio, 50};
+    e.Check(pvlm_transavg_solve(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), s.data(), (int)origin_idx, x.data(), w.data(), &prm, &sum), "pvlm_transavg_solve");
+  }
+  if (sum.termination == pvlm_transavg::kCostNotFinite || !std::isfinite(sum.final_cost)) return false;       // summary.IsSolutionUsable()
+  for (int c = 0; c < F; ++c) global_translations[(size_t)c] = {x[3 * (size_t)c], x[3 * (size_t)c + 1], x[3 * (size_t)c + 2]};
+  std::copy(s.begin(), s.begin() + P, scales.begin()); std::copy(w.begin(), w.begin() + P, weight.begin());
+  costs = sum.final_cost;
+  return true;
+}
+
+namespace {
+// :176-183, :424-432: the length of t_21, or 1 for a pair that never got a scale
+std::vector<double> StartScales(const std::vector<RelativePair>& image_pairs) {
+  std::vector<double> scales(image_pairs.size());
+  for (size_t i = 0; i < image_pairs.size(); ++i) {
+    const Vector3d& t = image_pairs[i].t_21;
+    scales[i] = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    if (image_pairs[i].lower_scale < 0 || image_pairs[i].upper_scale < 0) scales[i] = 1;
+  }
+  return scales;
+}
+}  // namespace
+
+bool TranslationAveragingSoftL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const double l1_loss_threshold,
+                                const float upper_scale_ratio, const float lower_scale_ratio, const bool host) {
+  std::vector<double> scales = StartScales(image_pairs), weight(image_pairs.size(), 1.0);
+  double costs = 0;
+  return TranslationAveragingL2(image_pairs, global_translations, scales, origin_idx, weight, costs, l1_loss_threshold, upper_scale_ratio, lower_scale_ratio, host);
+}
+
+bool TranslationAveragingL2IRLS(std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const int num_iteration,
+                                const float upper_scale_ratio, const float lower_scale_ratio, const bool host, int* iterations_run) {
+  std::vector<double> scales = StartScales(image_pairs), weight(image_pairs.size(), 1.0);
+  double curr_cost = 0, last_cost = 0;
+  if (iterations_run) *iterations_run = 0;
+  for (int iter = 0; iter < num_iteration; ++iter) {
+    if (!TranslationAveragingL2(image_pairs, global_translations, scales, origin_idx, weight, curr_cost, 0.01, upper_scale_ratio, lower_scale_ratio, host)) return false;
+    if (iterations_run) *iterations_run = iter + 1;
+    if (std::fabs(last_cost - curr_cost) / curr_cost < 0.05 || curr_cost < 10) break;       // :443 as written
+    last_cost = curr_cost;
+    std::vector<RelativePair> good_matches; std::vector<double> good_scales, good_weight;
+    for (size_t i = 0; i < scales.size(); ++i) {
+      if (scales[i] < 0) continue;
+      good_scales.push_back(scales[i]); good_weight.push_back(weight[i]); good_matches.push_back(image_pairs[i]);
+    }
+    if (good_scales.size() != scales.size()) { good_scales.swap(scales); good_weight.swap(weight); good_matches.swap(image_pairs); }
+  }
+  return true;
+}
+
+void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward) {
+  forward.clear(); backward.clear();
+  std::set<size_t> old_id;
+  for (const RelativePair& pair : pairs) { old_id.insert(pair.image_pair.first); old_id.insert(pair.image_pair.second); }
+  for (const RelativePair& pair : pairs)
+    for (const size_t id : {pair.image_pair.first, pair.image_pair.second})
+      if (forward.find(id) == forward.end()) {
+        const size_t dist = (size_t)std::distance(old_id.begin(), old_id.find(id));
+        forward[id] = dist; backward[dist] = id;
+      }
+}
+
+bool SetToOrigin(std::vector<Frame>& frames, size_t frame_idx) {
+  if (frame_idx > frames.size()) return false;                                  // `>` as written (:1387)
+  if (frame_idx == frames.size() || !PoseValidAsWritten(frames[frame_idx])) {   // (== size: upstream reads past the list)
+    for (frame_idx = 0; frame_idx < frames.size(); ++frame_idx) if (PoseValidAsWritten(frames[frame_idx])) break;
+    if (frame_idx == frames.size()) return false;                               // no frame has a pose (upstream reads past the list)
+  }
+  const Matrix3d Ro = frames[frame_idx].R_wc; const Vector3d to = frames[frame_idx].t_wc;
+  for (Frame& f : frames) {
+    if (!PoseValidAsWritten(f)) continue;
+    // T_ic = T_iw T_wc(origin), the new pose its inverse: R' = Ro^T R_i, t' = Ro^T (t_i - t_o), by rigid inverses (upstream: Eigen's general 4 x 4 inverse, ~1e-16 apart)
+    Matrix3d Ri; Vector3d ti, Ric_t;
+    RigidInverse(f.R_wc, f.t_wc, &Ri, &ti);
+    Matrix3d Ric;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) Ric[3 * r + c] = Ri[3 * r] * Ro[c] + Ri[3 * r + 1] * Ro[3 + c] + Ri[3 * r + 2] * Ro[6 + c];
+      Ric_t[r] = (Ri[3 * r] * to[0] + Ri[3 * r + 1] * to[1] + Ri[3 * r + 2] * to[2]) + ti[r];
+    }
+    Matrix3d Rn; Vector3d tn;
+    RigidInverse(Ric, Ric_t, &Rn, &tn);
+    f.R_wc = Rn; f.t_wc = tn; f.pose_valid = PoseValidAsWritten(f);
+  }
+  return true;
+}
+
+bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const TranslationOptions& o) {
+  if (!o.gps_path.empty() || o.init_translation_GPS) return Say(o, "GPS is not supported");
+  // the frames with a global rotation (:1067-1080)
+  std::set<size_t> frame_with_rotation;
+  for (const Frame& f : frames) if (!RotationIsZero(f)) frame_with_rotation.insert((size_t)f.id);
+  std::vector<RelativePair> pair_with_rotation;
+  for (const RelativePair& pair : image_pairs)
+    if (frame_with_rotation.count(pair.image_pair.first) > 0 && frame_with_rotation.count(pair.image_pair.second) > 0) pair_with_rotation.push_back(pair);
+  std::vector<RelativePair> pair_with_scale, pair_without_scale;
+  for (const RelativePair& p : pair_with_rotation) (p.upper_scale >= 0 && p.lower_scale >= 0 ? pair_with_scale : pair_without_scale).push_back(p);
+  std::set<size_t> largest_component_nodes;
+  image_pairs = LargestBiconnectedGraph(o.use_all_pairs_ta ? pair_with_rotation : pair_with_scale, largest_component_nodes);
+  if (image_pairs.empty()) return Say(o, "no nodes are bi-edge connected");
+  for (const RelativePair& p : image_pairs) if (p.image_pair.first >= frames.size() || p.image_pair.second >= frames.size()) return Say(o, "a pair names a frame that is not there");
+  pair_with_rotation.clear();
+  // the start: zero for camera 0, uniform [-1, 1] for the others (upstream: Eigen's Random() after srand(time); here splitmix64 on options.seed)
+  std::vector<Vector3d> global_translations(largest_component_nodes.size(), Vector3d{0, 0, 0});
+  {
+    uint64_t st = o.seed;
+    auto next = [&st]() { uint64_t z = (st += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); };
+    for (size_t i = 1; i < global_translations.size(); ++i) for (int k = 0; k < 3; ++k) global_translations[i][(size_t)k] = (double)(next() >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+  }
+  // 1. the global re-indexing (:1148-1159)
+  std::map<size_t, size_t> old_to_new_global, new_to_old_global;
+  ReIndex(image_pairs, old_to_new_global, new_to_old_global);
+  for (RelativePair& pair : pair_with_scale) { pair.image_pair.first = old_to_new_global[pair.image_pair.first]; pair.image_pair.second = old_to_new_global[pair.image_pair.second]; }
+  for (RelativePair& pair : image_pairs) { pair.image_pair.first = old_to_new_global[pair.image_pair.first]; pair.image_pair.second = old_to_new_global[pair.image_pair.second]; }
+  size_t origin_idx = 0;
+  // 2. the DLT start on the scaled pairs (:1165-1216)
+  if (o.init_translation_DLT && !pair_with_scale.empty()) {
+    std::map<size_t, size_t> old_to_new, new_to_old;
+    pair_with_scale = LargestBiconnectedGraph(pair_with_scale, largest_component_nodes);
+    ReIndex(pair_with_scale, old_to_new, new_to_old);
+    for (RelativePair& pair : pair_with_scale) { pair.image_pair.first = old_to_new[pair.image_pair.first]; pair.image_pair.second = old_to_new[pair.image_pair.second]; }
+    std::vector<Vector3d> global_translation_scale(largest_component_nodes.size());
+    // :1183 as written: ALL pairs under the global indices into an output sized by the scaled component.  Every index fits when the scaled pairs cover the same
+    // frames; when one does not, upstream writes out of range — refused here
+    for (const RelativePair& p : image_pairs)
+      if (p.image_pair.first >= global_translation_scale.size() || p.image_pair.second >= global_translation_scale.size())
+        return Say(o, "Translation average DLT: the pair list names a camera past the scaled component (sfm/SfM.cpp:1183 writes out of range here)");
+    if (global_translation_scale.empty() || !TranslationAveragingDLT(image_pairs, global_translation_scale, o.host)) return Say(o, "Translation average DLT failed");
+    origin_idx = new_to_old_global[new_to_old[0]];
+    for (size_t i = 0; i < global_translation_scale.size(); ++i) {
+      Frame& f = frames[new_to_old_global[new_to_old[i]]];
+      SetTranslationOf(f, MinusRt(f.R_wc, global_translation_scale[i]));
+    }
+    SetToOrigin(frames, origin_idx);
+    for (size_t i = 0; i < global_translations.size(); ++i) {
+      const auto it = new_to_old_global.find(i);
+      if (it == new_to_old_global.end()) continue;
+      if (!PoseValidAsWritten(frames[it->second])) continue;
+      Matrix3d Ri; Vector3d ti;
+      RigidInverse(frames[it->second].R_wc, frames[it->second].t_wc, &Ri, &ti);
+      global_translations[i] = ti;
+    }
+    origin_idx = old_to_new_global[origin_idx];
+  }
+  // 3. the averaging
+  bool success = false;
+  if (method == TRANSLATION_AVERAGING_SOFTL1)
+    success = TranslationAveragingSoftL1(image_pairs, global_translations, origin_idx, 0.01, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
+  else if (method == TRANSLATION_AVERAGING_L2IRLS)
+    success = TranslationAveragingL2IRLS(image_pairs, global_translations, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
+  else return Say(o, "Translaton average method not supported");       // L1 (the LP), chordal, BATA and LUD are not built; the text is upstream's (:1308)
+  if (!success) return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : "Translation average L2 IRLS failed");
+  for (RelativePair& pair : image_pairs) { pair.image_pair.first = new_to_old_global[pair.image_pair.first]; pair.image_pair.second = new_to_old_global[pair.image_pair.second]; }
+  std::set<size_t> frame_with_translation;
+  for (size_t i = 0; i < global_translations.size(); ++i) {
+    Frame& f = frames[new_to_old_global[i]];
+    SetTranslationOf(f, MinusRt(f.R_wc, global_translations[i]));       // t_wc = -R_wc t_cw
+    frame_with_translation.insert(new_to_old_global[i]);
+  }
+  std::vector<RelativePair> good_pair;
+  for (const RelativePair& p : image_pairs) {
+    const size_t idx1 = p.image_pair.first, idx2 = p.image_pair.second;
+    if (frame_with_translation.count(idx1) && frame_with_translation.count(idx2) && frame_with_rotation.count(idx1) && frame_with_rotation.count(idx2)) good_pair.push_back(p);
+  }
+  good_pair.swap(image_pairs);
   return true;
 }
 
