@@ -515,6 +515,42 @@ pvlm_status pvlm_transavg_solve(pvlm_ctx* ctx, int n_cameras, int n_pairs, const
                                 double* weight /* in/out, n_pairs */, const pvlm_transavg_params* params, pvlm_transavg_summary* summary);
 int pvlm_transavg_group_size(void);
 
+/* ---- K40: rotation averaging (SfM::EstimateGlobalRotation sfm/SfM.cpp:811-905; RotationAveragingRefineL1 / RotationAveragingL2 sfm/RotationAveraging.cpp:317-582) ---- *
+ * The definition (csrc/pvlm_rotavg_core.h).  F cameras, P pairs (first, second, R_21 row-major), rotations R_cw row-major, 9 per camera.
+ * pvlm_rotavg_l1 is RotationAveragingRefineL1 with weight function 1 (:428-582): rotations[start_idx] is the identity and stays it.  Pair error
+ * e_p = log(R_2w^T R_21 R_1w) (:476-478).  L1 stage (:460-503): per outer iteration the errors b, then the ADMM of least absolute deviations (rho = 1, alpha = 1,
+ * absolute tolerance 1e-4, relative tolerance 1e-2, at most 1000 iterations, stopped by the two-norm tests of the method; not converged is not an error, as upstream
+ * ignores Solve's return value); curr_e = |x|, break before the update when last_e < curr_e, R <- R exp(x_r), continue while ++iter < 32 && curr_e > 1e-5 &&
+ * (last_e - curr_e) / curr_e > 1e-2.  IRLS stage (:505-580): errors = A x_prev - b, weights = |errors|^-1.5 per row and component, A^T W A x = A^T W b, the same
+ * update, curr_e = |x_prev - x|, the same loop condition.  summary: the L1 outer iterations, the ADMM iterations of all of them, the IRLS iterations and info:
+ * 0, or k > 0 when an IRLS system was not finite or not positive definite (a pair error of zero gives an infinite weight); the rotations are then those of the last
+ * completed iteration (upstream returns false, :553-557).
+ * pvlm_rotavg_l2 is RotationAveragingL2 (:317-374): one angle-axis vector per camera, none fixed, r_p = log(R_2w R_1w^T R_21^T) (PairWiseRotationResidual,
+ * base/CostFunction.h:17-47) under SoftLOneLoss(loss_a) on |r|^2 (no loss when loss_a < 0), LM with ceres_like::Solve's policy and Solver::Options' defaults, the
+ * Jacobi scaling and LM diagonal of K42.  summary: K42's fields and termination numbering (6: no pairs).  The result is unusable only if it is not finite (the
+ * rotations are then left as they came).
+ * Deliberate divergences.  Upstream carries every pair twice, (i, j, R_21) and (j, i, R_21^T), in the order of a std::map; the mirrored half of every ADMM vector is
+ * the negative of the first half, so P rows are carried with the factors 2 and sqrt(2) that follow (A^T A = 2 L (x) I_3, L the Laplacian of the pair graph without
+ * start_idx); x, y and z decouple in the L1 stage: (2 L)^-1 is formed ONCE per call as a dense matrix of order F - 1 (pvlm_spd_solve with the identity as right-hand
+ * sides) and the x-update of every ADMM iteration is a dense product with three columns, where upstream factorises once and substitutes; the IRLS systems go through
+ * the solver behind pvlm_spd_solve_blocks (upstream: SimplicialLDLT); analytic 3 x 3 Jacobians replace the autodiff; R_21 is used directly instead of through an
+ * angle-axis vector (as K36 and K42); rotations_after_L1.txt is not written.
+ * Every sum has one order (per camera: its pairs in list order over pvlm_rotavg_group_size() lanes and a fixed butterfly; the scalars: a fixed tree over pairs or
+ * cameras; the dense product: a row over 64 lanes, lane l the columns l, l + 64, ..., and a fixed butterfly), so a call is bit-reproducible from run to run.
+ * PVLM_ERR_ARG, with no output touched: a NULL, a camera index out of range, first == second, the same camera pair named twice in either orientation (upstream's
+ * map would collapse it), an input that is not finite, start_idx out of range, rotations[start_idx] not the identity on entry to _l1, a pair graph that is not
+ * connected, n_cameras < 1, max_num_iterations < 0.
+ * The environment variable PVLM_ROTAVG_MAX_BLOCKS (read at every call) lowers the grids of the kernels; it changes no result, the tests use it to make them stride.
+ * With PVLM_ROTAVG_PROFILE set, each call prints one line on stderr: its wall clock split into kernels, solves, the forming of (2 L)^-1 and host. */
+typedef struct pvlm_rotavg_l1_summary { int l1_iterations, admm_iterations, irls_iterations, info; } pvlm_rotavg_l1_summary;
+typedef struct pvlm_rotavg_l2_params { double loss_a /* 0.07 */; int max_num_iterations /* 50 */; } pvlm_rotavg_l2_params;
+typedef struct pvlm_rotavg_l2_summary { double initial_cost, final_cost; int successful_steps, unsuccessful_steps, termination; } pvlm_rotavg_l2_summary;
+pvlm_status pvlm_rotavg_l1(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21 /* n_pairs * 9 */, int start_idx,
+                           double* rotations /* in/out, 9 per camera */, pvlm_rotavg_l1_summary* summary);
+pvlm_status pvlm_rotavg_l2(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21, double* rotations /* in/out */,
+                           const pvlm_rotavg_l2_params* params, pvlm_rotavg_l2_summary* summary);
+int pvlm_rotavg_group_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

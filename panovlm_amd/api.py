@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "pvlm_resset_plane_runs", "pvlm_resset_point_table", "pvlm_resset_point_table_debug",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
     "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size",
+    "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1789,6 +1790,60 @@ def transavg_solve(ctx, first, second, R_21, t_21, scales, origin_idx, translati
     intact = bool(np.all(t[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0))
     return dict(translations=t[:F], scales=s[:P], weight=w[:P], initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
                 unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
+
+
+class RotavgL1Summary(C.Structure):
+    _fields_ = [("l1_iterations", C.c_int), ("admm_iterations", C.c_int), ("irls_iterations", C.c_int), ("info", C.c_int)]
+
+
+class RotavgL2Params(C.Structure):
+    _fields_ = [("loss_a", C.c_double), ("max_num_iterations", C.c_int)]
+
+
+ROTAVG_GUARD = 8     # sentinel cameras the two wrappers keep behind the rotations
+
+
+def rotavg_group_size():
+    """pvlm_rotavg_group_size (K40): the lanes that share one camera's gather."""
+    return int(load_library().pvlm_rotavg_group_size())
+
+
+def _rotavg_inputs(first, second, R_21, rotations):
+    first = _i32(first); second = _i32(second); P = len(first)
+    R21 = _f64(np.asarray(R_21, np.float64).reshape(P, 9))
+    r_in = np.asarray(rotations, np.float64).reshape(-1, 9); F = len(r_in)
+    rot = np.full((F + ROTAVG_GUARD, 9), -7.0); rot[:F] = r_in
+    return first, second, P, R21, F, rot
+
+
+def rotavg_l1(ctx, first, second, R_21, start_idx, rotations, check=True):
+    """pvlm_rotavg_l1 (K40): RotationAveragingRefineL1, the L1 (ADMM) stage and the IRLS stage, from `rotations` (cameras x 3 x 3, R_cw, the identity at start_idx).
+    The inputs are not modified.  Returns a dict: rotations (cameras x 3 x 3), l1_iterations, admm_iterations, irls_iterations, info (0, or k > 0: an IRLS system
+    was not finite or not positive definite), guard_intact, rc.  An argument the library refuses raises PvlmError; with check=False the dict comes back with its rc
+    (the rotations then hold the input: the library touches nothing it refuses)."""
+    first, second, P, R21, F, rot = _rotavg_inputs(first, second, R_21, rotations)
+    sm = RotavgL1Summary(-7, -7, -7, -7)
+    rc = ctx.lib.pvlm_rotavg_l1(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R21, C.c_double), C.c_int(start_idx), _p(rot, C.c_double),
+                                C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_rotavg_l1")
+    return dict(rotations=rot[:F].reshape(F, 3, 3), l1_iterations=sm.l1_iterations, admm_iterations=sm.admm_iterations, irls_iterations=sm.irls_iterations, info=sm.info,
+                guard_intact=bool(np.all(rot[F:] == -7.0)), rc=int(rc))
+
+
+def rotavg_l2(ctx, first, second, R_21, rotations, loss_a=0.07, max_num_iterations=50, check=True):
+    """pvlm_rotavg_l2 (K40): RotationAveragingL2 under SoftLOneLoss(loss_a) (no loss when loss_a < 0).  The inputs are not modified.  Returns a dict: rotations
+    (cameras x 3 x 3), initial_cost, final_cost, successful_steps (accepted), unsuccessful_steps, termination (TRANSAVG_TERMINATIONS), guard_intact, rc.  An argument
+    the library refuses raises PvlmError; with check=False the dict comes back with its rc."""
+    first, second, P, R21, F, rot = _rotavg_inputs(first, second, R_21, rotations)
+    prm = RotavgL2Params(loss_a, max_num_iterations)
+    sm = TransavgSummary(-7.0, -7.0, -7, -7, -7)
+    rc = ctx.lib.pvlm_rotavg_l2(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R21, C.c_double), _p(rot, C.c_double), C.byref(prm),
+                                C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_rotavg_l2")
+    return dict(rotations=rot[:F].reshape(F, 3, 3), initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
+                unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=bool(np.all(rot[F:] == -7.0)), rc=int(rc))
 
 
 def device_sort(ctx, keys):

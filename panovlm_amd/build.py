@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip", "pvlm_rotavg.hip")
 
 
 def _hipcc():
@@ -125,7 +125,10 @@ DISPATCH_ORDER_CHECK = os.path.join(HERE, "build", "dispatch_order_check")
 SIFT_DRIVER = os.path.join(HERE, "build", "pvlm_sift_driver")
 TRANSAVG_DRIVER = os.path.join(HERE, "build", "pvlm_transavg_driver")
 TRANSAVG_CHECK = os.path.join(HERE, "build", "libtransavg_check.so")
+ROTAVG_DRIVER = os.path.join(HERE, "build", "pvlm_rotavg_driver")
 TRANSAVG_CHECK_MAIN = os.path.join(HERE, "build", "transavg_check_main")
+ROTAVG_CHECK = os.path.join(HERE, "build", "librotavg_check.so")
+ROTAVG_CHECK_MAIN = os.path.join(HERE, "build", "rotavg_check_main")
 
 
 def build_host(force=False):
@@ -245,6 +248,14 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", gdrv, "-o", TRANSAVG_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     build_transavg_check()
+    # the rotation-averaging driver (EstimateGlobalRotation into EstimateGlobalTranslation and the pieces of the former, on the host compile or through the device:
+    # K40) and the host compile of the K40 core for the tests
+    adrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_rotavg_driver.cpp")
+    if os.path.exists(adrv) and (force or not os.path.exists(ROTAVG_DRIVER) or
+                                 os.path.getmtime(ROTAVG_DRIVER) < max(os.path.getmtime(adrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", adrv, "-o", ROTAVG_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    build_rotavg_check()
     return HOST_LIB
 
 
@@ -260,6 +271,21 @@ def build_transavg_check(main=False, sanitize=False):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(chk), os.path.getmtime(core), os.path.getmtime(backend)):
         mode = ["-O1", "-g", "-DTRANSAVG_CHECK_MAIN"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off"] + mode + [chk, "-o", out])
+    return out
+
+
+def build_rotavg_check(main=False, sanitize=False):
+    """The host compile of the K40 core (csrc/pvlm_rotavg_core.h behind tests/cpp/rotavg_core_check.cpp; no device, -ffp-contract=off as the device build of
+    pvlm_rotavg.hip): build/librotavg_check.so for the tests, or with main=True the stand-alone program of the same file (sanitize: the host sanitizers)."""
+    chk = os.path.join(HERE, "..", "tests", "cpp", "rotavg_core_check.cpp")
+    deps = [chk, os.path.join(HERE, "csrc", "pvlm_rotavg_core.h"), os.path.join(HERE, "csrc", "pvlm_transavg_core.h"), os.path.join(HERE, "host", "pvlm_host_rotavg.hpp")]
+    out = ROTAVG_CHECK_MAIN if main else ROTAVG_CHECK
+    if not os.path.exists(chk):
+        return None
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        mode = ["-O1", "-g", "-DROTAVG_CHECK_MAIN"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off"] + mode + [chk, "-o", out])
     return out
 

@@ -847,6 +847,44 @@ bool SetToOrigin(std::vector<Frame>& frames, size_t frame_idx);
 // writes out of range); GPS is not supported.
 bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const TranslationOptions& options = TranslationOptions());
 
+// ---- K40: rotation averaging (sfm/RotationAveraging.cpp:11-183, :278-582; sfm/PoseGraph.cpp:195-226; sfm/SfM.cpp:705-778, :811-905) ------------------------------
+// base/common.h.  L1 (the method of both shipped configs) is built; L2 needs the eigenvectors of a dense 3 F x 3 F matrix for its start (RotationAveragingLeastSquare)
+// and is not: EstimateGlobalRotation returns false with a message.
+enum RotationAveragingMethod { ROTATION_AVERAGING_L1 = 1, ROTATION_AVERAGING_L2 = 2 };
+// what base/Config.h holds for the stage.  host = true runs every solve through the host compile of csrc/pvlm_rotavg_core.h (pvlm_host_rotavg.hpp; no device).
+// message: where the text of upstream's LOG(ERROR) goes when the call returns false.
+struct RotationOptions {
+  bool use_all_pairs_ra = true;
+  bool host = false;
+  std::string* message = nullptr;
+};
+struct Triplet { uint32_t i, j, k; };
+// PoseGraph::FindTriplet (sfm/PoseGraph.cpp:195-226): per edge in the set's order, the nodes adjacent to both its ends, then the edge leaves the adjacency
+std::vector<Triplet> FindTriplet(const std::set<std::pair<size_t, size_t>>& edges);
+// SfM::FilterByTriplet (:705-778) as written: a triplet is kept when acos(clamp(trace(R_13 R_32 R_21) / 3)) in degrees is below angle_threshold; the pairs of the
+// kept triplets, then LargestBiconnectedGraph.  Every pair must have first < second (upstream asserts): an empty list comes back otherwise.
+std::vector<RelativePair> FilterByTriplet(const std::vector<RelativePair>& init_pairs, const double angle_threshold, std::set<size_t>& covered_frames);
+// FilterPairs (sfm/RotationAveraging.cpp:11-183): the X84 threshold (median + 5.2 MAD of the pair errors) when angle_threshold <= 0, then the frame rule of
+// :101-165 (three neighbours before and three after within 10 frames, filled from the rejected pairs by ascending error).  threshold_out: the threshold in radians.
+std::vector<RelativePair> FilterPairs(const std::vector<RelativePair>& image_pairs, const std::vector<Matrix3d>& global_rotations, double angle_threshold,
+                                      double* threshold_out = nullptr);
+// RotationAveragingSpanningTree (:278-315).  DIVERGENCE: upstream runs lemon's Kruskal over all-equal weights, whose edge order nothing here can pin down; this is
+// Kruskal over the pairs in list order by union-find, the tree walked breadth-first from start_idx (a node's tree edges in the order they were taken); a child's
+// rotation is R_cp R_parent.  false: the pairs do not reach every camera, or name one past global_rotations.
+bool RotationAveragingSpanningTree(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx);
+// RotationAveragingRefineL1 (:428-582), weight function 1, through pvlm_rotavg_l1 (see pvlm.h for the definition and its divergences).  false: the library refused
+// the arguments (a camera pair named twice, which upstream's map would collapse, among them) or an IRLS system could not be factorised (:553-557).
+bool RotationAveragingRefineL1(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx, const bool host = false);
+// RotationAveragingL1 (:376-426): the spanning tree, the refinement, FilterPairs.  rotations_after_L1.txt is not written.
+bool RotationAveragingL1(std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx, double angle_threshold, const bool host = false);
+// RotationAveragingL2 (:317-374) through pvlm_rotavg_l2.  false: the result is not finite, or the library refused the arguments — a pair list that FilterPairs left
+// in more than one piece among them (upstream refines every piece; here the rotations stay as they came).
+bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host = false);
+// SfM::EstimateGlobalRotation (:811-905), operation by operation: the use_all_pairs_ra filter, LargestBiconnectedGraph, FilterByTriplet(0.1), ReIndex,
+// RotationAveragingL1(pairs, rotations, 0, -1), RotationAveragingL2 (a failure is only reported, as upstream), then pair.R_21 = R_2w R_1w^T and frames[i].R_wc.
+// image_pairs is replaced by the pairs that survive.  false with a message: no pair survives the filters, a pair with first >= second, method 2, or L1 failed.
+bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const RotationOptions& options = RotationOptions());
+
 // ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------
 // base/common.h's FrameMatchMethod and sfm/VLAD.h's normalisation types
 enum FrameMatchMethod { EXHAUSTIVE = 1, CONTIGUOUS = 2, VLAD = 4, GPS = 8, GPS_VLAD = 16 };

@@ -4,8 +4,12 @@
 // CameraLidarOptimizer::GlobalBundleAdjustment (joint_optimization/CameraLidarOptimizer.cpp:732-740); and what builds the structure they refine —
 // TriangulateTracks / FilterTracksToFar (sfm/Structure.cpp:8-119), CameraLidarOptimizer::EstimateStructure (:720-729), MVS::EstimateStructure
 // (mvs/MVS.cpp:44-59); and the step between the relative and the global poses — EstimateGlobalTranslation with TranslationAveragingDLT / L2 / SoftL1 / L2IRLS, ReIndex,
-// SetToOrigin (sfm/SfM.cpp:1047-1344, sfm/TranslationAveraging.cpp; K42).
+// SetToOrigin (sfm/SfM.cpp:1047-1344, sfm/TranslationAveraging.cpp; K42) after EstimateGlobalRotation with FindTriplet, FilterByTriplet, FilterPairs and
+// RotationAveragingSpanningTree / RefineL1 / L1 / L2 (sfm/SfM.cpp:705-905, sfm/RotationAveraging.cpp, sfm/PoseGraph.cpp:195-226; K40).
 // Host logic only; the reprojection blocks are solved and the tracks are triangulated and tested by libpvlm.so on the GPU (K9 / K31 / K32).
+#include <array>
+#include <queue>
+
 #include "pvlm_host_internal.hpp"
 #include "pvlm_host_structure.hpp"
 #include "../csrc/pvlm_triangulate_core.h"
@@ -15,6 +19,7 @@
 #include "pvlm_host_relpose.hpp"
 #include "../csrc/pvlm_depthfill_core.h"
 #include "pvlm_host_transavg.hpp"
+#include "pvlm_host_rotavg.hpp"
 
 namespace pvlm {
 
@@ -1056,6 +1061,254 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
     if (frame_with_translation.count(idx1) && frame_with_translation.count(idx2) && frame_with_rotation.count(idx1) && frame_with_rotation.count(idx2)) good_pair.push_back(p);
   }
   good_pair.swap(image_pairs);
+  return true;
+}
+
+// ================================================================================================
+// K40: rotation averaging — FindTriplet, FilterByTriplet, FilterPairs, RotationAveragingSpanningTree / RefineL1 / L1 / L2 (sfm/RotationAveraging.cpp), EstimateGlobalRotation
+// ================================================================================================
+namespace {
+// the arrays of pvlm_rotavg_* from a pair list and the rotations; false: a pair names a camera past the rotations
+struct RotavgInputs {
+  std::vector<int> first, second; std::vector<double> R, rot;
+  bool Fill(const std::vector<RelativePair>& pairs, const std::vector<Matrix3d>& rotations) {
+    for (const RelativePair& p : pairs) {
+      if (p.image_pair.first >= rotations.size() || p.image_pair.second >= rotations.size()) return false;
+      first.push_back((int)p.image_pair.first); second.push_back((int)p.image_pair.second);
+      R.insert(R.end(), p.R_21.begin(), p.R_21.end());
+    }
+    for (const Matrix3d& m : rotations) rot.insert(rot.end(), m.begin(), m.end());
+    first.push_back(0); second.push_back(0); R.resize(R.size() + 9);   // never empty
+    return !rotations.empty();
+  }
+  void Read(std::vector<Matrix3d>& rotations) const { for (size_t c = 0; c < rotations.size(); ++c) std::copy(rot.begin() + 9 * c, rot.begin() + 9 * c + 9, rotations[c].begin()); }
+};
+bool Say(const RotationOptions& o, const char* m) { if (o.message) *o.message = m; return false; }
+Matrix3d MulNT(const Matrix3d& A, const Matrix3d& B) { Matrix3d C; pvlm_rotavg::mul_nt(A.data(), B.data(), C.data()); return C; }
+}  // namespace
+
+std::vector<Triplet> FindTriplet(const std::set<std::pair<size_t, size_t>>& edges) {
+  std::vector<Triplet> triplets;
+  std::map<uint32_t, std::set<uint32_t>> adjacency;            // upstream: an unordered_map that is only looked up, never walked
+  for (const std::pair<size_t, size_t>& e : edges) { adjacency[(uint32_t)e.first].insert((uint32_t)e.second); adjacency[(uint32_t)e.second].insert((uint32_t)e.first); }
+  std::vector<uint32_t> node_candidate;
+  for (const std::pair<size_t, size_t>& e : edges) {
+    const std::set<uint32_t>& neighbor1 = adjacency.find((uint32_t)e.first)->second;
+    const std::set<uint32_t>& neighbor2 = adjacency.find((uint32_t)e.second)->second;
+    node_candidate.clear();
+    std::set_intersection(neighbor1.cbegin(), neighbor1.cend(), neighbor2.cbegin(), neighbor2.cend(), std::back_inserter(node_candidate));
+    for (const uint32_t node : node_candidate) {
+      std::array<uint32_t, 3> idx = {node, (uint32_t)e.first, (uint32_t)e.second};
+      std::sort(idx.begin(), idx.end());
+      triplets.push_back(Triplet{idx[0], idx[1], idx[2]});
+    }
+    adjacency[(uint32_t)e.first].erase((uint32_t)e.second);
+    adjacency[(uint32_t)e.second].erase((uint32_t)e.first);
+  }
+  return triplets;
+}
+
+std::vector<RelativePair> FilterByTriplet(const std::vector<RelativePair>& init_pairs, const double angle_threshold, std::set<size_t>& covered_frames) {
+  covered_frames.clear();
+  std::set<std::pair<size_t, size_t>> pairs;
+  std::map<std::pair<size_t, size_t>, Matrix3d> map_rotations;
+  for (const RelativePair& p : init_pairs) {
+    if (!(p.image_pair.first < p.image_pair.second)) return {};                 // upstream asserts
+    pairs.insert(p.image_pair);
+    map_rotations[p.image_pair] = p.R_21;
+  }
+  const std::vector<Triplet> triplets = FindTriplet(pairs);
+  pairs.clear();
+  for (const Triplet& t : triplets) {
+    const Matrix3d& R_21 = map_rotations[{t.i, t.j}]; const Matrix3d& R_32 = map_rotations[{t.j, t.k}]; const Matrix3d& R_31 = map_rotations[{t.i, t.k}];
+    Matrix3d a, rot;
+    pvlm_rotavg::mul_tn(R_31.data(), R_32.data(), a.data());                    // (R_13 R_32) R_21
+    pvlm_rotavg::mul_nn(a.data(), R_21.data(), rot.data());
+    double cos_theta = (rot[0] + rot[4] + rot[8]) / 3.0;                        // as written (:740): the trace over 3
+    cos_theta = std::min(1.0, std::max(cos_theta, -1.0));
+    const double angle_error = std::acos(cos_theta) * 180.0 / M_PI;
+    if (angle_error < angle_threshold) {
+      pairs.insert({t.i, t.j}); pairs.insert({t.j, t.k}); pairs.insert({t.i, t.k});
+    }
+  }
+  std::vector<RelativePair> pairs_after_triplet_filter;
+  for (const RelativePair& m : init_pairs) if (pairs.count(m.image_pair) > 0) pairs_after_triplet_filter.push_back(m);
+  return LargestBiconnectedGraph(pairs_after_triplet_filter, covered_frames);
+}
+
+std::vector<RelativePair> FilterPairs(const std::vector<RelativePair>& image_pairs, const std::vector<Matrix3d>& global_rotations, double angle_threshold, double* threshold_out) {
+  std::vector<double> errors;
+  errors.reserve(image_pairs.size());
+  for (const RelativePair& p : image_pairs) {
+    double e[3];
+    pvlm_rotavg::pair_error(global_rotations[p.image_pair.first].data(), global_rotations[p.image_pair.second].data(), p.R_21.data(), e);
+    errors.push_back(std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
+  }
+  double threshold = 0;
+  if (angle_threshold > 0) threshold = angle_threshold / 180.0 * M_PI;
+  else if (!errors.empty()) {                                                   // X84: median + 5.2 MAD, both taken at position size / 2
+    std::vector<double> data(errors);
+    std::vector<double>::iterator mid = data.begin() + errors.size() / 2;
+    std::nth_element(data.begin(), mid, data.end());
+    const double median = *mid;
+    for (size_t i = 0; i < errors.size(); ++i) data[i] = std::fabs(errors[i] - median);
+    std::nth_element(data.begin(), mid, data.end());
+    threshold = median + 5.2 * (*mid);
+  }
+  if (threshold_out) *threshold_out = threshold;
+  std::set<size_t> valid_pair_idx, invalid_pair_idx;
+  for (size_t i = 0; i < errors.size(); ++i) (errors[i] < threshold ? valid_pair_idx : invalid_pair_idx).insert(i);
+  // :101-165: every frame wants neighbor_size pairs before it and after it within `range` frames
+  std::vector<std::pair<int, int>> num_neighbor_frames(global_rotations.size(), std::make_pair(0, 0));
+  const size_t range = 10; const int neighbor_size = 3;
+  for (const size_t idx : valid_pair_idx) {
+    const RelativePair& p = image_pairs[idx];
+    if ((p.image_pair.second - p.image_pair.first) <= range) { num_neighbor_frames[p.image_pair.first].second++; num_neighbor_frames[p.image_pair.second].first++; }
+  }
+  std::map<int, std::vector<int>> bad_frames;
+  for (size_t i = 0; i < num_neighbor_frames.size(); ++i)
+    if (num_neighbor_frames[i].first < neighbor_size || num_neighbor_frames[i].second < neighbor_size) bad_frames[(int)i] = std::vector<int>();
+  for (const size_t idx : invalid_pair_idx) {
+    const RelativePair& p = image_pairs[idx];
+    if ((p.image_pair.second - p.image_pair.first) <= range) {
+      if (bad_frames.find((int)p.image_pair.first) != bad_frames.end() && num_neighbor_frames[p.image_pair.first].second < neighbor_size) bad_frames[(int)p.image_pair.first].push_back((int)idx);
+      if (bad_frames.find((int)p.image_pair.second) != bad_frames.end() && num_neighbor_frames[p.image_pair.second].first < neighbor_size) bad_frames[(int)p.image_pair.second].push_back((int)idx);
+    }
+  }
+  for (auto& it : bad_frames) {
+    const int frame_id = it.first;
+    if (num_neighbor_frames[(size_t)frame_id].first >= neighbor_size && num_neighbor_frames[(size_t)frame_id].second >= neighbor_size) continue;
+    // upstream: std::sort by the error alone; equal errors are ordered by the pair index here
+    std::sort(it.second.begin(), it.second.end(), [&](const int a, const int b) { return errors[(size_t)a] < errors[(size_t)b] || (errors[(size_t)a] == errors[(size_t)b] && a < b); });
+    for (size_t count = 0; num_neighbor_frames[(size_t)frame_id].first < neighbor_size && count < it.second.size(); ++count) {
+      const RelativePair& p = image_pairs[(size_t)it.second[count]];
+      if (p.image_pair.second != (size_t)frame_id) continue;
+      valid_pair_idx.insert((size_t)it.second[count]);
+      num_neighbor_frames[p.image_pair.first].second++; num_neighbor_frames[p.image_pair.second].first++;
+      invalid_pair_idx.erase((size_t)it.second[count]);
+    }
+    for (size_t count = 0; num_neighbor_frames[(size_t)frame_id].second < neighbor_size && count < it.second.size(); ++count) {
+      const RelativePair& p = image_pairs[(size_t)it.second[count]];
+      if (p.image_pair.first != (size_t)frame_id) continue;
+      valid_pair_idx.insert((size_t)it.second[count]);
+      num_neighbor_frames[p.image_pair.first].second++; num_neighbor_frames[p.image_pair.second].first++;
+      invalid_pair_idx.erase((size_t)it.second[count]);
+    }
+  }
+  std::vector<RelativePair> valid_pairs;
+  for (const size_t idx : valid_pair_idx) valid_pairs.push_back(image_pairs[idx]);
+  return valid_pairs;
+}
+
+bool RotationAveragingSpanningTree(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx) {
+  const size_t F = global_rotations.size();
+  if (start_idx >= F) return false;
+  std::vector<size_t> root(F);
+  for (size_t c = 0; c < F; ++c) root[c] = c;
+  auto find = [&](size_t c) { while (root[c] != c) { root[c] = root[root[c]]; c = root[c]; } return c; };
+  struct Edge { size_t to, pair; bool child_is_first; };
+  std::vector<std::vector<Edge>> tree(F);
+  for (size_t p = 0; p < image_pairs.size(); ++p) {
+    const size_t i = image_pairs[p].image_pair.first, j = image_pairs[p].image_pair.second;
+    if (i >= F || j >= F) return false;
+    const size_t a = find(i), b = find(j);
+    if (a == b) continue;
+    root[a] = b;
+    tree[i].push_back(Edge{j, p, false}); tree[j].push_back(Edge{i, p, true});
+  }
+  std::vector<char> seen(F, 0);
+  std::queue<size_t> queue;
+  global_rotations[start_idx] = Matrix3d{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+  seen[start_idx] = 1; queue.push(start_idx);
+  size_t reached = 1;
+  while (!queue.empty()) {
+    const size_t c = queue.front(); queue.pop();
+    for (const Edge& e : tree[c]) {
+      if (seen[e.to]) continue;
+      const Matrix3d& R = image_pairs[e.pair].R_21;                             // child = second: R_cp = R_21; child = first: R_cp = R_21^T
+      if (e.child_is_first) pvlm_rotavg::mul_tn(R.data(), global_rotations[c].data(), global_rotations[e.to].data());
+      else pvlm_rotavg::mul_nn(R.data(), global_rotations[c].data(), global_rotations[e.to].data());
+      seen[e.to] = 1; queue.push(e.to); ++reached;
+    }
+  }
+  return reached == F;
+}
+
+bool RotationAveragingRefineL1(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx, const bool host) {
+  RotavgInputs in;
+  if (!in.Fill(image_pairs, global_rotations)) return false;
+  const int F = (int)global_rotations.size(), P = (int)image_pairs.size();
+  pvlm_rotavg_l1_summary sum{0, 0, 0, 0};
+  if (host) {
+    pvlm_rotavg::L1Summary hs;
+    if (rotavg_detail::L1Host(F, P, in.first.data(), in.second.data(), in.R.data(), (int)start_idx, in.rot.data(), &hs)) return false;
+    sum.info = hs.info;
+  } else {
+    Engine& e = Engine::Default();
+    if (pvlm_rotavg_l1(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), (int)start_idx, in.rot.data(), &sum) != PVLM_OK) return false;
+  }
+  in.Read(global_rotations);                                                    // the rotations of the last completed iteration, also when info > 0
+  return sum.info == 0;
+}
+
+bool RotationAveragingL1(std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx, double angle_threshold, const bool host) {
+  if (!RotationAveragingSpanningTree(image_pairs, global_rotations, start_idx)) return false;
+  if (!RotationAveragingRefineL1(image_pairs, global_rotations, start_idx, host)) return false;
+  image_pairs = FilterPairs(image_pairs, global_rotations, angle_threshold);
+  return true;
+}
+
+bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host) {
+  RotavgInputs in;
+  if (!in.Fill(image_pairs, global_rotations)) return false;
+  const int F = (int)global_rotations.size(), P = (int)image_pairs.size();
+  pvlm_rotavg_l2_summary sum{0, 0, 0, 0, 0};
+  if (host) {
+    pvlm_transavg::Summary hs;
+    if (rotavg_detail::L2Host(F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), 0.07, 50, &hs)) return false;
+    sum.final_cost = hs.final_cost; sum.termination = hs.termination;
+  } else {
+    Engine& e = Engine::Default();
+    const pvlm_rotavg_l2_params prm{0.07, 50};
+    if (pvlm_rotavg_l2(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), &prm, &sum) != PVLM_OK) return false;
+  }
+  if (sum.termination == pvlm_transavg::kCostNotFinite || !std::isfinite(sum.final_cost) || !pvlm_transavg::finite_all(in.rot.data(), 9 * (size_t)F)) return false;
+  in.Read(global_rotations);
+  return true;
+}
+
+bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const RotationOptions& o) {
+  if (!o.use_all_pairs_ra) {
+    std::vector<RelativePair> pairs_with_scale;
+    for (const RelativePair& p : image_pairs) if (p.upper_scale >= 0 && p.lower_scale >= 0) pairs_with_scale.push_back(p);
+    pairs_with_scale.swap(image_pairs);
+  }
+  for (const RelativePair& p : image_pairs) {
+    if (p.image_pair.first >= frames.size() || p.image_pair.second >= frames.size()) return Say(o, "a pair names a frame that is not there");
+    if (!(p.image_pair.first < p.image_pair.second)) return Say(o, "a pair with first >= second (upstream asserts)");
+  }
+  std::set<size_t> covered_frames;
+  image_pairs = LargestBiconnectedGraph(image_pairs, covered_frames);
+  image_pairs = FilterByTriplet(image_pairs, 0.1, covered_frames);
+  if (image_pairs.empty()) return Say(o, "no pair is left after the graph and triplet filters");
+  std::map<size_t, size_t> old_to_new, new_to_old;
+  ReIndex(image_pairs, old_to_new, new_to_old);
+  for (RelativePair& pair : image_pairs) { pair.image_pair.first = old_to_new[pair.image_pair.first]; pair.image_pair.second = old_to_new[pair.image_pair.second]; }
+  std::vector<Matrix3d> global_rotations(old_to_new.size(), Matrix3d{{0, 0, 0, 0, 0, 0, 0, 0, 0}});
+  if (method == ROTATION_AVERAGING_L1) {
+    if (!RotationAveragingL1(image_pairs, global_rotations, 0, -1, o.host)) return Say(o, "Rotation averaging L1 failed");
+    if (!RotationAveragingL2(image_pairs, global_rotations, o.host) && o.message) *o.message = "Rotation averaging refine L2 failed";       // reported, not returned (:886-887)
+  } else return Say(o, "Rotation averaging method not supported: L2 needs the eigenvectors of a dense 3 F x 3 F matrix for its start and is not built");
+  for (RelativePair& pair : image_pairs) {
+    pair.R_21 = MulNT(global_rotations[pair.image_pair.second], global_rotations[pair.image_pair.first]);      // R_2w R_1w^T
+    pair.image_pair.first = new_to_old[pair.image_pair.first]; pair.image_pair.second = new_to_old[pair.image_pair.second];
+  }
+  for (size_t i = 0; i < global_rotations.size(); ++i) {
+    Frame& f = frames[new_to_old[i]];
+    const Matrix3d& R = global_rotations[i];
+    f.R_wc = Matrix3d{{R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]}};                                 // the averaging gives R_cw, a frame keeps R_wc
+    f.pose_valid = PoseValidAsWritten(f);
+  }
   return true;
 }
 
