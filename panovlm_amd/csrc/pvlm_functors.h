@@ -42,25 +42,34 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // atan(t)/t on [0, tan^2(pi/8)], max relative error 2.2e-16 measured against mpmath).
 // A Horner step p * u + c costs ONE v_fma_f64 when the coefficient sits in a scalar register pair; written as fma(p, u, literal) the
 // compiler keeps the ten literals in VGPRs and pays a 64-bit move per step to feed the two-address v_fmac_f64 (ISA of round 3:
-// 20 of the ~330 VALU instructions of a two-row iteration) — hence the operand constraint below.  Same instruction, same bits.
-__device__ __forceinline__ double fma_sconst(double p, double u, double c) {
+// 20 of the ~330 VALU instructions of a two-row iteration) — hence the operand constraints below.  Same instruction, same bits.
+// The FIRST step has two constants, c0 * u + c1: the constant bus takes one scalar operand per instruction, so c0 is copied out of its
+// scalar pair right in front of the fma and that pair of VGPRs carries the chain.
+// The whole chain is ONE asm statement.  With a statement per step the compiler must assume that each writes its result through a
+// destination select and pads every dependent pair of statements with an s_nop (ten per row, an issue slot each); a plain v_fma_f64
+// feeding the next needs no wait state.
+__device__ __forceinline__ double horner10_sconst(double u, double c0, double c1, double c2, double c3, double c4, double c5, double c6, double c7,
+                                                  double c8, double c9) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  double d;
-  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(p), "v"(u), "s"(c));
-  return d;
+  double p;
+  asm("v_mov_b64 %0, %2\n\t"
+      "v_fma_f64 %0, %0, %1, %3\n\t"
+      "v_fma_f64 %0, %0, %1, %4\n\t"
+      "v_fma_f64 %0, %0, %1, %5\n\t"
+      "v_fma_f64 %0, %0, %1, %6\n\t"
+      "v_fma_f64 %0, %0, %1, %7\n\t"
+      "v_fma_f64 %0, %0, %1, %8\n\t"
+      "v_fma_f64 %0, %0, %1, %9\n\t"
+      "v_fma_f64 %0, %0, %1, %10\n\t"
+      "v_fma_f64 %0, %0, %1, %11\n\t"
+      "v_fma_f64 %0, %0, %1, 1.0"
+      : "=&v"(p)
+      : "v"(u), "s"(c0), "s"(c1), "s"(c2), "s"(c3), "s"(c4), "s"(c5), "s"(c6), "s"(c7), "s"(c8), "s"(c9));
+  return p;
 #else
-  return fma(p, u, c);
-#endif
-}
-// The FIRST step has two constants, p0 * u + c1.  With p0 as the "v" operand of fma_sconst it sits in a VGPR pair for the whole row loop; the constant bus
-// takes one scalar operand per instruction, so p0 is copied out of its scalar pair right in front of the fma and the pair of VGPRs is the step's result.
-__device__ __forceinline__ double fma_sconst2(double p0, double u, double c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  double d;
-  asm("v_mov_b64 %0, %1\n\tv_fma_f64 %0, %0, %2, %3" : "=&v"(d) : "s"(p0), "v"(u), "s"(c));
-  return d;
-#else
-  return fma(p0, u, c);
+  double p = fma(c0, u, c1);
+  for (double c : {c2, c3, c4, c5, c6, c7, c8, c9, 1.0}) p = fma(p, u, c);
+  return p;
 #endif
 }
 // A wave-uniform double that the compiler cannot prove uniform (a product of kernel arguments is computed on the vector ALU: gfx9 has no scalar fp64) forced
@@ -76,23 +85,14 @@ __device__ __forceinline__ double uniform_sgpr(double x) {
 }
 __device__ __forceinline__ double atan_small(double t) {
   const double u = t * t;
-  double p = fma_sconst2(2.11272689568591313e-02, u, -4.34739031566048761e-02);
-  p = fma_sconst(p, u, 5.68812005923421543e-02);
-  p = fma_sconst(p, u, -6.64019012732186553e-02);
-  p = fma_sconst(p, u, 7.68994845277858746e-02);
-  p = fma_sconst(p, u, -9.09077271667437237e-02);
-  p = fma_sconst(p, u, 1.11111061650365134e-01);
-  p = fma_sconst(p, u, -1.42857141805968924e-01);
-  p = fma_sconst(p, u, 1.99999999988503901e-01);
-  p = fma_sconst(p, u, -3.33333333333284132e-01);
-  p = fma(p, u, 1.0);
-  return t * p;
+  return t * horner10_sconst(u, 2.11272689568591313e-02, -4.34739031566048761e-02, 5.68812005923421543e-02, -6.64019012732186553e-02,
+                             7.68994845277858746e-02, -9.09077271667437237e-02, 1.11111061650365134e-01, -1.42857141805968924e-01,
+                             1.99999999988503901e-01, -3.33333333333284132e-01);
 }
 // atan2(y, x) for y >= 0.  When every lane of the wave has its angle below pi/8 (the normal ICP
 // regime) one reciprocal and the polynomial suffice; otherwise octant folding as in FastAtan2
 // (min/max) and the reduction atan(a) = pi/4 + atan((a-1)/(a+1)) are applied, branch-free.
-__device__ __forceinline__ double atan2_pos(double y, double x) {
-  if (__all(y <= 0.41421356237309503 * x)) return atan_small(y * fast_rcp(x));
+__device__ __forceinline__ double atan2_octants(double y, double x) {
   const double ax = fabs(x);
   const double mn = fmin(y, ax), mx = fmax(y, ax);
   const double a = mn * fast_rcp(mx);
@@ -103,6 +103,27 @@ __device__ __forceinline__ double atan2_pos(double y, double x) {
   r = (y > ax) ? 1.57079632679489661923 - r : r;
   return (x < 0.0) ? 3.14159265358979323846 - r : r;
 }
+__device__ __forceinline__ double atan2_pos(double y, double x) {
+  if (__all(y <= 0.41421356237309503 * x)) return atan_small(y * fast_rcp(x));
+  return atan2_octants(y, x);
+}
+// The same angle together with inv_h2 = 1 / (x^2 + y^2), the factor of its gradient (-y, x) / (x^2 + y^2); a lane that is not live
+// gets 0 for both.  On the small-angle path x > 0 on every lane and ONE reciprocal R = 1 / (x h2) serves both quotients:
+// 1/x = h2 R (for t = y/x) and 1/h2 = x R; R = 0 switches a lane off (t = 0, atan 0 = 0).  The octant path, where x may be <= 0,
+// takes the reciprocal of h2 itself.
+__device__ __forceinline__ double atan2_pos_grad(double y, double x, bool live, double& inv_h2) {
+  const double h2 = fma(x, x, y * y);
+  double r;
+  if (__all(y <= 0.41421356237309503 * x)) {
+    const double R = live ? fast_rcp(x * h2) : 0.0;
+    inv_h2 = x * R;
+    r = atan_small(y * (h2 * R));
+  } else {
+    inv_h2 = live ? fast_rcp(h2) : 0.0;
+    r = live ? atan2_octants(y, x) : 0.0;
+  }
+  return r;
+}
 
 // VectorAngle3D (base/Geometry.hpp:450-466), un-normalised form, with gradients wrt v1, v2.
 // Returns false when the clamped branches (constant result, zero gradient) were taken — decided on the cosine like
@@ -110,7 +131,6 @@ __device__ __forceinline__ double atan2_pos(double y, double x) {
 // with w = v1 x v2: the same angle and derivatives as acos of the normalised dot product, without its loss of eps / r
 // near r -> 0 (upstream's double evaluation is the less accurate side there; tests/test_eval_gpu.py compares both with
 // an extended-precision evaluation of upstream's statements).
-__device__ __forceinline__ double atan2_pos(double y, double x);
 __device__ __forceinline__ bool angle_between(const double* v1, const double* v2, double& r, double* g1, double* g2) {
   const double d = dot3(v1, v2);
   const double q1 = dot3(v1, v1), q2 = dot3(v2, v2);
@@ -176,26 +196,37 @@ __device__ __forceinline__ void residual_grad(const double* P, const double* rec
     // r = angle(vec1, vec2) = atan2(y, x) — the same angle the reference obtains from acos of the
     // normalised dot product, without its cancellation near cos = 1.  r depends on P through
     // (sd, nu) only: grad sd = n, grad nu = u/nu.
+    // atan2 is homogeneous, so both arguments are taken times nu:  X = nu - sd d,  Y = |sd| q,  r = atan2(Y, X),  D' = X^2 + Y^2.
+    // d r = (X dY - Y dX) / D' with dY = s q dsd + |sd| dq (dq = u/q . dP, since u is the in-plane part of P and n.u = 0) and
+    // dX = dnu - d dsd (dnu = u/nu . dP):
+    //   g = A n + B u,   A = (X s q + Y d) / D' = s q (X + sd d) / D' = s q nu / D'                      (X + sd d = nu)
+    //                    B = (X |sd| / q - Y / nu) / D' = |sd| (X nu - q^2) / (q nu D') = |sd| d (d - sd nu) / (q nu D')
+    // (X nu - q^2 = nu^2 - q^2 - sd d nu = d^2 - sd d nu).  1 / D' comes out of atan2_pos_grad, which shares it with its own quotient.
+    // q = 0 (P on the normal through the origin): invq = 0 makes Y = 0 and A = B = 0;  d = 0: B = 0.
     const double* n = rec + 3;
     const double dd = n[3];
     const double sd = n[0] * P[0] + n[1] * P[1] + n[2] * P[2] + dd;
-    const double s = sd < 0.0 ? -1.0 : 1.0;
-    const double dis = s * sd;
+    const double dis = fabs(sd);
     const double u[3] = {P[0] - (sd - dd) * n[0], P[1] - (sd - dd) * n[1], P[2] - (sd - dd) * n[2]};
     const double q2 = dot3(u, u);
     const double nu2 = q2 + dd * dd;
     const double inv_nu = fast_rsqrt(nu2);
     const double invq = q2 > 0.0 ? fast_rsqrt(q2) : 0.0;
-    const double q = q2 * invq;
-    const double x = 1.0 - sd * dd * inv_nu, y = dis * q * inv_nu;
-    const double invD = fast_rcp(x * x + y * y);
+    const double q = q2 * invq, nu = nu2 * inv_nu;
+    const double X = fma(-sd, dd, nu), Y = dis * q;
     const bool live = dis >= 1e-3;  // dis < 1e-3 -> residual 0, zero Jacobian (CostFunction.h:680-684)
-    r = live ? atan2_pos(y, x) : 0.0;
-    const double k0 = live ? inv_nu * invD : 0.0;
-    const double fsd = (x * s * q + y * dd) * k0;
-    const double cu = (x * dis * dd * dd * invq - y * sd * dd) * (inv_nu * inv_nu) * k0;
+    // A D' and B D' first: the branch inside atan2_pos_grad then has q, nu, their reciprocals and d behind it.  The empty asm pins them there: left
+    // alone the compiler sinks the six operations below the branch and carries their operands across it (headline kernel: 8 B of scratch at 128 VGPRs)
+    double AD = q * nu, BD = dis * dd * fma(-sd, nu, dd) * (invq * inv_nu);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(AD), "+v"(BD));
+#endif
+    double k0;                      // 1 / D' on a live lane, else 0
+    r = atan2_pos_grad(Y, X, live, k0);
+    const double A = copysign(AD * k0, sd);                                        // s q nu / D': the sign bit of sd, no multiplication by +-1
+    const double B = BD * k0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) g[k] = fsd * n[k] + cu * u[k];
+    for (int k = 0; k < 3; ++k) g[k] = A * n[k] + B * u[k];
   } else if (KIND == PVLM_POINT2PLANE_ANGLE) {
     // base/CostFunction.h:679-717 (weight is NOT applied by the reference)
     const double* n = rec + 3;
