@@ -352,31 +352,57 @@ __device__ __forceinline__ double wave_sum(double x) {
   return x;
 }
 
+#ifndef PVLM_HUBER_SLOT
+#define PVLM_HUBER_SLOT 1   // 1: a slot without Huber outliers accumulates without the weights (0: every row pays for them, the form before)
+#endif
+
+// S += rho' v v^T, gv += rho' v r, cost += rho/2 of one row.  WEIGHTED = false: rho' = 1 — the same fmas without the six scalings (1.0 * x == x: same bits).
+// The fmas are the ones the contraction of acc += wa * vv[b] gives; said explicitly, so that no pass splits one into a product and an addition.
+template <bool WEIGHTED>
+__device__ __forceinline__ void accumulate_outer(const double (&vv)[6], double r, double rho1, double half_rho, double* acc) {
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const double wa = WEIGHTED ? rho1 * vv[a] : vv[a];
+#pragma unroll
+    for (int b = a; b < 6; ++b, ++q) acc[q] = fma(wa, vv[b], acc[q]);
+    acc[21 + a] = fma(wa, r, acc[21 + a]);
+  }
+  acc[27] += half_rho;
+}
+
 // one residual block: evaluate, robustify, accumulate  S += rho' v v^T, gv += rho' v r, cost += rho/2
 template <int KIND, bool NORM, int NCOLS, int LOSS>
 __device__ __forceinline__ void accumulate_row(const double* rec, const double* T, double weight, double loss_a, double a2, double mh_a2, double* acc) {
   Wrench w;
   eval_wrench<KIND, NORM>(rec, T, weight, w);
   const double s = w.r * w.r;
-  double rho1 = 1.0, half_rho = 0.5 * s;
-  if (LOSS == PVLM_LOSS_HUBER) {
-    // ceres::HuberLoss(a): s > a^2 -> rho = 2 a sqrt(s) - a^2, rho' = max(DBL_MIN, a / sqrt(s))
-    const double rr = fabs(w.r);
-    const bool out = s > a2;
-    const double inv = fast_rcp(out ? rr : 1.0);
-    rho1 = out ? fmax(std::numeric_limits<double>::min(), loss_a * inv) : 1.0;
-    half_rho = out ? fma(loss_a, rr, mh_a2) : half_rho;   // mh_a2 = -0.5 * a2, computed once per kernel
-  }
   const double vv[6] = {w.c[0], w.c[1], w.c[2], w.g[0], w.g[1], w.g[2]};
-  int q = 0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    const double wa = rho1 * vv[a];
-#pragma unroll
-    for (int b = a; b < 6; ++b) acc[q++] += wa * vv[b];
-    acc[21 + a] += wa * w.r;
-  }
-  acc[27] += half_rho;
+  if (LOSS != PVLM_LOSS_HUBER) { accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc); return; }
+  // ceres::HuberLoss(a): s > a^2 -> rho = 2 a sqrt(s) - a^2, rho' = max(DBL_MIN, a / sqrt(s))
+  const bool out = s > a2;
+  auto general = [&]() {
+    const double rr = fabs(w.r);
+    const double inv = fast_rcp(out ? rr : 1.0);
+    const double rho1 = out ? fmax(std::numeric_limits<double>::min(), loss_a * inv) : 1.0;
+    const double half_rho = out ? fma(loss_a, rr, mh_a2) : 0.5 * s;   // mh_a2 = -0.5 * a2, computed once per kernel
+    accumulate_outer<true>(vv, w.r, rho1, half_rho, acc);
+  };
+#if PVLM_HUBER_SLOT && defined(__HIP_DEVICE_COMPILE__)
+  // Huber by slot (the 64 rows the wave evaluates together): when no active lane is an outlier, rho' = 1 and rho / 2 = s / 2 on every lane, and the wave
+  // skips the reciprocal, the max, the selects and the six scalings.  Lanes switched off in a partly filled last trip do not vote.
+  // TWO tests in a row on the same wave-uniform mask, each around an update of acc in place — not if / else.  The compiler lays the two arms of an if / else
+  // inside this divergent loop out one behind the other and keeps the 28 accumulators of the untaken arm alive across the taken one (56 more VGPRs: 108 B of
+  // scratch in the headline kernel), or merges the arms' fmas again and feeds them through moves.  The empty asm hides from it that the second test is the
+  // complement of the first; both are scalar branches.
+  const unsigned long long outliers = __ballot(out);
+  unsigned long long none = outliers;
+  asm("" : "+s"(none));
+  if (outliers != 0) general();
+  if (none == 0) accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc);
+#else
+  general();
+#endif
 }
 
 // Sums of N <= 32 per-lane values over the wave with a fixed tree: at offset 32 every lane keeps one half of the values and trades

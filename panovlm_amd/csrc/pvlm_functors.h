@@ -48,10 +48,28 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // The whole chain is ONE asm statement.  With a statement per step the compiler must assume that each writes its result through a
 // destination select and pads every dependent pair of statements with an s_nop (ten per row, an issue slot each); a plain v_fma_f64
 // feeding the next needs no wait state.
+// ENTRY > 0 enters the chain at coefficient c[ENTRY] (the short tier of atan_small below): the same statement without its first ENTRY steps, the same
+// scalar pairs for the coefficients that remain.
+#ifndef PVLM_ATAN_TIER
+#define PVLM_ATAN_TIER 1         // 1: a slot whose lanes all have tan r <= 1/32 takes the short chain (0: every slot the full chain)
+#endif
+#define PVLM_ATAN_TIER_ENTRY 6   // the short chain starts at the seventh coefficient; tests/test_atan_tier_cpu.py reads this line and holds it to its condition
+template <int ENTRY = 0>
 __device__ __forceinline__ double horner10_sconst(double u, double c0, double c1, double c2, double c3, double c4, double c5, double c6, double c7,
                                                   double c8, double c9) {
+  static_assert(ENTRY == 0 || ENTRY == 6, "entry points with a statement below");
 #if defined(__HIP_DEVICE_COMPILE__)
   double p;
+  if (ENTRY == 6) {
+    asm("v_mov_b64 %0, %2\n\t"
+        "v_fma_f64 %0, %0, %1, %3\n\t"
+        "v_fma_f64 %0, %0, %1, %4\n\t"
+        "v_fma_f64 %0, %0, %1, %5\n\t"
+        "v_fma_f64 %0, %0, %1, 1.0"
+        : "=&v"(p)
+        : "v"(u), "s"(c6), "s"(c7), "s"(c8), "s"(c9));
+    return p;
+  }
   asm("v_mov_b64 %0, %2\n\t"
       "v_fma_f64 %0, %0, %1, %3\n\t"
       "v_fma_f64 %0, %0, %1, %4\n\t"
@@ -67,8 +85,9 @@ __device__ __forceinline__ double horner10_sconst(double u, double c0, double c1
       : "v"(u), "s"(c0), "s"(c1), "s"(c2), "s"(c3), "s"(c4), "s"(c5), "s"(c6), "s"(c7), "s"(c8), "s"(c9));
   return p;
 #else
-  double p = fma(c0, u, c1);
-  for (double c : {c2, c3, c4, c5, c6, c7, c8, c9, 1.0}) p = fma(p, u, c);
+  const double c[11] = {c0, c1, c2, c3, c4, c5, c6, c7, c8, c9, 1.0};
+  double p = c[ENTRY];
+  for (int k = ENTRY + 1; k < 11; ++k) p = fma(p, u, c[k]);
   return p;
 #endif
 }
@@ -83,11 +102,14 @@ __device__ __forceinline__ double uniform_sgpr(double x) {
   return x;
 #endif
 }
+// ENTRY > 0: the short tier, for |t| <= 1/32 (u <= 2^-10), where the terms in front of c[ENTRY] are below the rounding of the result: entered at the
+// seventh coefficient the worst relative error on (0, 1/32] stays under the full chain's own worst on (0, tan(pi/8)] (tests/test_atan_tier_cpu.py).
+template <int ENTRY = 0>
 __device__ __forceinline__ double atan_small(double t) {
   const double u = t * t;
-  return t * horner10_sconst(u, 2.11272689568591313e-02, -4.34739031566048761e-02, 5.68812005923421543e-02, -6.64019012732186553e-02,
-                             7.68994845277858746e-02, -9.09077271667437237e-02, 1.11111061650365134e-01, -1.42857141805968924e-01,
-                             1.99999999988503901e-01, -3.33333333333284132e-01);
+  return t * horner10_sconst<ENTRY>(u, 2.11272689568591313e-02, -4.34739031566048761e-02, 5.68812005923421543e-02, -6.64019012732186553e-02,
+                                    7.68994845277858746e-02, -9.09077271667437237e-02, 1.11111061650365134e-01, -1.42857141805968924e-01,
+                                    1.99999999988503901e-01, -3.33333333333284132e-01);
 }
 // atan2(y, x) for y >= 0.  When every lane of the wave has its angle below pi/8 (the normal ICP
 // regime) one reciprocal and the polynomial suffice; otherwise octant folding as in FastAtan2
@@ -104,7 +126,11 @@ __device__ __forceinline__ double atan2_octants(double y, double x) {
   return (x < 0.0) ? 3.14159265358979323846 - r : r;
 }
 __device__ __forceinline__ double atan2_pos(double y, double x) {
-  if (__all(y <= 0.41421356237309503 * x)) return atan_small(y * fast_rcp(x));
+  const bool tiny = PVLM_ATAN_TIER && __all(32.0 * y <= x);   // every lane at or below tan r = 1/32: the short chain (see atan2_pos_grad)
+  if (tiny || __all(y <= 0.41421356237309503 * x)) {
+    const double t = y * fast_rcp(x);
+    return tiny ? atan_small<PVLM_ATAN_TIER_ENTRY>(t) : atan_small(t);
+  }
   return atan2_octants(y, x);
 }
 // The same angle together with inv_h2 = 1 / (x^2 + y^2), the factor of its gradient (-y, x) / (x^2 + y^2); a lane that is not live
@@ -114,10 +140,14 @@ __device__ __forceinline__ double atan2_pos(double y, double x) {
 __device__ __forceinline__ double atan2_pos_grad(double y, double x, bool live, double& inv_h2) {
   const double h2 = fma(x, x, y * y);
   double r;
-  if (__all(y <= 0.41421356237309503 * x)) {
+  // a slot whose lanes are all at or below tan r = 1/32 (77 % of the headline's slots) puts the same quotient into the short chain.  Tested first; a slot
+  // that fails pays a product and a comparison more.  A row's bits depend on the tier its slot took, as they already do on the octant path.
+  const bool tiny = PVLM_ATAN_TIER && __all(32.0 * y <= x);
+  if (tiny || __all(y <= 0.41421356237309503 * x)) {
     const double R = live ? fast_rcp(x * h2) : 0.0;
     inv_h2 = x * R;
-    r = atan_small(y * (h2 * R));
+    const double t = y * (h2 * R);
+    r = tiny ? atan_small<PVLM_ATAN_TIER_ENTRY>(t) : atan_small(t);
   } else {
     inv_h2 = live ? fast_rcp(h2) : 0.0;
     r = live ? atan2_octants(y, x) : 0.0;
