@@ -2,6 +2,7 @@
 next to this file so that it travels to the GPU box with the repo snapshot."""
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -124,11 +125,7 @@ SCALE_DRIVER = os.path.join(HERE, "build", "pvlm_scale_driver")
 DISPATCH_ORDER_CHECK = os.path.join(HERE, "build", "dispatch_order_check")
 SIFT_DRIVER = os.path.join(HERE, "build", "pvlm_sift_driver")
 TRANSAVG_DRIVER = os.path.join(HERE, "build", "pvlm_transavg_driver")
-TRANSAVG_CHECK = os.path.join(HERE, "build", "libtransavg_check.so")
 ROTAVG_DRIVER = os.path.join(HERE, "build", "pvlm_rotavg_driver")
-TRANSAVG_CHECK_MAIN = os.path.join(HERE, "build", "transavg_check_main")
-ROTAVG_CHECK = os.path.join(HERE, "build", "librotavg_check.so")
-ROTAVG_CHECK_MAIN = os.path.join(HERE, "build", "rotavg_check_main")
 
 
 def build_host(force=False):
@@ -259,35 +256,39 @@ def build_host(force=False):
     return HOST_LIB
 
 
-def build_transavg_check(main=False, sanitize=False):
-    """The host compile of the K42 core (csrc/pvlm_transavg_core.h behind tests/cpp/transavg_core_check.cpp; no device, -ffp-contract=off as the device build of
-    pvlm_transavg.hip): build/libtransavg_check.so for the tests, or with main=True the stand-alone program of the same file (sanitize: the host sanitizers)."""
-    chk = os.path.join(HERE, "..", "tests", "cpp", "transavg_core_check.cpp")
-    core = os.path.join(HERE, "csrc", "pvlm_transavg_core.h")
-    backend = os.path.join(HERE, "host", "pvlm_host_transavg.hpp")
-    out = TRANSAVG_CHECK_MAIN if main else TRANSAVG_CHECK
+def _include_closure(src):
+    """src and every file it reaches through #include "..." lines, transitively."""
+    seen, todo = set(), [os.path.normpath(src)]
+    while todo:
+        f = todo.pop()
+        if f in seen or not os.path.exists(f):
+            continue
+        seen.add(f)
+        todo += [os.path.normpath(os.path.join(os.path.dirname(f), m)) for m in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M)]
+    return sorted(seen)
+
+
+def build_core_check(kind, main=False, sanitize=False):
+    """The host compile of a pair-graph stage's core (kind "transavg": K42, "rotavg": K40; csrc/pvlm_<kind>_core.h behind tests/cpp/<kind>_core_check.cpp; no device,
+    -ffp-contract=off as the device build of pvlm_<kind>.hip): build/lib<kind>_check.so for the tests, or with main=True the stand-alone program of the same file
+    (sanitize: the host sanitizers).  Rebuilt when the source or any header it includes, directly or not, is newer."""
+    chk = os.path.join(HERE, "..", "tests", "cpp", kind + "_core_check.cpp")
+    out = os.path.join(HERE, "build", kind + "_check_main" if main else "lib" + kind + "_check.so")
     if not os.path.exists(chk):
         return None
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(chk), os.path.getmtime(core), os.path.getmtime(backend)):
-        mode = ["-O1", "-g", "-DTRANSAVG_CHECK_MAIN"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
+    if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in _include_closure(chk)):
+        mode = ["-O1", "-g", "-D%s_CHECK_MAIN" % kind.upper()] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off"] + mode + [chk, "-o", out])
     return out
+
+
+def build_transavg_check(main=False, sanitize=False):
+    return build_core_check("transavg", main, sanitize)
 
 
 def build_rotavg_check(main=False, sanitize=False):
-    """The host compile of the K40 core (csrc/pvlm_rotavg_core.h behind tests/cpp/rotavg_core_check.cpp; no device, -ffp-contract=off as the device build of
-    pvlm_rotavg.hip): build/librotavg_check.so for the tests, or with main=True the stand-alone program of the same file (sanitize: the host sanitizers)."""
-    chk = os.path.join(HERE, "..", "tests", "cpp", "rotavg_core_check.cpp")
-    deps = [chk, os.path.join(HERE, "csrc", "pvlm_rotavg_core.h"), os.path.join(HERE, "csrc", "pvlm_transavg_core.h"), os.path.join(HERE, "host", "pvlm_host_rotavg.hpp")]
-    out = ROTAVG_CHECK_MAIN if main else ROTAVG_CHECK
-    if not os.path.exists(chk):
-        return None
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if main or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-        mode = ["-O1", "-g", "-DROTAVG_CHECK_MAIN"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []) if main else ["-O2", "-fPIC", "-shared"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off"] + mode + [chk, "-o", out])
-    return out
+    return build_core_check("rotavg", main, sanitize)
 
 
 if __name__ == "__main__":

@@ -7,15 +7,16 @@
 //   k_ra_product     X = G g, three columns: one wave per row of G, lane l takes the columns l, l + kTile, ..., an xor butterfly over the wave.  G is read once per
 //                    ADMM iteration, row by row, each row contiguous: the kernel is bound by that stream (8 (F - 1)^2 bytes);
 //   k_ra_admm        a lane per pair: A x, the shrinkage, the u-update, the next w, z+ - z and the pair's three norm terms;
-//   k_ra_tree        one node level of the fixed reduction tree (pvlm_transavg's shape: kChunk leaves per workgroup, halved in LDS);
+//   k_pg_tree        one node level of the pair-graph layer's fixed reduction tree (pvlm_pairgraph.h: kChunk leaves per workgroup, halved in LDS);
 //   k_ra_update      a lane per camera: R <- R exp(x);
 //   k_ra_irls        a lane per pair: b, the weights |A x_prev - b|^-1.5, weights * b, the off-diagonal block straight into the solver's block list;
 //   k_ra_gather_irls the per-camera sums of the weights (the diagonal block) and of the signed weights * b (the right-hand side);
-//   k_ra_l2_*        the L2 stage on K42's pattern: per-pair linearisation, per-camera gather, camera step, per-pair candidate terms.
+//   k_ra_l2_*        the L2 stage, an LM backend of the layer: per-pair cost, linearisation and candidate terms; the gather (k_pg_gather_lm), the camera step
+//                    (k_pg_cam_step) and the camera system are the layer's.  The three gathers here share its skeleton (camera_gather).
 // The rotations, b, z, u, x and the per-pair records stay on the device for the whole call.  G = (2 L)^-1 is formed ONCE per call by the library's dense SPD solver
 // with the identity as right-hand sides (pvlm_spd_solve takes and returns host memory: 2 L goes up and G comes back and is sent up again, once per call).  Per ADMM
 // iteration the host reads five scalars and decides convergence — every iteration, so the iterates and the count are those of the definition; per IRLS / LM iteration
-// it reads the gather, hands the solver behind pvlm_spd_solve_blocks its right-hand side and sends the step back.  Every loop is bounded by P, F, a CSR row or an
+// it reads the gather, hands the solver behind the layer's solve_cameras its right-hand side and sends the step back.  Every loop is bounded by P, F, a CSR row or an
 // iteration cap; every index is checked on the host before the first launch.  Vector stores and plain C++ only.
 #include <chrono>
 #include <cmath>
@@ -25,15 +26,13 @@
 #include <vector>
 
 #include "pvlm_internal.h"
+#include "pvlm_pairgraph.h"
 #include "pvlm_rotavg_core.h"
 
 namespace {
 
 namespace ra = pvlm_rotavg;
-namespace ta = pvlm_transavg;
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1024;           // the kernels stride past kMaxBlocks workgroups
 static_assert(ra::kTile == 64, "the dense product gives one wave of 64 lanes to a row");
 
 __device__ __forceinline__ void load9(const double* __restrict__ p, double* v) { for (int k = 0; k < 9; ++k) v[k] = p[k]; }
@@ -53,30 +52,15 @@ __global__ __launch_bounds__(kThreads) void k_ra_begin(int P, const int* __restr
 // g: component-major 3 x (F - 1) over the rows of G; cterms: [0 .. F) = |A^T (z+ - z)|^2, [F .. 2 F) = |A^T u|^2 per camera
 __global__ __launch_bounds__(kThreads) void k_ra_gather_admm(int F, long long P, int start, const int* __restrict__ row_off, const int* __restrict__ ent,
                                                              const double* __restrict__ rec, double* __restrict__ g, double* __restrict__ cterms) {
-  const int lane = (int)threadIdx.x % ra::kGroup, per_block = kThreads / ra::kGroup;
-  // the trip count is uniform over the workgroup: every lane of a group takes part in the butterfly, a group past F with an empty row
-  for (long long c0 = (long long)blockIdx.x * per_block; c0 < F; c0 += (long long)gridDim.x * per_block) {
-    const long long c = c0 + (int)threadIdx.x / ra::kGroup;
-    const bool live = c < F;
-    double part[9];
-    ra::gather_lane<9>(rec, P, ent, live ? row_off[c] : 0, live ? row_off[c + 1] : 0, lane, ra::kW, 0x1ffu, part);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      double v = part[k];
-      for (int m = 1; m < ra::kGroup; m <<= 1) v += __shfl_xor(v, m, ra::kGroup);
-      part[k] = v;
-    }
-    if (live && lane == 0) {
-      if (c == start) { cterms[c] = 0.0; cterms[F + c] = 0.0; }
-      else {
-        double gc[3], s2, atu2;
-        ra::admm_camera(part, gc, &s2, &atu2);
-        const long long n = F - 1, row = c - (c > start);
-        g[row] = gc[0]; g[n + row] = gc[1]; g[2 * n + row] = gc[2];
-        cterms[c] = s2; cterms[F + c] = atu2;
-      }
-    }
-  }
+  camera_gather<9>(F, row_off, [&](int e0, int e1, int lane, double* part) { pg::gather_lane<9>(rec, P, ent, e0, e1, lane, ra::kW, 0x1ffu, part); },
+                   [&](long long c, const double* part) {
+                     if (c == start) { cterms[c] = 0.0; cterms[F + c] = 0.0; return; }
+                     double gc[3], s2, atu2;
+                     ra::admm_camera(part, gc, &s2, &atu2);
+                     const long long n = F - 1, row = c - (c > start);
+                     g[row] = gc[0]; g[n + row] = gc[1]; g[2 * n + row] = gc[2];
+                     cterms[c] = s2; cterms[F + c] = atu2;
+                   });
 }
 
 // X (component-major 3 x F, the camera of row i is i + (i >= start); the entries of start stay zero) = G g
@@ -86,13 +70,13 @@ __global__ __launch_bounds__(kThreads) void k_ra_product(int n, int start, const
   // the row is uniform over a wave: all its lanes take part in the butterfly, a wave past n with nothing to add
   for (long long i0 = (long long)blockIdx.x * per_block; i0 < n; i0 += (long long)gridDim.x * per_block) {
     const long long i = i0 + (int)threadIdx.x / ra::kTile;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};
     if (i < n) {
       const double* __restrict__ row = G + i * n;
-      for (int j = lane; j < n; j += ra::kTile) { const double a = row[j]; a0 += a * g[j]; a1 += a * g[(long long)n + j]; a2 += a * g[2 * (long long)n + j]; }
+      for (int j = lane; j < n; j += ra::kTile) { const double a = row[j]; acc[0] += a * g[j]; acc[1] += a * g[(long long)n + j]; acc[2] += a * g[2 * (long long)n + j]; }
     }
-    for (int m = 1; m < ra::kTile; m <<= 1) { a0 += __shfl_xor(a0, m, ra::kTile); a1 += __shfl_xor(a1, m, ra::kTile); a2 += __shfl_xor(a2, m, ra::kTile); }
-    if (i < n && lane == 0) { const long long c = i + (i >= start); X[c] = a0; X[F + c] = a1; X[2 * F + c] = a2; }
+    group_sum<3, ra::kTile>(acc);
+    if (i < n && lane == 0) { const long long c = i + (i >= start); X[c] = acc[0]; X[F + c] = acc[1]; X[2 * F + c] = acc[2]; }
   }
 }
 
@@ -103,19 +87,6 @@ __global__ __launch_bounds__(kThreads) void k_ra_admm(int P, long long F, const 
     load_x(X, F, first[p], xi); load_x(X, F, second[p], xj);
     ra::admm_pair(xi, xj, rec + p, P, terms + p, P);
   }
-}
-
-// out[col * out_stride + b] = the node over in[col * in_stride + b * kChunk ..]
-__global__ __launch_bounds__(ta::kChunk) void k_ra_tree(const double* __restrict__ in, long long n, long long in_stride, double* __restrict__ out, long long out_stride) {
-  __shared__ double buf[ta::kChunk];
-  const long long j = (long long)blockIdx.x * ta::kChunk + threadIdx.x;
-  buf[threadIdx.x] = j < n ? in[(long long)blockIdx.y * in_stride + j] : 0.0;
-  __syncthreads();
-  for (int s = ta::kChunk / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) buf[threadIdx.x] = buf[threadIdx.x] + buf[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(long long)blockIdx.y * out_stride + blockIdx.x] = buf[0];
 }
 
 __global__ __launch_bounds__(kThreads) void k_ra_update(int F, int start, const double* __restrict__ x, double* __restrict__ rot) {
@@ -142,23 +113,11 @@ __global__ __launch_bounds__(kThreads) void k_ra_irls(int P, long long F, const 
 // cam: 6 per camera (sum of weights 3, signed sum of weights * b 3); the diagonal of the camera's block of A^T W A
 __global__ __launch_bounds__(kThreads) void k_ra_gather_irls(int F, long long P, const int* __restrict__ row_off, const int* __restrict__ ent, const double* __restrict__ rec,
                                                              double* __restrict__ cam, double* __restrict__ diag_blocks) {
-  const int lane = (int)threadIdx.x % ra::kGroup, per_block = kThreads / ra::kGroup;
-  for (long long c0 = (long long)blockIdx.x * per_block; c0 < F; c0 += (long long)gridDim.x * per_block) {
-    const long long c = c0 + (int)threadIdx.x / ra::kGroup;
-    const bool live = c < F;
-    double part[6];
-    ra::gather_lane<6>(rec, P, ent, live ? row_off[c] : 0, live ? row_off[c + 1] : 0, lane, ra::kIw, 0x38u, part);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      double v = part[k];
-      for (int m = 1; m < ra::kGroup; m <<= 1) v += __shfl_xor(v, m, ra::kGroup);
-      part[k] = v;
-    }
-    if (live && lane == 0) {
-      for (int k = 0; k < 6; ++k) cam[6 * c + k] = part[k];
-      for (int k = 0; k < 3; ++k) diag_blocks[36 * c + 7 * k] = 2.0 * part[k];
-    }
-  }
+  camera_gather<6>(F, row_off, [&](int e0, int e1, int lane, double* part) { pg::gather_lane<6>(rec, P, ent, e0, e1, lane, ra::kIw, 0x38u, part); },
+                   [&](long long c, const double* part) {
+                     for (int k = 0; k < 6; ++k) cam[6 * c + k] = part[k];
+                     for (int k = 0; k < 3; ++k) diag_blocks[36 * c + 7 * k] = 2.0 * part[k];
+                   });
 }
 
 __global__ __launch_bounds__(kThreads) void k_ra_l2_cost(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R21,
@@ -181,38 +140,6 @@ __global__ __launch_bounds__(kThreads) void k_ra_l2_pairs(int P, const int* __re
   }
 }
 
-__global__ __launch_bounds__(kThreads) void k_ra_l2_gather(int F, long long P, const int* __restrict__ row_off, const int* __restrict__ ent, const double* __restrict__ rec,
-                                                           double* __restrict__ cam, double* __restrict__ diag_blocks) {
-  const int lane = (int)threadIdx.x % ta::kGroup, per_block = kThreads / ta::kGroup;
-  for (long long c0 = (long long)blockIdx.x * per_block; c0 < F; c0 += (long long)gridDim.x * per_block) {
-    const long long c = c0 + (int)threadIdx.x / ta::kGroup;
-    const bool live = c < F;
-    double part[ta::kCam];
-    ta::gather_lane(rec, P, ent, live ? row_off[c] : 0, live ? row_off[c + 1] : 0, lane, part);
-#pragma unroll
-    for (int k = 0; k < ta::kCam; ++k) {
-      double v = part[k];
-      for (int m = 1; m < ta::kGroup; m <<= 1) v += __shfl_xor(v, m, ta::kGroup);
-      part[k] = v;
-    }
-    if (live && lane == 0) {
-      for (int k = 0; k < ta::kCam; ++k) cam[ta::kCam * c + k] = part[k];
-      double* B = diag_blocks + 36 * c;
-      B[0] = part[0]; B[1] = part[1]; B[2] = part[2]; B[6] = part[1]; B[7] = part[3]; B[8] = part[4]; B[12] = part[2]; B[13] = part[4]; B[14] = part[5];
-    }
-  }
-}
-
-// candidate vectors and the cameras' terms: [0] = |step|^2, [1] = |aa|^2
-__global__ __launch_bounds__(kThreads) void k_ra_l2_cam_step(int F, const double* __restrict__ aa, const double* __restrict__ step, double* __restrict__ aa_cand,
-                                                             double* __restrict__ cterms) {
-  for (long long c = (long long)blockIdx.x * kThreads + threadIdx.x; c < F; c += (long long)gridDim.x * kThreads) {
-    double d2 = 0, x2 = 0;
-    for (int k = 0; k < 3; ++k) { const double x = aa[3 * c + k], d = step[3 * c + k]; aa_cand[3 * c + k] = x + d; d2 += d * d; x2 += x * x; }
-    cterms[c] = d2; cterms[F + c] = x2;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void k_ra_l2_step(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R21,
                                                          const double* __restrict__ rec, const double* __restrict__ step, const double* __restrict__ aa_cand, double a,
                                                          double* __restrict__ terms) {
@@ -225,60 +152,15 @@ __global__ __launch_bounds__(kThreads) void k_ra_l2_step(int P, const int* __res
   }
 }
 
-// wall clock of the stages of a call, each of which ends in a wait for the stream.  Printed on stderr when PVLM_ROTAVG_PROFILE is set (tools/rotavg_bench.py).
-struct StageClock {
-  double kernels_ms = 0, solve_ms = 0, form_g_ms = 0; int solves = 0;
-  std::chrono::steady_clock::time_point t0;
-  void start() { t0 = std::chrono::steady_clock::now(); }
-  double stop() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-unsigned grid_for(long long n, int per_block, long long limit) { const long long g = (n + per_block - 1) / per_block; return (unsigned)(g < 1 ? 1 : (g > limit ? limit : g)); }
-
-// what the two backends share: the pair list and its CSR on the device, the partials of the reduction tree
-struct DeviceGraph {
-  pvlm_call& c; int F, P; long long blocks_limit;
-  int *d_first = nullptr, *d_second = nullptr, *d_off = nullptr, *d_ent = nullptr;
-  double *d_R21 = nullptr, *d_part[2] = {nullptr, nullptr};
-  StageClock clock;
-
-  DeviceGraph(pvlm_call& call, int F_, int P_) : c(call), F(F_), P(P_) { blocks_limit = pvlm_i_env_limit("PVLM_ROTAVG_MAX_BLOCKS", kMaxBlocks); }
-  void setup(const int* first, const int* second, const double* R21, int max_cols) {
-    std::vector<int> off, ent;
-    ta::build_csr(F, P, first, second, &off, &ent);
-    d_first = c.upload(first, (size_t)P); d_second = c.upload(second, (size_t)P);
-    d_off = c.upload(off.data(), off.size()); d_ent = c.upload(ent.data(), ent.size());
-    d_R21 = c.upload(R21, 9 * (size_t)P);
-    const long long most = P > F ? P : F, stride = (most + ta::kChunk - 1) / ta::kChunk;
-    for (int k = 0; k < 2; ++k) d_part[k] = c.alloc<double>((size_t)max_cols * (size_t)stride);
-  }
-  bool failed() const { return c.st != PVLM_OK; }
-  unsigned pair_grid() const { return grid_for(P, kThreads, blocks_limit); }
-  unsigned camera_grid() const { return grid_for(F, kThreads, blocks_limit); }
-  unsigned group_grid(int group) const { return grid_for(F, kThreads / group, blocks_limit); }
-  // the roots of `cols` trees over in[col * in_stride + 0 .. n) land in out[0 .. cols) at the next sync
-  void reduce(const double* in, long long n, long long in_stride, int cols, double* out) {
-    int k = 0;
-    for (;;) {
-      const long long m = (n + ta::kChunk - 1) / ta::kChunk;
-      c.launch(k_ra_tree, dim3((unsigned)m, (unsigned)cols), dim3(ta::kChunk), 0, in, n, in_stride, d_part[k], m);
-      in = d_part[k]; in_stride = m; n = m; k ^= 1;
-      if (m == 1) break;
-    }
-    c.check_launches();
-    c.d2h(out, in, (size_t)cols * sizeof(double));
-  }
-};
-
 struct L1DeviceBackend : DeviceGraph {
   int start, n;
-  ta::CameraSystem sys;
+  pg::CameraSystem sys;
   double *d_rot = nullptr, *d_rec = nullptr, *d_G = nullptr, *d_g = nullptr, *d_X = nullptr, *d_terms = nullptr, *d_cterms = nullptr, *d_cam = nullptr, *d_blocks = nullptr,
          *d_xp = nullptr;
   std::vector<double> cam;
   int info_g = 0;
 
-  L1DeviceBackend(pvlm_call& call, int F_, int P_, int start_) : DeviceGraph(call, F_, P_), start(start_), n(F_ - 1) {}
+  L1DeviceBackend(pvlm_call& call, int F_, int P_, int start_) : DeviceGraph(call, "PVLM_ROTAVG_MAX_BLOCKS", F_, P_), start(start_), n(F_ - 1) {}
 
   void setup(const int* first, const int* second, const double* R21, const double* rotations) {
     DeviceGraph::setup(first, second, R21, ra::kL1Terms);
@@ -306,14 +188,14 @@ struct L1DeviceBackend : DeviceGraph {
   }
 
   void gather_admm() {
-    c.launch(k_ra_gather_admm, dim3(group_grid(ra::kGroup)), dim3(kThreads), 0, F, (long long)P, start, d_off, d_ent, d_rec, d_g, d_cterms);
+    c.launch(k_ra_gather_admm, dim3(group_grid()), dim3(kThreads), 0, F, (long long)P, start, d_off, d_ent, d_rec, d_g, d_cterms);
   }
   double admm_begin() {
     double b2 = 0.0;
     clock.start();
     c.launch(k_ra_begin, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_rot, d_rec, d_terms);
     gather_admm();
-    reduce(d_terms, P, P, 1, &b2);
+    reduce<false>(d_terms, P, P, 1, &b2);
     const bool bad = c.sync() != PVLM_OK;
     clock.kernels_ms += clock.stop();
     return bad ? std::nan("") : b2;
@@ -324,8 +206,8 @@ struct L1DeviceBackend : DeviceGraph {
     c.launch(k_ra_product, dim3(grid_for(n, kThreads / ra::kTile, blocks_limit)), dim3(kThreads), 0, n, start, d_G, d_g, d_X);
     c.launch(k_ra_admm, dim3(pair_grid()), dim3(kThreads), 0, P, (long long)F, d_first, d_second, d_X, d_rec, d_terms);
     gather_admm();
-    reduce(d_terms, P, P, ra::kL1Terms, pt);          // the staged copy of the roots is ordered on the stream before the next tree reuses the partials
-    reduce(d_cterms, F, F, 2, ct);
+    reduce<false>(d_terms, P, P, ra::kL1Terms, pt);          // the staged copy of the roots is ordered on the stream before the next tree reuses the partials
+    reduce<false>(d_cterms, F, F, 2, ct);
     const bool bad = c.sync() != PVLM_OK;
     clock.kernels_ms += clock.stop();
     if (bad) return ra::AdmmNorms{std::nan(""), 0, 0, 0, 0};
@@ -345,7 +227,7 @@ struct L1DeviceBackend : DeviceGraph {
     clock.start();
     c.h2d(d_xp, x_prev.data(), x_prev.size() * sizeof(double));
     c.launch(k_ra_irls, dim3(pair_grid()), dim3(kThreads), 0, P, (long long)F, d_first, d_second, d_R21, d_rot, d_xp, d_rec, d_blocks + 36 * (size_t)F);
-    c.launch(k_ra_gather_irls, dim3(group_grid(ra::kGroup)), dim3(kThreads), 0, F, (long long)P, d_off, d_ent, d_rec, d_cam, d_blocks);
+    c.launch(k_ra_gather_irls, dim3(group_grid()), dim3(kThreads), 0, F, (long long)P, d_off, d_ent, d_rec, d_cam, d_blocks);
     c.check_launches();
     c.d2h(cam.data(), d_cam, cam.size() * sizeof(double));
     const bool bad = c.sync() != PVLM_OK;
@@ -353,83 +235,56 @@ struct L1DeviceBackend : DeviceGraph {
     if (bad) return -1;
     if (!ra::irls_prepare(&sys, cam.data())) return sys.n + 1;
     int info = 0;
-    clock.start();
-    const pvlm_status st = pvlm_i_spd_solve_blocks(c.ctx, sys.n, F + P, sys.rows.data(), sys.cols.data(), sys.mirror.data(), d_blocks, true, sys.sigma.data(),
-                                                   sys.diag.data(), sys.rhs.data(), &info);
-    clock.solve_ms += clock.stop(); ++clock.solves;
-    if (st) { c.st = st; return -1; }
+    if (!solve_cameras(c, sys, d_blocks, F + P, clock, &info)) return -1;
     if (info != 0) return info;
-    if (!ta::finite_all(sys.rhs.data(), sys.rhs.size())) return sys.n + 1;
+    if (!pg::finite_all(sys.rhs.data(), sys.rhs.size())) return sys.n + 1;
     ra::irls_expand(sys, x);
     return 0;
   }
 };
 
-struct L2DeviceBackend : DeviceGraph {
-  ta::Options opt;
-  ta::CameraSystem sys;
-  double *d_rec = nullptr, *d_blocks = nullptr, *d_cam = nullptr, *d_step = nullptr, *d_terms = nullptr, *d_cterms = nullptr;
+// the LM backend of the L2 stage: the layer's graph, camera system and camera step; the angle-axis vectors and the per-pair records are its own
+struct L2DeviceBackend : LmDevice {
+  double *d_rec = nullptr, *d_terms = nullptr;
   double* d_aa[2] = {nullptr, nullptr};
   int cur = 0;
-  std::vector<double> cam, step;
 
-  L2DeviceBackend(pvlm_call& call, const ta::Options& o, int F_, int P_) : DeviceGraph(call, F_, P_), opt(o) {}
+  L2DeviceBackend(pvlm_call& call, const pg::Options& o, int F_, int P_) : LmDevice(call, "PVLM_ROTAVG_MAX_BLOCKS", o, F_, P_) {}
 
   void setup(const int* first, const int* second, const double* R21, const double* aa0) {
-    DeviceGraph::setup(first, second, R21, 2);
-    sys.init(F, P, first, second, -1);
+    LmDevice::setup(first, second, R21, 2, -1);
     d_aa[0] = c.upload(aa0, 3 * (size_t)F); d_aa[1] = c.alloc<double>(3 * (size_t)F);
-    d_rec = c.alloc<double>((size_t)ra::kL2Slots * (size_t)P); d_blocks = c.alloc<double>(36 * ((size_t)F + (size_t)P)); d_cam = c.alloc<double>((size_t)ta::kCam * (size_t)F);
-    d_step = c.alloc<double>(3 * (size_t)F); d_terms = c.alloc<double>(2 * (size_t)P); d_cterms = c.alloc<double>(2 * (size_t)F);
-    c.memset(d_blocks, 0, 36 * ((size_t)F + (size_t)P) * sizeof(double));
-    cam.assign((size_t)ta::kCam * (size_t)F, 0.0);
+    d_rec = c.alloc<double>((size_t)ra::kL2Slots * (size_t)P); d_terms = c.alloc<double>(2 * (size_t)P);
   }
   double initial_cost() {
     double cost = 0.0;
     clock.start();
     c.launch(k_ra_l2_cost, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_aa[cur], opt.loss_a, d_terms);
-    reduce(d_terms, P, P, 1, &cost);
+    reduce<false>(d_terms, P, P, 1, &cost);
     const bool bad = c.sync() != PVLM_OK;
     clock.kernels_ms += clock.stop();
     return bad ? std::nan("") : cost;
   }
   double linearise(double, bool first) {
     clock.start();
-    c.launch(k_ra_l2_pairs, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_aa[cur], opt.loss_a, d_rec, d_blocks + 36 * (size_t)F);
-    c.launch(k_ra_l2_gather, dim3(group_grid(ta::kGroup)), dim3(kThreads), 0, F, (long long)P, d_off, d_ent, d_rec, d_cam, d_blocks);
-    c.check_launches();
-    c.d2h(cam.data(), d_cam, cam.size() * sizeof(double));
-    const bool bad = c.sync() != PVLM_OK;
+    c.launch(k_ra_l2_pairs, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_aa[cur], opt.loss_a, d_rec, off_blocks());
+    const bool ok = gather(d_rec);
     clock.kernels_ms += clock.stop();
-    if (bad) return 0.0;
+    if (!ok) return 0.0;
     if (first) sys.set_sigma(cam.data());
     return sys.gradient_max(cam.data());
   }
-  bool solve(double radius) {
-    if (failed()) return false;
-    sys.prepare(cam.data(), true, radius, opt);
-    int info = 0;
-    clock.start();
-    const pvlm_status st = pvlm_i_spd_solve_blocks(c.ctx, sys.n, F + P, sys.rows.data(), sys.cols.data(), sys.mirror.data(), d_blocks, true, sys.sigma.data(),
-                                                   sys.diag.data(), sys.rhs.data(), &info);
-    clock.solve_ms += clock.stop(); ++clock.solves;
-    if (st) { c.st = st; return false; }
-    if (info != 0) return false;
-    sys.expand(&step);
-    c.h2d(d_step, step.data(), step.size() * sizeof(double));
-    return !failed();
-  }
-  ta::Scalars candidate() {
+  pg::Scalars candidate() {
     double pt[2] = {0, 0}, ct[2] = {0, 0};
     clock.start();
-    c.launch(k_ra_l2_cam_step, dim3(camera_grid()), dim3(kThreads), 0, F, d_aa[cur], d_step, d_aa[cur ^ 1], d_cterms);
+    step_cameras(d_aa[cur], d_aa[cur ^ 1]);
     c.launch(k_ra_l2_step, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_rec, d_step, d_aa[cur ^ 1], opt.loss_a, d_terms);
-    reduce(d_terms, P, P, 2, pt);
-    reduce(d_cterms, F, F, 2, ct);
+    reduce<false>(d_terms, P, P, 2, pt);
+    camera_terms(ct);
     const bool bad = c.sync() != PVLM_OK;
     clock.kernels_ms += clock.stop();
-    if (bad) return ta::Scalars{std::nan(""), 0, 0, 0};
-    return ta::Scalars{pt[ta::kTermCost], pt[ta::kTermModel], ct[0], ct[1]};
+    if (bad) return pg::Scalars{std::nan(""), 0, 0, 0};
+    return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], ct[0], ct[1]};
   }
   void accept() { cur ^= 1; }
 };
@@ -472,35 +327,35 @@ extern "C" pvlm_status pvlm_rotavg_l1(pvlm_ctx* ctx, int n_cameras, int n_pairs,
 
 extern "C" pvlm_status pvlm_rotavg_l2(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21, double* rotations,
                                       const pvlm_rotavg_l2_params* params, pvlm_rotavg_l2_summary* summary) {
-  static_assert(sizeof(ta::Summary) == sizeof(pvlm_rotavg_l2_summary), "pvlm_rotavg_l2_summary is the core's Summary");
+  static_assert(sizeof(pg::Summary) == sizeof(pvlm_rotavg_l2_summary), "pvlm_rotavg_l2_summary is the core's Summary");
   const char* who = "pvlm_rotavg_l2";
   if (!ctx) return PVLM_ERR_ARG;
   if (!params || !summary) { PVLM_SET_ERR(ctx, "%s: null argument", who); return PVLM_ERR_ARG; }
   if (const char* bad = ra::check_args(n_cameras, n_pairs, first, second, R_21, rotations, -1, false)) { PVLM_SET_ERR(ctx, "%s: %s", who, bad); return PVLM_ERR_ARG; }
   if (params->max_num_iterations < 0 || !std::isfinite(params->loss_a)) { PVLM_SET_ERR(ctx, "%s: max_num_iterations < 0 or loss_a not finite", who); return PVLM_ERR_ARG; }
   const int F = n_cameras, P = n_pairs;
-  ta::Summary s{0.0, 0.0, 0, 0, ta::kNoPairs};
+  pg::Summary s{0.0, 0.0, 0, 0, pg::kNoPairs};
   if (P == 0) { std::memcpy(summary, &s, sizeof s); return PVLM_OK; }
   const auto call_t0 = std::chrono::steady_clock::now();
   std::vector<double> aa(3 * (size_t)F);
   for (int k = 0; k < F; ++k) ra::log_rotation(rotations + 9 * (size_t)k, &aa[3 * (size_t)k]);
   pvlm_call c(ctx, who);
   if (c.enter()) return c.st;
-  ta::Options opt;
+  pg::Options opt;
   opt.loss_a = params->loss_a; opt.max_num_iterations = params->max_num_iterations;
   L2DeviceBackend be(c, opt, F, P);
   be.setup(first, second, R_21, aa.data());
-  ta::lm_solve(be, opt, &s);
+  pg::lm_solve(be, opt, &s);
   c.d2h(aa.data(), be.d_aa[be.cur], aa.size() * sizeof(double));
   if (c.sync()) return c.st;
-  if (ta::finite_all(aa.data(), aa.size())) for (int k = 0; k < F; ++k) ra::exp_rotation(&aa[3 * (size_t)k], rotations + 9 * (size_t)k);
+  if (pg::finite_all(aa.data(), aa.size())) for (int k = 0; k < F; ++k) ra::exp_rotation(&aa[3 * (size_t)k], rotations + 9 * (size_t)k);
   std::memcpy(summary, &s, sizeof s);
   if (std::getenv("PVLM_ROTAVG_PROFILE"))
     print_profile("l2", F, P, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call_t0).count(), be.clock, s.successful_steps + s.unsuccessful_steps);
   return PVLM_OK;
 }
 
-extern "C" int pvlm_rotavg_group_size(void) { return ra::kGroup; }
+extern "C" int pvlm_rotavg_group_size(void) { return pg::kGroup; }
 
 // pvlm_preload: loads this file's code object at context set-up instead of at the first call (see pvlm_ba.hip)
 __global__ void k_preload_rotavg() {}

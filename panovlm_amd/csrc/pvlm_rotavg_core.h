@@ -1,5 +1,5 @@
 // K40: the definition of rotation averaging (RotationAveragingRefineL1 and RotationAveragingL2, sfm/RotationAveraging.cpp:317-374, :428-582) — host and device.
-// Compiled for the device by pvlm_rotavg.hip and for the host by tests/cpp/rotavg_core_check.cpp; both run the SAME drivers (l1_solve below, pvlm_transavg's lm_solve)
+// Compiled for the device by pvlm_rotavg.hip and for the host by tests/cpp/rotavg_core_check.cpp; both run the SAME drivers (l1_solve below, lm_solve of pvlm_pairgraph_core.h)
 // over a backend that evaluates, gathers, multiplies, solves and steps.  F cameras, P pairs (first, second, R_21 row-major), rotations R_cw row-major.
 //
 // Pair error (:476-478): e_p = log((R_2w^T R_21) R_1w), log = RotationMatrixToAngleAxis of host/pvlm_host.cpp with its branches.
@@ -19,9 +19,10 @@
 //   is not finite or not positive definite ends the call with info > 0 and the rotations of the last completed iteration (upstream returns false, :553-557).
 // L2 refinement (:317-374; PairWiseRotationResidual, base/CostFunction.h:17-47): one angle-axis vector per camera, none fixed, r_p = log((R_2w R_1w^T) R_21^T) under
 //   SoftLOneLoss(a) on |r|^2; R_21 is used directly instead of through its angle-axis vector (the divergence K36 and K42 document).  Analytic Jacobians in place of
-//   the autodiff: with M = R_2w R_1w^T, d r / d aa_2 = J_l^-1(r) J_l(aa_2), d r / d aa_1 = -J_l^-1(r) M J_l(aa_1).  LM: pvlm_transavg's lm_solve, CameraSystem (no
+//   the autodiff: with M = R_2w R_1w^T, d r / d aa_2 = J_l^-1(r) J_l(aa_2), d r / d aa_1 = -J_l^-1(r) M J_l(aa_1).  LM: the pair-graph layer's lm_solve, CameraSystem (no
 //   origin), Jacobi scaling and LM diagonal.
-// Sums: per camera its pairs in list order over kGroup lanes and an xor butterfly; every scalar the root of pvlm_transavg's fixed tree over pairs or cameras.
+// Sums: per camera its pairs in list order over kGroup lanes and an xor butterfly; every scalar the root of the fixed tree over pairs or cameras
+// (pvlm_pairgraph_core.h).
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -30,7 +31,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "pvlm_transavg_core.h"
+#include "pvlm_pairgraph_core.h"
 
 #if defined(__HIPCC__)
 #define PVLM_RA_HD __host__ __device__ __forceinline__
@@ -40,16 +41,16 @@
 
 namespace pvlm_rotavg {
 
-namespace ta = pvlm_transavg;
+namespace pg = pvlm_pairgraph;
 
-constexpr int kGroup = 8;             // lanes that share one camera's gather
+using pg::kGroup;                     // lanes that share one camera's gather: the layer's (pvlm_rotavg_group_size)
 constexpr int kTile = 64;             // lanes across one row of the dense product
 constexpr int kAdmmMaxIterations = 1000, kOuterMaxIterations = 32;
 // L1 / IRLS per-pair record, component-major (component k of pair p at [k * P + p])
 enum { kB = 0, kZ = 3, kW = 6, kDz = 9, kU = 12, kL1Slots = 15 };     // ADMM: b | z | w = b + z - u | z+ - z | u (the last three are what a camera gathers)
 enum { kIw = 0, kIwb = 3 };                                            // IRLS (the same storage): weights | weights * b
 enum { kTermR2 = 0, kTermAx2 = 1, kTermZ2 = 2, kL1Terms = 3 };
-// L2 per-pair record: side 0 (first) and side 1 (second) as ta::kCam numbers each (no elimination: the reduced pieces equal the unreduced), then
+// L2 per-pair record: side 0 (first) and side 1 (second) as pg::kCam numbers each (no elimination: the reduced pieces equal the unreduced), then
 enum { kJ1 = 30, kJ2 = 39, kRes = 48, kRw = 51, kL2Slots = 52 };
 
 struct L1Summary { int l1_iterations, admm_iterations, irls_iterations, info; };     // == pvlm_rotavg_l1_summary
@@ -162,16 +163,6 @@ PVLM_RA_HD void admm_pair(const double* xi, const double* xj, double* rec, long 
   }
   terms[kTermR2 * tstride] = r2; terms[kTermAx2 * tstride] = ax2; terms[kTermZ2 * tstride] = z2;
 }
-// lane `lane` of the kGroup lanes of one camera: N consecutive slots from slot0 over its part of the row ent[e0 .. e1) (entry = 2 * pair + side) in list order;
-// slot k takes the sign of the incidence (- for first, + for second) when bit k of signed_mask is set
-template <int N> PVLM_RA_HD void gather_lane(const double* rec, long long P, const int* ent, int e0, int e1, int lane, int slot0, unsigned signed_mask, double* part) {
-  for (int k = 0; k < N; ++k) part[k] = 0.0;
-  for (int e = e0 + lane; e < e1; e += kGroup) {
-    const int p = ent[e] >> 1, side = ent[e] & 1;
-    const double* s = rec + (long long)slot0 * P + p;
-    for (int k = 0; k < N; ++k) { const double v = s[(long long)k * P]; part[k] += ((signed_mask >> k) & 1u) && side == 0 ? -v : v; }
-  }
-}
 // one camera's ADMM gather (w | z+ - z | u, signed) -> its right-hand side g = A^T (b + z - u) and its terms |A^T (z+ - z)|^2, |A^T u|^2 (A over the 2 P rows)
 PVLM_RA_HD void admm_camera(const double* v, double* g, double* s2, double* atu2) {
   double s = 0, a = 0;
@@ -219,7 +210,7 @@ PVLM_RA_HD void l2_jacobians(const double* aa1, const double* aa2, const double*
 PVLM_RA_HD double l2_pair_cost(const double* aa1, const double* aa2, const double* R21, double a) {
   double r[3], M[9], rho, rho1;
   l2_residual(aa1, aa2, R21, r, M);
-  ta::loss(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rho1);
+  pg::loss(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rho1);
   return 0.5 * rho;
 }
 // the linearisation of one pair: rec (stride P), off: rho' J1^T J2 between first (rows) and second (columns) inside a 6 x 6 row-major block
@@ -227,8 +218,8 @@ PVLM_RA_HD void l2_linearise_pair(const double* aa1, const double* aa2, const do
   double r[3], M[9], J1[9], J2[9], rho, rw;
   l2_residual(aa1, aa2, R21, r, M);
   l2_jacobians(aa1, aa2, r, M, J1, J2);
-  ta::loss(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rw);
-  double* si = rec; double* sj = rec + (long long)ta::kCam * P;
+  pg::loss(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rw);
+  double* si = rec; double* sj = rec + (long long)pg::kCam * P;
   int q = 0;
   for (int x = 0; x < 3; ++x)
     for (int y = x; y < 3; ++y, ++q) {
@@ -255,8 +246,8 @@ PVLM_RA_HD void l2_step_pair(const double* R21, const double* rec, long long P, 
     for (int y = 0; y < 3; ++y) u += rec[(kJ1 + 3 * k + y) * P] * d1[y] + rec[(kJ2 + 3 * k + y) * P] * d2[y];
     ru += rec[(kRes + k) * P] * u; uu += u * u;
   }
-  terms[ta::kTermCost * tstride] = l2_pair_cost(c1, c2, R21, a);
-  terms[ta::kTermModel * tstride] = -(rw * ru + 0.5 * rw * uu);
+  terms[pg::kTermCost * tstride] = l2_pair_cost(c1, c2, R21, a);
+  terms[pg::kTermModel * tstride] = -(rw * ru + 0.5 * rw * uu);
 }
 
 // ---- host side: shared by the device entry points and by the host compile ----------------------------------------------------------------------------------
@@ -275,13 +266,13 @@ inline const char* check_args(int F, int P, const int* first, const int* second,
   for (int p = 0; p < P; ++p) {
     if (first[p] < 0 || first[p] >= F || second[p] < 0 || second[p] >= F) return "a pair names a camera that is not there";
     if (first[p] == second[p]) return "a pair of a camera with itself";
-    if (!ta::finite_all(R21 + 9 * (size_t)p, 9)) return "a relative rotation is not finite";
+    if (!pg::finite_all(R21 + 9 * (size_t)p, 9)) return "a relative rotation is not finite";
     keys[(size_t)p] = std::make_pair(std::min(first[p], second[p]), std::max(first[p], second[p]));
     root[(size_t)find(first[p])] = find(second[p]);
   }
   std::sort(keys.begin(), keys.end());
   for (int p = 1; p < P; ++p) if (keys[(size_t)p] == keys[(size_t)p - 1]) return "a camera pair is named twice";
-  if (!ta::finite_all(rotations, 9 * (size_t)F)) return "a rotation is not finite";
+  if (!pg::finite_all(rotations, 9 * (size_t)F)) return "a rotation is not finite";
   if (has_start && !is_identity(rotations + 9 * (size_t)start)) return "the rotation of start_idx is not the identity";
   for (int c = 1; c < F; ++c) if (find(c) != find(0)) return "the pair graph is not connected";
   return nullptr;
@@ -308,7 +299,7 @@ inline double table_norm(const std::vector<double>& x, const std::vector<double>
     for (int k = 0; k < 3; ++k) { const double d = x[(size_t)k * F + c] - (y ? (*y)[(size_t)k * F + c] : 0.0); s += d * d; }
     t[(size_t)c] = s;
   }
-  return std::sqrt(ta::tree_reduce_host<false>(t.data(), F));
+  return std::sqrt(pg::tree_reduce_host<false>(t.data(), F));
 }
 
 // The two stages of RotationAveragingRefineL1.  Backend: bool failed(); double admm_begin() -> |b|^2 over the P rows; AdmmNorms admm_iterate();
@@ -350,10 +341,10 @@ template <class B> inline void l1_solve(B& be, int F, int P, L1Summary* out) {
   *out = s;
 }
 
-// the IRLS system on the host's side: pvlm_transavg's CameraSystem with start_idx as its origin, no scaling, no LM diagonal.  cam: 6 per camera (sum of weights 3,
+// the IRLS system on the host's side: the pair-graph layer's CameraSystem with start_idx as its origin, no scaling, no LM diagonal.  cam: 6 per camera (sum of weights 3,
 // signed sum of weights * b 3).  false: the gather is not finite
-inline bool irls_prepare(ta::CameraSystem* sys, const double* cam) {
-  if (!ta::finite_all(cam, 6 * (size_t)sys->F)) return false;
+inline bool irls_prepare(pg::CameraSystem* sys, const double* cam) {
+  if (!pg::finite_all(cam, 6 * (size_t)sys->F)) return false;
   for (int c = 0; c < sys->F; ++c) {
     if (sys->index(c) < 0) continue;
     for (int k = 0; k < 3; ++k) { const size_t i = (size_t)sys->index(c) + k; sys->sigma[i] = 1.0; sys->diag[i] = 0.0; sys->rhs[i] = 2.0 * cam[6 * (size_t)c + 3 + k]; }
@@ -361,7 +352,7 @@ inline bool irls_prepare(ta::CameraSystem* sys, const double* cam) {
   return true;
 }
 // the solved rhs -> a component-major 3 x F table, zero at the origin
-inline void irls_expand(const ta::CameraSystem& sys, std::vector<double>* x) {
+inline void irls_expand(const pg::CameraSystem& sys, std::vector<double>* x) {
   x->assign(3 * (size_t)sys.F, 0.0);
   for (int c = 0; c < sys.F; ++c) if (sys.index(c) >= 0) for (int k = 0; k < 3; ++k) (*x)[(size_t)k * sys.F + c] = sys.rhs[(size_t)sys.index(c) + k];
 }

@@ -1,6 +1,6 @@
 // K40 on the host: the definition of csrc/pvlm_rotavg_core.h (rotation averaging) behind host backends that do what the kernels of csrc/pvlm_rotavg.hip do — the
-// per-pair work, the per-camera gather over kGroup lanes and their butterfly, the dense product over kTile lanes and its butterfly, the fixed reduction tree — with
-// a dense host Cholesky in place of the library's solvers.  No device, no dependency on the rest of the host mirror: the equality partner of pvlm_rotavg_l1 /
+// per-pair work, the per-camera gathers over kGroup lanes and the dense product over kTile lanes with their butterflies, the fixed reduction tree — on the host's
+// pair-graph layer (pvlm_host_pairgraph.hpp), whose dense Cholesky stands in for the library's solvers.  No device, no dependency on the rest of the host mirror: the equality partner of pvlm_rotavg_l1 /
 // pvlm_rotavg_l2 (tests/cpp/rotavg_core_check.cpp).
 #pragma once
 #include <cmath>
@@ -8,73 +8,28 @@
 #include <vector>
 
 #include "../csrc/pvlm_rotavg_core.h"
+#include "pvlm_host_pairgraph.hpp"
 
 namespace pvlm {
 namespace rotavg_detail {
 
 namespace ra = pvlm_rotavg;
-namespace ta = pvlm_transavg;
-
-// Cholesky of the row-major SPD matrix M (order n, lower triangle read, overwritten by L) and the solution of M X = B for nrhs right-hand sides stored one after
-// the other (B[r * n + i]).  Returns 0, or k > 0 when the leading minor of order k is not positive definite.
-inline int dense_spd_solve(int n, std::vector<double>& M, int nrhs, double* B) {
-  for (int j = 0; j < n; ++j) {
-    double v = M[(size_t)j * n + j];
-    for (int k = 0; k < j; ++k) v -= M[(size_t)j * n + k] * M[(size_t)j * n + k];
-    if (!(v > 0.0) || !std::isfinite(v)) return j + 1;
-    const double l = std::sqrt(v);
-    M[(size_t)j * n + j] = l;
-    for (int i = j + 1; i < n; ++i) {
-      double w = M[(size_t)i * n + j];
-      for (int k = 0; k < j; ++k) w -= M[(size_t)i * n + k] * M[(size_t)j * n + k];
-      M[(size_t)i * n + j] = w / l;
-    }
-  }
-  for (int r = 0; r < nrhs; ++r) {
-    double* x = B + (size_t)r * n;
-    for (int i = 0; i < n; ++i) { double w = x[i]; for (int k = 0; k < i; ++k) w -= M[(size_t)i * n + k] * x[k]; x[i] = w / M[(size_t)i * n + i]; }
-    for (int i = n - 1; i >= 0; --i) { double w = x[i]; for (int k = i + 1; k < n; ++k) w -= M[(size_t)k * n + i] * x[k]; x[i] = w / M[(size_t)i * n + i]; }
-  }
-  return 0;
-}
-
-// M = D (sum of the 6 x 6 blocks) D + diag of a CameraSystem, dense row-major; the solution replaces sys->rhs
-inline int solve_camera_system(ta::CameraSystem* sys, const std::vector<double>& blocks) {
-  const int n = sys->n;
-  std::vector<double> M((size_t)n * n, 0.0);
-  for (size_t b = 0; b < (size_t)sys->F + sys->P; ++b)
-    for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < 6; ++c) {
-        const int i = sys->rows[6 * b + r], j = sys->cols[6 * b + c];
-        if (i < 0 || j < 0) continue;
-        const double v = blocks[36 * b + 6 * r + c] * sys->sigma[(size_t)i] * sys->sigma[(size_t)j];
-        M[(size_t)i * n + j] += v;
-        if (sys->mirror[b]) M[(size_t)j * n + i] += v;
-      }
-  for (int i = 0; i < n; ++i) M[(size_t)i * n + i] += sys->diag[(size_t)i];
-  return dense_spd_solve(n, M, 1, sys->rhs.data());
-}
-
-// the xor butterfly of a lane group: lane 0's sum
-template <int LANES, int N> inline void butterfly(double (*part)[N]) {
-  double nxt[LANES][N];
-  for (int m = 1; m < LANES; m <<= 1) {
-    for (int l = 0; l < LANES; ++l) for (int k = 0; k < N; ++k) nxt[l][k] = part[l][k] + part[l ^ m][k];
-    std::memcpy(part, nxt, sizeof nxt);
-  }
-}
+namespace pg = pvlm_pairgraph;
+using pairgraph_detail::butterfly;
+using pairgraph_detail::dense_spd_solve;
+using pairgraph_detail::solve_camera_system;
 
 struct L1HostBackend {
   int F, P, start, n;
   const int *first, *second; const double* R21;
   std::vector<double> rot, rec, G, g, X, terms, cterms, cam, blocks;
   std::vector<int> off, ent;
-  ta::CameraSystem sys;
+  pg::CameraSystem sys;
   int info_g = 0;
 
   L1HostBackend(int F_, int P_, const int* fi, const int* se, const double* R21_, int start_, const double* rotations)
       : F(F_), P(P_), start(start_), n(F_ - 1), first(fi), second(se), R21(R21_), rot(rotations, rotations + 9 * (size_t)F_) {
-    ta::build_csr(F, P, first, second, &off, &ent);
+    pg::build_csr(F, P, first, second, &off, &ent);
     sys.init(F, P, first, second, start);
     rec.assign((size_t)ra::kL1Slots * P, 0.0); g.assign(3 * (size_t)n, 0.0); X.assign(3 * (size_t)F, 0.0);
     terms.assign((size_t)ra::kL1Terms * P, 0.0); cterms.assign(2 * (size_t)F, 0.0); cam.assign(6 * (size_t)F, 0.0); blocks.assign(36 * ((size_t)F + P), 0.0);
@@ -83,7 +38,7 @@ struct L1HostBackend {
     ra::laplacian2(F, P, first, second, start, &A);
     G.assign((size_t)n * n, 0.0);
     for (int i = 0; i < n; ++i) G[(size_t)i * n + i] = 1.0;
-    info_g = dense_spd_solve(n, A, n, G.data());
+    info_g = dense_spd_solve(n, A, n, G.data(), true);
   }
   bool failed() const { return false; }
   int camera_of(int row) const { return row + (row >= start); }
@@ -91,9 +46,9 @@ struct L1HostBackend {
 
   void gather_admm() {
     for (int c = 0; c < F; ++c) {
-      double part[ra::kGroup][9];
-      for (int l = 0; l < ra::kGroup; ++l) ra::gather_lane<9>(rec.data(), P, ent.data(), off[(size_t)c], off[(size_t)c + 1], l, ra::kW, 0x1ffu, part[l]);
-      butterfly<ra::kGroup, 9>(part);
+      double part[pg::kGroup][9];
+      for (int l = 0; l < pg::kGroup; ++l) pg::gather_lane<9>(rec.data(), P, ent.data(), off[(size_t)c], off[(size_t)c + 1], l, ra::kW, 0x1ffu, part[l]);
+      butterfly<pg::kGroup, 9>(part);
       if (c == start) { cterms[(size_t)c] = 0.0; cterms[(size_t)F + c] = 0.0; continue; }
       double gc[3];
       ra::admm_camera(part[0], gc, &cterms[(size_t)c], &cterms[(size_t)F + c]);
@@ -103,7 +58,7 @@ struct L1HostBackend {
   double admm_begin() {
     for (int p = 0; p < P; ++p) ra::admm_begin_pair(&rot[9 * (size_t)first[p]], &rot[9 * (size_t)second[p]], R21 + 9 * (size_t)p, &rec[(size_t)p], P, &terms[(size_t)p]);
     gather_admm();
-    return ta::tree_reduce_host<false>(terms.data(), P);
+    return pg::tree_reduce_host<false>(terms.data(), P);
   }
   ra::AdmmNorms admm_iterate() {
     for (int i = 0; i < n; ++i) {                                // X = G g: row i over kTile lanes, then their butterfly
@@ -121,9 +76,9 @@ struct L1HostBackend {
     }
     gather_admm();
     ra::AdmmNorms nm;
-    nm.r2 = ta::tree_reduce_host<false>(&terms[(size_t)ra::kTermR2 * P], P); nm.ax2 = ta::tree_reduce_host<false>(&terms[(size_t)ra::kTermAx2 * P], P);
-    nm.z2 = ta::tree_reduce_host<false>(&terms[(size_t)ra::kTermZ2 * P], P);
-    nm.s2 = ta::tree_reduce_host<false>(&cterms[0], F); nm.atu2 = ta::tree_reduce_host<false>(&cterms[(size_t)F], F);
+    nm.r2 = pg::tree_reduce_host<false>(&terms[(size_t)ra::kTermR2 * P], P); nm.ax2 = pg::tree_reduce_host<false>(&terms[(size_t)ra::kTermAx2 * P], P);
+    nm.z2 = pg::tree_reduce_host<false>(&terms[(size_t)ra::kTermZ2 * P], P);
+    nm.s2 = pg::tree_reduce_host<false>(&cterms[0], F); nm.atu2 = pg::tree_reduce_host<false>(&cterms[(size_t)F], F);
     return nm;
   }
   void fetch_x(std::vector<double>* x) const { *x = X; }
@@ -141,16 +96,16 @@ struct L1HostBackend {
       ra::irls_pair(&rot[9 * (size_t)first[p]], &rot[9 * (size_t)second[p]], R21 + 9 * (size_t)p, xi, xj, &rec[(size_t)p], P, &blocks[36 * ((size_t)F + p)]);
     }
     for (int c = 0; c < F; ++c) {
-      double part[ra::kGroup][6];
-      for (int l = 0; l < ra::kGroup; ++l) ra::gather_lane<6>(rec.data(), P, ent.data(), off[(size_t)c], off[(size_t)c + 1], l, ra::kIw, 0x38u, part[l]);
-      butterfly<ra::kGroup, 6>(part);
+      double part[pg::kGroup][6];
+      for (int l = 0; l < pg::kGroup; ++l) pg::gather_lane<6>(rec.data(), P, ent.data(), off[(size_t)c], off[(size_t)c + 1], l, ra::kIw, 0x38u, part[l]);
+      butterfly<pg::kGroup, 6>(part);
       for (int k = 0; k < 6; ++k) cam[6 * (size_t)c + k] = part[0][k];
       for (int k = 0; k < 3; ++k) blocks[36 * (size_t)c + 7 * k] = 2.0 * part[0][k];
     }
     if (!ra::irls_prepare(&sys, cam.data())) return sys.n + 1;
-    const int info = solve_camera_system(&sys, blocks);
+    const int info = solve_camera_system(&sys, blocks, true);
     if (info != 0) return info;
-    if (!ta::finite_all(sys.rhs.data(), sys.rhs.size())) return sys.n + 1;
+    if (!pg::finite_all(sys.rhs.data(), sys.rhs.size())) return sys.n + 1;
     ra::irls_expand(sys, x);
     return 0;
   }
@@ -170,77 +125,51 @@ inline int L1Host(int F, int P, const int* first, const int* second, const doubl
   return 0;
 }
 
-struct L2HostBackend {
-  ta::Options opt; int F, P;
-  const int *first, *second; const double* R21;
-  std::vector<double> rec, blocks, cam, step, terms, cterms, gs;
+// the LM backend of the L2 stage on the host's layer; finite_pivot = true, as the Cholesky of this twin has always tested (pair-graph layer)
+struct L2HostBackend : pairgraph_detail::LmHost {
+  std::vector<double> rec, terms;
   std::vector<double> aa[2];
-  std::vector<int> off, ent;
-  ta::CameraSystem sys;
   int cur = 0;
 
-  L2HostBackend(const ta::Options& o, int F_, int P_, const int* fi, const int* se, const double* R21_, const double* aa0) : opt(o), F(F_), P(P_), first(fi), second(se), R21(R21_) {
-    ta::build_csr(F, P, first, second, &off, &ent);
-    sys.init(F, P, first, second, -1);
-    rec.assign((size_t)ra::kL2Slots * P, 0.0); blocks.assign(36 * ((size_t)F + P), 0.0); cam.assign((size_t)ta::kCam * F, 0.0);
-    terms.assign(2 * (size_t)P, 0.0); cterms.assign(2 * (size_t)F, 0.0);
+  L2HostBackend(const pg::Options& o, int F_, int P_, const int* fi, const int* se, const double* R21_, const double* aa0) : LmHost(o, F_, P_, fi, se, R21_, -1, true) {
+    rec.assign((size_t)ra::kL2Slots * P, 0.0); terms.assign(2 * (size_t)P, 0.0);
     aa[0].assign(aa0, aa0 + 3 * (size_t)F); aa[1] = aa[0];
   }
-  bool failed() const { return false; }
   double initial_cost() {
     for (int p = 0; p < P; ++p) terms[(size_t)p] = ra::l2_pair_cost(&aa[cur][3 * (size_t)first[p]], &aa[cur][3 * (size_t)second[p]], R21 + 9 * (size_t)p, opt.loss_a);
-    return ta::tree_reduce_host<false>(terms.data(), P);
+    return pg::tree_reduce_host<false>(terms.data(), P);
   }
   double linearise(double, bool first_time) {
     for (int p = 0; p < P; ++p)
-      ra::l2_linearise_pair(&aa[cur][3 * (size_t)first[p]], &aa[cur][3 * (size_t)second[p]], R21 + 9 * (size_t)p, opt.loss_a, &rec[(size_t)p], P, &blocks[36 * ((size_t)F + p)]);
-    for (int c = 0; c < F; ++c) {
-      double part[ta::kGroup][ta::kCam];
-      for (int l = 0; l < ta::kGroup; ++l) ta::gather_lane(rec.data(), P, ent.data(), off[(size_t)c], off[(size_t)c + 1], l, part[l]);
-      butterfly<ta::kGroup, ta::kCam>(part);
-      const double* v = part[0];
-      for (int k = 0; k < ta::kCam; ++k) cam[(size_t)ta::kCam * c + k] = v[k];
-      double* B = &blocks[36 * (size_t)c];
-      B[0] = v[0]; B[1] = v[1]; B[2] = v[2]; B[6] = v[1]; B[7] = v[3]; B[8] = v[4]; B[12] = v[2]; B[13] = v[4]; B[14] = v[5];
-    }
+      ra::l2_linearise_pair(&aa[cur][3 * (size_t)first[p]], &aa[cur][3 * (size_t)second[p]], R21 + 9 * (size_t)p, opt.loss_a, &rec[(size_t)p], P, off_block(p));
+    gather(rec);
     if (first_time) sys.set_sigma(cam.data());
     return sys.gradient_max(cam.data());
   }
-  bool solve(double radius) {
-    sys.prepare(cam.data(), true, radius, opt);
-    if (solve_camera_system(&sys, blocks) != 0) return false;
-    sys.expand(&step);
-    return true;
-  }
-  ta::Scalars candidate() {
-    std::vector<double>& ac = aa[cur ^ 1]; const std::vector<double>& an = aa[cur];
-    for (int c = 0; c < F; ++c) {
-      double d2 = 0, x2 = 0;
-      for (int k = 0; k < 3; ++k) { const double x = an[3 * (size_t)c + k], d = step[3 * (size_t)c + k]; ac[3 * (size_t)c + k] = x + d; d2 += d * d; x2 += x * x; }
-      cterms[(size_t)c] = d2; cterms[(size_t)F + c] = x2;
-    }
+  pg::Scalars candidate() {
+    std::vector<double>& ac = aa[cur ^ 1];
+    step_cameras(aa[cur], ac);
     for (int p = 0; p < P; ++p) {
       const size_t i = (size_t)first[p], j = (size_t)second[p];
       ra::l2_step_pair(R21 + 9 * (size_t)p, &rec[(size_t)p], P, &step[3 * i], &step[3 * j], &ac[3 * i], &ac[3 * j], opt.loss_a, &terms[(size_t)p], P);
     }
-    return ta::Scalars{ta::tree_reduce_host<false>(&terms[0], P), ta::tree_reduce_host<false>(&terms[(size_t)P], P), ta::tree_reduce_host<false>(&cterms[0], F),
-                       ta::tree_reduce_host<false>(&cterms[(size_t)F], F)};
+    return pg::Scalars{pg::tree_reduce_host<false>(&terms[0], P), pg::tree_reduce_host<false>(&terms[(size_t)P], P), camera_term(0), camera_term(1)};
   }
   void accept() { cur ^= 1; }
 };
 
 // pvlm_rotavg_l2 on the host.  Returns 0, or -1 (PVLM_ERR_ARG) with nothing written.
-inline int L2Host(int F, int P, const int* first, const int* second, const double* R21, double* rotations, double loss_a, int max_num_iterations, ta::Summary* summary) {
+inline int L2Host(int F, int P, const int* first, const int* second, const double* R21, double* rotations, double loss_a, int max_num_iterations, pg::Summary* summary) {
   if (!summary || max_num_iterations < 0 || !std::isfinite(loss_a) || ra::check_args(F, P, first, second, R21, rotations, -1, false)) return -1;
-  ta::Summary s{0.0, 0.0, 0, 0, ta::kNoPairs};
+  pg::Summary s{0.0, 0.0, 0, 0, pg::kNoPairs};
   if (P > 0) {
     std::vector<double> aa(3 * (size_t)F);
     for (int c = 0; c < F; ++c) ra::log_rotation(rotations + 9 * (size_t)c, &aa[3 * (size_t)c]);
-    ta::Options opt;
+    pg::Options opt;
     opt.loss_a = loss_a; opt.max_num_iterations = max_num_iterations;
     L2HostBackend be(opt, F, P, first, second, R21, aa.data());
-    ta::lm_solve(be, opt, &s);
-    if (ta::finite_all(be.aa[be.cur].data(), 3 * (size_t)F)) for (int c = 0; c < F; ++c) ra::exp_rotation(&be.aa[be.cur][3 * (size_t)c], rotations + 9 * (size_t)c);
+    pg::lm_solve(be, opt, &s);
+    if (pg::finite_all(be.aa[be.cur].data(), 3 * (size_t)F)) for (int c = 0; c < F; ++c) ra::exp_rotation(&be.aa[be.cur][3 * (size_t)c], rotations + 9 * (size_t)c);
   }
   *summary = s;
   return 0;

@@ -845,18 +845,27 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
 // K42: translation averaging — TranslationAveragingDLT / L2 / SoftL1 / L2IRLS (sfm/TranslationAveraging.cpp), ReIndex, SetToOrigin, EstimateGlobalTranslation
 // ================================================================================================
 namespace {
-// the arrays of pvlm_transavg_* from a pair list; false: a pair names a camera past n_cameras
-struct TransavgInputs {
-  std::vector<int> first, second; std::vector<double> R, t;
-  bool Fill(const std::vector<RelativePair>& pairs, size_t n_cameras) {
+// the arrays of pvlm_transavg_* and pvlm_rotavg_* from a pair list: the pair indices and R_21 always, t_21 for the former, the rotations for the latter
+struct PairGraphInputs {
+  std::vector<int> first, second; std::vector<double> R, t, rot;
+  // false: a pair names a camera past n_cameras
+  bool Fill(const std::vector<RelativePair>& pairs, size_t n_cameras, bool with_t = true) {
     for (const RelativePair& p : pairs) {
       if (p.image_pair.first >= n_cameras || p.image_pair.second >= n_cameras) return false;
       first.push_back((int)p.image_pair.first); second.push_back((int)p.image_pair.second);
-      R.insert(R.end(), p.R_21.begin(), p.R_21.end()); t.insert(t.end(), p.t_21.begin(), p.t_21.end());
+      R.insert(R.end(), p.R_21.begin(), p.R_21.end());
+      if (with_t) t.insert(t.end(), p.t_21.begin(), p.t_21.end());
     }
     first.push_back(0); second.push_back(0); R.resize(R.size() + 9); t.resize(t.size() + 3);   // never empty
     return true;
   }
+  // with the rotations instead of t_21; false also when there is no rotation
+  bool Fill(const std::vector<RelativePair>& pairs, const std::vector<Matrix3d>& rotations) {
+    if (!Fill(pairs, rotations.size(), false)) return false;
+    for (const Matrix3d& m : rotations) rot.insert(rot.end(), m.begin(), m.end());
+    return !rotations.empty();
+  }
+  void Read(std::vector<Matrix3d>& rotations) const { for (size_t c = 0; c < rotations.size(); ++c) std::copy(rot.begin() + 9 * c, rot.begin() + 9 * c + 9, rotations[c].begin()); }
 };
 bool RotationIsZero(const Frame& f) { for (double v : f.R_wc) if (v != 0.0) return false; return true; }
 // sensors/Frame.cpp:203-208 on the numbers themselves: the translation finite and the rotation not zero
@@ -869,7 +878,7 @@ bool Say(const TranslationOptions& o, const char* m) { if (o.message) *o.message
 }  // namespace
 
 bool TranslationAveragingDLT(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const bool host) {
-  TransavgInputs in;
+  PairGraphInputs in;
   if (!in.Fill(image_pairs, global_translations.size())) return false;      // upstream writes past the matrix here (sfm/SfM.cpp:1183 is the caller that can do it)
   const int F = (int)global_translations.size(), P = (int)image_pairs.size();
   std::vector<double> out(3 * (size_t)F + 3, 0.0);
@@ -883,7 +892,7 @@ bool TranslationAveragingDLT(const std::vector<RelativePair>& image_pairs, std::
 
 bool TranslationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, std::vector<double>& scales, const size_t origin_idx,
                             std::vector<double>& weight, double& costs, const double loss_a, const float upper_scale_ratio, const float lower_scale_ratio, const bool host) {
-  TransavgInputs in;
+  PairGraphInputs in;
   const int F = (int)global_translations.size(), P = (int)image_pairs.size();
   if (!in.Fill(image_pairs, global_translations.size()) || scales.size() != image_pairs.size() || weight.size() != image_pairs.size()) return false;
   std::vector<double> x(3 * (size_t)F + 3, 0.0), s(scales), w(weight);
@@ -891,7 +900,7 @@ bool TranslationAveragingL2(const std::vector<RelativePair>& image_pairs, std::v
   s.push_back(0.0); w.push_back(0.0);
   pvlm_transavg_summary sum{0, 0, 0, 0, 0};
   if (host) {
-    pvlm_transavg::Summary hs;
+    pvlm_pairgraph::Summary hs;
     if (transavg_detail::SolveHost(F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), s.data(), (int)origin_idx, x.data(), w.data(), loss_a, upper_scale_ratio,
                                    lower_scale_ratio, 50, &hs)) return false;
     sum.initial_cost = hs.initial_cost; sum.final_cost = hs.final_cost; sum.termination = hs.termination;
@@ -900,7 +909,7 @@ bool TranslationAveragingL2(const std::vector<RelativePair>& image_pairs, std::v
     const pvlm_transavg_params prm{loss_a, upper_scale_ratio, lower_scale_ratio, 50};
     e.Check(pvlm_transavg_solve(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.t.data(), s.data(), (int)origin_idx, x.data(), w.data(), &prm, &sum), "pvlm_transavg_solve");
   }
-  if (sum.termination == pvlm_transavg::kCostNotFinite || !std::isfinite(sum.final_cost)) return false;       // summary.IsSolutionUsable()
+  if (sum.termination == pvlm_pairgraph::kCostNotFinite || !std::isfinite(sum.final_cost)) return false;       // summary.IsSolutionUsable()
   for (int c = 0; c < F; ++c) global_translations[(size_t)c] = {x[3 * (size_t)c], x[3 * (size_t)c + 1], x[3 * (size_t)c + 2]};
   std::copy(s.begin(), s.begin() + P, scales.begin()); std::copy(w.begin(), w.begin() + P, weight.begin());
   costs = sum.final_cost;
@@ -1068,21 +1077,6 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
 // K40: rotation averaging — FindTriplet, FilterByTriplet, FilterPairs, RotationAveragingSpanningTree / RefineL1 / L1 / L2 (sfm/RotationAveraging.cpp), EstimateGlobalRotation
 // ================================================================================================
 namespace {
-// the arrays of pvlm_rotavg_* from a pair list and the rotations; false: a pair names a camera past the rotations
-struct RotavgInputs {
-  std::vector<int> first, second; std::vector<double> R, rot;
-  bool Fill(const std::vector<RelativePair>& pairs, const std::vector<Matrix3d>& rotations) {
-    for (const RelativePair& p : pairs) {
-      if (p.image_pair.first >= rotations.size() || p.image_pair.second >= rotations.size()) return false;
-      first.push_back((int)p.image_pair.first); second.push_back((int)p.image_pair.second);
-      R.insert(R.end(), p.R_21.begin(), p.R_21.end());
-    }
-    for (const Matrix3d& m : rotations) rot.insert(rot.end(), m.begin(), m.end());
-    first.push_back(0); second.push_back(0); R.resize(R.size() + 9);   // never empty
-    return !rotations.empty();
-  }
-  void Read(std::vector<Matrix3d>& rotations) const { for (size_t c = 0; c < rotations.size(); ++c) std::copy(rot.begin() + 9 * c, rot.begin() + 9 * c + 9, rotations[c].begin()); }
-};
 bool Say(const RotationOptions& o, const char* m) { if (o.message) *o.message = m; return false; }
 Matrix3d MulNT(const Matrix3d& A, const Matrix3d& B) { Matrix3d C; pvlm_rotavg::mul_nt(A.data(), B.data(), C.data()); return C; }
 }  // namespace
@@ -1235,7 +1229,7 @@ bool RotationAveragingSpanningTree(const std::vector<RelativePair>& image_pairs,
 }
 
 bool RotationAveragingRefineL1(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, size_t start_idx, const bool host) {
-  RotavgInputs in;
+  PairGraphInputs in;
   if (!in.Fill(image_pairs, global_rotations)) return false;
   const int F = (int)global_rotations.size(), P = (int)image_pairs.size();
   pvlm_rotavg_l1_summary sum{0, 0, 0, 0};
@@ -1259,12 +1253,12 @@ bool RotationAveragingL1(std::vector<RelativePair>& image_pairs, std::vector<Mat
 }
 
 bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host) {
-  RotavgInputs in;
+  PairGraphInputs in;
   if (!in.Fill(image_pairs, global_rotations)) return false;
   const int F = (int)global_rotations.size(), P = (int)image_pairs.size();
   pvlm_rotavg_l2_summary sum{0, 0, 0, 0, 0};
   if (host) {
-    pvlm_transavg::Summary hs;
+    pvlm_pairgraph::Summary hs;
     if (rotavg_detail::L2Host(F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), 0.07, 50, &hs)) return false;
     sum.final_cost = hs.final_cost; sum.termination = hs.termination;
   } else {
@@ -1272,7 +1266,7 @@ bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vect
     const pvlm_rotavg_l2_params prm{0.07, 50};
     if (pvlm_rotavg_l2(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), &prm, &sum) != PVLM_OK) return false;
   }
-  if (sum.termination == pvlm_transavg::kCostNotFinite || !std::isfinite(sum.final_cost) || !pvlm_transavg::finite_all(in.rot.data(), 9 * (size_t)F)) return false;
+  if (sum.termination == pvlm_pairgraph::kCostNotFinite || !std::isfinite(sum.final_cost) || !pvlm_pairgraph::finite_all(in.rot.data(), 9 * (size_t)F)) return false;
   in.Read(global_rotations);
   return true;
 }
