@@ -515,6 +515,35 @@ pvlm_status pvlm_transavg_solve(pvlm_ctx* ctx, int n_cameras, int n_pairs, const
                                 double* weight /* in/out, n_pairs */, const pvlm_transavg_params* params, pvlm_transavg_summary* summary);
 int pvlm_transavg_group_size(void);
 
+/* ---- K44: BATA translation averaging (BATA / LUDRevised / IRLS sfm/BATA.cpp:36-237; the wrapper TranslationAveragingBATA sfm/TranslationAveraging.cpp:483-525) ---- *
+ * The definition (csrc/pvlm_bata_core.h).  P pairs (first, second) with unit directions dir and positive start scales; the camera ids must lie in [0, n_cameras).
+ * As upstream (:197, :207) the cameras are F = max_id - min_id + 1 with the ids shifted by min_id: F * 3 numbers are written to centres (and lud_centres), the
+ * rest of an n_cameras * 3 buffer is left alone.  The pair's difference is d_k = t[first] - t[second]; camera 0 is the gauge and comes back as zero.
+ * LUD stage (init_iteration times): weights w_k = 1, then (|r_k|^2 + delta)^-1/2 (the double square root of :75 / :118 as written); min sum w_k |d_k - s_k dir_k|^2
+ * subject to sum_k dir_k . d_k = P and sum t = 0; s_k = d_k . dir_k / |dir_k|^2, r_k = d_k - s_k dir_k.  The start: scales0 * P / sum(scales0).
+ * IRLS stage (outer_iteration - 1 outers of inner_iteration inners): per outer e_k = |d_k / S_k - dir_k|, Wvec = 1 below robust_threshold, thr / e above, 0 at
+ * equality or NaN (:144-146); per inner S_k = |d_k|^2 / (d_k . dir_k), +inf where negative (:156, the row drops out), the Laplacian weight Wvec_k / S_k^2, the
+ * right-hand side +-(Wvec_k / S_k) dir_k, camera 0 fixed.  outer_iteration = 1 returns the LUD centres.  scales_out: the S of the last pass.
+ * Deliberate divergences.  Upstream factorises the indefinite (3 F + 4) KKT matrix of the LUD stage with SparseLU; here it is two positive definite solves of the
+ * grounded weighted Laplacian, x1 = L^-1 (2 A^T B), x2 = L^-1 c with c = At0^T vec(dir), t = x1 - lambda x2, lambda = (c^T x1 - P) / (c^T x2): exact, because c and
+ * A^T B are orthogonal to the translations, so the multiplier of sum t = 0 is zero, and upstream moves camera 0 to the origin anyway (:121-123) — the method
+ * diverges, not the result.  The system is L (x) I3 and goes through the solver behind pvlm_spd_solve_blocks, re-assembled for every right-hand side.  Upstream's
+ * SparseQR on A^T A (:161) is a Cholesky: a system that is not positive definite (a pair graph that is not connected, a camera whose pairs have all dropped) gives
+ * info > 0 where upstream returns some basic solution; a scale or solution that is not finite (0 / 0: two cameras on one point) gives info = -1 where upstream
+ * carries the NaN on.  Svec.txt, LUD.txt and LUD.pcd are not written.  Which pairs are unscaled (:192-193) and what they draw (:64) is the caller's business.
+ * info: 0; k > 0 not positive definite; -1 not finite; -2 no pairs.  Unless info is 0 no output is touched.
+ * Every sum has one order (per camera: its pairs in list order over pvlm_bata_group_size() lanes and a fixed butterfly; the scalars: a fixed tree over the pairs),
+ * so a call is bit-reproducible from run to run — for a pair list that names no camera pair more than twice (the solver adds repeated blocks atomically).
+ * PVLM_ERR_ARG, with no output touched: a NULL (the two optional outputs apart), a camera index out of range, first == second, an input that is not finite, a
+ * direction not of unit length within 1e-9, a scale <= 0, init_iteration < 1, inner_iteration < 1, outer_iteration < 1, n_cameras < 2.
+ * The environment variable PVLM_BATA_MAX_BLOCKS (read at every call) lowers the grid of the kernels; it changes no result, the tests use it to make them stride.
+ * With PVLM_BATA_PROFILE set, a call prints one line on stderr: its wall clock split into kernels, camera solves and host. */
+typedef struct pvlm_bata_params { double delta /* 1e-6 */; int init_iteration /* 10 */, inner_iteration /* 10 */, outer_iteration /* 10 */; double robust_threshold /* 0.1 */; } pvlm_bata_params;
+pvlm_status pvlm_transavg_bata(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* dir /* n_pairs * 3, unit */,
+                               const double* scales0 /* n_pairs, all > 0 */, const pvlm_bata_params* params, double* centres /* out, F * 3, camera 0 = 0 */,
+                               double* lud_centres_or_null, double* scales_out_or_null, int* info);
+int pvlm_bata_group_size(void);
+
 /* ---- K40: rotation averaging (SfM::EstimateGlobalRotation sfm/SfM.cpp:811-905; RotationAveragingRefineL1 / RotationAveragingL2 sfm/RotationAveraging.cpp:317-582) ---- *
  * The definition (csrc/pvlm_rotavg_core.h).  F cameras, P pairs (first, second, R_21 row-major), rotations R_cw row-major, 9 per camera.
  * pvlm_rotavg_l1 is RotationAveragingRefineL1 with weight function 1 (:428-582): rotations[start_idx] is the identity and stays it.  Pair error

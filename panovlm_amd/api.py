@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "pvlm_vlad_kmeans", "pvlm_vlad_embed", "pvlm_vladset_read", "pvlm_vlad_neighbors", "pvlm_vladset_destroy",
     "pvlm_resset_plane_runs", "pvlm_resset_point_table", "pvlm_resset_point_table_debug",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
-    "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size",
+    "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size", "pvlm_transavg_bata", "pvlm_bata_group_size",
     "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
@@ -1790,6 +1790,39 @@ def transavg_solve(ctx, first, second, R_21, t_21, scales, origin_idx, translati
     intact = bool(np.all(t[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0))
     return dict(translations=t[:F], scales=s[:P], weight=w[:P], initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
                 unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
+
+
+class BataParams(C.Structure):
+    _fields_ = [("delta", C.c_double), ("init_iteration", C.c_int), ("inner_iteration", C.c_int), ("outer_iteration", C.c_int), ("robust_threshold", C.c_double)]
+
+
+BATA_GUARD = 8     # sentinel records the wrapper keeps behind every output
+
+
+def bata_group_size():
+    """pvlm_bata_group_size (K44): the lanes that share one camera's gather."""
+    return int(load_library().pvlm_bata_group_size())
+
+
+def bata_solve(ctx, n_cameras, first, second, directions, scales0, delta=1e-6, init_iteration=10, inner_iteration=10, outer_iteration=10, robust_threshold=0.1,
+               check=True):
+    """pvlm_transavg_bata (K44): BATA translation averaging (a revised-LUD start, then the bilinear IRLS) on unit directions (pairs x 3) and positive start scales.
+    The cameras are F = max_id - min_id + 1, the ids shifted by min_id.  Returns a dict: centres and lud_centres (F x 3, camera 0 zero), scales (pairs), F, info (0;
+    k > 0: not positive definite; -1: not finite; -2: no pairs), untouched (the library wrote none of the outputs: they still hold -7), guard_intact (the BATA_GUARD
+    sentinel records behind each output were not written), rc.  An argument the library refuses raises PvlmError; with check=False the dict comes back with its rc."""
+    first = _i32(first); second = _i32(second); P = len(first); G = BATA_GUARD
+    d = _f64(np.asarray(directions, np.float64).reshape(P, 3)); s0 = _f64(np.asarray(scales0, np.float64).reshape(P))
+    F = int(max(first.max(), second.max()) - min(first.min(), second.min()) + 1) if P else 0
+    rows = max(int(n_cameras), F, 0)
+    cen = np.full((rows + G, 3), -7.0); lud = np.full((rows + G, 3), -7.0); s = np.full(P + G, -7.0); info = C.c_int(-7)
+    prm = BataParams(delta, init_iteration, inner_iteration, outer_iteration, robust_threshold)
+    rc = ctx.lib.pvlm_transavg_bata(ctx._h, C.c_int(n_cameras), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(d, C.c_double), _p(s0, C.c_double), C.byref(prm),
+                                    _p(cen, C.c_double), _p(lud, C.c_double), _p(s, C.c_double), C.byref(info))
+    if check:
+        ctx._check(rc, "pvlm_transavg_bata")
+    untouched = bool(np.all(cen == -7.0) and np.all(lud == -7.0) and np.all(s == -7.0))
+    intact = bool(np.all(cen[F:] == -7.0) and np.all(lud[F:] == -7.0) and np.all(s[P:] == -7.0))
+    return dict(centres=cen[:F], lud_centres=lud[:F], scales=s[:P], F=F, info=int(info.value), untouched=untouched, guard_intact=intact, rc=int(rc))
 
 
 class RotavgL1Summary(C.Structure):

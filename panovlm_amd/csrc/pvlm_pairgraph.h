@@ -1,4 +1,5 @@
-// The device half of the pair-graph layer (pvlm_pairgraph_core.h) under K40 (pvlm_rotavg.hip) and K42 (pvlm_transavg.hip); included after pvlm_internal.h.
+// The device half of the pair-graph layer (pvlm_pairgraph_core.h) under K40 (pvlm_rotavg.hip), K42 (pvlm_transavg.hip) and K44 (pvlm_bata.hip); included after
+// pvlm_internal.h.
 //   k_pg_tree       one node level of the fixed reduction tree (kChunk leaves per workgroup, halved in LDS), launched level by level until one number is left;
 //   camera_gather   the skeleton of every per-camera gather: kGroup lanes per camera walk its CSR row, an xor butterfly over the group adds the partial sums, lane 0
 //                   writes.  The stage gives the lane function and the epilogue;
@@ -104,7 +105,7 @@ struct DeviceGraph {
     pg::build_csr(F, P, first, second, &off, &ent);
     d_first = c.upload(first, (size_t)P); d_second = c.upload(second, (size_t)P);
     d_off = c.upload(off.data(), off.size()); d_ent = c.upload(ent.data(), ent.size());
-    d_R21 = c.upload(R21, 9 * (size_t)P);
+    d_R21 = R21 ? c.upload(R21, 9 * (size_t)P) : nullptr;        // a stage whose pairs carry no rotation (K44) passes none
     const long long most = P > F ? P : F, stride = (most + pg::kChunk - 1) / pg::kChunk;
     for (int k = 0; k < 2; ++k) d_part[k] = c.alloc<double>((size_t)max_cols * (size_t)stride);
   }

@@ -1,5 +1,6 @@
-// The pair-graph layer under K40 (rotation averaging) and K42 (translation averaging) — host and device.  Both stages hang residual blocks on the pairs of a camera
-// graph and solve for per-camera unknowns of three numbers; what they share is here and nothing in it knows what the unknowns are:
+// The pair-graph layer under K40 (rotation averaging), K42 (translation averaging) and K44 (BATA) — host and device.  The stages hang residual blocks on the pairs of a
+// camera graph and solve for per-camera unknowns of three numbers; what they share is here and nothing in it knows what the unknowns are (K44 takes the CSR, the gather,
+// the tree and the camera system, not the LM loop):
 //   the CSR of the cameras' incident pairs (entry = 2 * pair + side, pair-list order) and its gather: kGroup lanes per camera, lane l takes the entries l, l + kGroup,
 //     ..., an xor butterfly adds the partial sums.  One order per camera, whatever the degree, no floating-point atomics;
 //   the fixed reduction tree of every scalar (cost, model decrease, norms): leaves in chunks of kChunk, a halving tree inside a chunk, the chunk sums reduced the same

@@ -805,9 +805,12 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
                           std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options = EssentialOptions());
 
 // ---- K42: translation averaging (sfm/TranslationAveraging.cpp:31-204, :419-481; sfm/SfM.cpp:908-934, :1047-1344, :1385-1421) ----------------------------------
-// sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built; L1 (the LP), CHORDAL, BATA and LUD are not: EstimateGlobalTranslation returns false with upstream's "not supported".
+// sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built, and BATA (K44, below) behind TranslationOptions::enable_bata; L1 (the LP), CHORDAL and LUD are not:
+// EstimateGlobalTranslation returns false with upstream's "not supported".
 enum TranslationAveragingMethod { TRANSLATION_AVERAGING_SOFTL1 = 1, TRANSLATION_AVERAGING_L1 = 2, TRANSLATION_AVERAGING_CHORDAL = 3, TRANSLATION_AVERAGING_L2IRLS = 4,
                                   TRANSLATION_AVERAGING_BATA = 5, TRANSLATION_AVERAGING_LUD = 6 };
+// sfm/BATA.h's BATAConfig: what TranslationAveragingBATA hands BATA (upstream: always the defaults, :516)
+struct BATAConfig { double delta = 1e-6; int init_iteration = 10, inner_iteration = 10, outer_iteration = 10; double robust_threshold = 0.1; };
 // what base/Config.h holds for the stage, and what upstream draws from srand(time): the start translations are uniform [-1, 1] from splitmix64 on `seed` (K34's
 // answer to std::random_device).  host = true runs every solve through the host compile of csrc/pvlm_transavg_core.h (pvlm_host_transavg.hpp; no device).
 // message: where the text of upstream's LOG(ERROR) goes when the call returns false.
@@ -819,6 +822,10 @@ struct TranslationOptions {
   unsigned long long seed = 0;
   bool host = false;
   std::string* message = nullptr;
+  // Method 5 (BATA, K44) runs only when this is set.  The flag exists because tests/test_transavg_cpu.py::test_estimate_methods_not_built pins method 5 under default
+  // options to upstream's "not supported" text and existing tests do not change; a later change that may edit that test removes it.
+  bool enable_bata = false;
+  BATAConfig bata;
 };
 // TranslationAveragingDLT (:31-84) through pvlm_transavg_dlt: the normal equations with camera 0 fixed at zero.  Upstream's SparseQR returns SOME basic solution of a
 // system that is rank-deficient by the gauge t_i = R_i c; every caller runs SetToOrigin afterwards, which cancels the difference.  false: a pair names a camera
@@ -835,6 +842,16 @@ bool TranslationAveragingSoftL1(const std::vector<RelativePair>& image_pairs, st
 // scale went negative are dropped from image_pairs.  iterations_run: the solves done.
 bool TranslationAveragingL2IRLS(std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const int num_iteration,
                                 const float upper_scale_ratio, const float lower_scale_ratio, const bool host = false, int* iterations_run = nullptr);
+// K44 — TranslationAveragingBATA (:483-525) through pvlm_transavg_bata (see pvlm.h for the definition and its divergences), as written: per pair the observation
+// R_wc(frames[new_to_old[first]]) t_21, its norm as the start scale — none when 0.99 < norm < 1.01 (sfm/BATA.cpp:191-193) — and its direction; the centres come back
+// as -R_cw centre per camera (:519-523).  Upstream draws the start scale of a pair without one as |Eigen's Random()| after srand(time) (sfm/BATA.cpp:64); here it is
+// |uniform[-1, 1]| from splitmix64 on seed ^ 0xba7a5ca1e5ull — a stream of its own, distinct from the start translations' (which run on the seed itself) — with an
+// exact zero drawn again.  config stands for upstream's default-constructed BATAConfig.  global_translations is resized to max_id - min_id + 1 as upstream's
+// assignment does.  start_scales: when given, the scales handed to the solver (the tests look at the draw).  false: no pairs, a camera without an entry in
+// new_to_old, a relative translation of zero length or not finite, or info != 0 (not positive definite / not finite).
+bool TranslationAveragingBATA(const std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                              const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const BATAConfig& config = BATAConfig(), const unsigned long long seed = 0,
+                              const bool host = false, std::vector<double>* start_scales = nullptr);
 // SfM::ReIndex (sfm/SfM.cpp:908-934): the frame ids of a pair list onto 0 .. n - 1 in ascending order
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward);
 // SfM::SetToOrigin (:1385-1421) without the structure: every valid pose into the frame of frames[frame_idx] (the first valid frame when that one has no pose).

@@ -1,6 +1,6 @@
 // The pair-graph layer of csrc/pvlm_pairgraph_core.h on the host: what csrc/pvlm_pairgraph.h does on the device, done by loops — the gather over kGroup lanes and
 // their butterfly, the camera step — with a dense host Cholesky of the camera system in place of the library's solver.  Under the host twins of K40
-// (pvlm_host_rotavg.hpp) and K42 (pvlm_host_transavg.hpp); no device, no dependency on the rest of the host mirror.
+// (pvlm_host_rotavg.hpp), K42 (pvlm_host_transavg.hpp) and K44 (pvlm_host_bata.hpp); no device, no dependency on the rest of the host mirror.
 #pragma once
 #include <cmath>
 #include <cstring>

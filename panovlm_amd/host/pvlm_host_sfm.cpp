@@ -20,6 +20,7 @@
 #include "../csrc/pvlm_depthfill_core.h"
 #include "pvlm_host_transavg.hpp"
 #include "pvlm_host_rotavg.hpp"
+#include "pvlm_host_bata.hpp"
 
 namespace pvlm {
 
@@ -842,7 +843,8 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
 }
 
 // ================================================================================================
-// K42: translation averaging — TranslationAveragingDLT / L2 / SoftL1 / L2IRLS (sfm/TranslationAveraging.cpp), ReIndex, SetToOrigin, EstimateGlobalTranslation
+// K42: translation averaging — TranslationAveragingDLT / L2 / SoftL1 / L2IRLS (sfm/TranslationAveraging.cpp), ReIndex, SetToOrigin, EstimateGlobalTranslation;
+// K44: TranslationAveragingBATA (sfm/TranslationAveraging.cpp:483-525 around sfm/BATA.cpp)
 // ================================================================================================
 namespace {
 // the arrays of pvlm_transavg_* and pvlm_rotavg_* from a pair list: the pair indices and R_21 always, t_21 for the former, the rotations for the latter
@@ -956,6 +958,63 @@ bool TranslationAveragingL2IRLS(std::vector<RelativePair>& image_pairs, std::vec
   return true;
 }
 
+bool TranslationAveragingBATA(const std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                              const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const BATAConfig& config, const unsigned long long seed, const bool host,
+                              std::vector<double>* start_scales) {
+  (void)origin_idx;                                                      // upstream only asserts that its translation is zero (:489)
+  const int P = (int)image_pairs.size();
+  if (P == 0) return false;
+  std::vector<int> first, second; std::vector<double> dir, given, draw((size_t)P), scales((size_t)P);
+  size_t max_id = 0, min_id = (size_t)-1;
+  for (const RelativePair& pair : image_pairs) {
+    const auto it = new_to_old.find(pair.image_pair.first);
+    if (it == new_to_old.end() || it->second >= frames.size() || pair.image_pair.first > 0x3fffffff || pair.image_pair.second > 0x3fffffff) return false;
+    const Matrix3d& R = frames[it->second].R_wc; const Vector3d& t = pair.t_21;
+    const double v[3] = {R[0] * t[0] + R[1] * t[1] + R[2] * t[2], R[3] * t[0] + R[4] * t[1] + R[5] * t[2], R[6] * t[0] + R[7] * t[1] + R[8] * t[2]};      // :496
+    double scale = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return false;
+    for (int k = 0; k < 3; ++k) dir.push_back(v[k] / scale);              // sfm/BATA.cpp:195
+    if (scale > 0.99 && scale < 1.01) scale = -1;                        // sfm/BATA.cpp:192-193
+    given.push_back(scale);
+    first.push_back((int)pair.image_pair.first); second.push_back((int)pair.image_pair.second);
+    max_id = std::max(max_id, std::max(pair.image_pair.first, pair.image_pair.second)); min_id = std::min(min_id, std::min(pair.image_pair.first, pair.image_pair.second));
+  }
+  {
+    uint64_t st = seed ^ 0xba7a5ca1e5ull;
+    auto next = [&st]() { uint64_t z = (st += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); };
+    for (int p = 0; p < P; ++p) {
+      if (given[(size_t)p] >= 0) { draw[(size_t)p] = 1.0; continue; }    // not read
+      double u = 0.0;
+      while (u == 0.0) u = std::fabs((double)(next() >> 11) * (2.0 / 9007199254740992.0) - 1.0);
+      draw[(size_t)p] = u;
+    }
+  }
+  pvlm_bata::start_scales(P, given.data(), draw.data(), scales.data());
+  if (start_scales) *start_scales = scales;
+  const int n_cameras = (int)max_id + 1, F = (int)(max_id - min_id) + 1;
+  std::vector<double> out(3 * (size_t)n_cameras + 3, 0.0);
+  int info = 0;
+  if (host) {
+    pvlm_bata::Params prm;
+    prm.delta = config.delta; prm.init_iteration = config.init_iteration; prm.inner_iteration = config.inner_iteration; prm.outer_iteration = config.outer_iteration;
+    prm.robust_threshold = config.robust_threshold;
+    if (bata_detail::SolveHost(n_cameras, P, first.data(), second.data(), dir.data(), scales.data(), &prm, out.data(), nullptr, nullptr, &info)) return false;
+  } else {
+    Engine& e = Engine::Default();
+    const pvlm_bata_params prm{config.delta, config.init_iteration, config.inner_iteration, config.outer_iteration, config.robust_threshold};
+    e.Check(pvlm_transavg_bata(e.ctx(), n_cameras, P, first.data(), second.data(), dir.data(), scales.data(), &prm, out.data(), nullptr, nullptr, &info), "pvlm_transavg_bata");
+  }
+  if (info != 0) return false;
+  for (int i = 0; i < F; ++i) if (new_to_old.find((size_t)i) == new_to_old.end() || new_to_old.find((size_t)i)->second >= frames.size()) return false;      // :521 reads past the map
+  global_translations.assign((size_t)F, Vector3d{0, 0, 0});
+  for (int i = 0; i < F; ++i) {
+    const Matrix3d& R = frames[new_to_old.find((size_t)i)->second].R_wc;     // R_cw = R_wc^T; t_cw = -R_cw centre (:519-523)
+    const double* c = &out[3 * (size_t)i];
+    global_translations[(size_t)i] = {-(R[0] * c[0] + R[3] * c[1] + R[6] * c[2]), -(R[1] * c[0] + R[4] * c[1] + R[7] * c[2]), -(R[2] * c[0] + R[5] * c[1] + R[8] * c[2])};
+  }
+  return true;
+}
+
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward) {
   forward.clear(); backward.clear();
   std::set<size_t> old_id;
@@ -1055,8 +1114,10 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
     success = TranslationAveragingSoftL1(image_pairs, global_translations, origin_idx, 0.01, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
   else if (method == TRANSLATION_AVERAGING_L2IRLS)
     success = TranslationAveragingL2IRLS(image_pairs, global_translations, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
-  else return Say(o, "Translaton average method not supported");       // L1 (the LP), chordal, BATA and LUD are not built; the text is upstream's (:1308)
-  if (!success) return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : "Translation average L2 IRLS failed");
+  else if (method == TRANSLATION_AVERAGING_BATA && o.enable_bata)      // :1285-1294; behind the flag: see TranslationOptions
+    success = TranslationAveragingBATA(image_pairs, frames, global_translations, new_to_old_global, origin_idx, o.bata, o.seed, o.host);
+  else return Say(o, "Translaton average method not supported");       // L1 (the LP), chordal and LUD are not built, BATA only behind its flag; the text is upstream's (:1308)
+  if (!success) return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : method == TRANSLATION_AVERAGING_BATA ? "Translation average BATA failed" : "Translation average L2 IRLS failed");
   for (RelativePair& pair : image_pairs) { pair.image_pair.first = new_to_old_global[pair.image_pair.first]; pair.image_pair.second = new_to_old_global[pair.image_pair.second]; }
   std::set<size_t> frame_with_translation;
   for (size_t i = 0; i < global_translations.size(); ++i) {
