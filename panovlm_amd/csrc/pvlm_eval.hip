@@ -12,6 +12,14 @@
 #include <cmath>
 #include <limits>
 
+// PVLM_EXP_PAIR_UB: timing experiments only (wrong results), the gate of profiles/eval_row_pairs_ab.txt.  1: the wave-uniform decisions of a row taken as constants
+// (short tier, no Huber outlier), the rows of a lane still one behind the other.  2: the same, and the two rows of a lane in ONE basic block (the loop over the rows
+// without its break; the pad row behind an odd last row is evaluated like any other).  3: the two rows as ONE stream, every operation of row 0 next to the same
+// operation of row 1 (angle_norm_wrench_short over dpair, pvlm_functors.h) — what interleaving two rows' dependent chains can give at most.
+#ifdef PVLM_EXP_PAIR_UB
+#define PVLM_EXP_CONST_PATHS 1
+#endif
+
 #include "pvlm_functors.h"
 #include "pvlm_internal.h"
 
@@ -115,6 +123,9 @@ __device__ __forceinline__ void stream_store1(double* p, double v) {
 }
 
 
+#ifndef PVLM_PT_LOAD_ORDER
+#define PVLM_PT_LOAD_ORDER 1   // 1: the point-table loads of a trip issue column by column, a lane's two rows back to back (0: wherever the scheduler puts them) — see k_eval_fused
+#endif
 #ifndef PVLM_PREFETCH
 #define PVLM_PREFETCH -1  // -1 = per-functor default, 0 / 1 force
 #endif
@@ -378,7 +389,7 @@ __device__ __forceinline__ void accumulate_row(const double* rec, const double* 
   eval_wrench<KIND, NORM>(rec, T, weight, w);
   const double s = w.r * w.r;
   const double vv[6] = {w.c[0], w.c[1], w.c[2], w.g[0], w.g[1], w.g[2]};
-  if (LOSS != PVLM_LOSS_HUBER) { accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc); return; }
+  if (LOSS != PVLM_LOSS_HUBER || PVLM_EXP_CONST_PATHS) { accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc); return; }
   // ceres::HuberLoss(a): s > a^2 -> rho = 2 a sqrt(s) - a^2, rho' = max(DBL_MIN, a / sqrt(s))
   const bool out = s > a2;
   auto general = [&]() {
@@ -507,8 +518,18 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
 #else
       if (PT) {
         const unsigned q0 = 8u * (qs & 0xffffu), q1 = 8u * (qs >> 16);
+        // A lane's two rows are neighbouring queries: the two loads of a column mostly want the same cache line.  Issued back to back the second finds the line
+        // (or its miss in flight); left to the scheduler they are grouped by address register — row 1's three columns, the plane entries, the word, then row 0's
+        // three — and with 16 waves of a CU gathering between them the line has to come from the L2 twice (a reading of the timings; no counter run).  The barrier
+        // keeps the source order: x0 x1 y0 y1 z0 z1, then the plane entries, and row 0's arithmetic starts while row 1's plane entries are still on their way
+        // (profiles/eval_row_pairs_ab.txt).
 #pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
+        for (int c = 0; c < NS; ++c) {
+          v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
+#if PVLM_PT_LOAD_ORDER && defined(__HIP_DEVICE_COMPILE__)
+          __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
       } else {
 #pragma unroll
         for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
@@ -525,9 +546,30 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
       }
       if (!kPrefetch) load_words(o_next >> 3);
     }
+#if defined(PVLM_EXP_PAIR_UB) && PVLM_EXP_PAIR_UB >= 3
+    if constexpr (KIND == PVLM_POINT2PLANE_ANGLE && NORM) {
+      dpair rec2[7], r2, c2[3], g2[3];
+#pragma unroll
+      for (int c = 0; c < NS; ++c) rec2[c] = {v[c].x, v[c].y};
+      if (PR) { rec2[3] = {pl[0][0].x, pl[1][0].x}; rec2[4] = {pl[0][0].y, pl[1][0].y}; rec2[5] = {pl[0][1].x, pl[1][1].x}; rec2[6] = {pl[0][1].y, pl[1][1].y}; }
+      angle_norm_wrench_short(rec2, T, r2, c2, g2);
+      const dpair vv[6] = {c2[0], c2[1], c2[2], g2[0], g2[1], g2[2]};
+      int q = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++q) acc[q] = fma(vv[a].b, vv[b].b, fma(vv[a].a, vv[b].a, acc[q]));
+        acc[21 + a] = fma(vv[a].b, r2.b, fma(vv[a].a, r2.a, acc[21 + a]));
+      }
+      acc[27] = fma(0.5, r2.b * r2.b, fma(0.5, r2.a * r2.a, acc[27]));
+      continue;
+    }
+#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
+#if !defined(PVLM_EXP_PAIR_UB) || PVLM_EXP_PAIR_UB < 2
       if (o + 8u * h >= span8) break;
+#endif
       double rec[NCOLS];
 #pragma unroll
       for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
@@ -778,6 +820,12 @@ static void launch_wrench(pvlm_ctx* ctx, const pvlm_resset* rs, double* d_w, int
                        rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, d_w, blk0, row0);
 }
 
+// PVLM_FUSED_LDS_PAD: bytes of dynamic LDS that a k_eval_fused launch takes and never touches — fewer workgroups per CU on the SAME code object (the occupancy
+// curve of profiles/eval_row_pairs_ab.txt: 48 KB and 56 KB give 3 and 2 workgroups per CU).  Read once; anything outside (0, 63 KB] is ignored.
+static unsigned fused_lds_pad() {
+  static const unsigned pad = [] { const char* e = getenv("PVLM_FUSED_LDS_PAD"); const long b = e ? atol(e) : 0; return (b > 0 && b <= 64512) ? (unsigned)b : 0u; }();
+  return pad;
+}
 template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
 static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
   const pvlm_plane_args pr = {rs->d_plane_idx, rs->d_pair_idx0, rs->d_chunk_plane0, rs->d_plane_tab, rs->d_pair_ptab, rs->d_order};
@@ -786,10 +834,10 @@ static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
                        rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a,
                        rs->d_partials, pr);
   else if (PR && rs->point_table)  // the point from the neighbour's table, the grid in the set's dispatch order (pvlm_i_plane_runs_build chose both)
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>), dim3(rs->n_positions), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
+    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>), dim3(rs->n_positions), dim3(256), fused_lds_pad(), ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
                        rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
   else
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>), dim3(rs->n_blocks), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
+    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>), dim3(rs->n_blocks), dim3(256), fused_lds_pad(), ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
                        rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
 }
 template <int KIND, bool NORM, int NCOLS>

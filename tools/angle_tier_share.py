@@ -2,7 +2,10 @@
 """Share of the evaluation slots of a bench-like point-to-plane set (64 scans x 8 neighbours, 4096 columns) whose 64 lanes all lie below a bound on the
 angle: a slot is what a wave of k_eval_fused evaluates together, the rows of equal parity of 128 consecutive rows of a segment.  The bounds are those of
 atan2_pos (pi/8), of two shorter polynomials (tan r <= 1/16, 1/32) and the Huber threshold of the bench (2 degrees: a slot of inliers only).
-python tools/angle_tier_share.py   (one JSON line; profiles/eval_angle_form_ab.txt section 6)"""
+"pair_share": the same per PAIR of slots, the even and the odd rows of one group of 128 rows — what one wave does in one trip of the row loop; which
+combination of tiers (short: both below 1/32 ... octant: a row above pi/8) and of Huber paths the two slots of a trip take, and the trips whose last row is a
+pad row (an odd segment end).
+python tools/angle_tier_share.py   (one JSON line; profiles/eval_angle_form_ab.txt section 6, profiles/eval_row_pairs_ab.txt)"""
 import json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -22,6 +25,8 @@ off = rs.download()[0]
 r = np.abs(np.asarray(r))
 bounds = {"pi/8": np.pi / 8, "1/16": np.arctan(1 / 16), "1/32": np.arctan(1 / 32), "huber 2 deg (all inliers)": 2 * np.pi / 180}
 slots = 0; ok = {k: 0 for k in bounds}; rows_ok = {k: 0 for k in bounds}
+t32, t8, hub = np.arctan(1 / 32), np.pi / 8, 2 * np.pi / 180
+trips = 0; pair = {k: 0 for k in ("short/short", "full/full", "short/full", "full/short", "an octant slot", "odd tail")}; pair_huber = {"inliers/inliers": 0, "an outlier slot": 0}
 for p in range(len(off) - 1):
     seg = r[off[p]:off[p + 1]]
     for h in (0, 1):
@@ -33,8 +38,23 @@ for p in range(len(off) - 1):
         slots += n
         for k, b in bounds.items():
             ok[k] += int((mx <= b).sum())
+    # slot pairs: the groups of 128 rows of the segment; a tail group with an odd number of rows has a pad row in its odd slot
+    n = (len(seg) + 127) // 128
+    if n:
+        pad = np.zeros(n * 128); pad[:len(seg)] = seg
+        mx = pad.reshape(n, 64, 2).max(1)              # [group, parity]
+        tier = np.where(mx <= t32, 0, np.where(mx <= t8, 1, 2))
+        odd = np.zeros(n, bool); odd[-1] = len(seg) % 2 == 1
+        trips += n
+        pair["odd tail"] += int(odd.sum())
+        pair["an octant slot"] += int(((tier.max(1) == 2) & ~odd).sum())
+        for name, a, b in (("short/short", 0, 0), ("full/full", 1, 1), ("short/full", 0, 1), ("full/short", 1, 0)):
+            pair[name] += int(((tier[:, 0] == a) & (tier[:, 1] == b) & ~odd).sum())
+        pair_huber["inliers/inliers"] += int((mx.max(1) <= hub).sum())
+        pair_huber["an outlier slot"] += int((mx.max(1) > hub).sum())
 for k, b in bounds.items():
     rows_ok[k] = float((r <= b).mean())
-out = {"rows": int(len(r)), "slots": slots, "live_rows": float((r > 0).mean()), "slot_share": {k: ok[k] / slots for k in bounds}, "row_share": rows_ok}
+out = {"rows": int(len(r)), "slots": slots, "live_rows": float((r > 0).mean()), "slot_share": {k: ok[k] / slots for k in bounds}, "row_share": rows_ok,
+       "trips": trips, "pair_share": {k: v / trips for k, v in pair.items()}, "pair_huber_share": {k: v / trips for k, v in pair_huber.items()}}
 print(json.dumps(out))
 rs.close(); ctx.close()
