@@ -157,13 +157,9 @@ struct TopK {
   // candidate (d2, idx), d2 a non-negative float (finite or +inf; the clouds are finite)
   PVLM_HD void push(float d2, int idx) {
     const topk_key c = key_make(f2u(d2) + PVLM_KEY_BIAS, (unsigned)idx);
-#ifdef PVLM_K2_NONET   // timing experiment only (wrong results): what the insertion network costs
-    key[0] = key_min(key[0], c);
-#else
 #pragma unroll
     for (int k = K - 1; k > 0; --k) key[k] = key_min(key[k], key_max(key[k - 1], c));
     key[0] = key_min(key[0], c);
-#endif
   }
   PVLM_HD bool full() const { return key_hi(key[K - 1]) < empty_hi; }
   PVLM_HD bool would_enter(float d2, int idx) const { return key_make(f2u(d2) + PVLM_KEY_BIAS, (unsigned)idx) < key[K - 1]; }

@@ -12,14 +12,6 @@
 #include <cmath>
 #include <limits>
 
-// PVLM_EXP_PAIR_UB: timing experiments only (wrong results), the gate of profiles/eval_row_pairs_ab.txt.  1: the wave-uniform decisions of a row taken as constants
-// (short tier, no Huber outlier), the rows of a lane still one behind the other.  2: the same, and the two rows of a lane in ONE basic block (the loop over the rows
-// without its break; the pad row behind an odd last row is evaluated like any other).  3: the two rows as ONE stream, every operation of row 0 next to the same
-// operation of row 1 (angle_norm_wrench_short over dpair, pvlm_functors.h) — what interleaving two rows' dependent chains can give at most.
-#ifdef PVLM_EXP_PAIR_UB
-#define PVLM_EXP_CONST_PATHS 1
-#endif
-
 #include "pvlm_functors.h"
 #include "pvlm_internal.h"
 
@@ -38,10 +30,11 @@ using namespace pvlm_dev;
 #endif
 typedef double pvlm_dbl2 __attribute__((ext_vector_type(2)));
 #if PVLM_GLOBAL_LOADS
-typedef const __attribute__((address_space(1))) pvlm_dbl2* pvlm_col_ptr;
+template <class T> using pvlm_gptr = const __attribute__((address_space(1))) T*;
 #else
-typedef const pvlm_dbl2* pvlm_col_ptr;
+template <class T> using pvlm_gptr = const T*;
 #endif
+typedef pvlm_gptr<pvlm_dbl2> pvlm_col_ptr;
 #ifndef PVLM_NT_LOADS_MATERIALISE   // the same hint in the kernels that also WRITE rows (k_eval_materialise, k_eval_wrench)
 #define PVLM_NT_LOADS_MATERIALISE 0
 #endif
@@ -70,12 +63,7 @@ struct pvlm_plane_args {
 };
 template <bool NT>
 __device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`: low and high half
-#if PVLM_GLOBAL_LOADS
-  typedef const __attribute__((address_space(1))) unsigned* ptr;
-#else
-  typedef const unsigned* ptr;
-#endif
-  ptr q = (ptr)(reinterpret_cast<const char*>(base) + 2u * row);
+  const auto q = (pvlm_gptr<unsigned>)(reinterpret_cast<const char*>(base) + 2u * row);
   return NT ? __builtin_nontemporal_load(q) : *q;
 }
 // The point-table form: the run numbers and the query numbers of the lane's two rows in ONE 8-byte load (x: runs, y: queries; low half = the even row), streamed
@@ -84,22 +72,12 @@ __device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsig
 template <bool NT>
 __device__ __forceinline__ uint2 stream_load_words(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`
   typedef unsigned pvlm_u2 __attribute__((ext_vector_type(2)));
-#if PVLM_GLOBAL_LOADS
-  typedef const __attribute__((address_space(1))) pvlm_u2* ptr;
-#else
-  typedef const pvlm_u2* ptr;
-#endif
-  ptr q = (ptr)(reinterpret_cast<const char*>(base) + 4u * row);
+  const auto q = (pvlm_gptr<pvlm_u2>)(reinterpret_cast<const char*>(base) + 4u * row);
   const pvlm_u2 v = NT ? __builtin_nontemporal_load(q) : *q;
   return make_uint2(v.x, v.y);
 }
 __device__ __forceinline__ double table_load(const double* base, unsigned bytes) {
-#if PVLM_GLOBAL_LOADS
-  typedef const __attribute__((address_space(1))) double* ptr;
-#else
-  typedef const double* ptr;
-#endif
-  return *(ptr)(reinterpret_cast<const char*>(base) + bytes);
+  return *(pvlm_gptr<double>)(reinterpret_cast<const char*>(base) + bytes);
 }
 // ... and the stores of the materialising kernels (r, the 1 x 12 rows, the wrench rows).  Non-temporal STORES were measured and lose:
 // k_eval_materialise 4.80 TB/s against 5.04 TB/s with ordinary stores (profiles/r2_ab_eval_loads.txt) — off.
@@ -211,6 +189,29 @@ __global__ void k_pair_table(int P, const int* __restrict__ ref, const int* __re
     for (int j = 0; j < 3; ++j) o[24 + i * 3 + j] = -(R[i * 3] * b[9 + j] + R[i * 3 + 1] * b[9 + 3 + j] + R[i * 3 + 2] * b[9 + 6 + j]);
 }
 
+// The segment of one work-list entry: rows [lo, hi) of pair p — what every evaluation kernel below reads first.  Each kernel chooses `entry` its own way (a block of
+// the launch, a slot of the dispatch order, a wave's unit) and loads as much of the pair table as it needs.  The order of the statements counts: the scalar prologue is scheduled from it (tools/isa_same.py).
+struct pvlm_segment {
+  int p;                // the pair
+  const double* cols;   // first row of the pair's segment, column 0
+  int64_t n_dev;        // column stride of the pair's block
+  int64_t o0;           // first compact (host-order) row of the pair, relative to row0
+  int64_t lo, hi;       // the entry's chunk, in rows of the pair
+};
+__device__ __forceinline__ pvlm_segment load_segment(int entry, const double* const* __restrict__ pair_cols, const int64_t* __restrict__ pair_stride,
+                                                     const int64_t* __restrict__ out_start, const int* __restrict__ blk_pair,
+                                                     const int* __restrict__ blk_chunk, int chunk_rows, int64_t row0 = 0) {
+  pvlm_segment s;
+  s.p = blk_pair[entry];
+  s.cols = pair_cols[s.p];
+  s.n_dev = pair_stride[s.p];
+  s.o0 = out_start[s.p] - row0;
+  const int64_t len = out_start[s.p + 1] - out_start[s.p];
+  s.lo = (int64_t)blk_chunk[entry] * chunk_rows;
+  s.hi = min(len, s.lo + (int64_t)chunk_rows);
+  return s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // materialise: r[n], J[n x 12] in compact (host) order.
 // ---------------------------------------------------------------------------------------------
@@ -223,14 +224,7 @@ __global__ __launch_bounds__(256) void k_eval_materialise(const double* const* _
                                                           double* __restrict__ r_out, double* __restrict__ J_out, int blk0, int64_t row0) {
   // blk0 / row0: the launch covers work-list blocks [blk0, blk0 + gridDim.x) whose first compact row is row0; outputs are
   // indexed relative to row0 (a bounded staging buffer filled slice by slice, pvlm_eval_host_async)
-  const int bi = blockIdx.x + blk0;
-  const int p = blk_pair[bi];
-  const double* __restrict__ cols = pair_cols[p];   // first row of the pair's segment, column 0
-  const int64_t n_dev = pair_stride[p];             // column stride of the pair's block
-  const int64_t o0 = out_start[p] - row0;
-  const int64_t len = out_start[p + 1] - out_start[p];
-  const int64_t lo = (int64_t)blk_chunk[bi] * chunk_rows;
-  const int64_t hi = min(len, lo + (int64_t)chunk_rows);
+  const auto [p, cols, n_dev, o0, lo, hi] = load_segment(blockIdx.x + blk0, pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows, row0);
   double T[PVLM_PAIR_TAB];
 #pragma unroll
   for (int k = 0; k < PVLM_PAIR_TAB; ++k) T[k] = pair_tab[(size_t)p * PVLM_PAIR_TAB + k];
@@ -303,14 +297,7 @@ __global__ __launch_bounds__(256) void k_eval_wrench(const double* const* __rest
                                                      const int64_t* __restrict__ out_start, const int* __restrict__ blk_pair,
                                                      const int* __restrict__ blk_chunk, int chunk_rows, const double* __restrict__ pair_tab,
                                                      double weight, double* __restrict__ w_out, int blk0, int64_t row0) {
-  const int bi = blockIdx.x + blk0;
-  const int p = blk_pair[bi];
-  const double* __restrict__ cols = pair_cols[p];
-  const int64_t n_dev = pair_stride[p];
-  const int64_t o0 = out_start[p] - row0;
-  const int64_t len = out_start[p + 1] - out_start[p];
-  const int64_t lo = (int64_t)blk_chunk[bi] * chunk_rows;
-  const int64_t hi = min(len, lo + (int64_t)chunk_rows);
+  const auto [p, cols, n_dev, o0, lo, hi] = load_segment(blockIdx.x + blk0, pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows, row0);
   double T[15];
 #pragma unroll
   for (int k = 0; k < 15; ++k) T[k] = pair_tab[(size_t)p * PVLM_PAIR_TAB + k];
@@ -389,7 +376,7 @@ __device__ __forceinline__ void accumulate_row(const double* rec, const double* 
   eval_wrench<KIND, NORM>(rec, T, weight, w);
   const double s = w.r * w.r;
   const double vv[6] = {w.c[0], w.c[1], w.c[2], w.g[0], w.g[1], w.g[2]};
-  if (LOSS != PVLM_LOSS_HUBER || PVLM_EXP_CONST_PATHS) { accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc); return; }
+  if (LOSS != PVLM_LOSS_HUBER) { accumulate_outer<false>(vv, w.r, 1.0, 0.5 * s, acc); return; }
   // ceres::HuberLoss(a): s > a^2 -> rho = 2 a sqrt(s) - a^2, rho' = max(DBL_MIN, a / sqrt(s))
   const bool out = s > a2;
   auto general = [&]() {
@@ -451,12 +438,7 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   const int slot = (PT && pr.order) ? pr.order[blockIdx.x] : (int)blockIdx.x;
   if (PT && slot < 0) return;     // padding position
   constexpr int NS = PR ? 3 : NCOLS;                // columns streamed row by row (PR: the point; the plane comes from the run table)
-  const int p = blk_pair[slot];
-  const double* __restrict__ cols = pair_cols[p];   // first row of the pair's segment, column 0
-  const int64_t n_dev = pair_stride[p];             // column stride of the pair's block
-  const int64_t len = out_start[p + 1] - out_start[p];
-  const int64_t lo = (int64_t)blk_chunk[slot] * chunk_rows;
-  const int64_t hi = min(len, lo + (int64_t)chunk_rows);
+  const auto [p, cols, n_dev, o0, lo, hi] = load_segment(slot, pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows);
   double T[15];
 #pragma unroll
   for (int k = 0; k < 15; ++k) T[k] = pair_tab[(size_t)p * PVLM_PAIR_TAB + k];
@@ -511,30 +493,23 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
 #pragma unroll
         for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o + 4096));
       }
-    } else {
-#ifdef PVLM_EXP_SKIP   // timing experiment only (wrong results): how does the rate respond to fewer bytes per evaluation?
+    } else if (PT) {
+      const unsigned q0 = 8u * (qs & 0xffffu), q1 = 8u * (qs >> 16);
+      // A lane's two rows are neighbouring queries: the two loads of a column mostly want the same cache line.  Issued back to back the second finds the line
+      // (or its miss in flight); left to the scheduler they are grouped by address register — row 1's three columns, the plane entries, the word, then row 0's
+      // three — and with 16 waves of a CU gathering between them the line has to come from the L2 twice (a reading of the timings; no counter run).  The barrier
+      // keeps the source order: x0 x1 y0 y1 z0 z1, then the plane entries, and row 0's arithmetic starts while row 1's plane entries are still on their way
+      // (profiles/eval_row_pairs_ab.txt).
 #pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = *reinterpret_cast<const double2*>(colb[c < NS - PVLM_EXP_SKIP ? c : 0] + (o >> 3));
-#else
-      if (PT) {
-        const unsigned q0 = 8u * (qs & 0xffffu), q1 = 8u * (qs >> 16);
-        // A lane's two rows are neighbouring queries: the two loads of a column mostly want the same cache line.  Issued back to back the second finds the line
-        // (or its miss in flight); left to the scheduler they are grouped by address register — row 1's three columns, the plane entries, the word, then row 0's
-        // three — and with 16 waves of a CU gathering between them the line has to come from the L2 twice (a reading of the timings; no counter run).  The barrier
-        // keeps the source order: x0 x1 y0 y1 z0 z1, then the plane entries, and row 0's arithmetic starts while row 1's plane entries are still on their way
-        // (profiles/eval_row_pairs_ab.txt).
-#pragma unroll
-        for (int c = 0; c < NS; ++c) {
-          v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
+      for (int c = 0; c < NS; ++c) {
+        v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
 #if PVLM_PT_LOAD_ORDER && defined(__HIP_DEVICE_COMPILE__)
-          __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #endif
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
       }
-#endif
+    } else {
+#pragma unroll
+      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
     }
     double2 pl[2][2];              // PR: {a, b}, {c, d} of the lane's two rows (a pad row behind an odd last row names entry 0)
     if (PR) {
@@ -546,30 +521,9 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
       }
       if (!kPrefetch) load_words(o_next >> 3);
     }
-#if defined(PVLM_EXP_PAIR_UB) && PVLM_EXP_PAIR_UB >= 3
-    if constexpr (KIND == PVLM_POINT2PLANE_ANGLE && NORM) {
-      dpair rec2[7], r2, c2[3], g2[3];
-#pragma unroll
-      for (int c = 0; c < NS; ++c) rec2[c] = {v[c].x, v[c].y};
-      if (PR) { rec2[3] = {pl[0][0].x, pl[1][0].x}; rec2[4] = {pl[0][0].y, pl[1][0].y}; rec2[5] = {pl[0][1].x, pl[1][1].x}; rec2[6] = {pl[0][1].y, pl[1][1].y}; }
-      angle_norm_wrench_short(rec2, T, r2, c2, g2);
-      const dpair vv[6] = {c2[0], c2[1], c2[2], g2[0], g2[1], g2[2]};
-      int q = 0;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-#pragma unroll
-        for (int b = a; b < 6; ++b, ++q) acc[q] = fma(vv[a].b, vv[b].b, fma(vv[a].a, vv[b].a, acc[q]));
-        acc[21 + a] = fma(vv[a].b, r2.b, fma(vv[a].a, r2.a, acc[21 + a]));
-      }
-      acc[27] = fma(0.5, r2.b * r2.b, fma(0.5, r2.a * r2.a, acc[27]));
-      continue;
-    }
-#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-#if !defined(PVLM_EXP_PAIR_UB) || PVLM_EXP_PAIR_UB < 2
       if (o + 8u * h >= span8) break;
-#endif
       double rec[NCOLS];
 #pragma unroll
       for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
@@ -607,12 +561,7 @@ __global__ __launch_bounds__(256, PVLM_FUSED_WAVES_WAVEFORM) void k_eval_fused_w
   // into scalar registers (30 VGPRs less) instead of 64 identical vector loads
   const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
   if (unit >= n_units) return;
-  const int p = blk_pair[unit];
-  const double* __restrict__ cols = pair_cols[p];
-  const int64_t n_dev = pair_stride[p];
-  const int64_t len = out_start[p + 1] - out_start[p];
-  const int64_t lo = (int64_t)blk_chunk[unit] * chunk_rows;
-  const int64_t hi = min(len, lo + (int64_t)chunk_rows);
+  const auto [p, cols, n_dev, o0, lo, hi] = load_segment(unit, pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows);
   double T[15];
 #pragma unroll
   for (int k = 0; k < 15; ++k) T[k] = pair_tab[(size_t)p * PVLM_PAIR_TAB + k];
@@ -804,41 +753,29 @@ static pvlm_status ensure_pair_table(pvlm_ctx* ctx, const pvlm_resset* crs) {
   return PVLM_OK;
 }
 
+// `kernel` over `grid` workgroups of 256 threads on the context stream: the segment arguments every evaluation kernel starts with (load_segment), then `rest`
+template <class K, class... A>
+static void launch_eval(K kernel, unsigned grid, pvlm_ctx* ctx, const pvlm_resset* rs, A... rest) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk,
+                     rs->chunk_rows, rest...);
+}
 template <int KIND, bool NORM, int NCOLS>
 static void launch_materialise(pvlm_ctx* ctx, const pvlm_resset* rs, double* d_r, double* d_J, int blk0 = 0, int nblk = -1, int64_t row0 = 0) {
-  hipLaunchKernelGGL((k_eval_materialise<KIND, NORM, NCOLS>), dim3(nblk < 0 ? rs->n_blocks : nblk), dim3(256), 0, ctx->stream, rs->d_pair_cols,
-                     rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, d_r, d_J,
-                     blk0, row0);
+  launch_eval(k_eval_materialise<KIND, NORM, NCOLS>, nblk < 0 ? rs->n_blocks : nblk, ctx, rs, rs->d_pair_tab, rs->weight, d_r, d_J, blk0, row0);
 }
 template <int KIND, bool NORM, int NCOLS>
 static void launch_wrench(pvlm_ctx* ctx, const pvlm_resset* rs, double* d_w, int blk0, int nblk, int64_t row0, bool force_only) {
-  if (force_only)
-    hipLaunchKernelGGL((k_eval_wrench<KIND, NORM, NCOLS, 4>), dim3(nblk), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
-                       rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, d_w, blk0, row0);
-  else
-    hipLaunchKernelGGL((k_eval_wrench<KIND, NORM, NCOLS, 7>), dim3(nblk), dim3(256), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
-                       rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, d_w, blk0, row0);
-}
-
-// PVLM_FUSED_LDS_PAD: bytes of dynamic LDS that a k_eval_fused launch takes and never touches — fewer workgroups per CU on the SAME code object (the occupancy
-// curve of profiles/eval_row_pairs_ab.txt: 48 KB and 56 KB give 3 and 2 workgroups per CU).  Read once; anything outside (0, 63 KB] is ignored.
-static unsigned fused_lds_pad() {
-  static const unsigned pad = [] { const char* e = getenv("PVLM_FUSED_LDS_PAD"); const long b = e ? atol(e) : 0; return (b > 0 && b <= 64512) ? (unsigned)b : 0u; }();
-  return pad;
+  launch_eval(force_only ? k_eval_wrench<KIND, NORM, NCOLS, 4> : k_eval_wrench<KIND, NORM, NCOLS, 7>, nblk, ctx, rs, rs->d_pair_tab, rs->weight, d_w, blk0, row0);
 }
 template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR>
 static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
   const pvlm_plane_args pr = {rs->d_plane_idx, rs->d_pair_idx0, rs->d_chunk_plane0, rs->d_plane_tab, rs->d_pair_ptab, rs->d_order};
   if (rs->wave_units)            // many short segments: one wave per (pair, chunk)
-    hipLaunchKernelGGL((k_eval_fused_wave<KIND, NORM, NCOLS, LOSS, PR>), dim3((unsigned)((rs->n_blocks + 3) / 4)), dim3(256), 0, ctx->stream, rs->d_pair_cols,
-                       rs->d_pair_stride, rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->n_blocks, rs->d_pair_tab, rs->weight, a,
-                       rs->d_partials, pr);
+    launch_eval(k_eval_fused_wave<KIND, NORM, NCOLS, LOSS, PR>, (rs->n_blocks + 3) / 4, ctx, rs, rs->n_blocks, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
   else if (PR && rs->point_table)  // the point from the neighbour's table, the grid in the set's dispatch order (pvlm_i_plane_runs_build chose both)
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>), dim3(rs->n_positions), dim3(256), fused_lds_pad(), ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
-                       rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
+    launch_eval(k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>, rs->n_positions, ctx, rs, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
   else
-    hipLaunchKernelGGL((k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>), dim3(rs->n_blocks), dim3(256), fused_lds_pad(), ctx->stream, rs->d_pair_cols, rs->d_pair_stride,
-                       rs->d_out_start, rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
+    launch_eval(k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>, rs->n_blocks, ctx, rs, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
 }
 template <int KIND, bool NORM, int NCOLS>
 static void launch_fused(pvlm_ctx* ctx, const pvlm_resset* rs, int loss, double a) {
@@ -944,24 +881,24 @@ static pvlm_status eval_to_host(pvlm_ctx* ctx, const pvlm_resset* crs, int mode,
   int64_t stage_rows = 32ll << 20;
   if (const char* e = getenv("PVLM_STAGE_ROWS")) { const long long v = atoll(e); if (v > 0) stage_rows = v; }
   const int width = mode == 1 ? 7 : (mode == 2 ? 4 : (h_b ? 13 : 1));
-  int64_t need = 0;      // the staging buffer holds the largest run of pairs that fits stage_rows (at least one pair)
-  for (int p = 0; p < rs->n_pairs;) {
-    int q = p; int64_t rows = 0;
-    while (q < rs->n_pairs && (q == p || rows + (rs->h_out_start[q + 1] - rs->h_out_start[q]) <= stage_rows)) { rows += rs->h_out_start[q + 1] - rs->h_out_start[q]; ++q; }
-    need = std::max(need, rows);
-    p = q;
-  }
+  // a slice: the run of whole pairs [p, q) that fits stage_rows (at least one pair); returns q
+  auto slice_end = [&](int p) {
+    int q = p + 1;
+    while (q < rs->n_pairs && rs->h_out_start[q + 1] - rs->h_out_start[p] <= stage_rows) ++q;
+    return q;
+  };
+  int64_t need = 0;      // the staging buffer holds the largest slice
+  for (int p = 0, q; p < rs->n_pairs; p = q) { q = slice_end(p); need = std::max<int64_t>(need, rs->h_out_start[q] - rs->h_out_start[p]); }
   if (rs->stage_doubles < (size_t)need * width) {
     if (ctx->capturing) { PVLM_SET_ERR(ctx, "staging buffer would grow inside a graph capture"); return PVLM_ERR_STATE; }
     pvlm_i_free(ctx, rs->d_stage); rs->d_stage = nullptr; rs->stage_doubles = 0;
     if ((st = pvlm_i_alloc(ctx, &rs->d_stage, (size_t)need * width))) return st;
     rs->stage_doubles = (size_t)need * width;
   }
-  for (int p = 0; p < rs->n_pairs;) {
-    int q = p; int64_t rows = 0;
-    while (q < rs->n_pairs && (q == p || rows + (rs->h_out_start[q + 1] - rs->h_out_start[q]) <= stage_rows)) { rows += rs->h_out_start[q + 1] - rs->h_out_start[q]; ++q; }
+  for (int p = 0, q; p < rs->n_pairs; p = q) {
+    q = slice_end(p);
     const int blk0 = rs->h_pair_blk_start[p], nblk = rs->h_pair_blk_start[q] - blk0;
-    const int64_t row0 = rs->h_out_start[p];
+    const int64_t row0 = rs->h_out_start[p], rows = rs->h_out_start[q] - row0;
     if (nblk > 0) {
       double* d_r = rs->d_stage;
       double* d_J = rs->d_stage + rows;
@@ -977,7 +914,6 @@ static pvlm_status eval_to_host(pvlm_ctx* ctx, const pvlm_resset* crs, int mode,
         if (h_b) PVLM_HIP(ctx, hipMemcpyAsync(h_b + (size_t)row0 * 12, d_J, (size_t)rows * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       }
     }
-    p = q;
   }
   return PVLM_OK;
 }

@@ -53,9 +53,6 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 #ifndef PVLM_ATAN_TIER
 #define PVLM_ATAN_TIER 1         // 1: a slot whose lanes all have tan r <= 1/32 takes the short chain (0: every slot the full chain)
 #endif
-#ifndef PVLM_EXP_CONST_PATHS
-#define PVLM_EXP_CONST_PATHS 0   // timing experiment only (wrong results): 1 takes the wave-uniform decisions of a row as constants — every slot the short tier here, no
-#endif                           // slot a Huber outlier in accumulate_row — so that a row is straight-line code (pvlm_eval.hip sets it for the builds of its row-pair gate)
 #define PVLM_ATAN_TIER_ENTRY 6   // the short chain starts at the seventh coefficient; tests/test_atan_tier_cpu.py reads this line and holds it to its condition
 template <int ENTRY = 0>
 __device__ __forceinline__ double horner10_sconst(double u, double c0, double c1, double c2, double c3, double c4, double c5, double c6, double c7,
@@ -145,7 +142,7 @@ __device__ __forceinline__ double atan2_pos_grad(double y, double x, bool live, 
   double r;
   // a slot whose lanes are all at or below tan r = 1/32 (77 % of the headline's slots) puts the same quotient into the short chain.  Tested first; a slot
   // that fails pays a product and a comparison more.  A row's bits depend on the tier its slot took, as they already do on the octant path.
-  const bool tiny = PVLM_EXP_CONST_PATHS || (PVLM_ATAN_TIER && __all(32.0 * y <= x));
+  const bool tiny = PVLM_ATAN_TIER && __all(32.0 * y <= x);
   if (tiny || __all(y <= 0.41421356237309503 * x)) {
     const double R = live ? fast_rcp(x * h2) : 0.0;
     inv_h2 = x * R;
@@ -306,97 +303,6 @@ __device__ __forceinline__ void residual_grad(const double* P, const double* rec
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) g[kk] = gP[kk] + t * d[kk];
   }
-}
-
-// ---- two rows at a time ---------------------------------------------------------------------------
-// The Point2Plane_Angle + normalize row of residual_grad above on the small-angle path, written over a value type: double, or dpair = the two rows of a lane with
-// every operation element-wise, so that the two rows' dependent chains stand side by side in the source.  The wave-uniform tier (ENTRY of atan_small) is the
-// caller's decision.  Only the row-pair gate of pvlm_eval.hip (a timing experiment) instantiates it so far.
-struct dpair { double a, b; };
-struct bpair { bool a, b; };
-__device__ __forceinline__ dpair operator+(dpair x, dpair y) { return {x.a + y.a, x.b + y.b}; }
-__device__ __forceinline__ dpair operator-(dpair x, dpair y) { return {x.a - y.a, x.b - y.b}; }
-__device__ __forceinline__ dpair operator*(dpair x, dpair y) { return {x.a * y.a, x.b * y.b}; }
-__device__ __forceinline__ dpair operator-(dpair x) { return {-x.a, -x.b}; }
-__device__ __forceinline__ dpair operator+(double x, dpair y) { return {x + y.a, x + y.b}; }
-__device__ __forceinline__ dpair operator+(dpair x, double y) { return {x.a + y, x.b + y}; }
-__device__ __forceinline__ dpair operator-(dpair x, double y) { return {x.a - y, x.b - y}; }
-__device__ __forceinline__ dpair operator*(double x, dpair y) { return {x * y.a, x * y.b}; }
-__device__ __forceinline__ double vfma(double x, double y, double z) { return fma(x, y, z); }
-__device__ __forceinline__ dpair vfma(dpair x, dpair y, dpair z) { return {fma(x.a, y.a, z.a), fma(x.b, y.b, z.b)}; }
-__device__ __forceinline__ double vabs(double x) { return fabs(x); }
-__device__ __forceinline__ dpair vabs(dpair x) { return {fabs(x.a), fabs(x.b)}; }
-__device__ __forceinline__ double vcopysign(double x, double s) { return copysign(x, s); }
-__device__ __forceinline__ dpair vcopysign(dpair x, dpair s) { return {copysign(x.a, s.a), copysign(x.b, s.b)}; }
-__device__ __forceinline__ double vrcp(double x) { return fast_rcp(x); }
-__device__ __forceinline__ dpair vrcp(dpair x) {                 // the two estimates first, then the two Newton steps
-  const double ra = __builtin_amdgcn_rcp(x.a), rb = __builtin_amdgcn_rcp(x.b);
-  return {fma(ra, fma(-x.a, ra, 1.0), ra), fma(rb, fma(-x.b, rb, 1.0), rb)};
-}
-__device__ __forceinline__ double vrsqrt(double x) { return fast_rsqrt(x); }
-__device__ __forceinline__ dpair vrsqrt(dpair x) {
-  const double ra = __builtin_amdgcn_rsq(x.a), rb = __builtin_amdgcn_rsq(x.b);
-  return {fma(ra, fma(-x.a * ra, 0.5 * ra, 0.5), ra), fma(rb, fma(-x.b * rb, 0.5 * rb, 0.5), rb)};
-}
-__device__ __forceinline__ bool vgt(double x, double c) { return x > c; }
-__device__ __forceinline__ bpair vgt(dpair x, double c) { return {x.a > c, x.b > c}; }
-__device__ __forceinline__ bool vge(double x, double c) { return x >= c; }
-__device__ __forceinline__ bpair vge(dpair x, double c) { return {x.a >= c, x.b >= c}; }
-__device__ __forceinline__ double vsel0(bool m, double x) { return m ? x : 0.0; }
-__device__ __forceinline__ dpair vsel0(bpair m, dpair x) { return {m.a ? x.a : 0.0, m.b ? x.b : 0.0}; }
-// the short chain of horner10_sconst for the two rows in ONE statement, step by step in turn: the same instructions on each row as horner10_sconst<6> issues
-__device__ __forceinline__ dpair horner_short_pair(dpair u, double c6, double c7, double c8, double c9) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  dpair p;
-  asm("v_mov_b64 %0, %4\n\t"
-      "v_mov_b64 %1, %4\n\t"
-      "v_fma_f64 %0, %0, %2, %5\n\t"
-      "v_fma_f64 %1, %1, %3, %5\n\t"
-      "v_fma_f64 %0, %0, %2, %6\n\t"
-      "v_fma_f64 %1, %1, %3, %6\n\t"
-      "v_fma_f64 %0, %0, %2, %7\n\t"
-      "v_fma_f64 %1, %1, %3, %7\n\t"
-      "v_fma_f64 %0, %0, %2, 1.0\n\t"
-      "v_fma_f64 %1, %1, %3, 1.0"
-      : "=&v"(p.a), "=&v"(p.b)
-      : "v"(u.a), "v"(u.b), "s"(c6), "s"(c7), "s"(c8), "s"(c9));
-  return p;
-#else
-  return {fma(fma(fma(fma(c6, u.a, c7), u.a, c8), u.a, c9), u.a, 1.0), fma(fma(fma(fma(c6, u.b, c7), u.b, c8), u.b, c9), u.b, 1.0)};
-#endif
-}
-__device__ __forceinline__ double atan_short(double t) { return atan_small<PVLM_ATAN_TIER_ENTRY>(t); }
-__device__ __forceinline__ dpair atan_short(dpair t) {
-  const dpair p = horner_short_pair(t * t, 1.11111061650365134e-01, -1.42857141805968924e-01, 1.99999999988503901e-01, -3.33333333333284132e-01);
-  return t * p;
-}
-// r, the moment c and the force g of one row (V = double) or of a lane's two rows (V = dpair) on the SHORT tier: eval_wrench + residual_grad for that case.
-// rec = the point (3) and the plane (4) of the row(s); T as in eval_wrench.
-template <class V>
-__device__ __forceinline__ void angle_norm_wrench_short(const V* rec, const double* T, V& r, V* c, V* g) {
-  const double* R = T; const double* trn = T + 9; const double* trw = T + 12;
-  const V P[3] = {R[0] * rec[0] + R[1] * rec[1] + R[2] * rec[2] + trn[0], R[3] * rec[0] + R[4] * rec[1] + R[5] * rec[2] + trn[1],
-                  R[6] * rec[0] + R[7] * rec[1] + R[8] * rec[2] + trn[2]};
-  const V* n = rec + 3;
-  const V dd = n[3];
-  const V sd = n[0] * P[0] + n[1] * P[1] + n[2] * P[2] + dd;
-  const V dis = vabs(sd);
-  const V u[3] = {P[0] - (sd - dd) * n[0], P[1] - (sd - dd) * n[1], P[2] - (sd - dd) * n[2]};
-  const V q2 = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
-  const V nu2 = q2 + dd * dd;
-  const V inv_nu = vrsqrt(nu2);
-  const V invq = vsel0(vgt(q2, 0.0), vrsqrt(q2));
-  const V q = q2 * invq, nu = nu2 * inv_nu;
-  const V X = vfma(-sd, dd, nu), Y = dis * q;
-  const V AD = q * nu, BD = dis * dd * vfma(-sd, nu, dd) * (invq * inv_nu);
-  const V h2 = vfma(X, X, Y * Y);
-  const V Rc = vsel0(vge(dis, 1e-3), vrcp(X * h2));
-  const V k0 = X * Rc;
-  r = atan_short(Y * (h2 * Rc));
-  const V A = vcopysign(AD * k0, sd), B = BD * k0;
-  for (int k = 0; k < 3; ++k) g[k] = A * n[k] + B * u[k];
-  const V m[3] = {P[0] - trw[0], P[1] - trw[1], P[2] - trw[2]};
-  c[0] = m[1] * g[2] - m[2] * g[1]; c[1] = m[2] * g[0] - m[0] * g[2]; c[2] = m[0] * g[1] - m[1] * g[0];
 }
 
 // Full wrench for any kind.  T = pair table row (R_rn[9] | t_rn[3] | t_rw[3] | ...).
