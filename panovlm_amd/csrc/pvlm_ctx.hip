@@ -357,7 +357,6 @@ pvlm_status pvlm_destroy(pvlm_ctx* ctx) {
   for (hipEvent_t e : ctx->grow_ev) if (e) hipEventDestroy(e);
   if (ctx->h_grow_in) (void)hipHostFree(ctx->h_grow_in);
   if (ctx->h_grow_out) (void)hipHostFree(ctx->h_grow_out);
-  for (hipEvent_t e : ctx->aux_ev) if (e) hipEventDestroy(e);
   hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return PVLM_OK;

@@ -84,10 +84,9 @@ struct pvlm_ctx {
   // pinned staging arena of every other host <-> device copy (pvlm_i_h2d_q / pvlm_i_d2h_q / pvlm_i_sync)
   pvlm_stage stage;
   hipStream_t own_stream = nullptr;
-  // the context's second stream, created on first use by whoever needs one: the look-ahead Cholesky (K10), the ring batches' result download beside K23 / K24
-  // (pvlm_ring.hip) and the fuse upload (pvlm_fuse.hip).  Each user orders it behind the main stream with an event and drains it before its call returns.
+  // the context's second stream, created on first use by whoever needs one: the ring batches' result download beside K23 / K24 (pvlm_ring.hip) and the fuse
+  // upload (pvlm_fuse.hip).  Each user orders it behind the main stream with an event and drains it before its call returns.
   hipStream_t aux_stream = nullptr;
-  hipEvent_t aux_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   // K27 (pvlm_line_grow_begin / _finish): its own stream — the line growth of one device batch of scans runs beside the range-image stages of the next —, three
   // events (ordering behind the main stream, kernel timing) and two grow-only pinned buffers (inputs; counters, statuses and the kept segments coming back)
   hipStream_t grow_stream = nullptr;

@@ -23,95 +23,10 @@
 // below is multiplied by that inverse, (3) the trailing lower triangle gets its rank-32 update in 64 x 64 tiles on the
 // f64 matrix core (both panel slices staged in LDS).  *info != 0 (set by a non-positive pivot, 1-based
 // like LAPACK) makes every later kernel of the sequence return at once.
+// The forms that lost their measurement (separate diagonal and panel launches, a register-tiled VALU update, a two-stream look-ahead) are no longer in the
+// tree: numbers in profiles/r1_chol_bench.jsonl and DESIGN.md §3 K10, where to find the code in profiles/HISTORY.md.
 #define PVLM_CHOL_NB 32
 
-// Measured variants that lost (round 1's separate diagonal / panel launches, the register-tiled VALU trailing update, the two-stream
-// look-ahead) are compiled only into a library built with -DPVLM_MEASURED_VARIANTS=1 (python -m panovlm_amd.build --variant measured
-// -DPVLM_MEASURED_VARIANTS=1), where PVLM_CHOL_SPLIT / PVLM_CHOL_VALU / PVLM_CHOL_LOOKAHEAD select them; their numbers are in
-// profiles/r1_chol_bench.jsonl and DESIGN.md §3 K10.
-#ifndef PVLM_MEASURED_VARIANTS
-#define PVLM_MEASURED_VARIANTS 0
-#endif
-#if PVLM_MEASURED_VARIANTS
-__global__ __launch_bounds__(256) void k_chol_diag(double* __restrict__ M, int n, int k0, int kb, double* __restrict__ Linv, int* __restrict__ info) {
-  __shared__ double a[PVLM_CHOL_NB][PVLM_CHOL_NB + 1];
-  __shared__ double inv[PVLM_CHOL_NB][PVLM_CHOL_NB + 1];
-  __shared__ int fail;
-  if (*info != 0) return;
-  const int t = threadIdx.x;
-  if (t == 0) fail = 0;
-  for (int e = t; e < PVLM_CHOL_NB * PVLM_CHOL_NB; e += 256) {
-    const int i = e / PVLM_CHOL_NB, j = e % PVLM_CHOL_NB;
-    a[i][j] = (i < kb && j <= i) ? M[(size_t)(k0 + i) * n + k0 + j] : 0.0;
-    inv[i][j] = (i == j && i < kb) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  // right-looking factorisation of the block; the same eliminations applied to an identity give L^-1 on the way
-  // (Y = I; row j of Y is divided by the pivot, rows below get Y[i] -= L[i][j] Y[j]): no extra barriers.
-  for (int j = 0; j < kb; ++j) {
-    if (t == 0) { const double d = a[j][j]; if (!(d > 0.0)) fail = j + 1; else a[j][j] = sqrt(d); }
-    __syncthreads();
-    if (fail) break;
-    const double piv = a[j][j];
-    if (t > j && t < kb) a[t][j] /= piv;
-    if (t >= 64 && t - 64 <= j) inv[j][t - 64] /= piv;          // second wave: row j of the inverse (columns <= j)
-    __syncthreads();
-    for (int e = t; e < PVLM_CHOL_NB * PVLM_CHOL_NB; e += 256) {
-      const int i = e / PVLM_CHOL_NB, c = e % PVLM_CHOL_NB;
-      if (i > j && i < kb) {
-        if (c > j && c <= i) a[i][c] -= a[i][j] * a[c][j];
-        else if (c <= j) inv[i][c] -= a[i][j] * inv[j][c];
-      }
-    }
-    __syncthreads();
-  }
-  if (fail) { if (t == 0) *info = k0 + fail; return; }
-  double* Lk = Linv + (size_t)(k0 / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
-  for (int e = t; e < PVLM_CHOL_NB * PVLM_CHOL_NB; e += 256) {
-    const int i = e / PVLM_CHOL_NB, j = e % PVLM_CHOL_NB;
-    if (i < kb && j <= i) M[(size_t)(k0 + i) * n + k0 + j] = a[i][j];
-    Lk[e] = inv[i][j];
-  }
-}
-
-// panel below the diagonal block: X = A L_kk^-T, i.e. X[row][c] = sum_{d <= c} A[row][d] Linv[c][d] — a small product,
-// 8 rows x 32 columns per workgroup, no dependency chain (the first version solved the triangular system per row:
-// 25 us per block column; a fully unrolled register version of that needed 512 registers + scratch and mis-behaved).
-__global__ __launch_bounds__(256) void k_chol_panel(double* __restrict__ M, int n, int k0, int kb, const double* __restrict__ Linv,
-                                                    const int* __restrict__ info) {
-  __shared__ double inv[PVLM_CHOL_NB][PVLM_CHOL_NB + 1];
-  __shared__ double As[8][PVLM_CHOL_NB + 1];
-  if (*info != 0) return;
-  const int t = threadIdx.x;
-  const double* Lk = Linv + (size_t)(k0 / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
-  for (int e = t; e < PVLM_CHOL_NB * PVLM_CHOL_NB; e += 256) inv[e / PVLM_CHOL_NB][e % PVLM_CHOL_NB] = Lk[e];
-  const int lr = t / PVLM_CHOL_NB, c = t % PVLM_CHOL_NB;
-  const int row = k0 + kb + blockIdx.x * 8 + lr;
-  const bool live = row < n && c < kb;
-  As[lr][c] = live ? M[(size_t)row * n + k0 + c] : 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int sub = 0; sub < SUBS; ++sub) {
-    double x = 0.0;
-    for (int d = 0; d <= c; ++d) x += As[8 * sub + lr][d] * inv[c][d];
-    if (lives[sub]) M[(size_t)rows[sub] * n + k0 + c] = x;
-  }
-}
-#endif  // PVLM_MEASURED_VARIANTS
-
-// MEASURED VARIANT (-DPVLM_CHOL_CLOCK=1): where workgroup 0 of k_chol_diag_panel spends its time, 100 MHz wall clock, summed over the launches
-// of a solve and printed by chol_factor_solve: [0] entry -> block + rows in LDS, [1] the 32-pivot chain + inverse, [2] stores + panel rows, [3] launches.
-#ifndef PVLM_CHOL_CLOCK
-#define PVLM_CHOL_CLOCK 0
-#endif
-#if PVLM_CHOL_CLOCK
-__device__ unsigned long long g_chol_clock[4];
-#define CHOL_NOW() wall_clock64()
-#define CHOL_ADD(i, v) do { if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(&g_chol_clock[i], (unsigned long long)(v)); } while (0)
-#else
-#define CHOL_NOW() 0ull
-#define CHOL_ADD(i, v) do { (void)(v); } while (0)
-#endif
 __device__ __forceinline__ double bcast_f64(double v, int src_lane) {     // v of lane src_lane (wave-uniform source) for every lane
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
   return __hiloint2double(hi, lo);
@@ -141,7 +56,6 @@ __device__ __forceinline__ void chol_diag_panel_body(double* __restrict__ M, int
   __shared__ double As[8 * SUBS][PVLM_CHOL_NB + 1];
   __shared__ int fail;
   if (*info != 0) return;
-  const unsigned long long ck0 = CHOL_NOW();
   const int t = threadIdx.x;
   if (t == 0) fail = 0;
   {
@@ -175,7 +89,6 @@ __device__ __forceinline__ void chol_diag_panel_body(double* __restrict__ M, int
     for (int sub = 0; sub < SUBS; ++sub) As[8 * sub + lr][c] = lives[sub] ? a_row[sub] : 0.0;
   }
   __syncthreads();
-  const unsigned long long ck1 = CHOL_NOW();
   if (t < 64) {
     // One wave, no LDS and no barrier inside the chain: lane i keeps ROW i of the block in registers (fully unrolled, so
     // every register index is a compile-time constant); the pivot and the column entries l_cj a lane needs from another
@@ -195,7 +108,7 @@ __device__ __forceinline__ void chol_diag_panel_body(double* __restrict__ M, int
         if (!(d > 0.0)) bad = j + 1;
         else {
           // 1 / sqrt(d) by v_rsq_f64 + three Newton steps (12 dependent instructions) instead of sqrt and a division per pivot (~45, a fifth
-          // of the chain's time: the chain is ONE wave's dependent instructions, 23.6 us per block column measured with -DPVLM_CHOL_CLOCK=1);
+          // of the chain's time: the chain is ONE wave's dependent instructions, 23.6 us per block column measured with a phase clock in the kernel);
           // l_jj = d y, l_ij = a_ij y: last-bit differences against sqrt-and-divide, as any other summation order gives
           double y = __builtin_amdgcn_rsq(d);
           y = y * (1.5 - 0.5 * d * y * y);
@@ -237,7 +150,6 @@ __device__ __forceinline__ void chol_diag_panel_body(double* __restrict__ M, int
     }
   }
   __syncthreads();
-  const unsigned long long ck2 = CHOL_NOW();
   if (fail) { if (t == 0 && wg == 0) { *fail_out = k0 + fail; } return; }
   if (wg == 0) {
     double* Lk = Linv + (size_t)(k0 / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
@@ -254,7 +166,6 @@ __device__ __forceinline__ void chol_diag_panel_body(double* __restrict__ M, int
     for (int d = 0; d <= c; ++d) x += As[8 * sub + lr][d] * inv[c][d];
     if (lives[sub]) M[(size_t)rows[sub] * n + k0 + c] = x;
   }
-  CHOL_ADD(0, ck1 - ck0); CHOL_ADD(1, ck2 - ck1); CHOL_ADD(2, CHOL_NOW() - ck2); CHOL_ADD(3, 1);
 }
 
 __global__ __launch_bounds__(256) void k_chol_diag_panel(double* __restrict__ M, int n, int k0, int kb, double* __restrict__ Linv, int* __restrict__ info,
@@ -273,8 +184,8 @@ __global__ __launch_bounds__(256) void k_nd_panel(double* __restrict__ M, int n,
 }
 
 // Which 64 x 64 tile (ti >= tj) of the trailing lower triangle a workgroup updates.  part 0: all tiles, linear id -> lower
-// triangle; part 1: the first tile column only (tj = 0: the columns the NEXT block column's factorisation needs);
-// part 2: the rest (tj >= 1) — parts 1 and 2 run on two streams (look-ahead, chol_factor_solve).
+// triangle; part 1: the first tile column only (tj = 0); part 2: the rest (tj >= 1).  The host always passes 0 (parts 1 and 2
+// were the two halves of a look-ahead on two streams that lost its measurement; the parameter stays so that the device code does).
 __device__ __forceinline__ bool chol_tile_of(int id, int tiles, int part, int* ti_out, int* tj_out) {
   if (part == 1) { if (id >= tiles) return false; *ti_out = id; *tj_out = 0; return true; }
   const int shift = part == 2 ? 1 : 0, t = tiles - shift;
@@ -301,49 +212,6 @@ __device__ __forceinline__ void chol_fwd_rows(const double* __restrict__ M, int 
   for (int c = 0; c < kb; ++c) sacc += r[c] * y[c];
   b[i] -= sacc;
 }
-
-#if PVLM_MEASURED_VARIANTS
-__global__ __launch_bounds__(256) void k_chol_update(double* __restrict__ M, int n, int k0, int kb, int tiles, const int* __restrict__ info,
-                                                     int n_tile_blocks, double* __restrict__ fwd_b, const double* __restrict__ fwd_y, int part) {
-  if ((int)blockIdx.x >= n_tile_blocks) { if (*info == 0) chol_fwd_rows(M, n, k0, kb, (int)blockIdx.x - n_tile_blocks, fwd_b, fwd_y); return; }
-  __shared__ double As[64][PVLM_CHOL_NB + 1];
-  __shared__ double Bs[64][PVLM_CHOL_NB + 1];
-  if (*info != 0) return;
-  // linear block id -> (ti >= tj) of the lower triangle of the tile grid
-  int ti, tj;
-  if (!chol_tile_of((int)blockIdx.x, tiles, part, &ti, &tj)) return;
-  const int base = k0 + kb, r0 = base + ti * 64, c0 = base + tj * 64;
-  for (int e = threadIdx.x; e < 64 * PVLM_CHOL_NB; e += 256) {
-    const int i = e / PVLM_CHOL_NB, c = e % PVLM_CHOL_NB;
-    As[i][c] = (r0 + i < n && c < kb) ? M[(size_t)(r0 + i) * n + k0 + c] : 0.0;
-    Bs[i][c] = (c0 + i < n && c < kb) ? M[(size_t)(c0 + i) * n + k0 + c] : 0.0;
-  }
-  __syncthreads();
-  const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
-  double acc[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll 8
-  for (int c = 0; c < PVLM_CHOL_NB; ++c) {
-    double av[4], bv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { av[q] = As[ty * 4 + q][c]; bv[q] = Bs[tx * 4 + q][c]; }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[p][q] += av[p] * bv[q];
-  }
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int row = r0 + ty * 4 + p;
-    if (row >= n) continue;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int col = c0 + tx * 4 + q;
-      if (col <= row) M[(size_t)row * n + col] -= acc[p][q];
-    }
-  }
-}
-
-#endif  // PVLM_MEASURED_VARIANTS
 
 // The same rank-32 trailing update on the matrix core: v_mfma_f64_16x16x4_f64 (the one GEMM-shaped kernel of this
 // library).  A 64 x 64 tile per workgroup, wave w owns the 16-row band [16w, 16w + 16) and all four 16-column tiles:
@@ -1110,116 +978,47 @@ __global__ __launch_bounds__(256) void k_bwd_step(const double* __restrict__ M, 
 // factorises d_M (n x n row-major, lower triangle used and overwritten by L) and solves for nrhs right-hand sides stored
 // one after the other in d_B; all on ctx->stream.
 // d_Linv: ceil(n / 32) x 32 x 32 doubles (inverses of the diagonal blocks), d_y: n doubles (forward-solve result).
-// Tile-sparse form (plan != nullptr): block column k only touches the 64-row tiles that hold one of its nonzeros — lists made by the
+// Tile-sparse form (lists != nullptr): block column k only touches the 64-row tiles that hold one of its nonzeros — lists made by the
 // symbolic factorisation of SpdPlan, below — instead of every row below it.
 struct SpdTileLists {
   const int* d_row_tiles; const int2* d_pairs;          // concatenated over the block columns
   const int* row_off; const int* pair_off;              // host: steps + 1 offsets
 };
-static void chol_factor_solve(pvlm_ctx* ctx, int n, double* d_M, double* d_B, int nrhs, double* d_Linv, double* d_y, int* d_info, const SpdTileLists* plan = nullptr) {
-  hipStream_t s = ctx->stream;
-#if PVLM_MEASURED_VARIANTS
-  static const bool use_mfma = getenv("PVLM_CHOL_VALU") == nullptr;   // PVLM_CHOL_VALU=1: the register-tiled VALU update (measured variant)
-  static const bool fused = getenv("PVLM_CHOL_SPLIT") == nullptr;      // PVLM_CHOL_SPLIT=1: round 1's launch structure (k_chol_diag, k_chol_panel, k_fwd_step)
-  static const bool want_ahead = getenv("PVLM_CHOL_LOOKAHEAD") != nullptr;   // opt-in: measured SLOWER (below)
-#else
-  const bool fused = true, want_ahead = false;                        // the default library: fused diagonal + panel launch, MFMA-f64 update, one stream
-#endif
-  const bool ride = fused && nrhs >= 1;                                // the first right-hand side's forward substitution rides along
-  // Look-ahead on a second stream (PVLM_CHOL_LOOKAHEAD=1; built, measured, not adopted: 5.45 ms against 4.56 ms at n = 2724 —
-  // two event records and two stream waits per block column cost more on this runtime than the 20 us of overlap they buy):
-  // block column k + 1 can be factorised as soon as the FIRST tile column of update k is done;
-  // the rest of update k (part 2) runs beside it.  Stream A (the context stream): F(k), U1(k) [first tile column + rhs rows];
-  // stream B: U2(k).  U2(k) waits for F(k) (it needs the panel); U1(k) waits for U2(k - 1) (they touch the same columns);
-  // everything else is ordered by the streams themselves.
-  bool ahead = fused && want_ahead && !ctx->capturing && n > 8 * PVLM_CHOL_NB;
-  if (ahead && !ctx->aux_stream) {
-    ahead = hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) == hipSuccess;
-    for (int q = 0; q < 8 && ahead; ++q) ahead = hipEventCreateWithFlags(&ctx->aux_ev[q], hipEventDisableTiming) == hipSuccess;
-    if (!ahead) ctx->aux_stream = nullptr;
-  }
-  hipStream_t sb = ahead ? ctx->aux_stream : s;
-  if (ahead) { hipEventRecord(ctx->aux_ev[0], s); hipStreamWaitEvent(sb, ctx->aux_ev[0], 0); }
-  int step = 0, last_u2 = -1;
-  auto launch_update = [&](hipStream_t st, int k0, int kb, int tiles, int part, int tile_blocks, int fwd_blocks) {
-    if (tile_blocks + fwd_blocks <= 0) return;
-#if PVLM_MEASURED_VARIANTS
-    if (!use_mfma) { hipLaunchKernelGGL(k_chol_update, dim3((unsigned)(tile_blocks + fwd_blocks)), dim3(256), 0, st, d_M, n, k0, kb, tiles, d_info, tile_blocks, d_B, d_y, part); return; }
-#endif
-    hipLaunchKernelGGL(k_chol_update_mfma, dim3((unsigned)(tile_blocks + fwd_blocks)), dim3(256), 0, st, d_M, n, k0, kb, tiles, d_info, tile_blocks, d_B, d_y, part,
-                       (const int2*)nullptr);
-  };
+// Per block column (1) diagonal block + panel and (2) the trailing update on the matrix core — with tile lists the two launches cover the listed tiles, without
+// them every row below the block; the forward substitution of the first right-hand side rides along in both.  Then (3) the forward solves of the remaining
+// right-hand sides and (4) the backward solves.  nrhs >= 1.  Launch errors are the caller's to collect (c.check_launches()).
+static void chol_factor_solve(pvlm_call& c, int n, double* d_M, double* d_B, int nrhs, double* d_Linv, double* d_y, int* d_info, const SpdTileLists* lists = nullptr) {
+  int step = 0;
   for (int k0 = 0; k0 < n; k0 += PVLM_CHOL_NB, ++step) {
     const int kb = std::min(PVLM_CHOL_NB, n - k0), rem = n - k0 - kb;
-    if (plan) {
-      const int nrt = plan->row_off[step + 1] - plan->row_off[step], npr = plan->pair_off[step + 1] - plan->pair_off[step];
-      hipLaunchKernelGGL(k_chol_diag_panel, dim3((unsigned)std::max(1, nrt * 8)), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, d_info, d_info,
-                         ride ? (const double*)d_B : nullptr, d_y, plan->d_row_tiles + plan->row_off[step], nrt);
-      const int fwd_blocks = (ride && rem > 0) ? (rem + 255) / 256 : 0;
-      if (npr + fwd_blocks > 0)
-        hipLaunchKernelGGL(k_chol_update_mfma, dim3((unsigned)(npr + fwd_blocks)), dim3(256), 0, s, d_M, n, k0, kb, 0, d_info, npr, d_B, d_y, 0,
-                           plan->d_pairs + plan->pair_off[step]);
-      continue;
+    const int* row_tiles = nullptr; const int2* pairs = nullptr;
+    int n_row_tiles = 0, panel_groups = (rem + 7) / 8, tiles = (rem + 63) / 64, tile_blocks = (int)((long long)tiles * (tiles + 1) / 2);
+    if (lists) {
+      row_tiles = lists->d_row_tiles + lists->row_off[step]; n_row_tiles = lists->row_off[step + 1] - lists->row_off[step];
+      pairs = lists->d_pairs + lists->pair_off[step]; tile_blocks = lists->pair_off[step + 1] - lists->pair_off[step];
+      panel_groups = n_row_tiles * 8; tiles = 0;
     }
-    if (fused) {
-      // a failed pivot: every workgroup finds it itself (same arithmetic on the same block) and returns; workgroup 0 records it
-      // in *info, which the later launches test on entry
-      hipLaunchKernelGGL(k_chol_diag_panel, dim3(std::max(1, (rem + 7) / 8)), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, d_info, d_info,
-                         ride ? (const double*)d_B : nullptr, d_y, (const int*)nullptr, 0);
-    }
-#if PVLM_MEASURED_VARIANTS
-    else {
-      hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, d_info);
-      if (rem > 0) hipLaunchKernelGGL(k_chol_panel, dim3((rem + 7) / 8), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, d_info);
-    }
-#endif
-    if (rem > 0) {
-      const int tiles = (rem + 63) / 64;
-      const int fwd_blocks = ride ? (rem + 255) / 256 : 0;
-      if (ahead && tiles >= 2) {
-        hipEvent_t ef = ctx->aux_ev[1 + (step & 1)], eu = ctx->aux_ev[3 + (step & 3)];
-        hipEventRecord(ef, s);                                   // F(k) done: the panel exists
-        hipStreamWaitEvent(sb, ef, 0);
-        launch_update(sb, k0, kb, tiles, 2, (int)((long long)(tiles - 1) * tiles / 2), 0);
-        hipEventRecord(eu, sb);
-        if (last_u2 >= 0) hipStreamWaitEvent(s, ctx->aux_ev[3 + (last_u2 & 3)], 0);    // U1(k) after U2(k - 1)
-        launch_update(s, k0, kb, tiles, 1, tiles, fwd_blocks);
-        last_u2 = step;
-      } else {
-        if (ahead && last_u2 >= 0) { hipStreamWaitEvent(s, ctx->aux_ev[3 + (last_u2 & 3)], 0); last_u2 = -1; }
-        launch_update(s, k0, kb, tiles, 0, (int)((long long)tiles * (tiles + 1) / 2), fwd_blocks);
-      }
-    }
+    // a failed pivot: every workgroup finds it itself (same arithmetic on the same block) and returns; workgroup 0 records it
+    // in *info, which the later launches test on entry
+    c.launch(k_chol_diag_panel, dim3((unsigned)std::max(1, panel_groups)), dim3(256), 0, d_M, n, k0, kb, d_Linv, d_info, d_info, (const double*)d_B, d_y, row_tiles, n_row_tiles);
+    const int fwd_blocks = (rem + 255) / 256;                    // the rows of the right-hand side below the block
+    if (tile_blocks + fwd_blocks > 0)
+      c.launch(k_chol_update_mfma, dim3((unsigned)(tile_blocks + fwd_blocks)), dim3(256), 0, d_M, n, k0, kb, tiles, (const int*)d_info, tile_blocks, d_B, (const double*)d_y,
+               0 /* part: always all tiles, see chol_tile_of */, pairs);
   }
-  if (ahead && last_u2 >= 0) hipStreamWaitEvent(s, ctx->aux_ev[3 + (last_u2 & 3)], 0);
   for (int r = 0; r < nrhs; ++r) {
     double* b = d_B + (size_t)r * n;
-    if (!(ride && r == 0))
+    if (r > 0)
       for (int k0 = 0; k0 < n; k0 += PVLM_CHOL_NB) {
         const int kb = std::min(PVLM_CHOL_NB, n - k0), rem = n - k0 - kb;
-        hipLaunchKernelGGL(k_fwd_step, dim3(std::max(1, (rem + 255) / 256)), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, b, d_y, d_info);
+        c.launch(k_fwd_step, dim3((unsigned)std::max(1, (rem + 255) / 256)), dim3(256), 0, (const double*)d_M, n, k0, kb, (const double*)d_Linv, b, d_y, (const int*)d_info);
       }
     for (int k0 = ((n - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB; k0 >= 0; k0 -= PVLM_CHOL_NB) {
       const int kb = std::min(PVLM_CHOL_NB, n - k0);
-      hipLaunchKernelGGL(k_bwd_step, dim3(std::max(1, (k0 + 255) / 256)), dim3(256), 0, s, d_M, n, k0, kb, d_Linv, b, d_y, d_info);
+      c.launch(k_bwd_step, dim3((unsigned)std::max(1, (k0 + 255) / 256)), dim3(256), 0, (const double*)d_M, n, k0, kb, (const double*)d_Linv, b, d_y, (const int*)d_info);
     }
   }
-#if PVLM_CHOL_CLOCK
-  {
-    unsigned long long h[4] = {}, z[4] = {};
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_chol_clock), sizeof h);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chol_clock), z, sizeof z);
-    const double L = (double)std::max<unsigned long long>(h[3], 1);
-    fprintf(stderr, "[chol clock] %llu panel launches | us per launch (workgroup 0): load %.2f  chain %.2f  stores + rows %.2f\n", h[3], h[0] * 0.01 / L, h[1] * 0.01 / L, h[2] * 0.01 / L);
-  }
-#endif
 }
-
-// The same factorisation and the two triangular solves by the level schedule: per level ONE panel launch (every block column of the level) and ONE update
-// launch (every tile the level's columns reach + the right-hand side rows), then the backward substitution level by level in descending order.
-struct SpdPlan;
-static void chol_factor_solve_levels(pvlm_ctx* ctx, int n, double* d_M, double* d_b, double* d_Linv, double* d_y, int* d_info, const SpdPlan* P);
 
 // dense M (n x n, symmetric) += scatter of 6x6 blocks: entry (r, c) of block b goes to (row_idx[6b + r], col_idx[6b + c])
 // scaled by scale[i] * scale[j]; blocks flagged `mirror` (two different poses) are also added to the other triangle.
@@ -1298,7 +1097,10 @@ struct SpdPlan {
   // the permuted index lists of the structure on the device, made by the first solve with this plan: the LM steps of a Solve change the values only
   int* d_idx_rows = nullptr; int* d_idx_cols = nullptr; int* d_idx_mirror = nullptr; bool idx_on_device = false;
   NdFlowTask* d_flow_tasks = nullptr; NdFlowSource* d_flow_sources = nullptr; int* d_flow_cols = nullptr; int* d_flow_below_off = nullptr; int* d_flow_below = nullptr;
+  std::vector<void*> owned;                    // every device block above, as spd_plan_alloc handed it out: what spd_plan_free gives back
 };
+// the flag words of the one-launch form: two tickets, a word per task, then per tile column: inverse, y, x (tail_flag_words is the same with T * T tile words)
+static size_t flow_flag_words(size_t tasks, int T) { return (size_t)2 + tasks + 3 * (size_t)T; }
 
 static unsigned long long spd_hash(int n, int n_blocks, const int* row_idx, const int* col_idx, const int* mirror) {
   unsigned long long h = 1469598103934665603ull;
@@ -1357,13 +1159,16 @@ static void spd_prefetch_drop(pvlm_ctx* ctx) {
 
 static void spd_plan_free(pvlm_ctx* ctx, SpdPlan* p) {
   if (!p) return;
-  pvlm_i_free(ctx, p->d_row_tiles); pvlm_i_free(ctx, p->d_pairs);
-  pvlm_i_free(ctx, p->d_cols); pvlm_i_free(ctx, p->d_row_off); pvlm_i_free(ctx, p->d_pwg); pvlm_i_free(ctx, p->d_pwt); pvlm_i_free(ctx, p->d_targets); pvlm_i_free(ctx, p->d_sources);
-  pvlm_i_free(ctx, p->d_ftargets); pvlm_i_free(ctx, p->d_fsources);
-  pvlm_i_free(ctx, p->d_tail_inv); pvlm_i_free(ctx, p->d_tail_flags);
-  pvlm_i_free(ctx, p->d_idx_rows); pvlm_i_free(ctx, p->d_idx_cols); pvlm_i_free(ctx, p->d_idx_mirror);
-  pvlm_i_free(ctx, p->d_flow_tasks); pvlm_i_free(ctx, p->d_flow_sources); pvlm_i_free(ctx, p->d_flow_cols); pvlm_i_free(ctx, p->d_flow_below_off); pvlm_i_free(ctx, p->d_flow_below);
+  for (void* d : p->owned) pvlm_i_free(ctx, d);
   delete p;
+}
+// A device block that lives as long as the plan (at least 256 bytes, so that an empty list is a valid pointer too).  std::bad_alloc from the list is the caller's.
+template <typename T>
+static pvlm_status spd_plan_alloc(pvlm_ctx* ctx, SpdPlan* P, T** d, size_t bytes) {
+  P->owned.reserve(P->owned.size() + 1);
+  const pvlm_status st = pvlm_i_alloc_bytes(ctx, (void**)d, std::max<size_t>(bytes, 256));
+  if (!st) P->owned.push_back(*d);
+  return st;
 }
 void pvlm_i_spd_plan_release(pvlm_ctx* ctx) { spd_prefetch_drop(ctx); spd_plan_free(ctx, static_cast<SpdPlan*>(ctx->spd_plan)); ctx->spd_plan = nullptr; }
 
@@ -1381,7 +1186,7 @@ static pvlm_status spd_plan_adopt(pvlm_ctx* ctx, int n, SpdHostPlan& H, SpdPlan*
   pvlm_status st = PVLM_OK;
   auto up = [&](void** d, const void* src, size_t bytes) {
     if (st) return;
-    st = pvlm_i_alloc_bytes(ctx, d, std::max<size_t>(bytes, 256));
+    st = spd_plan_alloc(ctx, P, d, bytes);
     if (!st && bytes) st = pvlm_i_h2d_q(ctx, *d, src, bytes);
   };
   if (H.kind == 1) {
@@ -1405,15 +1210,15 @@ static pvlm_status spd_plan_adopt(pvlm_ctx* ctx, int n, SpdHostPlan& H, SpdPlan*
     static const bool want_flow = !(getenv("PVLM_SPD_FLOW") && atoi(getenv("PVLM_SPD_FLOW")) == 0);
     P->flow_possible = want_flow && L.flow.ready && L.flow.tile_cols >= 2 && L.flow.tile_cols <= 4096;
     static_assert(sizeof(pvlm_spd::FlowTask) == sizeof(NdFlowTask) && sizeof(pvlm_spd::FlowSource) == sizeof(NdFlowSource), "flow lists are uploaded as they are");
-    if (want_flow && ctx->spd_one_launch && L.flow.ready && L.flow.tile_cols >= 2 && L.flow.tile_cols <= 4096) {
+    if (P->flow_possible && ctx->spd_one_launch) {
       const pvlm_spd::FlowPlan& F = L.flow;
       up((void**)&P->d_flow_tasks, F.tasks.data(), F.tasks.size() * sizeof(NdFlowTask));
       up((void**)&P->d_flow_sources, F.sources.data(), F.sources.size() * sizeof(NdFlowSource));
       up((void**)&P->d_flow_cols, F.col_order.data(), F.col_order.size() * sizeof(int));
       up((void**)&P->d_flow_below_off, F.below_off.data(), F.below_off.size() * sizeof(int));
       up((void**)&P->d_flow_below, F.below.data(), F.below.size() * sizeof(int));
-      if (!st) st = pvlm_i_alloc_bytes(ctx, (void**)&P->d_tail_inv, (size_t)F.tile_cols * 4096 * sizeof(double));
-      if (!st) st = pvlm_i_alloc_bytes(ctx, (void**)&P->d_tail_flags, ((size_t)2 + F.tasks.size() + 3 * (size_t)F.tile_cols) * sizeof(unsigned));
+      if (!st) st = spd_plan_alloc(ctx, P, &P->d_tail_inv, (size_t)F.tile_cols * 4096 * sizeof(double));
+      if (!st) st = spd_plan_alloc(ctx, P, &P->d_tail_flags, flow_flag_words(F.tasks.size(), F.tile_cols) * sizeof(unsigned));
       if (!st) st = pvlm_i_sync(ctx);
       if (st) return st;
       P->flow_T = F.tile_cols; P->flow_tasks = (int)F.tasks.size(); P->flow_depth = F.depth;
@@ -1423,8 +1228,8 @@ static pvlm_status spd_plan_adopt(pvlm_ctx* ctx, int n, SpdHostPlan& H, SpdPlan*
     if (want_tail && L.tail_col0 < L.cols_total) {
       const int r0 = L.tail_col0 * PVLM_CHOL_NB, T = (L.n_pad - r0) / 64;
       if (T >= 2 && T <= 1024 && r0 % 64 == 0) {
-        st = pvlm_i_alloc_bytes(ctx, (void**)&P->d_tail_inv, (size_t)T * 4096 * sizeof(double));
-        if (!st) st = pvlm_i_alloc_bytes(ctx, (void**)&P->d_tail_flags, tail_flag_words(T) * sizeof(unsigned));
+        st = spd_plan_alloc(ctx, P, &P->d_tail_inv, (size_t)T * 4096 * sizeof(double));
+        if (!st) st = spd_plan_alloc(ctx, P, &P->d_tail_flags, tail_flag_words(T) * sizeof(unsigned));
         if (st) return st;
         P->n_main = L.main_levels; P->tail_r0 = r0; P->tail_T = T;
       }
@@ -1441,78 +1246,74 @@ static pvlm_status spd_plan_adopt(pvlm_ctx* ctx, int n, SpdHostPlan& H, SpdPlan*
   return PVLM_OK;
 }
 
-static void chol_factor_solve_levels(pvlm_ctx* ctx, int n, double* d_M, double* d_b, double* d_Linv, double* d_y, int* d_info, const SpdPlan* P) {
-  hipStream_t s = ctx->stream;
+// PVLM_SPD_TAIL_CLOCK=1: the stamps of nd_tile_flow, twelve per tile column — a zeroed table on the device for the launch, read back and printed after it
+static unsigned long long* tile_clock_begin(pvlm_call& c, int T) {
+  static const bool want_clock = getenv("PVLM_SPD_TAIL_CLOCK") && atoi(getenv("PVLM_SPD_TAIL_CLOCK")) != 0;
+  if (!want_clock) return nullptr;
+  unsigned long long* d_clk = c.alloc<unsigned long long>((size_t)T * 12);
+  c.memset(d_clk, 0, (size_t)T * 12 * sizeof(unsigned long long));
+  return d_clk;
+}
+// waits for the stream.  from_first_stamp: microseconds count from the smallest non-zero first stamp of any column (the one launch takes its tickets in task
+// order), else from column 0's.
+static void tile_clock_print(pvlm_call& c, const unsigned long long* d_clk, int T, bool from_first_stamp, const char* header) {
+  if (!d_clk) return;
+  std::vector<unsigned long long> v((size_t)T * 12);
+  c.d2h(v.data(), d_clk, v.size() * sizeof(unsigned long long));
+  if (c.sync()) return;
+  unsigned long long t0 = v[0];
+  if (from_first_stamp) { t0 = ~0ull; for (int j = 0; j < T; ++j) if (v[(size_t)12 * j]) t0 = std::min(t0, v[(size_t)12 * j]); }
+  fprintf(stderr, "%s\n", header);
+  for (int j = 0; j < T; ++j) {
+    fprintf(stderr, "%3d |", j);
+    for (int q = 0; q < 12; ++q) { const unsigned long long s = v[(size_t)12 * j + q]; if (q == 6) fprintf(stderr, " |"); if (s) fprintf(stderr, " %8.2f", (double)(long long)(s - t0) * 0.01); else fprintf(stderr, "        -"); }
+    fprintf(stderr, "\n");
+  }
+}
+
+// The same factorisation and the two triangular solves by the schedule of a level plan.  One launch (flow_T > 0): k_nd_flow, then k_nd_flow_bwd.  Otherwise per
+// level ONE panel launch (every block column of the level) and ONE update launch (every tile the level's columns reach + the right-hand side rows), the top
+// separator as a dense tail in one launch when the plan has one, then the backward substitution level by level in descending order.
+static void chol_factor_solve_levels(pvlm_call& c, int n, double* d_M, double* d_b, double* d_Linv, double* d_y, int* d_info, const SpdPlan* P) {
   if (P->flow_T > 0) {
     const int T = P->flow_T;
-    (void)hipMemsetAsync(P->d_tail_flags, 0, ((size_t)2 + (size_t)P->flow_tasks + 3 * (size_t)T) * sizeof(unsigned), s);
-    static const bool want_clock = getenv("PVLM_SPD_TAIL_CLOCK") && atoi(getenv("PVLM_SPD_TAIL_CLOCK")) != 0;
-    unsigned long long* d_clk = nullptr;
-    if (want_clock && pvlm_i_alloc_bytes(ctx, (void**)&d_clk, (size_t)T * 12 * sizeof(unsigned long long)) != PVLM_OK) d_clk = nullptr;
-    if (d_clk) (void)hipMemsetAsync(d_clk, 0, (size_t)T * 12 * sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(k_nd_flow, dim3((unsigned)std::min(P->flow_tasks, 1024)), dim3(256), 0, s, d_M, n, T, P->d_tail_inv, P->d_tail_flags, d_info, d_b, d_y,
-                       (const NdFlowTask*)P->d_flow_tasks, (const NdFlowSource*)P->d_flow_sources, P->flow_tasks, d_clk, ctx->spd_withhold_task);
-    if (d_clk) {
-      std::vector<unsigned long long> c((size_t)T * 12);
-      if (hipMemcpyAsync(c.data(), d_clk, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-        unsigned long long t0 = ~0ull;
-        for (int j = 0; j < T; ++j) if (c[(size_t)12 * j]) t0 = std::min(t0, c[(size_t)12 * j]);
-        fprintf(stderr, "k_nd_flow clocks (us from the first ticket): tile column | ticket dep-seen products tile-in-LDS factored published | first tile below: inverse-seen published | 32 pivots, update, 32 pivots\n");
-        for (int j = 0; j < T; ++j) {
-          fprintf(stderr, "%3d |", j);
-          for (int q = 0; q < 12; ++q) { const unsigned long long v = c[(size_t)12 * j + q]; if (q == 6) fprintf(stderr, " |"); if (v) fprintf(stderr, " %8.2f", (double)(long long)(v - t0) * 0.01); else fprintf(stderr, "        -"); }
-          fprintf(stderr, "\n");
-        }
-      }
-      pvlm_i_free(ctx, d_clk);
-    }
-    hipLaunchKernelGGL(k_nd_flow_bwd, dim3((unsigned)T), dim3(256), 0, s, (const double*)d_M, n, T, (const double*)P->d_tail_inv, P->d_tail_flags, P->flow_tasks, d_info, d_b,
-                       (const double*)d_y, (const int*)P->d_flow_cols, (const int*)P->d_flow_below_off, (const int*)P->d_flow_below);
+    c.memset(P->d_tail_flags, 0, flow_flag_words((size_t)P->flow_tasks, T) * sizeof(unsigned));
+    unsigned long long* d_clk = tile_clock_begin(c, T);
+    c.launch(k_nd_flow, dim3((unsigned)std::min(P->flow_tasks, 1024)), dim3(256), 0, d_M, n, T, P->d_tail_inv, P->d_tail_flags, d_info, d_b, d_y,
+             (const NdFlowTask*)P->d_flow_tasks, (const NdFlowSource*)P->d_flow_sources, P->flow_tasks, d_clk, c.ctx->spd_withhold_task);
+    tile_clock_print(c, d_clk, T, true, "k_nd_flow clocks (us from the first ticket): tile column | ticket dep-seen products tile-in-LDS factored published | first tile below: inverse-seen published | 32 pivots, update, 32 pivots");
+    c.launch(k_nd_flow_bwd, dim3((unsigned)T), dim3(256), 0, (const double*)d_M, n, T, (const double*)P->d_tail_inv, P->d_tail_flags, P->flow_tasks, d_info, d_b,
+             (const double*)d_y, (const int*)P->d_flow_cols, (const int*)P->d_flow_below_off, (const int*)P->d_flow_below);
     return;
   }
   const int n_main = P->tail_T > 0 ? P->n_main : P->n_levels;
-  if (P->tail_T > 0) (void)hipMemsetAsync(P->d_tail_flags, 0, tail_flag_words(P->tail_T) * sizeof(unsigned), s);     // ahead of the levels: not between two dependent launches
+  if (P->tail_T > 0) c.memset(P->d_tail_flags, 0, tail_flag_words(P->tail_T) * sizeof(unsigned));     // ahead of the levels: not between two dependent launches
   for (int l = 0; l < n_main; ++l) {
     const int npw = P->pwg_off[(size_t)l + 1] - P->pwg_off[(size_t)l], ntg = P->upd_off[(size_t)l + 1] - P->upd_off[(size_t)l], nft = P->fwd_off[(size_t)l + 1] - P->fwd_off[(size_t)l];
     // eight-row workgroups while they fit the device in about one round (256 CUs x 8 resident workgroups), whole tiles beyond
     const int npt = P->pwt_off[(size_t)l + 1] - P->pwt_off[(size_t)l];
     if (npw > 3072)
-      hipLaunchKernelGGL(k_nd_panel<8>, dim3((unsigned)npt), dim3(256), 0, s, d_M, n, d_Linv, d_info, (const double*)d_b, d_y, (const int2*)P->d_pwt + P->pwt_off[(size_t)l],
-                         (const int*)P->d_row_off, (const int*)P->d_row_tiles);
+      c.launch(k_nd_panel<8>, dim3((unsigned)npt), dim3(256), 0, d_M, n, d_Linv, d_info, (const double*)d_b, d_y, (const int2*)P->d_pwt + P->pwt_off[(size_t)l],
+               (const int*)P->d_row_off, (const int*)P->d_row_tiles);
     else if (npw > 0)
-      hipLaunchKernelGGL(k_nd_panel<1>, dim3((unsigned)npw), dim3(256), 0, s, d_M, n, d_Linv, d_info, (const double*)d_b, d_y, (const int2*)P->d_pwg + P->pwg_off[(size_t)l],
-                         (const int*)P->d_row_off, (const int*)P->d_row_tiles);
+      c.launch(k_nd_panel<1>, dim3((unsigned)npw), dim3(256), 0, d_M, n, d_Linv, d_info, (const double*)d_b, d_y, (const int2*)P->d_pwg + P->pwg_off[(size_t)l],
+               (const int*)P->d_row_off, (const int*)P->d_row_tiles);
     if (ntg + nft > 0)
-      hipLaunchKernelGGL(k_nd_update, dim3((unsigned)(ntg + nft)), dim3(256), 0, s, d_M, n, (const int*)d_info, (const NdTarget*)P->d_targets + P->upd_off[(size_t)l], ntg,
-                         (const int*)P->d_sources, (const NdRowTarget*)P->d_ftargets + P->fwd_off[(size_t)l], (const int*)P->d_fsources, d_b, (const double*)d_y);
+      c.launch(k_nd_update, dim3((unsigned)(ntg + nft)), dim3(256), 0, d_M, n, (const int*)d_info, (const NdTarget*)P->d_targets + P->upd_off[(size_t)l], ntg,
+               (const int*)P->d_sources, (const NdRowTarget*)P->d_ftargets + P->fwd_off[(size_t)l], (const int*)P->d_fsources, d_b, (const double*)d_y);
   }
   if (P->tail_T > 0) {
     const int T = P->tail_T, n_tiles = T * (T + 1) / 2;
-    static const bool want_clock = getenv("PVLM_SPD_TAIL_CLOCK") && atoi(getenv("PVLM_SPD_TAIL_CLOCK")) != 0;
-    unsigned long long* d_clk = nullptr;
-    if (want_clock && pvlm_i_alloc_bytes(ctx, (void**)&d_clk, (size_t)T * 12 * sizeof(unsigned long long)) != PVLM_OK) d_clk = nullptr;
-    if (d_clk) (void)hipMemsetAsync(d_clk, 0, (size_t)T * 12 * sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(k_nd_tail, dim3((unsigned)std::min(n_tiles, 512)), dim3(256), 0, s, d_M, n, P->tail_r0, T, P->d_tail_inv, P->d_tail_flags, d_info, d_b, d_y, d_clk);
-    hipLaunchKernelGGL(k_nd_tail_bwd, dim3((unsigned)T), dim3(256), 0, s, (const double*)d_M, n, P->tail_r0, T, (const double*)P->d_tail_inv, P->d_tail_flags, d_info, d_b, (const double*)d_y);
-    if (d_clk) {
-      std::vector<unsigned long long> c((size_t)T * 12);
-      if (hipMemcpyAsync(c.data(), d_clk, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-        const unsigned long long t0 = c[0];
-        fprintf(stderr, "k_nd_tail clocks (us from the first ticket): col | ticket dep-seen products tile-in-LDS factored published | below: inverse-seen published\n");
-        for (int j = 0; j < T; ++j) {
-          fprintf(stderr, "%3d |", j);
-          for (int q = 0; q < 12; ++q) { const unsigned long long v = c[(size_t)12 * j + q]; if (q == 6) fprintf(stderr, " |"); if (v) fprintf(stderr, " %8.2f", (double)(long long)(v - t0) * 0.01); else fprintf(stderr, "        -"); }
-          fprintf(stderr, "\n");
-        }
-      }
-      pvlm_i_free(ctx, d_clk);
-    }
+    unsigned long long* d_clk = tile_clock_begin(c, T);
+    c.launch(k_nd_tail, dim3((unsigned)std::min(n_tiles, 512)), dim3(256), 0, d_M, n, P->tail_r0, T, P->d_tail_inv, P->d_tail_flags, d_info, d_b, d_y, d_clk);
+    c.launch(k_nd_tail_bwd, dim3((unsigned)T), dim3(256), 0, (const double*)d_M, n, P->tail_r0, T, (const double*)P->d_tail_inv, P->d_tail_flags, d_info, d_b, (const double*)d_y);
+    tile_clock_print(c, d_clk, T, false, "k_nd_tail clocks (us from the first ticket): col | ticket dep-seen products tile-in-LDS factored published | below: inverse-seen published");
   }
   for (int l = n_main - 1; l >= 0; --l) {
     const int nc = P->col_off[(size_t)l + 1] - P->col_off[(size_t)l];
     if (nc > 0)
-      hipLaunchKernelGGL(k_nd_bwd, dim3((unsigned)nc), dim3(1024), 0, s, (const double*)d_M, n, (const double*)d_Linv, d_b, (const double*)d_y, (const int*)d_info,
-                         (const int*)P->d_cols + P->col_off[(size_t)l], (const int*)P->d_row_off, (const int*)P->d_row_tiles);
+      c.launch(k_nd_bwd, dim3((unsigned)nc), dim3(1024), 0, (const double*)d_M, n, (const double*)d_Linv, d_b, (const double*)d_y, (const int*)d_info,
+               (const int*)P->d_cols + P->col_off[(size_t)l], (const int*)P->d_row_off, (const int*)P->d_row_tiles);
   }
 }
 
@@ -1529,6 +1330,211 @@ pvlm_status pvlm_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int*
 
 }  // extern "C"
 
+// ---- pvlm_i_spd_solve_blocks, step by step: plan lookup, permute and pad, device run, timeout report; the entry point below strings them together ---------------
+
+// Is (n, rows, cols, mirror) the structure that have_* was recorded for?  Entry by entry, not by hash: with a colliding structure the tile lists of the old one would
+// skip the new one's non-zeros and the solve would be wrong with info = 0 (three memcmp of ~100 KB at Floor size against a 10 ms solve).
+static bool spd_same_structure(int n, int n_blocks, const int* rows, const int* cols, const int* mirror, int have_n, const std::vector<int>& have_rows,
+                               const std::vector<int>& have_cols, const std::vector<int>& have_mirror) {
+  const size_t idx = (size_t)n_blocks * 6;
+  if (have_n != n || have_rows.size() != idx || have_cols.size() != idx || have_mirror.size() != (size_t)n_blocks) return false;
+  return n_blocks == 0 || (std::memcmp(have_rows.data(), rows, idx * sizeof(int)) == 0 && std::memcmp(have_cols.data(), cols, idx * sizeof(int)) == 0 &&
+                           std::memcmp(have_mirror.data(), mirror, (size_t)n_blocks * sizeof(int)) == 0);
+}
+
+// what the caller of pvlm_i_spd_solve_blocks handed in
+struct SpdSystem {
+  int n, n_blocks;
+  const int* row_idx; const int* col_idx; const int* mirror;
+  const double* blocks; bool blocks_on_device;
+  const double* scale; const double* diag_add;
+  double* rhs;
+};
+
+// The plan of this structure (ordering + tile lists): the context's while the index lists and the choice between one launch and level launches stay the same, else
+// a new one — the old plan is freed first, then the host half is taken from pvlm_spd_plan_prefetch when that was given exactly these lists (it has been running beside
+// the caller's GPU work) or made now.  May throw std::bad_alloc.
+static pvlm_status spd_plan_lookup(pvlm_ctx* ctx, const SpdSystem& A, SpdPlan** out) {
+  const int n = A.n, n_blocks = A.n_blocks;
+  SpdPlan* plan = static_cast<SpdPlan*>(ctx->spd_plan);
+  const unsigned long long key = spd_hash(n, n_blocks, A.row_idx, A.col_idx, A.mirror);
+  *out = plan;
+  if (plan && plan->key == key && (!plan->levels || (plan->flow_T > 0) == (ctx->spd_one_launch != 0 && plan->flow_possible)) &&
+      spd_same_structure(n, n_blocks, A.row_idx, A.col_idx, A.mirror, plan->n, plan->key_rows, plan->key_cols, plan->key_mirror))
+    return PVLM_OK;
+  *out = nullptr;
+  PVLM_TRY_SYNC(ctx);
+  pvlm_i_trace("spd solve: before the plan");
+  spd_plan_free(ctx, plan); ctx->spd_plan = nullptr;      // the old plan only: a prefetch in flight is looked at below
+  plan = new SpdPlan();
+  ctx->spd_plan = plan;
+  plan->key = key;
+  plan->key_rows.assign(A.row_idx, A.row_idx + (size_t)n_blocks * 6); plan->key_cols.assign(A.col_idx, A.col_idx + (size_t)n_blocks * 6);
+  plan->key_mirror.assign(A.mirror, A.mirror + n_blocks);
+  SpdPrefetch* pre = static_cast<SpdPrefetch*>(ctx->spd_prefetch);
+  bool taken = false;
+  pvlm_status st = PVLM_OK;
+  if (pre) {
+    const auto tj = std::chrono::steady_clock::now();
+    if (pre->worker.joinable()) pre->worker.join();
+    if (getenv("PVLM_TRACE")) {
+      char msg[128];
+      snprintf(msg, sizeof msg, "spd plan prefetch: thread %.2f ms, joined after %.2f ms", pre->worker_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj).count());
+      pvlm_i_trace(msg);
+    }
+    if (!pre->failed && spd_same_structure(n, n_blocks, A.row_idx, A.col_idx, A.mirror, pre->n, pre->rows, pre->cols, pre->mirror)) {
+      st = spd_plan_adopt(ctx, n, pre->host, plan);
+      taken = true;
+    }
+    spd_prefetch_drop(ctx);
+  }
+  ctx->spd_prefetch_hits += taken ? 1 : 0;
+  if (!taken) {
+    SpdHostPlan host;
+    spd_plan_host(n, n_blocks, A.row_idx, A.col_idx, &host);
+    st = spd_plan_adopt(ctx, n, host, plan);
+  }
+  if (st) { pvlm_i_spd_plan_release(ctx); return st; }
+  if (getenv("PVLM_TRACE")) { char msg[96]; snprintf(msg, sizeof msg, "spd plan built: %s, update fraction %.3f, n %d, blocks %d", plan->sparse ? "tile-sparse" : "dense", plan->update_fraction, n, n_blocks); pvlm_i_trace(msg); }
+  *out = plan;
+  return PVLM_OK;
+}
+
+// The system as the device sees it: n rows (the level plan pads), lists and vectors in the plan's order.  A dense plan keeps the caller's order and arrays; rows and
+// cols are null when the plan has the permuted lists on the device already.
+struct SpdPermuted {
+  int n = 0;
+  const int* rows = nullptr; const int* cols = nullptr;
+  const double* scale = nullptr; const double* diag = nullptr;
+  double* rhs = nullptr;                                  // in: the right-hand side; out: the solution (spd_unpermute takes it back to the caller's order)
+  std::vector<int> own_rows, own_cols; std::vector<double> own_scale, own_diag, own_rhs;     // what the pointers above point into for a tile-sparse plan
+};
+static void spd_permute(const SpdPlan* plan, const SpdSystem& A, SpdPermuted* p) {
+  p->n = plan->levels ? plan->n_pad : A.n;
+  p->rows = A.row_idx; p->cols = A.col_idx; p->scale = A.scale; p->diag = A.diag_add; p->rhs = A.rhs;
+  if (!plan->sparse) return;
+  const std::vector<int>& nw = plan->new_of_old;
+  const int n = A.n;
+  p->rows = p->cols = nullptr;
+  if (!plan->idx_on_device) {
+    p->own_rows.resize((size_t)A.n_blocks * 6); p->own_cols.resize((size_t)A.n_blocks * 6);
+    for (size_t k = 0; k < p->own_rows.size(); ++k) {
+      p->own_rows[k] = A.row_idx[k] >= 0 && A.row_idx[k] < n ? nw[(size_t)A.row_idx[k]] : -1;
+      p->own_cols[k] = A.col_idx[k] >= 0 && A.col_idx[k] < n ? nw[(size_t)A.col_idx[k]] : -1;
+    }
+    p->rows = p->own_rows.data(); p->cols = p->own_cols.data();
+  }
+  // dummy rows of the padding are identity rows (scale 1, diagonal 1, right-hand side 0 -> solution 0)
+  p->own_scale.assign((size_t)p->n, 1.0); p->own_diag.assign((size_t)p->n, 1.0); p->own_rhs.assign((size_t)p->n, 0.0);
+  for (int i = 0; i < n; ++i) { const size_t q = (size_t)nw[(size_t)i]; p->own_scale[q] = A.scale[i]; p->own_diag[q] = A.diag_add[i]; p->own_rhs[q] = A.rhs[i]; }
+  p->scale = p->own_scale.data(); p->diag = p->own_diag.data(); p->rhs = p->own_rhs.data();
+}
+static void spd_unpermute(const SpdPlan* plan, const SpdPermuted& p, const SpdSystem& A) {
+  if (plan->sparse) for (int i = 0; i < A.n; ++i) A.rhs[i] = p.own_rhs[(size_t)plan->new_of_old[(size_t)i]];
+}
+
+// Assembles M = D (sum of blocks) D + diag on the device, factorises it by the plan's form and solves; *info and the solution (into p.rhs) have landed when it
+// returns PVLM_OK.  The matrix and the vectors live in the context's grow-only workspace; the index lists of a tile-sparse plan go to the device once and stay with
+// the plan.  Order on the stream: zero M, values and lists, assembly, d_info = 0, factorisation and solves, downloads.
+static pvlm_status spd_device_run(pvlm_call& c, SpdPlan* plan, const SpdSystem& A, const SpdPermuted& p, int* info) {
+  pvlm_ctx* ctx = c.ctx;
+  const int n = p.n, n_blocks = A.n_blocks;
+  const size_t n_idx = (size_t)n_blocks * 6;
+  const size_t linv_count = (size_t)((n + PVLM_CHOL_NB - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
+  const size_t staged_blocks = A.blocks_on_device ? 0 : (size_t)n_blocks * 36;          // values the caller holds on the device are read where they are
+  const size_t need = pad256((size_t)n * n * 8) + pad256(staged_blocks * 8) + 3 * pad256(n_idx * 4) + 4 * pad256((size_t)n * 8) + pad256(linv_count * 8) + 256;
+  if ((c.st = ws_reserve(ctx, need))) return c.st;
+  WsCarver ws{static_cast<char*>(ctx->d_ws)};
+  double* d_M = ws.take<double>((size_t)n * n); double* d_staged = ws.take<double>(staged_blocks);
+  int* d_row = ws.take<int>(n_idx); int* d_col = ws.take<int>(n_idx); int* d_mir = ws.take<int>(n_idx);
+  double* d_scale = ws.take<double>(n); double* d_diag = ws.take<double>(n); double* d_rhs = ws.take<double>(n);
+  double* d_y = ws.take<double>(n); double* d_Linv = ws.take<double>(linv_count);
+  int* d_info = ws.take<int>(1);
+  // only the tiles the one launch reads have to start from zero
+  if (plan->flow_T > 0) c.launch(k_zero_flow_tiles, dim3((unsigned)plan->flow_tasks), dim3(256), 0, d_M, n, (const NdFlowTask*)plan->d_flow_tasks);
+  else c.memset(d_M, 0, (size_t)n * n * sizeof(double));
+  const double* d_blocks = A.blocks;
+  if (n_blocks) {
+    // through the pinned arena (1.3 MB of blocks at Room scale, once per LM step: a pageable copy locks the caller's pages)
+    if (!A.blocks_on_device) { c.h2d(d_staged, A.blocks, (size_t)n_blocks * 36 * sizeof(double)); d_blocks = d_staged; }
+    if (plan->sparse && !plan->idx_on_device) {
+      // the (permuted) index lists of this structure stay on the device with the plan: later solves send the values only
+      if (!c.st) c.st = spd_plan_alloc(ctx, plan, &plan->d_idx_rows, n_idx * sizeof(int));
+      if (!c.st) c.st = spd_plan_alloc(ctx, plan, &plan->d_idx_cols, n_idx * sizeof(int));
+      if (!c.st) c.st = spd_plan_alloc(ctx, plan, &plan->d_idx_mirror, (size_t)n_blocks * sizeof(int));
+      c.h2d(plan->d_idx_rows, p.rows, n_idx * sizeof(int));
+      c.h2d(plan->d_idx_cols, p.cols, n_idx * sizeof(int));
+      c.h2d(plan->d_idx_mirror, A.mirror, (size_t)n_blocks * sizeof(int));
+      if (!c.st) plan->idx_on_device = true;
+    }
+    if (plan->idx_on_device) { d_row = plan->d_idx_rows; d_col = plan->d_idx_cols; d_mir = plan->d_idx_mirror; }
+    else {
+      c.h2d(d_row, p.rows, n_idx * sizeof(int));
+      c.h2d(d_col, p.cols, n_idx * sizeof(int));
+      c.h2d(d_mir, A.mirror, (size_t)n_blocks * sizeof(int));
+    }
+  }
+  c.h2d(d_scale, p.scale, (size_t)n * sizeof(double));
+  c.h2d(d_diag, p.diag, (size_t)n * sizeof(double));
+  c.h2d(d_rhs, p.rhs, (size_t)n * sizeof(double));
+  if (n_blocks) c.launch(k_scatter_blocks, dim3((unsigned)(((long long)n_blocks * 36 + 255) / 256)), dim3(256), 0, n, n_blocks, d_row, d_col, d_mir, d_blocks, (const double*)d_scale, d_M);
+  c.launch(k_add_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, n, (const double*)d_diag, d_M);
+  c.check_launches();
+  c.memset(d_info, 0, sizeof(int));                      // after the assembly, ahead of the first launch that tests it
+  if (plan->levels) chol_factor_solve_levels(c, n, d_M, d_rhs, d_Linv, d_y, d_info, plan);
+  else {
+    const SpdTileLists lists{plan->d_row_tiles, plan->d_pairs, plan->row_off.data(), plan->pair_off.data()};
+    chol_factor_solve(c, n, d_M, d_rhs, 1, d_Linv, d_y, d_info, plan->sparse ? &lists : nullptr);
+  }
+  c.check_launches();
+  c.d2h(info, d_info, sizeof(int));
+  c.d2h(p.rhs, d_rhs, (size_t)n * sizeof(double));
+  return c.sync();
+}
+
+// A wait inside the one-launch factorisation ran into its limit (info = -1, see tail_wait): says where, and with PVLM_SPD_FLOW_DEBUG what every workgroup that had
+// not finished its task was doing.  The record is cleared: the next event writes its own.
+static void spd_timeout_report(const SpdPlan* plan) {
+  unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const unsigned zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (hipMemcpyFromSymbol(w, HIP_SYMBOL(g_tail_timeout), sizeof w) != hipSuccess) { (void)hipGetLastError(); return; }
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tail_timeout), zero8, sizeof zero8);
+  fprintf(stderr, "pvlm_spd_solve_blocks: a wait of the one-launch factorisation ran into its limit (site %u, task / ticket %u, flag word %u of %d tasks + 3 x %d, tickets %u / %u, workgroup %u)\n",
+          w[1], w[2], w[3], plan->flow_tasks, plan->flow_T, w[4], w[5], w[6]);
+  std::vector<unsigned> wg(2048, 0);
+  if (!getenv("PVLM_SPD_FLOW_DEBUG") || hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_wg_state), wg.size() * 4) != hipSuccess) return;
+  std::vector<NdFlowTask> tk((size_t)plan->flow_tasks);
+  (void)hipMemcpy(tk.data(), plan->d_flow_tasks, tk.size() * sizeof(NdFlowTask), hipMemcpyDeviceToHost);
+  std::vector<unsigned> fl(flow_flag_words(tk.size(), plan->flow_T));
+  (void)hipMemcpy(fl.data(), plan->d_tail_flags, fl.size() * 4, hipMemcpyDeviceToHost);
+  for (int g = 0; g < 1024; ++g) {
+    const unsigned task = wg[2 * g], ph = wg[2 * g + 1];
+    if ((ph & 255u) >= 9u || task >= tk.size()) continue;
+    const NdFlowTask& q = tk[task];
+    fprintf(stderr, "  wg %4d task %6u (I %3d J %3d n_src %3d prev %6d final %d) phase %u source %u | own flag %u prev flag %d inv flag %u\n", g, task, q.I, q.J, q.n_src, q.prev, q.final_,
+            ph & 255u, ph >> 8, fl[2 + task], q.prev >= 0 ? (int)fl[2 + (size_t)q.prev] : -1, fl[2 + tk.size() + (size_t)q.J]);
+  }
+}
+
+// One pass of the solve with the plan the context's state selects.  *redo: the one launch did not get through (reported); nothing of the caller's has been written.
+// Otherwise, on PVLM_OK, the solution is in A.rhs and *info_out set.
+static pvlm_status spd_solve_pass(pvlm_call& c, const SpdSystem& A, int* info_out, bool* redo) {
+  *redo = false;
+  SpdPlan* plan = nullptr;
+  const pvlm_status pst = spd_plan_lookup(c.ctx, A, &plan);
+  if (pst) return c.st = pst;
+  SpdPermuted p;
+  spd_permute(plan, A, &p);
+  int info = 0;
+  if (spd_device_run(c, plan, A, p, &info)) return c.st;
+  if (info == -1) spd_timeout_report(plan);            // the step is reported as failed unless the solve can be redone
+  if (info == -1 && plan->flow_T > 0) { *redo = true; return PVLM_OK; }
+  pvlm_i_trace("spd solve: factorised and solved");
+  spd_unpermute(plan, p, A);
+  *info_out = info;
+  return PVLM_OK;
+}
+
 // The same solve for a caller inside the library whose block VALUES already sit on the device (blocks_on_device: `blocks` is a device pointer that stays valid and
 // unchanged until the call returns; the copy through the pinned arena is skipped and the scatter reads it in place).  Everything else is the caller's host memory.
 pvlm_status pvlm_i_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const int* row_idx, const int* col_idx, const int* mirror, const double* blocks,
@@ -1537,174 +1543,21 @@ pvlm_status pvlm_i_spd_solve_blocks(pvlm_ctx* ctx, int n, int n_blocks, const in
     return PVLM_ERR_ARG;
   *info_out = 0;
   if (n == 0) return PVLM_OK;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  const int* const user_rows = row_idx; const int* const user_cols = col_idx; const double* const user_scale = scale; const double* const user_diag = diag_add;
-  // the plan of this structure (ordering + tile lists), built once and reused while the index lists stay the same
-  SpdPlan* plan = static_cast<SpdPlan*>(ctx->spd_plan);
-  std::vector<int> prow, pcol;
-  std::vector<double> pscale, pdiag, prhs;
+  pvlm_call c(ctx, "pvlm_spd_solve_blocks");
+  if (c.enter()) return c.st;
+  const SpdSystem A{n, n_blocks, row_idx, col_idx, mirror, blocks, blocks_on_device, scale, diag_add, rhs};
   try {
-    const unsigned long long key = spd_hash(n, n_blocks, row_idx, col_idx, mirror);
-    // a hit needs the SAME index lists, not only the same 64-bit hash: with a colliding structure the tile lists of the old one would skip the new
-    // one's non-zeros and the solve would be wrong with info = 0 (three memcmp of ~100 KB at Floor size against a 10 ms solve)
-    const bool same = plan && plan->key == key && plan->n == n && (!plan->levels || (plan->flow_T > 0) == (ctx->spd_one_launch != 0 && plan->flow_possible)) && plan->key_rows.size() == (size_t)n_blocks * 6 && plan->key_mirror.size() == (size_t)n_blocks &&
-                      std::memcmp(plan->key_rows.data(), row_idx, (size_t)n_blocks * 6 * sizeof(int)) == 0 &&
-                      std::memcmp(plan->key_cols.data(), col_idx, (size_t)n_blocks * 6 * sizeof(int)) == 0 &&
-                      std::memcmp(plan->key_mirror.data(), mirror, (size_t)n_blocks * sizeof(int)) == 0;
-    if (!same) {
-      PVLM_TRY_SYNC(ctx);
-      pvlm_i_trace("spd solve: before the plan");
-      spd_plan_free(ctx, static_cast<SpdPlan*>(ctx->spd_plan)); ctx->spd_plan = nullptr;      // the old plan only: a prefetch in flight is looked at below
-      plan = new SpdPlan();
-      plan->key = key;
-      plan->key_rows.assign(row_idx, row_idx + (size_t)n_blocks * 6); plan->key_cols.assign(col_idx, col_idx + (size_t)n_blocks * 6);
-      plan->key_mirror.assign(mirror, mirror + n_blocks);
-      ctx->spd_plan = plan;
-      // the host half: taken from pvlm_spd_plan_prefetch when that was given exactly these lists (it has been running beside the caller's GPU work), else made now
-      SpdPrefetch* pre = static_cast<SpdPrefetch*>(ctx->spd_prefetch);
-      bool taken = false;
-      pvlm_status pst = PVLM_OK;
-      if (pre) {
-        const auto tj = std::chrono::steady_clock::now();
-        if (pre->worker.joinable()) pre->worker.join();
-        if (getenv("PVLM_TRACE")) {
-          char msg[128];
-          snprintf(msg, sizeof msg, "spd plan prefetch: thread %.2f ms, joined after %.2f ms", pre->worker_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tj).count());
-          pvlm_i_trace(msg);
-        }
-        if (!pre->failed && pre->n == n && pre->n_blocks == n_blocks && pre->rows == plan->key_rows && pre->cols == plan->key_cols && pre->mirror == plan->key_mirror) {
-          pst = spd_plan_adopt(ctx, n, pre->host, plan);
-          taken = true;
-        }
-        spd_prefetch_drop(ctx);
-      }
-      ctx->spd_prefetch_hits += taken ? 1 : 0;
-      if (!taken) {
-        SpdHostPlan host;
-        spd_plan_host(n, n_blocks, row_idx, col_idx, &host);
-        pst = spd_plan_adopt(ctx, n, host, plan);
-      }
-      if (pst) { pvlm_i_spd_plan_release(ctx); return pst; }
-      if (getenv("PVLM_TRACE")) { char msg[96]; snprintf(msg, sizeof msg, "spd plan built: %s, update fraction %.3f, n %d, blocks %d", plan->sparse ? "tile-sparse" : "dense", plan->update_fraction, n, n_blocks); pvlm_i_trace(msg); }
-    }
-    if (plan->sparse) {
-      const std::vector<int>& nw = plan->new_of_old;
-      if (!plan->idx_on_device) {
-        prow.resize((size_t)n_blocks * 6); pcol.resize((size_t)n_blocks * 6);
-        for (size_t k = 0; k < prow.size(); ++k) { prow[k] = row_idx[k] >= 0 && row_idx[k] < n ? nw[(size_t)row_idx[k]] : -1; pcol[k] = col_idx[k] >= 0 && col_idx[k] < n ? nw[(size_t)col_idx[k]] : -1; }
-      }
-      // the level plan pads the system: dummy rows are identity rows (scale 1, diagonal 1, right-hand side 0 -> solution 0)
-      const size_t np = plan->levels ? (size_t)plan->n_pad : (size_t)n;
-      pscale.assign(np, 1.0); pdiag.assign(np, 1.0); prhs.assign(np, 0.0);
-      for (int i = 0; i < n; ++i) { const size_t q = (size_t)nw[(size_t)i]; pscale[q] = scale[i]; pdiag[q] = diag_add[i]; prhs[q] = rhs[i]; }
-      if (!plan->idx_on_device) { row_idx = prow.data(); col_idx = pcol.data(); }
-      scale = pscale.data(); diag_add = pdiag.data();
-    }
+    bool redo = false;
+    if (spd_solve_pass(c, A, info_out, &redo) || !redo) return c.st;
+    // Not a property of the matrix: the launch did not get through (see tail_wait).  This context factorises by level launches from here on and this solve is
+    // redone with them — same inputs (the caller's right-hand side has not been touched yet), a fresh plan without the one launch, a deterministic result again.
+    ctx->spd_one_launch = 0; ctx->spd_fallbacks += 1;
+    fprintf(stderr, "pvlm_spd_solve_blocks: redone with the level launches; this context keeps them (pvlm_spd_one_launch)\n");
+    return spd_solve_pass(c, A, info_out, &redo);
   } catch (const std::bad_alloc&) {
     PVLM_SET_ERR(ctx, "pvlm_spd_solve_blocks: out of host memory");
     return PVLM_ERR_NOMEM;
   }
-  double* rhs_io = plan->sparse ? prhs.data() : rhs;
-  const int n_user = n;
-  if (plan->levels) n = plan->n_pad;                     // from here on the device works on the padded system
-  SpdTileLists lists{plan->d_row_tiles, plan->d_pairs, plan->row_off.data(), plan->pair_off.data()};
-  const size_t linv_count = (size_t)((n + PVLM_CHOL_NB - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB;
-  const size_t staged_blocks = blocks_on_device ? 0 : (size_t)n_blocks * 36;          // values the caller holds on the device are read where they are
-  const size_t need = pad256((size_t)n * n * 8) + pad256(staged_blocks * 8) + 3 * pad256((size_t)n_blocks * 6 * 4) + 4 * pad256((size_t)n * 8) +
-                      pad256(linv_count * 8) + 256;
-  pvlm_status st = ws_reserve(ctx, need);
-  if (st) return st;
-  WsCarver ws{static_cast<char*>(ctx->d_ws)};
-  double* d_M = ws.take<double>((size_t)n * n); double* d_blocks = ws.take<double>(staged_blocks);
-  int* d_row = ws.take<int>((size_t)n_blocks * 6); int* d_col = ws.take<int>((size_t)n_blocks * 6); int* d_mir = ws.take<int>((size_t)n_blocks * 6);
-  double* d_scale = ws.take<double>(n); double* d_diag = ws.take<double>(n); double* d_rhs = ws.take<double>(n);
-  double* d_y = ws.take<double>(n); double* d_Linv = ws.take<double>(linv_count);
-  int* d_info = ws.take<int>(1);
-  if (!st) {
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipSuccess;
-    if (plan->levels && plan->flow_T > 0) hipLaunchKernelGGL(k_zero_flow_tiles, dim3((unsigned)plan->flow_tasks), dim3(256), 0, s, d_M, n, (const NdFlowTask*)plan->d_flow_tasks);
-    else e = hipMemsetAsync(d_M, 0, (size_t)n * n * sizeof(double), s);
-    // through the pinned arena (1.3 MB of blocks at Room scale, once per LM step: a pageable copy locks the caller's pages)
-    if (e == hipSuccess && n_blocks) {
-      if (blocks_on_device) d_blocks = const_cast<double*>(blocks);
-      else st = pvlm_i_h2d_q(ctx, d_blocks, blocks, (size_t)n_blocks * 36 * sizeof(double));
-      if (plan->sparse && !plan->idx_on_device && !st) {
-        // the (permuted) index lists of this structure stay on the device with the plan: later solves send the values only
-        st = pvlm_i_alloc(ctx, &plan->d_idx_rows, (size_t)n_blocks * 6);
-        if (!st) st = pvlm_i_alloc(ctx, &plan->d_idx_cols, (size_t)n_blocks * 6);
-        if (!st) st = pvlm_i_alloc(ctx, &plan->d_idx_mirror, (size_t)n_blocks);
-        if (!st) st = pvlm_i_h2d_q(ctx, plan->d_idx_rows, row_idx, (size_t)n_blocks * 6 * sizeof(int));
-        if (!st) st = pvlm_i_h2d_q(ctx, plan->d_idx_cols, col_idx, (size_t)n_blocks * 6 * sizeof(int));
-        if (!st) st = pvlm_i_h2d_q(ctx, plan->d_idx_mirror, mirror, (size_t)n_blocks * sizeof(int));
-        if (!st) plan->idx_on_device = true;
-      }
-      if (plan->idx_on_device) { d_row = plan->d_idx_rows; d_col = plan->d_idx_cols; d_mir = plan->d_idx_mirror; }
-      else {
-        if (!st) st = pvlm_i_h2d_q(ctx, d_row, row_idx, (size_t)n_blocks * 6 * sizeof(int));
-        if (!st) st = pvlm_i_h2d_q(ctx, d_col, col_idx, (size_t)n_blocks * 6 * sizeof(int));
-        if (!st) st = pvlm_i_h2d_q(ctx, d_mir, mirror, (size_t)n_blocks * sizeof(int));
-      }
-    }
-    if (e == hipSuccess && !st) st = pvlm_i_h2d_q(ctx, d_scale, scale, (size_t)n * sizeof(double));
-    if (e == hipSuccess && !st) st = pvlm_i_h2d_q(ctx, d_diag, diag_add, (size_t)n * sizeof(double));
-    if (e == hipSuccess && !st) st = pvlm_i_h2d_q(ctx, d_rhs, rhs_io, (size_t)n * sizeof(double));
-    int info = 0;
-    if (e == hipSuccess && !st) {
-      if (n_blocks) hipLaunchKernelGGL(k_scatter_blocks, dim3((unsigned)(((long long)n_blocks * 36 + 255) / 256)), dim3(256), 0, s, n, n_blocks, d_row, d_col, d_mir, d_blocks, d_scale, d_M);
-      hipLaunchKernelGGL(k_add_diag, dim3((n + 255) / 256), dim3(256), 0, s, n, d_diag, d_M);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && !st) e = hipMemsetAsync(d_info, 0, sizeof(int), s);
-    if (e == hipSuccess && !st) {
-      if (plan->levels) chol_factor_solve_levels(ctx, n, d_M, d_rhs, d_Linv, d_y, d_info, plan);
-      else chol_factor_solve(ctx, n, d_M, d_rhs, 1, d_Linv, d_y, d_info, plan->sparse ? &lists : nullptr);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_spd_solve_blocks: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-    if (!st) st = pvlm_i_d2h_q(ctx, &info, d_info, sizeof(int));
-    if (!st) st = pvlm_i_d2h_q(ctx, rhs_io, d_rhs, (size_t)n * sizeof(double));
-    { const pvlm_status s2 = pvlm_i_sync(ctx); if (!st) st = s2; }
-    if (!st && info == -1) {                       // a wait inside the one-launch factorisation ran into its limit: say where (the step is reported as failed)
-      unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      const unsigned zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      const bool got = hipMemcpyFromSymbol(w, HIP_SYMBOL(g_tail_timeout), sizeof w) == hipSuccess;
-      if (got) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tail_timeout), zero8, sizeof zero8);        // the next event records its own site
-      if (got)
-      {
-        fprintf(stderr, "pvlm_spd_solve_blocks: a wait of the one-launch factorisation ran into its limit (site %u, task / ticket %u, flag word %u of %d tasks + 3 x %d, tickets %u / %u, workgroup %u)\n",
-                w[1], w[2], w[3], plan->flow_tasks, plan->flow_T, w[4], w[5], w[6]);
-        std::vector<unsigned> wg(2048, 0);
-        if (getenv("PVLM_SPD_FLOW_DEBUG") && hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_wg_state), wg.size() * 4) == hipSuccess) {
-          std::vector<NdFlowTask> tk((size_t)plan->flow_tasks);
-          (void)hipMemcpy(tk.data(), plan->d_flow_tasks, tk.size() * sizeof(NdFlowTask), hipMemcpyDeviceToHost);
-          std::vector<unsigned> fl((size_t)2 + tk.size() + 3 * (size_t)plan->flow_T);
-          (void)hipMemcpy(fl.data(), plan->d_tail_flags, fl.size() * 4, hipMemcpyDeviceToHost);
-          for (int g = 0; g < 1024; ++g) {
-            const unsigned task = wg[2 * g], ph = wg[2 * g + 1];
-            if ((ph & 255u) >= 9u || task >= tk.size()) continue;
-            const NdFlowTask& q = tk[task];
-            fprintf(stderr, "  wg %4d task %6u (I %3d J %3d n_src %3d prev %6d final %d) phase %u source %u | own flag %u prev flag %d inv flag %u\n", g, task, q.I, q.J, q.n_src, q.prev, q.final_,
-                    ph & 255u, ph >> 8, fl[2 + task], q.prev >= 0 ? (int)fl[2 + (size_t)q.prev] : -1, fl[2 + tk.size() + (size_t)q.J]);
-          }
-        }
-      }
-      else (void)hipGetLastError();
-    }
-    if (!st && info == -1 && plan->levels && plan->flow_T > 0) {
-      // Not a property of the matrix: the launch did not get through (see tail_wait).  This context factorises by level launches from here on and this solve is
-      // redone with them — same inputs (the caller's right-hand side has not been touched yet), a deterministic result again.
-      ctx->spd_one_launch = 0; ctx->spd_fallbacks += 1;
-      fprintf(stderr, "pvlm_spd_solve_blocks: redone with the level launches; this context keeps them (pvlm_spd_one_launch)\n");
-      return pvlm_i_spd_solve_blocks(ctx, n_user, n_blocks, user_rows, user_cols, mirror, blocks, blocks_on_device, user_scale, user_diag, rhs, info_out);
-    }
-    pvlm_i_trace("spd solve: factorised and solved");
-    if (!st && plan->sparse) for (int i = 0; i < n_user; ++i) rhs[i] = prhs[(size_t)plan->new_of_old[(size_t)i]];
-    *info_out = info;
-  } else {
-    hipStreamSynchronize(ctx->stream);
-  }
-  return st;
 }
 
 extern "C" {
@@ -1717,10 +1570,7 @@ pvlm_status pvlm_spd_plan_prefetch(pvlm_ctx* ctx, int n, int n_blocks, const int
   // a structure the context already holds a plan for needs none
   const SpdPlan* have = static_cast<const SpdPlan*>(ctx->spd_plan);
   try {
-    if (have && have->n == n && have->key_mirror.size() == (size_t)n_blocks && have->key_rows.size() == (size_t)n_blocks * 6 &&
-        (n_blocks == 0 || (std::memcmp(have->key_rows.data(), row_idx, (size_t)n_blocks * 6 * sizeof(int)) == 0 && std::memcmp(have->key_cols.data(), col_idx, (size_t)n_blocks * 6 * sizeof(int)) == 0 &&
-                           std::memcmp(have->key_mirror.data(), mirror, (size_t)n_blocks * sizeof(int)) == 0)))
-      return PVLM_OK;
+    if (have && spd_same_structure(n, n_blocks, row_idx, col_idx, mirror, have->n, have->key_rows, have->key_cols, have->key_mirror)) return PVLM_OK;
     SpdPrefetch* f = new SpdPrefetch();
     ctx->spd_prefetch = f;
     f->n = n; f->n_blocks = n_blocks;
@@ -1789,31 +1639,24 @@ pvlm_status pvlm_spd_solve(pvlm_ctx* ctx, int n, int nrhs, const double* A, doub
   if (!ctx || n < 0 || nrhs < 0 || !info_out || (n > 0 && (!A || (nrhs > 0 && !B)))) return PVLM_ERR_ARG;
   *info_out = 0;
   if (n == 0 || nrhs == 0) return PVLM_OK;
-  if (pvlm_i_bind(ctx)) return PVLM_ERR_HIP;
-  double *d_A = nullptr, *d_B = nullptr, *d_Linv = nullptr, *d_y = nullptr; int* d_info = nullptr;
-  pvlm_status st = pvlm_i_alloc(ctx, &d_A, (size_t)n * n);
-  if (!st) st = pvlm_i_alloc(ctx, &d_B, (size_t)n * nrhs);
-  if (!st) st = pvlm_i_alloc(ctx, &d_Linv, (size_t)((n + PVLM_CHOL_NB - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB);
-  if (!st) st = pvlm_i_alloc(ctx, &d_y, (size_t)n);
-  if (!st) st = pvlm_i_alloc(ctx, &d_info, (size_t)1);
-  if (!st) {
-    hipError_t e = hipMemcpyAsync(d_A, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_B, B, (size_t)n * nrhs * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    int info = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(d_info, 0, sizeof(int), ctx->stream);
-    if (e == hipSuccess) {
-      chol_factor_solve(ctx, n, d_A, d_B, nrhs, d_Linv, d_y, d_info);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(B, d_B, (size_t)n * nrhs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    *info_out = info;
-    if (e != hipSuccess) { PVLM_SET_ERR(ctx, "pvlm_spd_solve: %s", hipGetErrorString(e)); st = PVLM_ERR_HIP; }
-  }
-  hipStreamSynchronize(ctx->stream);
-  pvlm_i_free(ctx, d_A); pvlm_i_free(ctx, d_B); pvlm_i_free(ctx, d_Linv); pvlm_i_free(ctx, d_y); pvlm_i_free(ctx, d_info);
-  return st;
+  pvlm_call c(ctx, "pvlm_spd_solve");
+  if (c.enter()) return c.st;
+  double* d_A = c.alloc<double>((size_t)n * n);
+  double* d_B = c.alloc<double>((size_t)n * nrhs);
+  double* d_Linv = c.alloc<double>((size_t)((n + PVLM_CHOL_NB - 1) / PVLM_CHOL_NB) * PVLM_CHOL_NB * PVLM_CHOL_NB);
+  double* d_y = c.alloc<double>((size_t)n);
+  int* d_info = c.alloc<int>(1);
+  // the matrix and the right-hand sides straight from and to the caller's buffers: too large for the staging arena to pay
+  c.copy_pinned(d_A, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  c.copy_pinned(d_B, B, (size_t)n * nrhs * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  c.memset(d_info, 0, sizeof(int));
+  chol_factor_solve(c, n, d_A, d_B, nrhs, d_Linv, d_y, d_info);
+  c.check_launches();
+  int info = 0;
+  c.d2h(&info, d_info, sizeof(int));
+  c.copy_pinned(B, d_B, (size_t)n * nrhs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (c.sync() == PVLM_OK) *info_out = info;
+  return c.st;
 }
 
 }  // extern "C"

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Wall time of pvlm_spd_solve_blocks (K10: device assembly + blocked Cholesky + triangular solves) on a Room-sized
 reduced pose system: P poses (6 unknowns each), pose 0 constant, every pose coupled to its next `band` poses.
-PVLM_CHOL_VALU=1 selects the VALU trailing update instead of the MFMA-f64 one — only in a library built with
--DPVLM_MEASURED_VARIANTS=1 (PVLM_LIB=build/var/libpvlm_measured.so); the default library has the MFMA update only.  Checks the residual of the solution."""
+Checks the residual of the solution."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,8 +39,7 @@ def main():
     ts = []
     for _ in range(a.reps):
         t0 = time.perf_counter(); ctx.spd_solve_blocks(n, rows, cols, mirror, blocks, scale, diag, rhs); ts.append(time.perf_counter() - t0)
-    print(json.dumps(dict(unknowns=n, blocks=len(blocks), variant="valu" if os.environ.get("PVLM_CHOL_VALU") else "mfma_f64",
-                          residual_max=float(np.abs(y - rhs).max()), wall_ms_min=min(ts) * 1e3, wall_ms_median=float(np.median(ts)) * 1e3,
+    print(json.dumps(dict(unknowns=n, blocks=len(blocks), residual_max=float(np.abs(y - rhs).max()), wall_ms_min=min(ts) * 1e3, wall_ms_median=float(np.median(ts)) * 1e3,
                           gflops_factor_only=n ** 3 / 3 / min(ts) / 1e9)))
 
 
