@@ -580,6 +580,30 @@ pvlm_status pvlm_rotavg_l2(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int*
                            const pvlm_rotavg_l2_params* params, pvlm_rotavg_l2_summary* summary);
 int pvlm_rotavg_group_size(void);
 
+/* ---- K45: the least-square start of the L2 rotation-averaging method (RotationAveragingLeastSquare sfm/RotationAveraging.cpp:185-275) ---- *
+ * The definition (csrc/pvlm_rotstart_core.h).  F cameras, P pairs (first, second, R_21 row-major, either orientation).  M = A^T A of the equations
+ * R_2w - R_21 R_1w = 0 has one 3 x 3 block per pair; wanted is the invariant subspace of its three smallest eigenvalues, then per camera the polar factor of its
+ * 3 x 3 block, the sign rule det < 0 -> -rot and the product with rot_0^T (camera 0 ends as the identity up to rounding).
+ * STATED DIVERGENCE: upstream takes a dense SelfAdjointEigenSolver of the 3 F x 3 F matrix (72 F^2 bytes, 27 F^3 operations); here it is shift-and-invert subspace
+ * iteration of width 3 with Rayleigh-Ritz on the block-sparse matrix: sigma = shift_rel * d_max (d_max: the largest camera degree), per iteration three solves with
+ * M + sigma I through the solver behind pvlm_spd_solve_blocks, the Cholesky of the 3 x 3 Gram matrix, the 3 x 3 eigen-decomposition of Q^T M Q, until
+ * max_k |M x_k - theta_k x_k| <= tol * d_max.  The result depends only on the subspace (the core header says why), so the method differs and the result does not.
+ * rotations: on entry the start (9 per camera; the host mirror passes RotationAveragingSpanningTree's result, but any 3 F x 3 matrix of full rank serves), on
+ * exit R_cw.  summary: iterations, solves (three per iteration), info, the last residual over d_max, the three Ritz values.  info: 0; k > 0: M + sigma I is not
+ * positive definite (an R_21 far from a rotation); -1: something was not finite; -2: max_iterations reached; -3: a camera's block or a Gram matrix (the start's
+ * among them) is singular.  Unless info is 0, rotations is left as it came.
+ * Every sum has one order (per camera: its pairs in list order over pvlm_rotavg_group_size() lanes and a fixed butterfly; the scalars: a fixed tree over the
+ * cameras), so a call is bit-reproducible from run to run.
+ * PVLM_ERR_ARG, with no output touched: a NULL, a camera index out of range, first == second, the same camera pair named twice in either orientation, an input that
+ * is not finite, a pair graph that is not connected (a null space of six dimensions has no answer), n_cameras < 2 or n_pairs < 1 (upstream returns false),
+ * shift_rel <= 0, tol <= 0, max_iterations < 1.
+ * PVLM_ROTAVG_MAX_BLOCKS and PVLM_ROTAVG_PROFILE act as for K40. */
+typedef struct pvlm_rotavg_lsq_params { double shift_rel /* 1e-9 */, tol /* 1e-12 */; int max_iterations /* 100 */; } pvlm_rotavg_lsq_params;
+typedef struct pvlm_rotavg_lsq_summary { int iterations, solves, info; double residual /* last, / d_max */, theta[3]; } pvlm_rotavg_lsq_summary;
+pvlm_status pvlm_rotavg_least_square(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21 /* n_pairs * 9 */,
+                                     double* rotations /* in: the start, out: R_cw; 9 per camera */, const pvlm_rotavg_lsq_params* params,
+                                     pvlm_rotavg_lsq_summary* summary);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

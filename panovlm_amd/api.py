@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "pvlm_resset_plane_runs", "pvlm_resset_point_table", "pvlm_resset_point_table_debug",
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
     "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size", "pvlm_transavg_bata", "pvlm_bata_group_size",
-    "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size",
+    "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size", "pvlm_rotavg_least_square",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1877,6 +1877,31 @@ def rotavg_l2(ctx, first, second, R_21, rotations, loss_a=0.07, max_num_iteratio
         ctx._check(rc, "pvlm_rotavg_l2")
     return dict(rotations=rot[:F].reshape(F, 3, 3), initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
                 unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=bool(np.all(rot[F:] == -7.0)), rc=int(rc))
+
+
+class RotavgLsqParams(C.Structure):
+    _fields_ = [("shift_rel", C.c_double), ("tol", C.c_double), ("max_iterations", C.c_int)]
+
+
+class RotavgLsqSummary(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("solves", C.c_int), ("info", C.c_int), ("residual", C.c_double), ("theta", C.c_double * 3)]
+
+
+def rotavg_least_square(ctx, first, second, R_21, rotations, shift_rel=1e-9, tol=1e-12, max_iterations=100, check=True):
+    """pvlm_rotavg_least_square (K45): RotationAveragingLeastSquare, the start of the L2 method, by shift-and-invert subspace iteration from `rotations` (cameras x
+    3 x 3: the spanning-tree start, or any 3 F x 3 matrix of full rank).  The inputs are not modified.  Returns a dict: rotations (cameras x 3 x 3, R_cw with camera 0
+    the identity; the input when info is not 0), iterations, solves, info (0; k > 0: not positive definite; -1: not finite; -2: max_iterations reached; -3: a
+    singular block or Gram matrix), residual (the last, over the largest degree), theta (the three Ritz values), guard_intact, rc.  An argument the library refuses
+    raises PvlmError; with check=False the dict comes back with its rc (the summary then holds the sentinel -7: the library touches nothing it refuses)."""
+    first, second, P, R21, F, rot = _rotavg_inputs(first, second, R_21, rotations)
+    prm = RotavgLsqParams(shift_rel, tol, max_iterations)
+    sm = RotavgLsqSummary(-7, -7, -7, -7.0, (C.c_double * 3)(-7.0, -7.0, -7.0))
+    rc = ctx.lib.pvlm_rotavg_least_square(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R21, C.c_double), _p(rot, C.c_double),
+                                          C.byref(prm), C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_rotavg_least_square")
+    return dict(rotations=rot[:F].reshape(F, 3, 3), iterations=sm.iterations, solves=sm.solves, info=sm.info, residual=sm.residual, theta=np.array(list(sm.theta)),
+                guard_intact=bool(np.all(rot[F:] == -7.0)), rc=int(rc))
 
 
 def device_sort(ctx, keys):

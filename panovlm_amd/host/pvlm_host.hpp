@@ -865,15 +865,19 @@ bool SetToOrigin(std::vector<Frame>& frames, size_t frame_idx);
 bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const TranslationOptions& options = TranslationOptions());
 
 // ---- K40: rotation averaging (sfm/RotationAveraging.cpp:11-183, :278-582; sfm/PoseGraph.cpp:195-226; sfm/SfM.cpp:705-778, :811-905) ------------------------------
-// base/common.h.  L1 (the method of both shipped configs) is built; L2 needs the eigenvectors of a dense 3 F x 3 F matrix for its start (RotationAveragingLeastSquare)
-// and is not: EstimateGlobalRotation returns false with a message.
+// base/common.h.  L1 (the method of both shipped configs) is built, and L2 (its start RotationAveragingLeastSquare: K45, below) behind
+// RotationOptions::enable_l2_start; without the flag EstimateGlobalRotation returns false for method 2 with the message it has always had.
 enum RotationAveragingMethod { ROTATION_AVERAGING_L1 = 1, ROTATION_AVERAGING_L2 = 2 };
-// what base/Config.h holds for the stage.  host = true runs every solve through the host compile of csrc/pvlm_rotavg_core.h (pvlm_host_rotavg.hpp; no device).
-// message: where the text of upstream's LOG(ERROR) goes when the call returns false.
+// what base/Config.h holds for the stage.  host = true runs every solve through the host compiles of csrc/pvlm_rotavg_core.h and csrc/pvlm_rotstart_core.h
+// (pvlm_host_rotavg.hpp, pvlm_host_rotstart.hpp; no device).  message: where the text of upstream's LOG(ERROR) goes when the call returns false.
 struct RotationOptions {
   bool use_all_pairs_ra = true;
   bool host = false;
   std::string* message = nullptr;
+  // Method 2 (the least-square start, K45, then RotationAveragingL2) runs only when this is set.  The flag exists because tests/test_rotavg_cpu.py::
+  // test_estimate_global_rotation_host and tests/test_rotavg_gpu.py pin method 2 under default options to its refusal and existing tests do not change; a later
+  // change that may edit those tests removes it.
+  bool enable_l2_start = false;
 };
 struct Triplet { uint32_t i, j, k; };
 // PoseGraph::FindTriplet (sfm/PoseGraph.cpp:195-226): per edge in the set's order, the nodes adjacent to both its ends, then the edge leaves the adjacency
@@ -897,9 +901,16 @@ bool RotationAveragingL1(std::vector<RelativePair>& image_pairs, std::vector<Mat
 // RotationAveragingL2 (:317-374) through pvlm_rotavg_l2.  false: the result is not finite, or the library refused the arguments — a pair list that FilterPairs left
 // in more than one piece among them (upstream refines every piece; here the rotations stay as they came).
 bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host = false);
-// SfM::EstimateGlobalRotation (:811-905), operation by operation: the use_all_pairs_ra filter, LargestBiconnectedGraph, FilterByTriplet(0.1), ReIndex,
-// RotationAveragingL1(pairs, rotations, 0, -1), RotationAveragingL2 (a failure is only reported, as upstream), then pair.R_21 = R_2w R_1w^T and frames[i].R_wc.
-// image_pairs is replaced by the pairs that survive.  false with a message: no pair survives the filters, a pair with first >= second, method 2, or L1 failed.
+// K45 — RotationAveragingLeastSquare (:185-275) through pvlm_rotavg_least_square (see pvlm.h for the definition and its one divergence: the three eigenvectors come
+// from shift-and-invert subspace iteration on the block-sparse matrix, not from a dense decomposition; the result depends on their span alone).  The iteration starts
+// from RotationAveragingSpanningTree(pairs, rotations, 0).  global_rotations is written only on success.  false: no camera or no pair (upstream's "not enough
+// data"), the pairs do not reach every camera, the library refused the arguments, or info != 0.
+bool RotationAveragingLeastSquare(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host = false);
+// SfM::EstimateGlobalRotation (:811-905), operation by operation: the use_all_pairs_ra filter, LargestBiconnectedGraph, FilterByTriplet(0.1), ReIndex, then
+// method 1: RotationAveragingL1(pairs, rotations, 0, -1), RotationAveragingL2 (a failure is only reported, as upstream); method 2 with enable_l2_start:
+// RotationAveragingLeastSquare (a failure returns false with upstream's "Rotation averaging L2 failed"), RotationAveragingL2 (reported only; no FilterPairs on this
+// route, :859-869); then pair.R_21 = R_2w R_1w^T and frames[i].R_wc.  image_pairs is replaced by the pairs that survive.  false with a message: no pair survives
+// the filters, a pair with first >= second, method 2 without its flag, or the first stage of the method failed.
 bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const RotationOptions& options = RotationOptions());
 
 // ---- K35: the image pairs (sfm/VLAD.cpp, sfm/SfM.cpp:49-168) ------------------------------------------------------------------------------------------------

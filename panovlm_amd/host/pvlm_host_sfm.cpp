@@ -5,7 +5,7 @@
 // TriangulateTracks / FilterTracksToFar (sfm/Structure.cpp:8-119), CameraLidarOptimizer::EstimateStructure (:720-729), MVS::EstimateStructure
 // (mvs/MVS.cpp:44-59); and the step between the relative and the global poses — EstimateGlobalTranslation with TranslationAveragingDLT / L2 / SoftL1 / L2IRLS, ReIndex,
 // SetToOrigin (sfm/SfM.cpp:1047-1344, sfm/TranslationAveraging.cpp; K42) after EstimateGlobalRotation with FindTriplet, FilterByTriplet, FilterPairs and
-// RotationAveragingSpanningTree / RefineL1 / L1 / L2 (sfm/SfM.cpp:705-905, sfm/RotationAveraging.cpp, sfm/PoseGraph.cpp:195-226; K40).
+// RotationAveragingSpanningTree / RefineL1 / L1 / L2 (sfm/SfM.cpp:705-905, sfm/RotationAveraging.cpp, sfm/PoseGraph.cpp:195-226; K40) and RotationAveragingLeastSquare (K45).
 // Host logic only; the reprojection blocks are solved and the tracks are triangulated and tested by libpvlm.so on the GPU (K9 / K31 / K32).
 #include <array>
 #include <queue>
@@ -21,6 +21,7 @@
 #include "pvlm_host_transavg.hpp"
 #include "pvlm_host_rotavg.hpp"
 #include "pvlm_host_bata.hpp"
+#include "pvlm_host_rotstart.hpp"
 
 namespace pvlm {
 
@@ -1332,6 +1333,31 @@ bool RotationAveragingL2(const std::vector<RelativePair>& image_pairs, std::vect
   return true;
 }
 
+bool RotationAveragingLeastSquare(const std::vector<RelativePair>& image_pairs, std::vector<Matrix3d>& global_rotations, const bool host) {
+  if (global_rotations.empty() || image_pairs.empty()) return false;                 // :188-192
+  std::vector<Matrix3d> start(global_rotations.size(), Matrix3d{{0, 0, 0, 0, 0, 0, 0, 0, 0}});
+  if (!RotationAveragingSpanningTree(image_pairs, start, 0)) return false;
+  PairGraphInputs in;
+  if (!in.Fill(image_pairs, start)) return false;
+  const int F = (int)start.size(), P = (int)image_pairs.size();
+  int info = 0;
+  if (host) {
+    const pvlm_rotstart::Params prm;
+    pvlm_rotstart::Summary hs;
+    if (rotstart_detail::LeastSquareHost(F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), &prm, &hs)) return false;
+    info = hs.info;
+  } else {
+    Engine& e = Engine::Default();
+    const pvlm_rotavg_lsq_params prm{1e-9, 1e-12, 100};
+    pvlm_rotavg_lsq_summary sum{0, 0, 0, 0.0, {0.0, 0.0, 0.0}};
+    if (pvlm_rotavg_least_square(e.ctx(), F, P, in.first.data(), in.second.data(), in.R.data(), in.rot.data(), &prm, &sum) != PVLM_OK) return false;
+    info = sum.info;
+  }
+  if (info != 0) return false;
+  in.Read(global_rotations);
+  return true;
+}
+
 bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair>& image_pairs, const int method, const RotationOptions& o) {
   if (!o.use_all_pairs_ra) {
     std::vector<RelativePair> pairs_with_scale;
@@ -1353,6 +1379,9 @@ bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair
   if (method == ROTATION_AVERAGING_L1) {
     if (!RotationAveragingL1(image_pairs, global_rotations, 0, -1, o.host)) return Say(o, "Rotation averaging L1 failed");
     if (!RotationAveragingL2(image_pairs, global_rotations, o.host) && o.message) *o.message = "Rotation averaging refine L2 failed";       // reported, not returned (:886-887)
+  } else if (method == ROTATION_AVERAGING_L2 && o.enable_l2_start) {              // :859-869; behind the flag: see RotationOptions
+    if (!RotationAveragingLeastSquare(image_pairs, global_rotations, o.host)) return Say(o, "Rotation averaging L2 failed");
+    if (!RotationAveragingL2(image_pairs, global_rotations, o.host) && o.message) *o.message = "Rotation averaging refine L2 failed";       // reported, not returned (:867-868)
   } else return Say(o, "Rotation averaging method not supported: L2 needs the eigenvectors of a dense 3 F x 3 F matrix for its start and is not built");
   for (RelativePair& pair : image_pairs) {
     pair.R_21 = MulNT(global_rotations[pair.image_pair.second], global_rotations[pair.image_pair.first]);      // R_2w R_1w^T
