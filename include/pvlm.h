@@ -604,6 +604,41 @@ pvlm_status pvlm_rotavg_least_square(pvlm_ctx* ctx, int n_cameras, int n_pairs, 
                                      double* rotations /* in: the start, out: R_cw; 9 per camera */, const pvlm_rotavg_lsq_params* params,
                                      pvlm_rotavg_lsq_summary* summary);
 
+/* ---- K46: translation averaging on world-frame directions (TranslationAveragingL2Chordal sfm/TranslationAveraging.cpp:206-274; one solve of
+ *      TranslationAveragingLUD's loop :553-626; ChrodalResidual, LUDResidual, ScaleFactor base/CostFunction.h:89-173) ---- *
+ * The definition (csrc/pvlm_transdir_core.h).  Unknowns: the CENTRE c of every camera (upstream's t_wc; origin_idx constant and zero); dir[p] is the measured
+ * direction of pair p, a unit vector in the world frame (upstream: R_w2 t_21 normalised).  Both run K42's LM on the pair-graph layer (gather, fixed tree, camera
+ * system through the solver behind pvlm_spd_solve_blocks) with ceres_like::Solve's policy.
+ * pvlm_transavg_chordal: u = c[first] - c[second], r = u / |u| - dir (weight 1) under HuberLoss(loss_a) on |r|^2; max_num_iterations 300, function_tolerance 1e-7,
+ * parameter_tolerance 1e-8 upstream (:254-257).  There is no scale and nothing is eliminated.  THE COST IS INVARIANT UNDER c -> lambda c: the overall scale is a gauge
+ * that the LM damping alone holds, so the result keeps roughly the scale of its start; compare results after a scale fit.  Two cameras on one point make the cost
+ * not finite: at the start that is termination 5 with centres untouched, at a candidate a rejected step.
+ * pvlm_transavg_lud: one private scale per pair, e = c[first] - c[second] - s_p dir_p, ONE residual w_p |e|^(1/2), no loss; weight[p] = w_p is READ and applied
+ * (the LUD functor reads its weight, unlike K42's).  Scale block by the incoming scale s0: s0 != 1 (as written, :563) gives ScaleFactor(upper_scale_ratio s0,
+ * lower_scale_ratio s0) and the parameter bounds [0.5 s0, 3 s0]; otherwise ScaleFactor(2, 1) and a parameter LOWER bound of 1 only (:576-578; K42's unscaled pairs
+ * have none).  Per LM iteration the scales are eliminated (a 1 x 1 pivot), the camera system solved, the scale steps back-substituted, the candidate scales CLAMPED
+ * onto their parameter bounds and the step quality taken against the model at the clamped step — K42's stand-in for Ceres' projection plus line search, the same
+ * divergence.  Write-back (:615-626): weight[p] = (|e_p| + 1e-2)^-1/2, *sum_e = sum |e_p| over the fixed tree, both on dir_p (upstream normalises R_w2 t_21 in the
+ * functor and rotates the normalised t_21 in the weight: rounding apart, the same vector).
+ * Further divergence: where |e| == 0 at a linearisation point the pair contributes a zero row; upstream's Jet gives a non-finite derivative there and Ceres fails.
+ * summary: K42's fields and termination numbering (6: no pairs, nothing touched; 5: initial cost not finite, nothing but the summary touched).
+ * Every sum has one order (per camera: its pairs in list order over pvlm_transdir_group_size() lanes and a fixed butterfly; the scalars: a fixed tree), so a call is
+ * bit-reproducible from run to run — for a pair list that names no camera pair more than twice (the solver adds repeated blocks atomically).
+ * PVLM_ERR_ARG, with no output touched: a NULL, a camera index out of range, first == second, an input that is not finite, a direction not of unit length within
+ * 1e-9, for _lud a weight <= 0, origin_idx out of range, centres[origin_idx] not zero, max_num_iterations < 0.
+ * The environment variable PVLM_TRANSDIR_MAX_BLOCKS (read at every call) lowers the grids of the kernels; it changes no result, the tests use it to make them stride.
+ * With PVLM_TRANSDIR_PROFILE set, a call prints one line on stderr: its wall clock split into kernels, camera solves and host. */
+typedef struct pvlm_transdir_chordal_params { double loss_a /* 0.5 */; int max_num_iterations /* 300 */; } pvlm_transdir_chordal_params;
+typedef struct pvlm_transdir_lud_params { double upper_scale_ratio, lower_scale_ratio; int max_num_iterations /* 50 */; } pvlm_transdir_lud_params;
+typedef struct pvlm_transdir_summary { double initial_cost, final_cost; int successful_steps, unsuccessful_steps, termination; } pvlm_transdir_summary;
+pvlm_status pvlm_transavg_chordal(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* dir /* n_pairs * 3, unit */,
+                                  int origin_idx, double* centres /* in/out, 3 per camera */, const pvlm_transdir_chordal_params* params,
+                                  pvlm_transdir_summary* summary);
+pvlm_status pvlm_transavg_lud(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* dir /* n_pairs * 3, unit */,
+                              double* scales /* in/out, n_pairs */, double* weight /* in: w_p, out: the next weights; n_pairs */, int origin_idx,
+                              double* centres /* in/out, 3 per camera */, const pvlm_transdir_lud_params* params, double* sum_e, pvlm_transdir_summary* summary);
+int pvlm_transdir_group_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "pvlm_refine_relative_poses", "pvlm_relpose_workgroup_size",
     "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size", "pvlm_transavg_bata", "pvlm_bata_group_size",
     "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size", "pvlm_rotavg_least_square",
+    "pvlm_transavg_chordal", "pvlm_transavg_lud", "pvlm_transdir_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1789,6 +1790,64 @@ def transavg_solve(ctx, first, second, R_21, t_21, scales, origin_idx, translati
         ctx._check(rc, "pvlm_transavg_solve")
     intact = bool(np.all(t[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0))
     return dict(translations=t[:F], scales=s[:P], weight=w[:P], initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
+                unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
+
+
+class TransdirChordalParams(C.Structure):
+    _fields_ = [("loss_a", C.c_double), ("max_num_iterations", C.c_int)]
+
+
+class TransdirLudParams(C.Structure):
+    _fields_ = [("upper_scale_ratio", C.c_double), ("lower_scale_ratio", C.c_double), ("max_num_iterations", C.c_int)]
+
+
+TRANSDIR_GUARD = 8     # sentinel records the two wrappers keep behind every output
+
+
+def transdir_group_size():
+    """pvlm_transdir_group_size (K46): the lanes that share one camera's gather."""
+    return int(load_library().pvlm_transdir_group_size())
+
+
+def transavg_chordal(ctx, first, second, directions, origin_idx, centres, loss_a=0.5, max_num_iterations=300, check=True):
+    """pvlm_transavg_chordal (K46): TranslationAveragingL2Chordal on unit world-frame directions (pairs x 3) from the start `centres` (cameras x 3, zero at
+    origin_idx) under HuberLoss(loss_a).  The cost does not fix the overall scale: the result keeps roughly the scale of its start.  The inputs are not modified.
+    Returns a dict: centres, initial_cost, final_cost, successful_steps, unsuccessful_steps, termination (TRANSAVG_TERMINATIONS; 5 leaves the centres as they came),
+    guard_intact (the TRANSDIR_GUARD sentinel records behind the output were not written), rc.  An argument the library refuses raises PvlmError; with check=False
+    the dict comes back with its rc (the outputs then hold the inputs)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRANSDIR_GUARD
+    d = _f64(np.asarray(directions, np.float64).reshape(P, 3))
+    c_in = np.asarray(centres, np.float64).reshape(-1, 3); F = len(c_in)
+    c = np.full((F + G, 3), -7.0); c[:F] = c_in
+    prm = TransdirChordalParams(loss_a, max_num_iterations)
+    sm = TransavgSummary(-7.0, -7.0, -7, -7, -7)
+    rc = ctx.lib.pvlm_transavg_chordal(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(d, C.c_double), C.c_int(origin_idx), _p(c, C.c_double),
+                                       C.byref(prm), C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_transavg_chordal")
+    return dict(centres=c[:F], initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps, unsuccessful_steps=sm.unsuccessful_steps,
+                termination=sm.termination, guard_intact=bool(np.all(c[F:] == -7.0)), rc=int(rc))
+
+
+def transavg_lud(ctx, first, second, directions, scales, weight, origin_idx, centres, upper_scale_ratio=1.3, lower_scale_ratio=0.9, max_num_iterations=50, check=True):
+    """pvlm_transavg_lud (K46): one solve of TranslationAveragingLUD's loop on unit world-frame directions, start scales (1 = a pair without a length) and the
+    weights w_p > 0 of the residuals (None: all 1).  The inputs are not modified.  Returns a dict: centres (cameras x 3), scales, weight (the NEXT weights
+    (|e| + 1e-2)^-1/2), sum_e (the sum of |e|; -7 when the library wrote none), the summary fields of transavg_chordal, guard_intact, rc.  An argument the library
+    refuses raises PvlmError; with check=False the dict comes back with its rc (the outputs then hold the inputs)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRANSDIR_GUARD
+    d = _f64(np.asarray(directions, np.float64).reshape(P, 3))
+    c_in = np.asarray(centres, np.float64).reshape(-1, 3); F = len(c_in)
+    c = np.full((F + G, 3), -7.0); c[:F] = c_in
+    s = np.full(P + G, -7.0); s[:P] = np.asarray(scales, np.float64).reshape(P)
+    w = np.full(P + G, -7.0); w[:P] = 1.0 if weight is None else np.asarray(weight, np.float64).reshape(P)
+    prm = TransdirLudParams(upper_scale_ratio, lower_scale_ratio, max_num_iterations)
+    sm = TransavgSummary(-7.0, -7.0, -7, -7, -7); sum_e = (C.c_double * 2)(-7.0, -7.0)
+    rc = ctx.lib.pvlm_transavg_lud(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(d, C.c_double), _p(s, C.c_double), _p(w, C.c_double),
+                                   C.c_int(origin_idx), _p(c, C.c_double), C.byref(prm), sum_e, C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_transavg_lud")
+    intact = bool(np.all(c[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0) and sum_e[1] == -7.0)
+    return dict(centres=c[:F], scales=s[:P], weight=w[:P], sum_e=float(sum_e[0]), initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
                 unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
 
 

@@ -9,7 +9,7 @@
 //     policy over a backend that evaluates, gathers, solves and steps (lm_solve).  Trust region: the constants and the policy of ceres_like::Solve
 //     (host/pvlm_host.hpp Solver::Options): Jacobi scaling 1 / (1 + sqrt(H_kk)) from the first linearisation, radius / max(1/3, 1 - (2 rho - 1)^3) on success,
 //     radius / 2, / 4, ... on failure, min_relative_decrease 1e-3 and the three tolerances;
-//   SoftLOneLoss on a squared residual, the loss of both stages' pair blocks.
+//   SoftLOneLoss on a squared residual, the loss of both stages' pair blocks, and HuberLoss beside it (K46's chordal blocks).
 // The device half (kernels, buffers, the solver call) is pvlm_pairgraph.h, the host twin host/pvlm_host_pairgraph.hpp.
 #pragma once
 #include <cmath>
@@ -46,6 +46,12 @@ PVLM_PG_HD void loss(double a, double s2, double* rho, double* rho1) {
   if (a < 0) { *rho = s2; *rho1 = 1.0; return; }
   const double b = a * a, c = 1.0 / b, tmp = sqrt(1.0 + s2 * c);
   *rho = 2.0 * b * (tmp - 1.0); *rho1 = 1.0 / tmp;
+}
+// HuberLoss(a) at s2 = |r|^2: rho(s) = s up to a^2, 2 a sqrt(s) - a^2 past it, and rho' (K46's chordal blocks).  A NaN takes the outer branch and stays one.
+PVLM_PG_HD void huber(double a, double s2, double* rho, double* rho1) {
+  if (s2 <= a * a) { *rho = s2; *rho1 = 1.0; return; }
+  const double r = sqrt(s2);
+  *rho = 2.0 * a * r - a * a; *rho1 = a / r;
 }
 
 // lane `lane` of the kGroup lanes of one camera over a two-sided record (side 0 = first and side 1 = second as kCam numbers each, component k of pair p at

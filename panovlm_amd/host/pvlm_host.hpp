@@ -805,8 +805,8 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
                           std::set<size_t>& covered_frames, const int triangulation_num_threshold, const bool keep_no_scale, const EssentialOptions& options = EssentialOptions());
 
 // ---- K42: translation averaging (sfm/TranslationAveraging.cpp:31-204, :419-481; sfm/SfM.cpp:908-934, :1047-1344, :1385-1421) ----------------------------------
-// sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built, and BATA (K44, below) behind TranslationOptions::enable_bata; L1 (the LP), CHORDAL and LUD are not:
-// EstimateGlobalTranslation returns false with upstream's "not supported".
+// sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built, and BATA (K44), CHORDAL and LUD (K46, below) behind TranslationOptions::enable_bata / enable_chordal / enable_lud;
+// L1 (the LP) is not: EstimateGlobalTranslation returns false with upstream's "not supported".
 enum TranslationAveragingMethod { TRANSLATION_AVERAGING_SOFTL1 = 1, TRANSLATION_AVERAGING_L1 = 2, TRANSLATION_AVERAGING_CHORDAL = 3, TRANSLATION_AVERAGING_L2IRLS = 4,
                                   TRANSLATION_AVERAGING_BATA = 5, TRANSLATION_AVERAGING_LUD = 6 };
 // sfm/BATA.h's BATAConfig: what TranslationAveragingBATA hands BATA (upstream: always the defaults, :516)
@@ -826,6 +826,8 @@ struct TranslationOptions {
   // options to upstream's "not supported" text and existing tests do not change; a later change that may edit that test removes it.
   bool enable_bata = false;
   BATAConfig bata;
+  // Methods 3 (chordal) and 6 (LUD), K46, run only when these are set: the same test pins them under default options, for the same reason.
+  bool enable_chordal = false, enable_lud = false;
 };
 // TranslationAveragingDLT (:31-84) through pvlm_transavg_dlt: the normal equations with camera 0 fixed at zero.  Upstream's SparseQR returns SOME basic solution of a
 // system that is rank-deficient by the gauge t_i = R_i c; every caller runs SetToOrigin afterwards, which cancels the difference.  false: a pair names a camera
@@ -852,6 +854,20 @@ bool TranslationAveragingL2IRLS(std::vector<RelativePair>& image_pairs, std::vec
 bool TranslationAveragingBATA(const std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
                               const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const BATAConfig& config = BATAConfig(), const unsigned long long seed = 0,
                               const bool host = false, std::vector<double>* start_scales = nullptr);
+// K46 — TranslationAveragingL2Chordal (:206-274) through pvlm_transavg_chordal (see pvlm.h for the definition and its divergences), as written: t_cw -> t_wc at
+// entry with the rotation of frames[new_to_old[i]] (:216-220), per pair dir = R_w2 t_21.normalized() (:225-226), HuberLoss(l2_loss_threshold), back to t_cw at exit
+// (:267-271).  false: a camera without an entry in new_to_old, a pair that names a camera past global_translations, a relative translation of zero length or not
+// finite, or a summary that is not usable (the initial cost not finite: two cameras on one point).
+bool TranslationAveragingL2Chordal(const std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                                   const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const double l2_loss_threshold, const bool host = false);
+// K46 — TranslationAveragingLUD (:527-660) through pvlm_transavg_lud, as written: the start scales are |t_21|, or 1 for a pair without lower_scale / upper_scale
+// (:536-542), the weights start at 1; at most num_iteration solves, each followed by the new weights and sum_e = sum |e| (:615-626); the loop stops when
+// |last - curr| / curr < 0.05 || curr < 10 (:628); after a solve that did not stop, the pairs whose scale went negative are dropped from image_pairs (:635-651).
+// No input reaches that drop: every scale is held at or above 0.5 s0 or 1 by its parameter bound and the clamp puts every candidate on it; it is built as written.
+// iterations_run: the solves done.  false: as for the chordal function.
+bool TranslationAveragingLUD(std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                             const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const int num_iteration, const float upper_scale_ratio,
+                             const float lower_scale_ratio, const bool host = false, int* iterations_run = nullptr);
 // SfM::ReIndex (sfm/SfM.cpp:908-934): the frame ids of a pair list onto 0 .. n - 1 in ascending order
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward);
 // SfM::SetToOrigin (:1385-1421) without the structure: every valid pose into the frame of frames[frame_idx] (the first valid frame when that one has no pose).

@@ -22,6 +22,7 @@
 #include "pvlm_host_rotavg.hpp"
 #include "pvlm_host_bata.hpp"
 #include "pvlm_host_rotstart.hpp"
+#include "pvlm_host_transdir.hpp"
 
 namespace pvlm {
 
@@ -845,7 +846,7 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
 
 // ================================================================================================
 // K42: translation averaging — TranslationAveragingDLT / L2 / SoftL1 / L2IRLS (sfm/TranslationAveraging.cpp), ReIndex, SetToOrigin, EstimateGlobalTranslation;
-// K44: TranslationAveragingBATA (sfm/TranslationAveraging.cpp:483-525 around sfm/BATA.cpp)
+// K44: TranslationAveragingBATA (sfm/TranslationAveraging.cpp:483-525 around sfm/BATA.cpp); K46: TranslationAveragingL2Chordal (:206-274), TranslationAveragingLUD (:527-660)
 // ================================================================================================
 namespace {
 // the arrays of pvlm_transavg_* and pvlm_rotavg_* from a pair list: the pair indices and R_21 always, t_21 for the former, the rotations for the latter
@@ -1016,6 +1017,113 @@ bool TranslationAveragingBATA(const std::vector<RelativePair>& image_pairs, cons
   return true;
 }
 
+namespace {
+// What the two K46 functions share: the centres t_wc = -R_wc t_cw of every camera (:216-220, :544-548), per pair dir = R_w2 t_21.normalized() (:225-226, :623) and
+// the way back, t_cw = -R_cw t_wc (:267-271, :654-658).  false: a camera without a frame, a pair past the cameras, a t_21 without a direction.
+struct DirectionInputs {
+  std::vector<int> first, second; std::vector<double> dir, centres;
+  bool Fill(const std::vector<RelativePair>& pairs, const std::vector<Frame>& frames, const std::vector<Vector3d>& t_cw, const std::map<size_t, size_t>& new_to_old) {
+    const size_t F = t_cw.size();
+    centres.assign(3 * F + 3, 0.0);
+    for (size_t i = 0; i < F; ++i) {
+      const auto it = new_to_old.find(i);
+      if (it == new_to_old.end() || it->second >= frames.size()) return false;
+      const Vector3d c = MinusRt(frames[it->second].R_wc, t_cw[i]);
+      for (size_t k = 0; k < 3; ++k) centres[3 * i + k] = c[k];
+    }
+    first.clear(); second.clear(); dir.clear();
+    for (const RelativePair& p : pairs) {
+      if (p.image_pair.first >= F || p.image_pair.second >= F) return false;
+      const Matrix3d& R = frames[new_to_old.find(p.image_pair.second)->second].R_wc;
+      double d[3];
+      if (!pvlm_transavg::direction(p.t_21.data(), d)) return false;
+      for (int r = 0; r < 3; ++r) dir.push_back(R[3 * r] * d[0] + R[3 * r + 1] * d[1] + R[3 * r + 2] * d[2]);
+      first.push_back((int)p.image_pair.first); second.push_back((int)p.image_pair.second);
+    }
+    const bool ok = pvlm_transdir::check_pairs((int)F, (int)pairs.size(), first.data(), second.data(), dir.data()) == nullptr;      // a frame whose R_wc is no rotation
+    first.push_back(0); second.push_back(0); dir.resize(dir.size() + 3);      // never empty
+    return ok;
+  }
+  void Read(const std::vector<Frame>& frames, const std::map<size_t, size_t>& new_to_old, std::vector<Vector3d>& t_cw) const {
+    for (size_t i = 0; i < t_cw.size(); ++i) {
+      const Matrix3d& R = frames[new_to_old.find(i)->second].R_wc; const double* c = &centres[3 * i];
+      t_cw[i] = {-(R[0] * c[0] + R[3] * c[1] + R[6] * c[2]), -(R[1] * c[0] + R[4] * c[1] + R[7] * c[2]), -(R[2] * c[0] + R[5] * c[1] + R[8] * c[2])};
+    }
+  }
+};
+bool Usable(const pvlm_transdir_summary& s) { return s.termination != pvlm_pairgraph::kCostNotFinite && std::isfinite(s.final_cost); }       // summary.IsSolutionUsable()
+pvlm_transdir_summary FromCore(const pvlm_pairgraph::Summary& h) { return {h.initial_cost, h.final_cost, h.successful_steps, h.unsuccessful_steps, h.termination}; }
+}  // namespace
+
+bool TranslationAveragingL2Chordal(const std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                                   const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const double l2_loss_threshold, const bool host) {
+  DirectionInputs in;
+  if (!in.Fill(image_pairs, frames, global_translations, new_to_old)) return false;
+  const int F = (int)global_translations.size(), P = (int)image_pairs.size();
+  pvlm_transdir_summary sum{0, 0, 0, 0, 0};
+  if (host) {
+    pvlm_pairgraph::Summary hs;
+    if (transdir_detail::ChordalHost(F, P, in.first.data(), in.second.data(), in.dir.data(), (int)origin_idx, in.centres.data(), l2_loss_threshold, 300, &hs)) return false;
+    sum = FromCore(hs);
+  } else {
+    Engine& e = Engine::Default();
+    const pvlm_transdir_chordal_params prm{l2_loss_threshold, 300};
+    e.Check(pvlm_transavg_chordal(e.ctx(), F, P, in.first.data(), in.second.data(), in.dir.data(), (int)origin_idx, in.centres.data(), &prm, &sum), "pvlm_transavg_chordal");
+  }
+  if (!Usable(sum)) return false;
+  in.Read(frames, new_to_old, global_translations);
+  return true;
+}
+
+bool TranslationAveragingLUD(std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
+                             const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const int num_iteration, const float upper_scale_ratio,
+                             const float lower_scale_ratio, const bool host, int* iterations_run) {
+  std::vector<double> scales = StartScales(image_pairs), weight(image_pairs.size(), 1.0);
+  DirectionInputs in;
+  if (!in.Fill(image_pairs, frames, global_translations, new_to_old)) return false;
+  const int F = (int)global_translations.size();
+  double curr_cost = 0, last_cost = 0;
+  if (iterations_run) *iterations_run = 0;
+  for (int iter = 0; iter < num_iteration; ++iter) {
+    const int P = (int)image_pairs.size();
+    std::vector<double> s(scales), w(weight);
+    s.push_back(0.0); w.push_back(0.0);
+    pvlm_transdir_summary sum{0, 0, 0, 0, 0};
+    curr_cost = 0;
+    if (host) {
+      pvlm_pairgraph::Summary hs;
+      if (transdir_detail::LudHost(F, P, in.first.data(), in.second.data(), in.dir.data(), s.data(), w.data(), (int)origin_idx, in.centres.data(), upper_scale_ratio, lower_scale_ratio,
+                                   50, &curr_cost, &hs)) return false;
+      sum = FromCore(hs);
+    } else {
+      Engine& e = Engine::Default();
+      const pvlm_transdir_lud_params prm{upper_scale_ratio, lower_scale_ratio, 50};
+      e.Check(pvlm_transavg_lud(e.ctx(), F, P, in.first.data(), in.second.data(), in.dir.data(), s.data(), w.data(), (int)origin_idx, in.centres.data(), &prm, &curr_cost, &sum),
+              "pvlm_transavg_lud");
+    }
+    if (!Usable(sum)) return false;
+    std::copy(s.begin(), s.begin() + P, scales.begin()); std::copy(w.begin(), w.begin() + P, weight.begin());
+    if (iterations_run) *iterations_run = iter + 1;
+    if (std::fabs(last_cost - curr_cost) / curr_cost < 0.05 || curr_cost < 10) break;       // :628 as written
+    last_cost = curr_cost;
+    // :635-651 as written.  No input reaches it: a scaled pair is held at or above 0.5 s0 and an unscaled one at or above 1 by its parameter bound, onto which the
+    // clamp puts every candidate, so no scale is ever negative here (K42's L2IRLS carries the same loop for the same reason)
+    std::vector<RelativePair> good_matches; std::vector<double> good_scales, good_weight;
+    for (size_t i = 0; i < scales.size(); ++i) {
+      if (scales[i] < 0) continue;
+      good_scales.push_back(scales[i]); good_weight.push_back(weight[i]); good_matches.push_back(image_pairs[i]);
+    }
+    if (good_scales.size() != scales.size()) {
+      good_scales.swap(scales); good_weight.swap(weight); good_matches.swap(image_pairs);
+      const std::vector<double> centres = in.centres;                     // the pair arrays follow the list; the centres are carried over
+      if (!in.Fill(image_pairs, frames, global_translations, new_to_old)) return false;
+      in.centres = centres;
+    }
+  }
+  in.Read(frames, new_to_old, global_translations);
+  return true;
+}
+
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward) {
   forward.clear(); backward.clear();
   std::set<size_t> old_id;
@@ -1117,8 +1225,15 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
     success = TranslationAveragingL2IRLS(image_pairs, global_translations, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
   else if (method == TRANSLATION_AVERAGING_BATA && o.enable_bata)      // :1285-1294; behind the flag: see TranslationOptions
     success = TranslationAveragingBATA(image_pairs, frames, global_translations, new_to_old_global, origin_idx, o.bata, o.seed, o.host);
-  else return Say(o, "Translaton average method not supported");       // L1 (the LP), chordal and LUD are not built, BATA only behind its flag; the text is upstream's (:1308)
-  if (!success) return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : method == TRANSLATION_AVERAGING_BATA ? "Translation average BATA failed" : "Translation average L2 IRLS failed");
+  else if (method == TRANSLATION_AVERAGING_CHORDAL && o.enable_chordal)      // :1254-1263; behind the flag: see TranslationOptions
+    success = TranslationAveragingL2Chordal(image_pairs, frames, global_translations, new_to_old_global, origin_idx, 0.5, o.host);
+  else if (method == TRANSLATION_AVERAGING_LUD && o.enable_lud)        // :1295-1305; behind the flag
+    success = TranslationAveragingLUD(image_pairs, frames, global_translations, new_to_old_global, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
+  else return Say(o, "Translaton average method not supported");       // L1 (the LP) is not built, BATA, chordal and LUD only behind their flags; the text is upstream's (:1308)
+  if (!success)
+    return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : method == TRANSLATION_AVERAGING_BATA ? "Translation average BATA failed" :
+                  method == TRANSLATION_AVERAGING_CHORDAL ? "Translation average chordal failed" : method == TRANSLATION_AVERAGING_LUD ? "Translation average LUD failed" :
+                  "Translation average L2 IRLS failed");
   for (RelativePair& pair : image_pairs) { pair.image_pair.first = new_to_old_global[pair.image_pair.first]; pair.image_pair.second = new_to_old_global[pair.image_pair.second]; }
   std::set<size_t> frame_with_translation;
   for (size_t i = 0; i < global_translations.size(); ++i) {
