@@ -639,6 +639,44 @@ pvlm_status pvlm_transavg_lud(pvlm_ctx* ctx, int n_cameras, int n_pairs, const i
                               double* centres /* in/out, 3 per camera */, const pvlm_transdir_lud_params* params, double* sum_e, pvlm_transdir_summary* summary);
 int pvlm_transdir_group_size(void);
 
+/* ---- K47: TranslationAveragingL1, the triplet minimax programme (sfm/TranslationAveraging.cpp:277-417) ---- *
+ * The definition (csrc/pvlm_translp_core.h).  Unknowns: t_cw of every camera, one lambda per TRIPLET, one gamma.  triplet_pairs names, per triplet (i < j < k), the
+ * indices of its pairs (i,j), (j,k), (i,k) in the pair list (upstream: PoseGraph::FindTriplet over the pairs).  For each of the three pairs and each component c the
+ * rows  e_c - gamma <= 0  and  e_c + gamma >= 0  with e = t[second] - R_21 t[first] - lambda_T t_21: 18 rows per triplet (:328-380).  Bounds: the origin's
+ * translation fixed at zero, gamma >= 0 (implied by the row pairs), lambda_T >= lo_T = 0.9 x the mean of |t_21| over the triplet's pairs, t_21 NOT normalised
+ * (:381-385; the `first = 1` of :319 is overwritten).  Cost: gamma.  With the bound row -lambda_T <= -lo_T a triplet has 19 rows; `duals`, when given, receives the
+ * multiplier z >= 0 of every row, 19 per triplet: row 6 q + 2 c of pair slot q is e_c - gamma <= 0, row 6 q + 2 c + 1 is -e_c - gamma <= 0, row 18 the bound.
+ * DELIBERATE DIVERGENCES from upstream:
+ *   The method is a primal-dual interior-point iteration (Mehrotra's predictor and corrector on the normal equations, each lambda eliminated by a 1 x 1 pivot, the
+ *   gamma column taken as a 1 x 1 border, three camera solves per iteration through the solver behind pvlm_spd_solve_blocks), not Clp's simplex.
+ *   The optimum of this programme is a FACE, not a point.  Upstream returns whichever vertex Clp's pivoting reaches; this returns a point near the face's analytic
+ *   centre.  At gamma equal to 1e-11, a simplex vertex and an interior-point solution were seen 0.65 to 1.4 m apart on scenes 5 m across, and a rounding-sized
+ *   (1e-13 relative) disturbance of the solves moves the interior-point translations by up to 2e-4 m while gamma moves by 1e-13.  So gamma, feasibility and the dual
+ *   certificate are the contract; the translation values are not.
+ *   Gauge: cameras joined by a triplet form components.  origin_idx pins its own component; every other component has its lowest-numbered camera pinned at zero
+ *   (that component's translation is free in upstream's programme too: no optimum changes).  A camera in no triplet stays zero; what Clp leaves in a free column that
+ *   no row touches has not been verified.  Both are counted (n_components, n_loose).
+ *   The start is t = 0, whatever `translations` holds on entry.
+ * Start: lambda = lo + 1, gamma = max |e| + 1, s = h - G x, z = 1 / rows.  Step: 0.99 of the way to the boundary, capped at 1.  Stop when s^T z <= gap_tol
+ * max(1, |gamma|), |G x + s - h|_inf <= feas_tol and |c + G^T z|_inf <= feas_tol, or after max_iterations.  The camera systems are Jacobi-scaled with 1e-12 added to
+ * the scaled diagonal; a factorisation that fails multiplies that by 100 and is retried, at most three times in a call (bumps).
+ * summary: gamma, dual_objective (sum lo_T z_bound: by weak duality a lower bound of the optimum when dual_residual is zero), gap (s^T z), primal_residual,
+ * dual_residual, iterations, bumps, n_components, n_loose, termination: 0 converged, 1 iteration limit, 2 factorisation lost after the bumps, 3 not finite, 6 no
+ * triplets (nothing touched).  Unless termination is 0 or 1, no output but the summary is touched.
+ * Every sum has one order (per camera and per pair: its (triplet, slot) entries in triplet order over pvlm_translp_group_size() lanes and a fixed butterfly; the
+ * scalars: a fixed tree), so a call is bit-reproducible from run to run.
+ * PVLM_ERR_ARG, with no output touched: a NULL (duals apart), an index out of range, first >= second, a repeated pair, a triplet whose three pairs do not form
+ * (i,j), (j,k), (i,k) with i < j < k, an input that is not finite, translations[origin_idx] not zero, max_iterations < 1, a tolerance <= 0.
+ * The environment variable PVLM_TRANSLP_MAX_BLOCKS (read at every call) lowers the grids of the kernels; it changes no result, the tests use it to make them stride.
+ * With PVLM_TRANSLP_PROFILE set, a call prints one line on stderr: its wall clock split into kernels, camera solves and host. */
+typedef struct pvlm_translp_params { int max_iterations /* 60 */; double gap_tol /* 1e-9 */, feas_tol /* 1e-9 */; } pvlm_translp_params;
+typedef struct pvlm_translp_summary { double gamma, dual_objective, gap, primal_residual, dual_residual; int iterations, bumps, n_components, n_loose, termination; } pvlm_translp_summary;
+pvlm_status pvlm_transavg_l1(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21 /* n_pairs * 9, row-major */,
+                             const double* t_21 /* n_pairs * 3 */, int n_triplets, const int* triplet_pairs /* n_triplets * 3: indices of (i,j), (j,k), (i,k) */,
+                             int origin_idx, double* translations /* in/out, 3 per camera */, double* duals /* out, optional: 19 per triplet */,
+                             const pvlm_translp_params* params, pvlm_translp_summary* summary);
+int pvlm_translp_group_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

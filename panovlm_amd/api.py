@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "pvlm_transavg_dlt", "pvlm_transavg_solve", "pvlm_transavg_group_size", "pvlm_transavg_bata", "pvlm_bata_group_size",
     "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size", "pvlm_rotavg_least_square",
     "pvlm_transavg_chordal", "pvlm_transavg_lud", "pvlm_transdir_group_size",
+    "pvlm_transavg_l1", "pvlm_translp_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1849,6 +1850,50 @@ def transavg_lud(ctx, first, second, directions, scales, weight, origin_idx, cen
     intact = bool(np.all(c[F:] == -7.0) and np.all(s[P:] == -7.0) and np.all(w[P:] == -7.0) and sum_e[1] == -7.0)
     return dict(centres=c[:F], scales=s[:P], weight=w[:P], sum_e=float(sum_e[0]), initial_cost=sm.initial_cost, final_cost=sm.final_cost, successful_steps=sm.successful_steps,
                 unsuccessful_steps=sm.unsuccessful_steps, termination=sm.termination, guard_intact=intact, rc=int(rc))
+
+
+class TranslpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("gap_tol", C.c_double), ("feas_tol", C.c_double)]
+
+
+class TranslpSummary(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("dual_objective", C.c_double), ("gap", C.c_double), ("primal_residual", C.c_double), ("dual_residual", C.c_double),
+                ("iterations", C.c_int), ("bumps", C.c_int), ("n_components", C.c_int), ("n_loose", C.c_int), ("termination", C.c_int)]
+
+
+TRANSLP_GUARD = 8     # sentinel records the wrapper keeps behind every output
+TRANSLP_TERMINATIONS = {0: "converged", 1: "iteration limit", 2: "factorisation lost", 3: "not finite", 6: "no triplets"}
+
+
+def translp_group_size():
+    """pvlm_translp_group_size (K47): the lanes that share one camera's or one pair's gather."""
+    return int(load_library().pvlm_translp_group_size())
+
+
+def transavg_l1(ctx, first, second, R_21, t_21, triplet_pairs, origin_idx, translations, max_iterations=60, gap_tol=1e-9, feas_tol=1e-9, want_duals=True, check=True):
+    """pvlm_transavg_l1 (K47): TranslationAveragingL1, the triplet minimax programme, by an interior-point method.  triplet_pairs (triplets x 3): per triplet
+    i < j < k the indices of its pairs (i,j), (j,k), (i,k).  translations (cameras x 3, zero at origin_idx) only has to be finite: the call starts from zero.  The
+    inputs are not modified.  Returns a dict: translations, duals (triplets x 19, or None), gamma, dual_objective, gap, primal_residual, dual_residual, iterations,
+    bumps, n_components, n_loose, termination (TRANSLP_TERMINATIONS; only 0 and 1 write translations and duals), guard_intact (the TRANSLP_GUARD sentinel records
+    behind the outputs were not written), rc.  gamma, feasibility and the duals are the contract, the translation values are not (see pvlm.h).  An argument the
+    library refuses raises PvlmError; with check=False the dict comes back with its rc (the outputs then hold what went in, duals -7)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRANSLP_GUARD
+    R = _f64(np.asarray(R_21, np.float64).reshape(-1, 9)); t21 = _f64(np.asarray(t_21, np.float64).reshape(-1, 3))
+    tp = _i32(np.asarray(triplet_pairs, np.int32).reshape(-1, 3)); T = len(tp)
+    t_in = np.asarray(translations, np.float64).reshape(-1, 3); F = len(t_in)
+    t = np.full((F + G, 3), -7.0); t[:F] = t_in
+    duals = np.full((T + G, 19), -7.0) if want_duals else None
+    prm = TranslpParams(max_iterations, gap_tol, feas_tol)
+    sm = TranslpSummary(-7.0, -7.0, -7.0, -7.0, -7.0, -7, -7, -7, -7, -7)
+    rc = ctx.lib.pvlm_transavg_l1(ctx._h, C.c_int(F), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R, C.c_double), _p(t21, C.c_double), C.c_int(T),
+                                  _p(tp, C.c_int), C.c_int(origin_idx), _p(t, C.c_double), _p(duals, C.c_double), C.byref(prm), C.byref(sm))
+    if check:
+        ctx._check(rc, "pvlm_transavg_l1")
+    intact = bool(np.all(t[F:] == -7.0) and (duals is None or np.all(duals[T:] == -7.0)))
+    out = dict(translations=t[:F], duals=None if duals is None else duals[:T], guard_intact=intact, rc=int(rc))
+    for name, _ in TranslpSummary._fields_:
+        out[name] = getattr(sm, name)
+    return out
 
 
 class BataParams(C.Structure):

@@ -806,7 +806,7 @@ bool FilterImagePairsFull(const std::vector<Frame>& frames, const std::vector<Ma
 
 // ---- K42: translation averaging (sfm/TranslationAveraging.cpp:31-204, :419-481; sfm/SfM.cpp:908-934, :1047-1344, :1385-1421) ----------------------------------
 // sfm/SfM.h:71-76.  SOFTL1 and L2IRLS are built, and BATA (K44), CHORDAL and LUD (K46, below) behind TranslationOptions::enable_bata / enable_chordal / enable_lud;
-// L1 (the LP) is not: EstimateGlobalTranslation returns false with upstream's "not supported".
+// L1 (the triplet minimax programme, K47, below) behind enable_l1.  Without its flag a method gets upstream's "not supported".
 enum TranslationAveragingMethod { TRANSLATION_AVERAGING_SOFTL1 = 1, TRANSLATION_AVERAGING_L1 = 2, TRANSLATION_AVERAGING_CHORDAL = 3, TRANSLATION_AVERAGING_L2IRLS = 4,
                                   TRANSLATION_AVERAGING_BATA = 5, TRANSLATION_AVERAGING_LUD = 6 };
 // sfm/BATA.h's BATAConfig: what TranslationAveragingBATA hands BATA (upstream: always the defaults, :516)
@@ -828,6 +828,8 @@ struct TranslationOptions {
   BATAConfig bata;
   // Methods 3 (chordal) and 6 (LUD), K46, run only when these are set: the same test pins them under default options, for the same reason.
   bool enable_chordal = false, enable_lud = false;
+  // Method 2 (L1, K47) runs only when this is set: the same test pins it under default options, for the same reason.
+  bool enable_l1 = false;
 };
 // TranslationAveragingDLT (:31-84) through pvlm_transavg_dlt: the normal equations with camera 0 fixed at zero.  Upstream's SparseQR returns SOME basic solution of a
 // system that is rank-deficient by the gauge t_i = R_i c; every caller runs SetToOrigin afterwards, which cancels the difference.  false: a pair names a camera
@@ -868,6 +870,14 @@ bool TranslationAveragingL2Chordal(const std::vector<RelativePair>& image_pairs,
 bool TranslationAveragingLUD(std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
                              const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const int num_iteration, const float upper_scale_ratio,
                              const float lower_scale_ratio, const bool host = false, int* iterations_run = nullptr);
+// K47 — TranslationAveragingL1 (:277-417) through pvlm_transavg_l1 (see pvlm.h for the definition and its divergences: an interior-point method, a point near the
+// centre of the optimal face where upstream returns a vertex, further triplet components pinned, cameras in no triplet left at zero), as written: the triplets of
+// PoseGraph::FindTriplet over the pair list, a repeated pair resolved to its last index through the map (:289); upstream's new_to_old is read by nobody and is not
+// taken.  The call starts from t = 0.  summary: the call's, when given.  false: global_translations[origin_idx] not zero (upstream asserts), a pair with
+// first >= second or a camera past global_translations (upstream reads another pair's data or writes out of range), or a solve that did not converge ("Solve linear
+// program failed").  A pair list without a triplet leaves every translation zero and returns true.
+bool TranslationAveragingL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const bool host = false,
+                            pvlm_translp_summary* summary = nullptr);
 // SfM::ReIndex (sfm/SfM.cpp:908-934): the frame ids of a pair list onto 0 .. n - 1 in ascending order
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward);
 // SfM::SetToOrigin (:1385-1421) without the structure: every valid pose into the frame of frames[frame_idx] (the first valid frame when that one has no pose).

@@ -23,6 +23,7 @@
 #include "pvlm_host_bata.hpp"
 #include "pvlm_host_rotstart.hpp"
 #include "pvlm_host_transdir.hpp"
+#include "pvlm_host_translp.hpp"
 
 namespace pvlm {
 
@@ -1075,6 +1076,50 @@ bool TranslationAveragingL2Chordal(const std::vector<RelativePair>& image_pairs,
   return true;
 }
 
+// K47: TranslationAveragingL1 (sfm/TranslationAveraging.cpp:277-417)
+bool TranslationAveragingL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const bool host,
+                            pvlm_translp_summary* summary_out) {
+  const size_t F = global_translations.size();
+  if (origin_idx >= F || global_translations[origin_idx] != Vector3d{0, 0, 0}) return false;             // upstream asserts (:281)
+  std::map<std::pair<size_t, size_t>, size_t> image_pair_to_idx;                                         // :285-291: a repeated pair resolves to its last index
+  for (size_t i = 0; i < image_pairs.size(); ++i) {
+    const std::pair<size_t, size_t>& p = image_pairs[i].image_pair;
+    if (!(p.first < p.second) || p.second >= F) return false;
+    image_pair_to_idx[p] = i;
+  }
+  // the call's pair list: the distinct pairs in the map's order
+  std::vector<int> first, second, trip_pairs;
+  std::vector<double> R21, t21, t(3 * F, 0.0);
+  std::set<std::pair<size_t, size_t>> edges;
+  std::map<std::pair<size_t, size_t>, int> place;
+  for (const auto& kv : image_pair_to_idx) {
+    const RelativePair& p = image_pairs[kv.second];
+    place[kv.first] = (int)first.size();
+    first.push_back((int)kv.first.first); second.push_back((int)kv.first.second);
+    R21.insert(R21.end(), p.R_21.begin(), p.R_21.end()); t21.insert(t21.end(), p.t_21.begin(), p.t_21.end());
+    edges.insert(kv.first);
+  }
+  for (const Triplet& tr : FindTriplet(edges)) { trip_pairs.push_back(place[{tr.i, tr.j}]); trip_pairs.push_back(place[{tr.j, tr.k}]); trip_pairs.push_back(place[{tr.i, tr.k}]); }
+  const int P = (int)first.size(), T = (int)trip_pairs.size() / 3;
+  first.push_back(0); second.push_back(0); R21.resize(R21.size() + 9); t21.resize(t21.size() + 3); trip_pairs.push_back(0);      // never empty
+  pvlm_translp_summary sum{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const pvlm_translp_params prm{60, 1e-9, 1e-9};
+  if (host) {
+    pvlm_translp::Params hp; pvlm_translp::Summary hs;
+    if (translp_detail::L1Host((int)F, P, first.data(), second.data(), R21.data(), t21.data(), T, trip_pairs.data(), (int)origin_idx, t.data(), nullptr, &hp, &hs)) return false;
+    sum = {hs.gamma, hs.dual_objective, hs.gap, hs.primal_residual, hs.dual_residual, hs.iterations, hs.bumps, hs.n_components, hs.n_loose, hs.termination};
+  } else {
+    Engine& e = Engine::Default();
+    e.Check(pvlm_transavg_l1(e.ctx(), (int)F, P, first.data(), second.data(), R21.data(), t21.data(), T, trip_pairs.data(), (int)origin_idx, t.data(), nullptr, &prm, &sum),
+            "pvlm_transavg_l1");
+  }
+  if (summary_out) *summary_out = sum;
+  // no triplets: the programme has no rows, every column is free and stays zero
+  if (sum.termination != pvlm_translp::kConverged && sum.termination != pvlm_translp::kNoTriplets) return false;      // "Solve linear program failed"
+  for (size_t i = 0; i < F; ++i) global_translations[i] = {t[3 * i], t[3 * i + 1], t[3 * i + 2]};                     // :411-414
+  return true;
+}
+
 bool TranslationAveragingLUD(std::vector<RelativePair>& image_pairs, const std::vector<Frame>& frames, std::vector<Vector3d>& global_translations,
                              const std::map<size_t, size_t>& new_to_old, const size_t origin_idx, const int num_iteration, const float upper_scale_ratio,
                              const float lower_scale_ratio, const bool host, int* iterations_run) {
@@ -1229,10 +1274,12 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
     success = TranslationAveragingL2Chordal(image_pairs, frames, global_translations, new_to_old_global, origin_idx, 0.5, o.host);
   else if (method == TRANSLATION_AVERAGING_LUD && o.enable_lud)        // :1295-1305; behind the flag
     success = TranslationAveragingLUD(image_pairs, frames, global_translations, new_to_old_global, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
-  else return Say(o, "Translaton average method not supported");       // L1 (the LP) is not built, BATA, chordal and LUD only behind their flags; the text is upstream's (:1308)
+  else if (method == TRANSLATION_AVERAGING_L1 && o.enable_l1)          // :1264-1273; behind the flag
+    success = TranslationAveragingL1(image_pairs, global_translations, origin_idx, o.host);
+  else return Say(o, "Translaton average method not supported");       // L1, BATA, chordal and LUD only behind their flags; the text is upstream's (:1308)
   if (!success)
     return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : method == TRANSLATION_AVERAGING_BATA ? "Translation average BATA failed" :
-                  method == TRANSLATION_AVERAGING_CHORDAL ? "Translation average chordal failed" : method == TRANSLATION_AVERAGING_LUD ? "Translation average LUD failed" :
+                  method == TRANSLATION_AVERAGING_CHORDAL ? "Translation average chordal failed" : method == TRANSLATION_AVERAGING_LUD ? "Translation average LUD failed" : method == TRANSLATION_AVERAGING_L1 ? "Translation average L1 failed" :
                   "Translation average L2 IRLS failed");
   for (RelativePair& pair : image_pairs) { pair.image_pair.first = new_to_old_global[pair.image_pair.first]; pair.image_pair.second = new_to_old_global[pair.image_pair.second]; }
   std::set<size_t> frame_with_translation;
