@@ -640,7 +640,7 @@ pvlm_status pvlm_resset_point_table_debug(pvlm_ctx* ctx, const pvlm_resset* rs, 
         st = pvlm_i_d2h(ctx, tab.data(), rs->d_point_tab + (size_t)have * 3 * PVLM_POINT_TAB_STRIDE, tab.size() * sizeof(double));
       }
       for (int64_t j = 0; j < m && !st; ++j) {
-        const uint16_t q = words[(size_t)(4 * (j >> 1) + 2 + (j & 1))];
+        const uint16_t q = words[(size_t)(2 * j + 1)];     // one 32-bit word {run, query} per row: the high half
         if (qnum) qnum[o + j] = q;
         if (points) for (int c = 0; c < 3; ++c) points[(o + j) * 3 + c] = tab[(size_t)c * PVLM_POINT_TAB_STRIDE + q];
       }

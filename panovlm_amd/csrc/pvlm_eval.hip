@@ -2,8 +2,9 @@
 // and the small pose / pair table + epilogue kernels around them.  gfx950 (wave64) only.
 //
 // Data layout in HBM: a residual set is SoA, `ncols` fp64 columns of n_dev rows; every pair
-// segment starts on an even row so each lane streams two consecutive rows with one 16-byte load
-// per column (1 KiB per wave instruction).  The per-pair constants (R_rn, t_rn, t_rw, J_l blocks)
+// segment starts on an even row.  The wave-form, materialising and wrench kernels give a lane two consecutive rows, one 16-byte load
+// per column (1 KiB per wave instruction); the block form k_eval_fused gives a lane rows t and 64 + t of its wave's 128 (two half-trips of
+// 64 consecutive rows, one 8-byte load per column and half).  The per-pair constants (R_rn, t_rn, t_rw, J_l blocks)
 // are read through wave-uniform (scalar) loads.  Algorithmic HBM traffic per evaluation in fused
 // mode = 8*ncols bytes; materialise mode adds 8 + 96 B of stores.  Point-to-plane (7 columns, 56 B): a set whose planes repeat from row to row is read as
 // 24 B of point + a 2-byte run number per row + one 32-byte table entry per run of equal planes (pvlm_plane_args below): 26 + 32 / L bytes at mean run length L.
@@ -57,7 +58,7 @@ struct pvlm_plane_args {
   const int64_t* pair_idx0;
   const int64_t* chunk_plane0;   // per work-list entry: first table entry of the chunk
   const double* tab;             // {a, b, c, d} per run
-  // the point table (pvlm_resset::point_table, k_eval_fused<..., PT = true> only): idx then holds four words per PAIR of rows {run, run, query, query}
+  // the point table (pvlm_resset::point_table, k_eval_fused<..., PT = true> only): idx then holds ONE 32-bit word per row: run number in the low half, query number in the high half
   const double* const* pair_ptab;   // per pair: the table of its neighbour scan, 3 columns of PVLM_POINT_TAB_STRIDE doubles
   const int* order;                 // grid position -> work-list slot, -1 = padding; nullptr = identity (pvlm_dispatch_core.h)
 };
@@ -66,15 +67,24 @@ __device__ __forceinline__ unsigned stream_load_runs(const uint16_t* base, unsig
   const auto q = (pvlm_gptr<unsigned>)(reinterpret_cast<const char*>(base) + 2u * row);
   return NT ? __builtin_nontemporal_load(q) : *q;
 }
-// The point-table form: the run numbers and the query numbers of the lane's two rows in ONE 8-byte load (x: runs, y: queries; low half = the even row), streamed
-// like the run word; and a point coordinate out of the neighbour's table — an ordinary load: the table is read by every pair of the neighbour and is meant to
-// stay in the cache.
+// The block form k_eval_fused reads ONE row per lane and half-trip: 8 bytes of a streamed column, the 16-bit run number of a set without the point table, or
+// the 32-bit word {run, query} (low, high half) of a set on it.  `bytes` is the row's byte offset inside a column (8 * row); the run word sits at a
+// quarter of it, the {run, query} word at half.  Streamed like the columns.  A point coordinate out of the neighbour's table is an ordinary load: the
+// table is read by every pair of the neighbour and is meant to stay in the cache.
 template <bool NT>
-__device__ __forceinline__ uint2 stream_load_words(const uint16_t* base, unsigned row) {   // rows `row` (even) and `row + 1`
-  typedef unsigned pvlm_u2 __attribute__((ext_vector_type(2)));
-  const auto q = (pvlm_gptr<pvlm_u2>)(reinterpret_cast<const char*>(base) + 4u * row);
-  const pvlm_u2 v = NT ? __builtin_nontemporal_load(q) : *q;
-  return make_uint2(v.x, v.y);
+__device__ __forceinline__ double stream_load1(const double* p) {
+  const auto q = (pvlm_gptr<double>)(p);
+  return NT ? __builtin_nontemporal_load(q) : *q;
+}
+template <bool NT>
+__device__ __forceinline__ unsigned stream_load_run(const uint16_t* base, unsigned bytes) {
+  const auto q = (pvlm_gptr<uint16_t>)(reinterpret_cast<const char*>(base) + (bytes >> 2));
+  return NT ? __builtin_nontemporal_load(q) : *q;
+}
+template <bool NT>
+__device__ __forceinline__ unsigned stream_load_word(const uint16_t* base, unsigned bytes) {
+  const auto q = (pvlm_gptr<unsigned>)(reinterpret_cast<const char*>(base) + (bytes >> 1));
+  return NT ? __builtin_nontemporal_load(q) : *q;
 }
 __device__ __forceinline__ double table_load(const double* base, unsigned bytes) {
   return *(pvlm_gptr<double>)(reinterpret_cast<const char*>(base) + bytes);
@@ -101,8 +111,10 @@ __device__ __forceinline__ void stream_store1(double* p, double v) {
 }
 
 
-#ifndef PVLM_PT_LOAD_ORDER
-#define PVLM_PT_LOAD_ORDER 1   // 1: the point-table loads of a trip issue column by column, a lane's two rows back to back (0: wherever the scheduler puts them) — see k_eval_fused
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PVLM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)   // the instruction scheduler moves nothing across this point
+#else
+#define PVLM_SCHED_FENCE() ((void)0)
 #endif
 #ifndef PVLM_PREFETCH
 #define PVLM_PREFETCH -1  // -1 = per-functor default, 0 / 1 force
@@ -425,7 +437,7 @@ __device__ __forceinline__ double wave_transpose_sum(const double (&a)[N], int l
   return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR, bool PT>
+template <int KIND, bool NORM, int NCOLS, int LOSS, bool PR, bool PT, bool ROT>
 __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUSED_WAVES)) void k_eval_fused(const double* const* __restrict__ pair_cols,
                                                     const int64_t* __restrict__ pair_stride,
                                                     const int64_t* __restrict__ out_start,
@@ -434,6 +446,7 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
                                                     double loss_a, double* __restrict__ partials, pvlm_plane_args pr) {
   static_assert(!PR || NCOLS == 7, "plane runs: the 7-column kinds only");
   static_assert(!PT || PR, "the point table: on top of the plane runs only");
+  static_assert(!ROT || PR, "rotated halves: the plane-run forms only");
   // PT: the grid visits the work list in the order of pr.order (slots that read the same table slice together on one XCD); everything below is per SLOT
   const int slot = (PT && pr.order) ? pr.order[blockIdx.x] : (int)blockIdx.x;
   if (PT && slot < 0) return;     // padding position
@@ -446,12 +459,13 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
 #pragma unroll
   for (int k = 0; k < PVLM_PARTIAL; ++k) acc[k] = 0.0;
   const double a2 = uniform_sgpr(loss_a * loss_a), mh_a2 = uniform_sgpr(-0.5 * a2);   // wave-uniform: a2 lives in a scalar pair; mh_a2 shares its fma with loss_a (one scalar operand per instruction) and the compiler may keep it in VGPRs
-  // Each lane streams two consecutive rows per column with one 16-byte load.  The cheap (Meter)
-  // functors are latency-bound: their next tile is prefetched into registers while the current one
-  // is evaluated (+7 % on MI355X); the Angle functors are VALU-bound at 3 waves/SIMD and lose
-  // occupancy to the extra 28 VGPRs, so they load in place.
-  // (PT: the point's address comes out of the prefetched word — there is nothing to prefetch it with a trip ahead; in place for every kind)
-  constexpr bool kPrefetch = !PT && (PVLM_PREFETCH >= 0 ? (PVLM_PREFETCH != 0) : (KIND == PVLM_POINT2PLANE_METER || KIND == PVLM_POINT2LINE_METER));
+  // A wave's trip is 128 consecutive rows in two halves of 64: lane t takes row t of half A and row t of half B, in that order, so every load of a wave
+  // has adjacent lanes on adjacent rows (512 B of a streamed column per instruction; a gather whose neighbouring queries share their cache lines inside ONE
+  // instruction).  A slot — the 64 rows of a ballot (accumulate_row, the atan tier) — is one half.
+  // Without the plane runs the cheap (Meter) functors are latency-bound: their next trip is prefetched into registers while the current one is
+  // evaluated (+7 % on MI355X); the Angle functors lose occupancy to the extra registers and load in place.  The plane-run forms can rotate their halves instead (ROT, below; off by default).
+  constexpr bool kRotate = ROT;     // pvlm_resset::half_rotate (PVLM_HALF_ROTATE)
+  constexpr bool kPrefetch = !PR && (PVLM_PREFETCH >= 0 ? (PVLM_PREFETCH != 0) : (KIND == PVLM_POINT2PLANE_METER || KIND == PVLM_POINT2LINE_METER));
   // addresses = a wave-uniform column base (scalar registers) + one 32-bit row offset shared by the columns: the loads take the
   // saddr + voffset form and an iteration advances ONE register instead of a 64-bit pointer per column
   const double* colb[NS];
@@ -461,74 +475,98 @@ __global__ __launch_bounds__(256, (NCOLS == 7 ? PVLM_FUSED_WAVES_7COL : PVLM_FUS
   const double* tabb = nullptr;
   if (PR) { runb = pr.idx + (PT ? 2 : 1) * (pr.pair_idx0[p] + lo); tabb = pr.tab + 4 * pr.chunk_plane0[slot]; }
   const unsigned span = hi > lo ? (unsigned)(hi - lo) : 0u;
-  // The loop runs on ONE register: o, the byte offset of the lane's two rows inside a column (8 * row).  It addresses the columns, the run word (at o / 4)
-  // and carries the bounds; a row counter beside it costs the registers that the run word below needs.
-  const unsigned span8 = 8u * span;
-  unsigned o = 16u * threadIdx.x;
-  double2 nx[NS];
-  // PR: the run word's address depends on the row alone, and the addresses of the four table loads depend on the word.  It is fetched one trip ahead (one
-  // VGPR), so a trip issues its column loads, its table loads and the next word together and pays one memory round trip, not two in a row.  The next word's
-  // load has no branch around it — under an exec mask the wait-count merge puts a full wait in the middle of the table loads: the last trip re-reads its own
-  // word, which is in bounds.
-  // PT: the word pair {runs, queries}; the six point loads depend on it exactly as the four table loads do — still one round trip per trip.
-  unsigned nx_runs = 0, nx_qs = 0;
-  auto load_words = [&](unsigned row) {
-    if (PT) { const uint2 w = stream_load_words<PVLM_NT_LOADS != 0>(runb, row); nx_runs = w.x; nx_qs = w.y; }
-    else nx_runs = stream_load_runs<PVLM_NT_LOADS != 0>(runb, row);
+  // The loop runs on ONE register: o, the byte offset of the lane's half-A row inside a column (8 * row); half B is 512 bytes on.  It addresses the columns,
+  // the run word (at o / 4; the {run, query} word at o / 2) and carries the bounds.  No load has a branch around it — under an exec mask the wait-count merge
+  // puts full waits between the loads: a lane without a row in a half, or in the trip ahead, reads the chunk's last row instead (one address for all such
+  // lanes, in bounds, never evaluated).  last8 is only used where a lane has a row, that is span > 0.
+  const unsigned span8 = 8u * span, last8 = span8 - 8u;
+  unsigned o = 8u * (threadIdx.x + (threadIdx.x & ~63u));     // row 128 * wave + lane
+  auto row_at = [&](unsigned bytes) { return min(bytes, last8); };
+  double x[2][NS], nx[2][NS];   // per half: the streamed columns (PT: the point out of the table); nx: the trip ahead (kPrefetch)
+  double2 pl[2][2];             // PR, per half: {a, b}, {c, d}
+  unsigned w[2] = {0u, 0u};     // PR, per half: the run number; PT: the word {run, query}.  Fetched ahead of the loads whose addresses come out of it.
+  auto load_word = [&](int h, unsigned bytes) {
+    if (PT) w[h] = stream_load_word<PVLM_NT_LOADS != 0>(runb, bytes);
+    else w[h] = stream_load_run<PVLM_NT_LOADS != 0>(runb, bytes);
   };
-  if (PR && o < span8) load_words(o >> 3);
-  if (kPrefetch && o < span8) {
+  auto load_cols = [&](double (&dst)[NS], unsigned bytes) {
 #pragma unroll
-    for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
-  }
-  for (; o < span8; o += 4096) {     // 512 rows per trip
-    double2 v[NS];
-    const unsigned runs = nx_runs, qs = nx_qs;
-    const unsigned o_next = o + 4096 < span8 ? o + 4096 : o;
-    if (kPrefetch) {
+    for (int c = 0; c < NS; ++c) dst[c] = stream_load1<PVLM_NT_LOADS != 0>(at_byte(colb[c], bytes));
+  };
+  // one half's gather: the point (three 8-byte loads; adjacent lanes are adjacent rows, mostly neighbouring queries) and the plane entry's two 16-byte halves
+  // back to back.  The fence keeps the halves' loads apart and in this order.
+  auto gather = [&](int h, unsigned bytes) {
+    if (PT) {
+      const unsigned q = 8u * (w[h] >> 16);
 #pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = nx[c];
-      if (PR) load_words(o_next >> 3);
-      if (o + 4096 < span8) {
-#pragma unroll
-        for (int c = 0; c < NS; ++c) nx[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o + 4096));
-      }
-    } else if (PT) {
-      const unsigned q0 = 8u * (qs & 0xffffu), q1 = 8u * (qs >> 16);
-      // A lane's two rows are neighbouring queries: the two loads of a column mostly want the same cache line.  Issued back to back the second finds the line
-      // (or its miss in flight); left to the scheduler they are grouped by address register — row 1's three columns, the plane entries, the word, then row 0's
-      // three — and with 16 waves of a CU gathering between them the line has to come from the L2 twice (a reading of the timings; no counter run).  The barrier
-      // keeps the source order: x0 x1 y0 y1 z0 z1, then the plane entries, and row 0's arithmetic starts while row 1's plane entries are still on their way
-      // (profiles/eval_row_pairs_ab.txt).
-#pragma unroll
-      for (int c = 0; c < NS; ++c) {
-        v[c] = make_double2(table_load(colb[c], q0), table_load(colb[c], q1));
-#if PVLM_PT_LOAD_ORDER && defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-      }
+      for (int c = 0; c < NS; ++c) x[h][c] = table_load(colb[c], q);
     } else {
-#pragma unroll
-      for (int c = 0; c < NS; ++c) v[c] = stream_load2<PVLM_NT_LOADS != 0>(at_byte(colb[c], o));
+      load_cols(x[h], bytes);
     }
-    double2 pl[2][2];              // PR: {a, b}, {c, d} of the lane's two rows (a pad row behind an odd last row names entry 0)
     if (PR) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const unsigned at = 32u * (h ? runs >> 16 : runs & 0xffffu);
-        pl[h][0] = stream_load2<false>(at_byte(tabb, at));
-        pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
-      }
-      if (!kPrefetch) load_words(o_next >> 3);
+      const unsigned at = 32u * (w[h] & 0xffffu);
+      pl[h][0] = stream_load2<false>(at_byte(tabb, at));
+      pl[h][1] = stream_load2<false>(at_byte(tabb, at + 16u));
+      PVLM_SCHED_FENCE();
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (o + 8u * h >= span8) break;
+  };
+  auto evaluate = [&](int h, unsigned bytes) {
+    if (bytes < span8) {
       double rec[NCOLS];
 #pragma unroll
-      for (int c = 0; c < NS; ++c) rec[c] = h ? v[c].y : v[c].x;
+      for (int c = 0; c < NS; ++c) rec[c] = x[h][c];
       if (PR) { rec[3] = pl[h][0].x; rec[4] = pl[h][0].y; rec[5] = pl[h][1].x; rec[6] = pl[h][1].y; }
       accumulate_row<KIND, NORM, NCOLS, LOSS>(rec, T, weight, loss_a, a2, mh_a2, acc);
+    }
+  };
+  if (kRotate) {
+    // Measured against the schedule below: the same time on the Angle headline, slower on the Meter functor (profiles/eval_half_trips_ab.txt) — what a trip waits
+    // for is not its own gather.  Kept behind pvlm_resset::half_rotate for the next look at it.
+    // The halves rotate: when half A of trip k has been evaluated its 14 data registers are dead, and A's gather of trip k + 1 goes into them BEFORE half B
+    // of trip k is evaluated; B's gather of trip k + 1 goes out behind B's evaluation.  One half's gather is always in flight behind the other half's
+    // arithmetic (and that of the SIMD's other waves), and the 28 data registers are live as in the schedule that issues a whole trip and then evaluates it.
+    // A half's word is re-fetched right behind the gather that consumed it — for the trip after the one just issued — so at the top of a trip the loads in
+    // flight are, in order: A's 5, a word, B's 5, a word, and the waits are counted (vmcnt 7 before A's arithmetic, 6 before A's next gather).
+    if (o < span8) {
+      const unsigned ob = row_at(o + 512u);
+      load_word(0, o);
+      load_word(1, ob);
+      gather(0, o);
+      load_word(0, row_at(o + 4096u));
+      PVLM_SCHED_FENCE();
+      gather(1, ob);
+      load_word(1, row_at(o + 4608u));
+      PVLM_SCHED_FENCE();
+    }
+    for (; o < span8; o += 4096) {     // 512 rows per trip
+      evaluate(0, o);
+      PVLM_SCHED_FENCE();
+      gather(0, row_at(o + 4096u));
+      load_word(0, row_at(o + 8192u));
+      PVLM_SCHED_FENCE();
+      evaluate(1, o + 512u);
+      PVLM_SCHED_FENCE();
+      gather(1, row_at(o + 4608u));
+      load_word(1, row_at(o + 8704u));
+      PVLM_SCHED_FENCE();
+    }
+  } else {
+    // Both halves' loads, then both halves' arithmetic: one memory round trip per trip.  PR (ROT = false, PVLM_HALF_ROTATE = 0): the words come one trip ahead.
+    if (PR && o < span8) { load_word(0, o); load_word(1, row_at(o + 512u)); }
+    if (kPrefetch && o < span8) { load_cols(nx[0], o); load_cols(nx[1], row_at(o + 512u)); }
+    for (; o < span8; o += 4096) {     // 512 rows per trip
+      if (kPrefetch) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) { x[0][c] = nx[0][c]; x[1][c] = nx[1][c]; }
+        load_cols(nx[0], row_at(o + 4096u));
+        load_cols(nx[1], row_at(o + 4608u));
+      } else {
+        gather(0, o);
+        gather(1, row_at(o + 512u));
+        if (PR) { load_word(0, row_at(o + 4096u)); load_word(1, row_at(o + 4608u)); }
+      }
+      evaluate(0, o);
+      evaluate(1, o + 512u);
     }
   }
   __shared__ double red[4][PVLM_PARTIAL];
@@ -773,9 +811,11 @@ static void launch_fused_as(pvlm_ctx* ctx, const pvlm_resset* rs, double a) {
   if (rs->wave_units)            // many short segments: one wave per (pair, chunk)
     launch_eval(k_eval_fused_wave<KIND, NORM, NCOLS, LOSS, PR>, (rs->n_blocks + 3) / 4, ctx, rs, rs->n_blocks, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
   else if (PR && rs->point_table)  // the point from the neighbour's table, the grid in the set's dispatch order (pvlm_i_plane_runs_build chose both)
-    launch_eval(k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR>, rs->n_positions, ctx, rs, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
-  else
-    launch_eval(k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false>, rs->n_blocks, ctx, rs, rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
+    launch_eval(rs->half_rotate ? k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR, PR> : k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, PR, false>, rs->n_positions, ctx, rs,
+                rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
+  else                             // (a set without the plane runs has half_rotate = false: one instantiation)
+    launch_eval(PR && rs->half_rotate ? k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false, PR> : k_eval_fused<KIND, NORM, NCOLS, LOSS, PR, false, false>, rs->n_blocks, ctx, rs,
+                rs->d_pair_tab, rs->weight, a, rs->d_partials, pr);
 }
 template <int KIND, bool NORM, int NCOLS>
 static void launch_fused(pvlm_ctx* ctx, const pvlm_resset* rs, int loss, double a) {

@@ -22,6 +22,9 @@
 #define PVLM_PAIR_TAB 33
 // Fused partial: [S upper triangle (21) | gv (6) | cost (1)]
 #define PVLM_PARTIAL 28
+#ifndef PVLM_HALF_ROTATE
+#define PVLM_HALF_ROTATE 0   // the schedule of the plane-run forms of k_eval_fused (pvlm_eval.hip).  0: both halves' loads, then both halves' arithmetic; 1: rotated halves — measured: nothing on the Angle headline, 0.16 ms LOST on the Meter functor (profiles/eval_half_trips_ab.txt), so off.  The environment variable of the same name overrides it per set (A/B runs, the tests).
+#endif
 #define PVLM_POINT_TAB_STRIDE 65536   // entries per column of a neighbour's point table (pvlm_resset::d_point_tab): a query number is 16 bits
 
 // Device memory of a context comes from a caching sub-allocator: hipMalloc maps pages at 40-70 ms per GB on MI355X
@@ -163,15 +166,16 @@ struct pvlm_resset {
   // kernels then read 24 B of point + a 2-byte run number per row and the plane from the table.  The seven columns stay: every other path reads them.
   bool plane_runs = false;              // the fused kernels take the plane from d_plane_tab
   int64_t n_plane_runs = 0;             // table entries (runs of equal consecutive planes inside a chunk), 0 when the table was not counted
-  uint16_t* d_plane_idx = nullptr;      // per padded row, in pair order (pair p starts at d_pair_idx0[p]): the row's run number inside its chunk
+  uint16_t* d_plane_idx = nullptr;      // per padded row, in pair order (pair p starts at d_pair_idx0[p]): the row's run number inside its chunk (k_eval_fused reads one per row, k_eval_fused_wave a row pair's two at once: a pad row names run 0)
   double* d_plane_tab = nullptr;        // n_plane_runs x {a, b, c, d}
   int64_t* d_chunk_plane0 = nullptr;    // n_blocks: first table entry of the work-list entry
   int64_t* d_pair_idx0 = nullptr;       // n_pairs: first element of the pair in d_plane_idx (a multiple of 16)
   // Point table (sets made by the association, plane-run form, block form, every neighbour <= 65 536 queries): the local point of query q of a neighbour scan
   // — columns 0..2 of every row that q has in any pair with that neighbour — is kept ONCE per distinct neighbour (d_point_tab: 3 columns of
   // PVLM_POINT_TAB_STRIDE doubles per neighbour, a snapshot taken by the association), and a row names its query with 16 bits.  d_plane_idx then holds, per
-  // pair of rows, four 16-bit words {run(2k), run(2k+1), query(2k), query(2k+1)}: one 8-byte load per lane of k_eval_fused.  The three columns stay.
+  // row, one 32-bit word {run, query} (low, high half): one 4-byte load per lane and half-trip of k_eval_fused; pad rows hold nothing.  The three columns stay.
   bool point_table = false;             // k_eval_fused takes the point from d_point_tab
+  bool half_rotate = false;             // plane-run sets of the block form: k_eval_fused keeps one half-trip's gather in flight behind the other half's arithmetic
   std::vector<uint16_t*> d_q16;         // per column block, while the set is being made: query number of every row (freed by the finalize pass)
   std::vector<int> h_pair_tab;          // n_pairs: the pair's neighbour among the distinct neighbours of the call
   int n_point_tabs = 0;

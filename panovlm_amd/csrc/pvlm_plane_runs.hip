@@ -56,8 +56,8 @@ __global__ __launch_bounds__(pvlm_compact::kThreads) void k_plane_run_write(cons
                                                                             uint16_t* __restrict__ plane_idx, double* __restrict__ plane_tab,
                                                                             const uint16_t* const* __restrict__ pair_q16) {
   const PlaneChunk c = plane_chunk(pair_cols, pair_stride, out_start, blk_pair, blk_chunk, chunk_rows);
-  // pair_q16 (the point table, pvlm_resset::point_table): the pair's query numbers go in beside the run numbers, four 16-bit words per PAIR of rows
-  // {run(2k), run(2k+1), query(2k), query(2k+1)}; without it one word per row
+  // pair_q16 (the point table, pvlm_resset::point_table): the pair's query numbers go in beside the run numbers, one 32-bit word per row
+  // {run, query} (low, high half: k_eval_fused loads a row's word whole); without it one 16-bit word per row
   const uint16_t* q16 = pair_q16 ? pair_q16[c.p] : nullptr;
   uint16_t* idx = plane_idx + (q16 ? 2 : 1) * pair_idx0[c.p];                                    // indexed by the row inside the pair
   ulonglong2* tab = reinterpret_cast<ulonglong2*>(plane_tab) + 2 * chunk_plane0[blockIdx.x];    // two 16-byte halves per entry
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(pvlm_compact::kThreads) void k_plane_run_write(cons
     for (int k = 0; k < pvlm_compact::kWaves; ++k) { const int t = wave_runs[k]; before += k < wv ? t : 0; all += t; }
     if (j < c.hi) {
       const int run = before + upto - 1;                       // >= 0: the chunk's first row starts a run; < chunk_rows <= 65536 (pvlm_i_plane_runs_build)
-      if (q16) { const int64_t e = 4 * (j >> 1) + (j & 1); idx[e] = (uint16_t)run; idx[e + 2] = q16[j]; }
+      if (q16) reinterpret_cast<uint32_t*>(idx)[j] = (uint32_t)run | ((uint32_t)q16[j] << 16);      // idx is 4-byte aligned: 2 * pair_idx0 words into an allocation
       else idx[j] = (uint16_t)run;
       if (starts) { tab[2 * run] = make_ulonglong2(w[0], w[1]); tab[2 * run + 1] = make_ulonglong2(w[2], w[3]); }
     }
@@ -100,6 +100,7 @@ static const double kPlaneRunsMinMean = 1.25;
 static pvlm_status plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padded_rows) {
   rs->plane_runs = false;
   rs->point_table = false;
+  rs->half_rotate = false;
   if (rs->ncols != 7 || rs->n_blocks == 0 || rs->chunk_rows > 65536) return PVLM_OK;     // a run number is 16 bits (PVLM_WAVE_CHUNK can ask for longer chunks)
   int force = -1;
   if (const char* env = getenv("PVLM_PLANE_RUNS")) force = atoi(env) != 0;
@@ -157,9 +158,9 @@ static pvlm_status plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padd
     if ((st = pvlm_i_h2d_q(ctx, rs->d_pair_ptab, pair_ptab.data(), (size_t)P * sizeof(double*)))) return st;
   }
   if ((st = pvlm_i_h2d_q(ctx, rs->d_pair_idx0, pair_idx0.data(), (size_t)P * sizeof(int64_t)))) return st;
-  // a lane of the fused kernels loads the run numbers of its TWO rows at once: the pad row behind an odd last row must name an entry that exists (0)
-  // (and query 0: every table has the entry's memory, whatever it holds — the pad row is loaded, never evaluated)
-  PVLM_HIP(ctx, hipMemsetAsync(rs->d_plane_idx, 0, (size_t)padded_rows * (pt ? 2 : 1) * sizeof(uint16_t), ctx->stream));
+  // a lane of k_eval_fused_wave loads the run numbers of its TWO rows at once: the pad row behind an odd last row must name an entry that exists (0).
+  // k_eval_fused loads one word per row and none for a pad row: the {run, query} words of a set on the point table, which only it reads, need no such fill.
+  if (!pt) PVLM_HIP(ctx, hipMemsetAsync(rs->d_plane_idx, 0, (size_t)padded_rows * sizeof(uint16_t), ctx->stream));
   hipLaunchKernelGGL(k_plane_run_write, dim3(nb), dim3(pvlm_compact::kThreads), 0, ctx->stream, rs->d_pair_cols, rs->d_pair_stride, rs->d_out_start,
                      rs->d_blk_pair, rs->d_blk_chunk, rs->chunk_rows, rs->d_chunk_plane0, rs->d_pair_idx0, rs->d_plane_idx, rs->d_plane_tab,
                      (const uint16_t* const*)d_pair_q16);
@@ -167,6 +168,8 @@ static pvlm_status plane_runs_build(pvlm_ctx* ctx, pvlm_resset* rs, int64_t padd
   if ((st = pvlm_i_sync(ctx))) return st;           // pair_idx0 goes out of scope
   rs->plane_runs = true;
   rs->point_table = pt;
+  rs->half_rotate = PVLM_HALF_ROTATE != 0;
+  if (const char* env = getenv("PVLM_HALF_ROTATE")) rs->half_rotate = atoi(env) != 0;      // like PVLM_PLANE_RUNS: A/B runs and the tests
   mark("table built");
   return PVLM_OK;
 }

@@ -23,6 +23,8 @@ def assembly(tree, rel):
 def kernels(text):
     """{kernel: its lines} and the lines outside every kernel, without what differs from build to build"""
     lines = [l for l in text.split("\n") if l.strip() and not re.match(r"\s*(;|\.file\s|\.loc\s|\.ident\s)", l) and "__hip_cuid_" not in l]
+    # local labels carry the function's number in the module (.LBB<function>_<block>), which moves when kernels are added or removed in front of it
+    lines = [re.sub(r"\.LBB\d+_", ".LBB_", l) for l in lines]
     names = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M))
     out, rest, cur = {}, [], None
     for l in lines:
