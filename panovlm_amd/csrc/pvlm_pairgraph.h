@@ -1,13 +1,15 @@
-// The device half of the pair-graph layer (pvlm_pairgraph_core.h) under K40 (pvlm_rotavg.hip), K42 (pvlm_transavg.hip) and K44 (pvlm_bata.hip); included after
-// pvlm_internal.h.
+// The device half of the pair-graph layer (pvlm_pairgraph_core.h) under K40 (pvlm_rotavg.hip), K42 (pvlm_transavg.hip), K44 (pvlm_bata.hip), K45
+// (pvlm_rotstart.hip), K46 (pvlm_transdir.hip) and K47 (pvlm_translp.hip); included after pvlm_internal.h.
 //   k_pg_tree       one node level of the fixed reduction tree (kChunk leaves per workgroup, halved in LDS), launched level by level until one number is left;
 //   camera_gather   the skeleton of every per-camera gather: kGroup lanes per camera walk its CSR row, an xor butterfly over the group adds the partial sums, lane 0
 //                   writes.  The stage gives the lane function and the epilogue;
 //   k_pg_gather_lm  the gather of an LM linearisation: the two-sided kCam-number record into the camera's gather and its diagonal block of the solver's list;
-//   k_pg_cam_step   a lane per camera: the candidate of a 3-vector per camera and its terms.
-// On the host's side: the pair list, its CSR and the tree's partials on the device (DeviceGraph), the call of the library's block-sparse SPD solver (solve_cameras)
-// and what an LM backend keeps besides its own state vectors and per-pair kernels (LmDevice).
-// Both includers are separate code objects in one library: everything here sits in an unnamed namespace, so each has its own kernels and host stubs.
+//   k_pg_cam_step   a lane per camera: the candidate of a 3-vector per camera and its terms;
+//   k_pg_lm_cost, k_pg_lm_pairs, k_pg_lm_step   a lane per pair around the three methods of a pair model (pvlm_pairgraph_core.h, at lm_solve): the cost term, the
+//                   linearisation into the pair's record and the solver's block list, the candidate scale and the pair's terms.
+// On the host's side: the pair list, its CSR and the tree's partials on the device (DeviceGraph), the call of the library's block-sparse SPD solver (solve_cameras),
+// what every LM backend keeps on top of the graph (LmDevice) and the LM backend of a pair model (LmPairDevice), which K40's L2 stage, K42 and K46 instantiate.
+// The six includers are separate code objects in one library: everything here sits in an unnamed namespace, so each has its own kernels and host stubs.
 // Vector stores and plain C++ only.
 #pragma once
 #include <chrono>
@@ -81,8 +83,9 @@ __global__ __launch_bounds__(kThreads) void k_pg_cam_step(int F, const double* _
 }
 
 // wall clock of the stages of a call, each of which ends in a wait for the stream: `kernels` = the evaluations, gathers, steps and reductions with their copies,
-// `solve` = the camera system (plan, assembly, factorisation, substitution), `form_g` = K40's dense inverse (zero for K42).  Printed on stderr when
-// PVLM_ROTAVG_PROFILE / PVLM_TRANSAVG_PROFILE is set (tools/rotavg_bench.py, tools/transavg_bench.py).
+// `solve` = the camera system (plan, assembly, factorisation, substitution), `form_g` = the dense inverse of K40's L1 stage (zero everywhere else).  Every entry
+// point prints them as one profile line on stderr when its stage's variable is set — PVLM_ROTAVG_PROFILE (K40, K45), PVLM_TRANSAVG_PROFILE, PVLM_BATA_PROFILE,
+// PVLM_TRANSDIR_PROFILE, PVLM_TRANSLP_PROFILE — and the stage's tools/*_bench.py parses that line.
 struct StageClock {
   double kernels_ms = 0, solve_ms = 0, form_g_ms = 0; int solves = 0;
   std::chrono::steady_clock::time_point t0;
@@ -137,8 +140,8 @@ bool solve_cameras(pvlm_call& c, pg::CameraSystem& sys, double* d_blocks, int n_
   return !st;
 }
 
-// What an LM backend (pg::lm_solve) keeps on top of the graph: the camera system and its block list ([F diagonal | P off-diagonal]), the gather, the step.  The
-// stage adds its state vectors, its per-pair kernels and their records.
+// What an LM backend (pg::lm_solve) keeps on top of the graph, whatever its pair model: the camera system and its block list ([F diagonal | P off-diagonal]), the
+// gather, the step.
 struct LmDevice : DeviceGraph {
   pg::Options opt;
   pg::CameraSystem sys;
@@ -163,7 +166,7 @@ struct LmDevice : DeviceGraph {
     return c.sync() == PVLM_OK;
   }
   // info of the factorisation in *info_out when given
-  bool solve(double radius, bool damped = true, int* info_out = nullptr) {
+  bool solve(double radius, bool damped, int* info_out) {
     if (failed()) return false;
     sys.prepare(cam.data(), damped, radius, opt);
     int info = 0;
@@ -177,6 +180,107 @@ struct LmDevice : DeviceGraph {
   // the camera half of a candidate: x_cand = x + step and the cameras' terms, which camera_terms reduces
   void step_cameras(const double* d_x, double* d_x_cand) { c.launch(k_pg_cam_step, dim3(camera_grid()), dim3(kThreads), 0, F, d_x, d_step, d_x_cand, d_cterms); }
   void camera_terms(double* ct) { reduce<false>(d_cterms, F, F, 2, ct); }
+};
+
+// The three per-pair kernels of a pair model M (pvlm_pairgraph_core.h, at lm_solve): a lane per pair reads its cameras' vectors by first / second (strided) and, where
+// M::kScale, its scale; the record and the terms are component-major, so the lanes of a wave store side by side.  s, sigma, gs_abs and s_cand are null without kScale.
+template <class M> __global__ __launch_bounds__(kThreads) void k_pg_lm_cost(M m, int P, const int* __restrict__ first, const int* __restrict__ second,
+                                                                            const double* __restrict__ x, const double* __restrict__ s, double a, double* __restrict__ terms) {
+  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
+    double xi[3], xj[3];
+    for (int k = 0; k < 3; ++k) { xi[k] = x[3 * (long long)first[p] + k]; xj[k] = x[3 * (long long)second[p] + k]; }
+    terms[p] = m.cost(p, xi, xj, pg::pair_scale<M>(s, p), a);
+  }
+}
+
+template <class M> __global__ __launch_bounds__(kThreads) void k_pg_lm_pairs(M m, int P, const int* __restrict__ first, const int* __restrict__ second,
+                                                                             const double* __restrict__ x, const double* __restrict__ s, double a, double radius,
+                                                                             double min_diag, double max_diag, int first_time, double* __restrict__ sigma,
+                                                                             double* __restrict__ rec, double* __restrict__ off_blocks, double* __restrict__ gs_abs) {
+  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
+    double xi[3], xj[3];
+    for (int k = 0; k < 3; ++k) { xi[k] = x[3 * (long long)first[p] + k]; xj[k] = x[3 * (long long)second[p] + k]; }
+    m.linearise(p, xi, xj, pg::pair_scale<M>(s, p), a, radius, min_diag, max_diag, first_time != 0, pg::pair_slot<M>(sigma, p), rec + p, P, off_blocks + 36 * p);
+    if constexpr (M::kScale) gs_abs[p] = fabs(rec[(long long)M::kGs * P + p]);
+  }
+}
+
+template <class M> __global__ __launch_bounds__(kThreads) void k_pg_lm_step(M m, int P, const int* __restrict__ first, const int* __restrict__ second,
+                                                                            const double* __restrict__ rec, const double* __restrict__ step,
+                                                                            const double* __restrict__ x_cand, const double* __restrict__ s, double a,
+                                                                            double* __restrict__ s_cand, double* __restrict__ terms) {
+  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
+    const long long i = first[p], j = second[p];
+    double di[3], dj[3], ci[3], cj[3], sc = 0.0;
+    for (int k = 0; k < 3; ++k) { di[k] = step[3 * i + k]; dj[k] = step[3 * j + k]; ci[k] = x_cand[3 * i + k]; cj[k] = x_cand[3 * j + k]; }
+    m.step(p, rec + p, P, di, dj, ci, cj, pg::pair_scale<M>(s, p), a, M::kScale ? &sc : nullptr, terms + p, P);
+    if constexpr (M::kScale) s_cand[p] = sc;
+  }
+}
+
+// The LM backend of a pair model M.  The state (x: 3 numbers per camera; where M::kScale, s and the Jacobi scale sigma: one per pair), its candidate and the pair
+// records stay on the device for the whole call; per iteration the host reads the gather, hands the solver its right-hand side and LM diagonal, sends the camera step
+// back and reads the roots of the terms.  limit_env: the stage's PVLM_*_MAX_BLOCKS.  After setup() the stage sets `model` (its inputs uploaded through c; d_R21 is the
+// graph's) and may clear `damped`: no LM diagonal and no Jacobi scaling of the cameras, one plain solve of the linearisation (K42's DLT).
+template <class M> struct LmPairDevice : LmDevice {
+  M model{};
+  bool damped = true;
+  double *d_x[2] = {nullptr, nullptr}, *d_s[2] = {nullptr, nullptr}, *d_sigma = nullptr, *d_gs = nullptr, *d_rec = nullptr, *d_terms = nullptr;
+  int cur = 0;
+
+  LmPairDevice(pvlm_call& call, const char* limit_env, const pg::Options& o, int F_, int P_) : LmDevice(call, limit_env, o, F_, P_) {}
+
+  // x0: 3 F; s0: P where M::kScale, else unread; R21: see DeviceGraph
+  void setup(const int* first, const int* second, const double* R21, const double* x0, const double* s0, int origin) {
+    LmDevice::setup(first, second, R21, M::kTerms, origin);
+    d_x[0] = c.upload(x0, 3 * (size_t)F); d_x[1] = c.alloc<double>(3 * (size_t)F);
+    if constexpr (M::kScale) {
+      d_s[0] = c.upload(s0, (size_t)P); d_s[1] = c.alloc<double>((size_t)P);
+      d_sigma = c.alloc<double>((size_t)P); d_gs = c.alloc<double>((size_t)P);
+    }
+    d_rec = c.alloc<double>((size_t)M::kSlots * (size_t)P); d_terms = c.alloc<double>((size_t)M::kTerms * (size_t)P);
+  }
+  // the current state, for the entry point's download
+  const double* x() const { return d_x[cur]; }
+  const double* s() const { return d_s[cur]; }
+
+  double initial_cost() {
+    double cost = 0.0;
+    clock.start();
+    c.launch(k_pg_lm_cost<M>, dim3(pair_grid()), dim3(kThreads), 0, model, P, d_first, d_second, d_x[cur], d_s[cur], opt.loss_a, d_terms);
+    reduce<false>(d_terms, P, P, 1, &cost);
+    const bool bad = c.sync() != PVLM_OK;
+    clock.kernels_ms += clock.stop();
+    return bad ? std::nan("") : cost;
+  }
+  double linearise(double radius, bool first) {
+    double gs_max = 0.0;
+    clock.start();
+    c.launch(k_pg_lm_pairs<M>, dim3(pair_grid()), dim3(kThreads), 0, model, P, d_first, d_second, d_x[cur], d_s[cur], opt.loss_a, radius, opt.min_lm_diagonal,
+             opt.max_lm_diagonal, first ? 1 : 0, d_sigma, d_rec, off_blocks(), d_gs);
+    if constexpr (M::kScale) reduce<true>(d_gs, P, P, 1, &gs_max);
+    const bool ok = gather(d_rec);
+    clock.kernels_ms += clock.stop();
+    if (!ok) return 0.0;
+    if (first && damped) sys.set_sigma(cam.data());
+    const double g_max = sys.gradient_max(cam.data());
+    return M::kScale ? std::fmax(gs_max, g_max) : g_max;
+  }
+  bool solve(double radius, int* info_out = nullptr) { return LmDevice::solve(radius, damped, info_out); }
+  pg::Scalars candidate() {
+    double pt[4] = {0, 0, 0, 0}, ct[2] = {0, 0};
+    clock.start();
+    step_cameras(d_x[cur], d_x[cur ^ 1]);
+    c.launch(k_pg_lm_step<M>, dim3(pair_grid()), dim3(kThreads), 0, model, P, d_first, d_second, d_rec, d_step, d_x[cur ^ 1], d_s[cur], opt.loss_a, d_s[cur ^ 1], d_terms);
+    reduce<false>(d_terms, P, P, M::kTerms, pt);          // the staged copy of the roots is ordered on the stream before the next tree reuses the partials
+    camera_terms(ct);
+    const bool bad = c.sync() != PVLM_OK;
+    clock.kernels_ms += clock.stop();
+    if (bad) return pg::Scalars{std::nan(""), 0, 0, 0};
+    if constexpr (M::kScale) return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], pt[pg::kTermStep2] + ct[0], pt[pg::kTermX2] + ct[1]};
+    else return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], ct[0], ct[1]};
+  }
+  void accept() { cur ^= 1; }
 };
 
 }  // namespace

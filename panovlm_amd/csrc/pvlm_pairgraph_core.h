@@ -1,6 +1,7 @@
-// The pair-graph layer under K40 (rotation averaging), K42 (translation averaging) and K44 (BATA) — host and device.  The stages hang residual blocks on the pairs of a
-// camera graph and solve for per-camera unknowns of three numbers; what they share is here and nothing in it knows what the unknowns are (K44 takes the CSR, the gather,
-// the tree and the camera system, not the LM loop):
+// The pair-graph layer under the six stages that solve on a camera graph — K40 (rotation averaging), K42 (translation averaging), K44 (BATA), K45 (the L2 rotation
+// start), K46 (chordal / LUD) and K47 (the L1 translation LP) — host and device.  The stages hang residual blocks on the pairs of a camera graph and solve for
+// per-camera unknowns of three numbers; what they share is here and nothing in it knows what the unknowns are (K44, K45 and K47 take the CSR, the gather, the tree
+// and the camera system, not the LM loop):
 //   the CSR of the cameras' incident pairs (entry = 2 * pair + side, pair-list order) and its gather: kGroup lanes per camera, lane l takes the entries l, l + kGroup,
 //     ..., an xor butterfly adds the partial sums.  One order per camera, whatever the degree, no floating-point atomics;
 //   the fixed reduction tree of every scalar (cost, model decrease, norms): leaves in chunks of kChunk, a halving tree inside a chunk, the chunk sums reduced the same
@@ -9,8 +10,9 @@
 //     policy over a backend that evaluates, gathers, solves and steps (lm_solve).  Trust region: the constants and the policy of ceres_like::Solve
 //     (host/pvlm_host.hpp Solver::Options): Jacobi scaling 1 / (1 + sqrt(H_kk)) from the first linearisation, radius / max(1/3, 1 - (2 rho - 1)^3) on success,
 //     radius / 2, / 4, ... on failure, min_relative_decrease 1e-3 and the three tolerances;
-//   SoftLOneLoss on a squared residual, the loss of both stages' pair blocks, and HuberLoss beside it (K46's chordal blocks).
-// The device half (kernels, buffers, the solver call) is pvlm_pairgraph.h, the host twin host/pvlm_host_pairgraph.hpp.
+//   the pair model: what one LM problem on the graph (K40's L2 stage, K42, K46's two) gives the one backend per side that lm_solve drives (see lm_solve);
+//   SoftLOneLoss on a squared residual, the loss of K40's and K42's pair blocks, and HuberLoss beside it (K46's chordal blocks).
+// The device half (kernels, buffers, the solver call, the LM backend) is pvlm_pairgraph.h, the host twin host/pvlm_host_pairgraph.hpp.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -26,7 +28,7 @@ namespace pvlm_pairgraph {
 constexpr int kGroup = 8;            // lanes that share one camera's gather
 constexpr int kChunk = 256;          // leaves under one node of the reduction tree
 constexpr int kCam = 15;             // per camera: reduced diagonal block (6, upper triangle by rows), diagonal of the unreduced block (3), gradient (3), reduced gradient (3)
-enum { kTermCost = 0, kTermModel = 1 };      // the first two per-pair terms of a candidate
+enum { kTermCost = 0, kTermModel = 1, kTermStep2 = 2, kTermX2 = 3 };      // the per-pair terms of a candidate; the last two only where the pairs have a scale
 // termination codes on K36's numbering
 enum { kMaxIterations = 0, kFunctionTol = 1, kGradientTol = 2, kParameterTol = 3, kRadiusCollapsed = 4, kCostNotFinite = 5, kNoPairs = 6 };
 
@@ -159,6 +161,26 @@ struct Scalars { double cost, model, step2, x2; };
 
 // The LM loop.  Backend: double initial_cost(); double linearise(double radius, bool first) -> max |g|; bool solve(double radius) (false: no step);
 // Scalars candidate(); void accept(); bool failed() (a device error: the loop stops).
+//
+// There is one backend per side, LmPairDevice (pvlm_pairgraph.h) and LmPairHost (host/pvlm_host_pairgraph.hpp), both templated on a PAIR MODEL: the definition of
+// one LM problem on the graph.  A pair model is a small trivially copyable struct of the problem's per-pair input pointers and uniform scalars, passed by value to
+// the kernels and used as it is by the host twin (whose pointers are host memory).  The state is one 3-vector x per camera and, where kScale, one scale s per pair.
+//   static constexpr int kSlots, kTerms; static constexpr bool kScale;
+//     kSlots: the numbers of a pair's record, component-major (component k of pair p at [k * P + p]): side 0 (first) and side 1 (second) as kCam numbers each, then
+//       what step() needs of the linearisation.  kTerms: the per-pair terms of a candidate, 4 where kScale and 2 otherwise.
+//     kScale: one private scale per pair — eliminated by a 1 x 1 pivot, Jacobi-scaled by a per-pair sigma, clamped at the candidate.  Its gradient sits in the
+//       record's slot kGs (static constexpr int, only where kScale) and enters the gradient maximum; the terms kTermStep2 and kTermX2 exist iff kScale.
+//   double cost(p, xi, xj, s, a): the cost term of pair p at its cameras' vectors and its scale; a = Options::loss_a;
+//   void linearise(p, xi, xj, s, a, radius, min_diag, max_diag, first_time, sigma, rec, P, off): the record (rec points at the pair, stride P) and the 3 x 3 block
+//     between first (rows) and second (columns) inside the 6 x 6 row-major block off.  first_time: the Jacobi scale of s is taken here (*sigma), else read;
+//   void step(p, rec, P, di, dj, ci, cj, s, a, s_cand, terms, tstride): from the steps (di, dj) and the candidates (ci, cj) of its cameras the candidate scale
+//     and the pair's terms: cost at the candidate, model decrease, and where kScale the squared scale step and the squared scale.
+// Without kScale s is 0 and sigma and s_cand are null; a model ignores them and radius, min_diag, max_diag and first_time with them.  Every method is host /
+// device, loads the pair's own inputs by p and leaves the arithmetic to its stage's core.  The models: pvlm_rotavg::L2Model, pvlm_transavg::Model,
+// pvlm_transdir::Chordal and pvlm_transdir::Lud.
+template <class M> PVLM_PG_HD double pair_scale(const double* s, long long p) { if constexpr (M::kScale) return s[p]; else return 0.0; }
+template <class M> PVLM_PG_HD double* pair_slot(double* v, long long p) { if constexpr (M::kScale) return v + p; else return nullptr; }
+
 template <class B> inline void lm_solve(B& be, const Options& o, Summary* out) {
   Summary s{0.0, 0.0, 0, 0, -1};
   double cost = be.initial_cost();
@@ -201,7 +223,8 @@ template <class B> inline void lm_solve(B& be, const Options& o, Summary* out) {
 
 }  // namespace pvlm_pairgraph
 
-// The LM summary and the group size were K42's before the layer existed, and the host compiles of both stages (tests/cpp/*_core_check.cpp) still name them there.
+// The LM summary and the group size were K42's before the layer existed.  The host compiles of K40 and K42 (tests/cpp/rotavg_core_check.cpp, transavg_core_check.cpp)
+// name them there, and those two files must keep compiling as they stand against every later version of this header, so the names stay.
 namespace pvlm_transavg {
 using pvlm_pairgraph::kGroup;
 using pvlm_pairgraph::Summary;

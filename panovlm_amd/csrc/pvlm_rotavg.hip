@@ -11,8 +11,9 @@
 //   k_ra_update      a lane per camera: R <- R exp(x);
 //   k_ra_irls        a lane per pair: b, the weights |A x_prev - b|^-1.5, weights * b, the off-diagonal block straight into the solver's block list;
 //   k_ra_gather_irls the per-camera sums of the weights (the diagonal block) and of the signed weights * b (the right-hand side);
-//   k_ra_l2_*        the L2 stage, an LM backend of the layer: per-pair cost, linearisation and candidate terms; the gather (k_pg_gather_lm), the camera step
-//                    (k_pg_cam_step) and the camera system are the layer's.  The three gathers here share its skeleton (camera_gather).
+//   k_pg_lm_*        the L2 stage: the layer's LM backend (LmPairDevice of pvlm_pairgraph.h) over the pair model ra::L2Model — per-pair cost, linearisation and
+//                    candidate terms, the gather (k_pg_gather_lm), the camera step (k_pg_cam_step) and the camera system.  The two gathers here share its
+//                    skeleton (camera_gather).
 // The rotations, b, z, u, x and the per-pair records stay on the device for the whole call.  G = (2 L)^-1 is formed ONCE per call by the library's dense SPD solver
 // with the identity as right-hand sides (pvlm_spd_solve takes and returns host memory: 2 L goes up and G comes back and is sent up again, once per call).  Per ADMM
 // iteration the host reads five scalars and decides convergence — every iteration, so the iterates and the count are those of the definition; per IRLS / LM iteration
@@ -120,38 +121,6 @@ __global__ __launch_bounds__(kThreads) void k_ra_gather_irls(int F, long long P,
                    });
 }
 
-__global__ __launch_bounds__(kThreads) void k_ra_l2_cost(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R21,
-                                                         const double* __restrict__ aa, double a, double* __restrict__ terms) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], a1[3], a2[3];
-    load9(R21 + 9 * p, Rp);
-    for (int k = 0; k < 3; ++k) { a1[k] = aa[3 * (long long)first[p] + k]; a2[k] = aa[3 * (long long)second[p] + k]; }
-    terms[p] = ra::l2_pair_cost(a1, a2, Rp, a);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void k_ra_l2_pairs(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R21,
-                                                          const double* __restrict__ aa, double a, double* __restrict__ rec, double* __restrict__ off_blocks) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], a1[3], a2[3];
-    load9(R21 + 9 * p, Rp);
-    for (int k = 0; k < 3; ++k) { a1[k] = aa[3 * (long long)first[p] + k]; a2[k] = aa[3 * (long long)second[p] + k]; }
-    ra::l2_linearise_pair(a1, a2, Rp, a, rec + p, P, off_blocks + 36 * p);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void k_ra_l2_step(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R21,
-                                                         const double* __restrict__ rec, const double* __restrict__ step, const double* __restrict__ aa_cand, double a,
-                                                         double* __restrict__ terms) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], d1[3], d2[3], c1[3], c2[3];
-    const long long i = first[p], j = second[p];
-    load9(R21 + 9 * p, Rp);
-    for (int k = 0; k < 3; ++k) { d1[k] = step[3 * i + k]; d2[k] = step[3 * j + k]; c1[k] = aa_cand[3 * i + k]; c2[k] = aa_cand[3 * j + k]; }
-    ra::l2_step_pair(Rp, rec + p, P, d1, d2, c1, c2, a, terms + p, P);
-  }
-}
-
 struct L1DeviceBackend : DeviceGraph {
   int start, n;
   pg::CameraSystem sys;
@@ -243,52 +212,6 @@ struct L1DeviceBackend : DeviceGraph {
   }
 };
 
-// the LM backend of the L2 stage: the layer's graph, camera system and camera step; the angle-axis vectors and the per-pair records are its own
-struct L2DeviceBackend : LmDevice {
-  double *d_rec = nullptr, *d_terms = nullptr;
-  double* d_aa[2] = {nullptr, nullptr};
-  int cur = 0;
-
-  L2DeviceBackend(pvlm_call& call, const pg::Options& o, int F_, int P_) : LmDevice(call, "PVLM_ROTAVG_MAX_BLOCKS", o, F_, P_) {}
-
-  void setup(const int* first, const int* second, const double* R21, const double* aa0) {
-    LmDevice::setup(first, second, R21, 2, -1);
-    d_aa[0] = c.upload(aa0, 3 * (size_t)F); d_aa[1] = c.alloc<double>(3 * (size_t)F);
-    d_rec = c.alloc<double>((size_t)ra::kL2Slots * (size_t)P); d_terms = c.alloc<double>(2 * (size_t)P);
-  }
-  double initial_cost() {
-    double cost = 0.0;
-    clock.start();
-    c.launch(k_ra_l2_cost, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_aa[cur], opt.loss_a, d_terms);
-    reduce<false>(d_terms, P, P, 1, &cost);
-    const bool bad = c.sync() != PVLM_OK;
-    clock.kernels_ms += clock.stop();
-    return bad ? std::nan("") : cost;
-  }
-  double linearise(double, bool first) {
-    clock.start();
-    c.launch(k_ra_l2_pairs, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_aa[cur], opt.loss_a, d_rec, off_blocks());
-    const bool ok = gather(d_rec);
-    clock.kernels_ms += clock.stop();
-    if (!ok) return 0.0;
-    if (first) sys.set_sigma(cam.data());
-    return sys.gradient_max(cam.data());
-  }
-  pg::Scalars candidate() {
-    double pt[2] = {0, 0}, ct[2] = {0, 0};
-    clock.start();
-    step_cameras(d_aa[cur], d_aa[cur ^ 1]);
-    c.launch(k_ra_l2_step, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_rec, d_step, d_aa[cur ^ 1], opt.loss_a, d_terms);
-    reduce<false>(d_terms, P, P, 2, pt);
-    camera_terms(ct);
-    const bool bad = c.sync() != PVLM_OK;
-    clock.kernels_ms += clock.stop();
-    if (bad) return pg::Scalars{std::nan(""), 0, 0, 0};
-    return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], ct[0], ct[1]};
-  }
-  void accept() { cur ^= 1; }
-};
-
 void print_profile(const char* entry, int F, int P, double total, const StageClock& k, int iterations) {
   std::fprintf(stderr, "pvlm_rotavg_profile {\"entry\": \"%s\", \"cameras\": %d, \"pairs\": %d, \"total_ms\": %.3f, \"kernels_ms\": %.3f, \"solve_ms\": %.3f, \"form_g_ms\": %.3f, "
                "\"host_ms\": %.3f, \"solves\": %d, \"iterations\": %d}\n", entry, F, P, total, k.kernels_ms, k.solve_ms, k.form_g_ms, total - k.kernels_ms - k.solve_ms - k.form_g_ms,
@@ -343,10 +266,11 @@ extern "C" pvlm_status pvlm_rotavg_l2(pvlm_ctx* ctx, int n_cameras, int n_pairs,
   if (c.enter()) return c.st;
   pg::Options opt;
   opt.loss_a = params->loss_a; opt.max_num_iterations = params->max_num_iterations;
-  L2DeviceBackend be(c, opt, F, P);
-  be.setup(first, second, R_21, aa.data());
+  LmPairDevice<ra::L2Model> be(c, "PVLM_ROTAVG_MAX_BLOCKS", opt, F, P);
+  be.setup(first, second, R_21, aa.data(), nullptr, -1);
+  be.model = ra::L2Model{be.d_R21};
   pg::lm_solve(be, opt, &s);
-  c.d2h(aa.data(), be.d_aa[be.cur], aa.size() * sizeof(double));
+  c.d2h(aa.data(), be.x(), aa.size() * sizeof(double));
   if (c.sync()) return c.st;
   if (pg::finite_all(aa.data(), aa.size())) for (int k = 0; k < F; ++k) ra::exp_rotation(&aa[3 * (size_t)k], rotations + 9 * (size_t)k);
   std::memcpy(summary, &s, sizeof s);

@@ -250,6 +250,32 @@ PVLM_RA_HD void l2_step_pair(const double* R21, const double* rec, long long P, 
   terms[pg::kTermModel * tstride] = -(rw * ru + 0.5 * rw * uu);
 }
 
+// The pair model of the L2 stage (pvlm_pairgraph_core.h, at lm_solve): the cameras' vectors are their angle-axis vectors, no scale.  R21: 9 per pair.
+struct L2Model {
+  static constexpr int kSlots = kL2Slots, kTerms = 2;
+  static constexpr bool kScale = false;
+  const double* R21;
+
+  PVLM_RA_HD void load(long long p, double* Rp) const { for (int k = 0; k < 9; ++k) Rp[k] = R21[9 * p + k]; }
+  PVLM_RA_HD double cost(long long p, const double* aa1, const double* aa2, double, double a) const {
+    double Rp[9];
+    load(p, Rp);
+    return l2_pair_cost(aa1, aa2, Rp, a);
+  }
+  PVLM_RA_HD void linearise(long long p, const double* aa1, const double* aa2, double, double a, double, double, double, bool, double*, double* rec, long long P,
+                            double* off) const {
+    double Rp[9];
+    load(p, Rp);
+    l2_linearise_pair(aa1, aa2, Rp, a, rec, P, off);
+  }
+  PVLM_RA_HD void step(long long p, const double* rec, long long P, const double* d1, const double* d2, const double* c1, const double* c2, double, double a, double*,
+                       double* terms, long long tstride) const {
+    double Rp[9];
+    load(p, Rp);
+    l2_step_pair(Rp, rec, P, d1, d2, c1, c2, a, terms, tstride);
+  }
+};
+
 // ---- host side: shared by the device entry points and by the host compile ----------------------------------------------------------------------------------
 
 inline bool is_identity(const double* R) { for (int k = 0; k < 9; ++k) if (R[k] != (k % 4 == 0 ? 1.0 : 0.0)) return false; return true; }

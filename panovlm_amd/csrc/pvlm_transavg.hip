@@ -1,12 +1,13 @@
 // K42: translation averaging (TranslationAveragingL2 / TranslationAveragingDLT, sfm/TranslationAveraging.cpp:31-169) on the definition of pvlm_transavg_core.h.
 //
-// The unit of parallelism is the PAIR for everything that is per pair and the CAMERA for the gather:
-//   k_ta_pairs     (a) a lane per pair: residual, rho', the scale's pivot, the two reduced diagonal pieces and gradient pieces into the pair's component-major record,
+// The LM backend is the pair-graph layer's (LmPairDevice of pvlm_pairgraph.h) over the pair model ta::Model; the unit of parallelism is the PAIR for everything
+// that is per pair and the CAMERA for the gather:
+//   k_pg_lm_pairs  (a) a lane per pair: residual, rho', the scale's pivot, the two reduced diagonal pieces and gradient pieces into the pair's component-major record,
 //                      the off-diagonal 3 x 3 straight into the solver's block list;
-//   k_pg_gather_lm (b) the pair-graph layer's gather (pvlm_pairgraph.h): kGroup lanes per camera walk its CSR row, an xor butterfly adds the partial sums.  No
-//                      floating-point atomic: one order per camera, whatever the degree;
+//   k_pg_gather_lm (b) the layer's gather: kGroup lanes per camera walk its CSR row, an xor butterfly adds the partial sums.  No floating-point atomic: one order
+//                      per camera, whatever the degree;
 //   k_pg_tree      (c) the layer's fixed reduction tree, launched level by level until one number is left;
-//   k_ta_step      (d) a lane per pair: back-substitution of the scale step, the clamp onto the parameter bounds, the candidate scale and the pair's terms
+//   k_pg_lm_step   (d) a lane per pair: back-substitution of the scale step, the clamp onto the parameter bounds, the candidate scale and the pair's terms
 //                      (candidate cost, model decrease at the clamped step, squared step and squared parameter); k_pg_cam_step moves the cameras.
 // The LM state (translations, scales, their candidates, the Jacobi scales of the scales, the pair records) stays on the device for the whole call; per iteration the
 // host reads the gather (15 numbers per camera), hands the solver its right-hand side and LM diagonal, sends the camera step back and reads six scalars.  The camera
@@ -28,100 +29,15 @@ namespace {
 
 namespace ta = pvlm_transavg;
 
-__global__ __launch_bounds__(kThreads) void k_ta_pairs(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R,
-                                                       const double* __restrict__ d, const double* __restrict__ bnd, const double* __restrict__ t,
-                                                       const double* __restrict__ s, double a, double radius, double min_diag, double max_diag, int first_time, int dlt,
-                                                       double* __restrict__ sigma, double* __restrict__ rec, double* __restrict__ off_blocks, double* __restrict__ gs_abs) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], dp[3], bp[4], ti[3], tj[3];
-    for (int k = 0; k < 9; ++k) Rp[k] = R[9 * p + k];
-    for (int k = 0; k < 3; ++k) { dp[k] = d[3 * p + k]; ti[k] = t[3 * (long long)first[p] + k]; tj[k] = t[3 * (long long)second[p] + k]; }
-    for (int k = 0; k < 4; ++k) bp[k] = bnd[4 * p + k];
-    ta::linearise_pair(Rp, dp, bp, ti, tj, s[p], a, radius, min_diag, max_diag, first_time != 0, dlt != 0, sigma + p, rec + p, P, off_blocks + 36 * p);
-    gs_abs[p] = fabs(rec[(long long)ta::kGs * P + p]);
-  }
+using Backend = LmPairDevice<ta::Model>;
+const char* const kLimitEnv = "PVLM_TRANSAVG_MAX_BLOCKS";
+
+// the graph and the state on the device, then the model over the uploaded inputs of the pairs
+void setup(Backend& be, const int* first, const int* second, const double* R, const double* d, const double* bnd, const double* t0, const double* s0, int origin, bool dlt) {
+  be.setup(first, second, R, t0, s0, origin);
+  be.model = ta::Model{be.d_R21, be.c.upload(d, 3 * (size_t)be.P), be.c.upload(bnd, 4 * (size_t)be.P), dlt};
+  be.damped = !dlt;
 }
-
-__global__ __launch_bounds__(kThreads) void k_ta_cost(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R,
-                                                      const double* __restrict__ d, const double* __restrict__ bnd, const double* __restrict__ t,
-                                                      const double* __restrict__ s, double a, double* __restrict__ terms) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], dp[3], bp[4], ti[3], tj[3];
-    for (int k = 0; k < 9; ++k) Rp[k] = R[9 * p + k];
-    for (int k = 0; k < 3; ++k) { dp[k] = d[3 * p + k]; ti[k] = t[3 * (long long)first[p] + k]; tj[k] = t[3 * (long long)second[p] + k]; }
-    for (int k = 0; k < 4; ++k) bp[k] = bnd[4 * p + k];
-    terms[p] = ta::pair_cost(Rp, dp, bp, ti, tj, s[p], a);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void k_ta_step(int P, const int* __restrict__ first, const int* __restrict__ second, const double* __restrict__ R,
-                                                      const double* __restrict__ d, const double* __restrict__ bnd, const double* __restrict__ rec,
-                                                      const double* __restrict__ step, const double* __restrict__ t_cand, const double* __restrict__ s, double a,
-                                                      double* __restrict__ s_cand, double* __restrict__ terms) {
-  for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < P; p += (long long)gridDim.x * kThreads) {
-    double Rp[9], dp[3], bp[4], di[3], dj[3], ci[3], cj[3], sc;
-    const long long i = first[p], j = second[p];
-    for (int k = 0; k < 9; ++k) Rp[k] = R[9 * p + k];
-    for (int k = 0; k < 3; ++k) { dp[k] = d[3 * p + k]; di[k] = step[3 * i + k]; dj[k] = step[3 * j + k]; ci[k] = t_cand[3 * i + k]; cj[k] = t_cand[3 * j + k]; }
-    for (int k = 0; k < 4; ++k) bp[k] = bnd[4 * p + k];
-    ta::step_pair(Rp, dp, bp, rec + p, P, di, dj, ci, cj, s[p], a, &sc, terms + p, P);
-    s_cand[p] = sc;
-  }
-}
-
-// the LM backend: the layer's graph, camera system and camera step; the translations, the scales and the per-pair records are its own
-struct DeviceBackend : LmDevice {
-  double *d_d = nullptr, *d_bnd = nullptr, *d_sigma = nullptr, *d_rec = nullptr, *d_terms = nullptr, *d_gs = nullptr;
-  double *d_t[2] = {nullptr, nullptr}, *d_s[2] = {nullptr, nullptr};
-  int cur = 0; bool dlt = false;
-
-  DeviceBackend(pvlm_call& call, const pg::Options& o, int F_, int P_) : LmDevice(call, "PVLM_TRANSAVG_MAX_BLOCKS", o, F_, P_) {}
-
-  void setup(const int* first, const int* second, const double* R, const double* d, const double* bnd, const double* t0, const double* s0, int origin) {
-    LmDevice::setup(first, second, R, ta::kPairTerms, origin);
-    d_d = c.upload(d, 3 * (size_t)P); d_bnd = c.upload(bnd, 4 * (size_t)P);
-    d_t[0] = c.upload(t0, 3 * (size_t)F); d_t[1] = c.alloc<double>(3 * (size_t)F);
-    d_s[0] = c.upload(s0, (size_t)P); d_s[1] = c.alloc<double>((size_t)P);
-    d_sigma = c.alloc<double>((size_t)P); d_rec = c.alloc<double>((size_t)ta::kPairSlots * (size_t)P);
-    d_terms = c.alloc<double>((size_t)ta::kPairTerms * (size_t)P); d_gs = c.alloc<double>((size_t)P);
-  }
-
-  double initial_cost() {
-    double cost = 0.0;
-    clock.start();
-    c.launch(k_ta_cost, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_d, d_bnd, d_t[cur], d_s[cur], opt.loss_a, d_terms);
-    reduce<false>(d_terms, P, P, 1, &cost);
-    const bool bad = c.sync() != PVLM_OK;
-    clock.kernels_ms += clock.stop();
-    return bad ? std::nan("") : cost;
-  }
-  double linearise(double radius, bool first) {
-    double gs_max = 0.0;
-    clock.start();
-    c.launch(k_ta_pairs, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_d, d_bnd, d_t[cur], d_s[cur], opt.loss_a, radius, opt.min_lm_diagonal,
-             opt.max_lm_diagonal, first ? 1 : 0, dlt ? 1 : 0, d_sigma, d_rec, off_blocks(), d_gs);
-    reduce<true>(d_gs, P, P, 1, &gs_max);
-    const bool ok = gather(d_rec);
-    clock.kernels_ms += clock.stop();
-    if (!ok) return 0.0;
-    if (first && !dlt) sys.set_sigma(cam.data());
-    return std::fmax(gs_max, sys.gradient_max(cam.data()));
-  }
-  bool solve(double radius, int* info_out = nullptr) { return LmDevice::solve(radius, !dlt, info_out); }
-  pg::Scalars candidate() {
-    double pt[ta::kPairTerms] = {0, 0, 0, 0}, ct[2] = {0, 0};
-    clock.start();
-    step_cameras(d_t[cur], d_t[cur ^ 1]);
-    c.launch(k_ta_step, dim3(pair_grid()), dim3(kThreads), 0, P, d_first, d_second, d_R21, d_d, d_bnd, d_rec, d_step, d_t[cur ^ 1], d_s[cur], opt.loss_a, d_s[cur ^ 1], d_terms);
-    reduce<false>(d_terms, P, P, ta::kPairTerms, pt);          // the staged copy of the roots is ordered on the stream before the next tree reuses the partials
-    camera_terms(ct);
-    const bool bad = c.sync() != PVLM_OK;
-    clock.kernels_ms += clock.stop();
-    if (bad) return pg::Scalars{std::nan(""), 0, 0, 0};
-    return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], pt[ta::kTermStep2] + ct[0], pt[ta::kTermX2] + ct[1]};
-  }
-  void accept() { cur ^= 1; }
-};
 
 }  // namespace
 
@@ -140,10 +56,9 @@ extern "C" pvlm_status pvlm_transavg_dlt(pvlm_ctx* ctx, int n_cameras, int n_pai
   pvlm_call c(ctx, who);
   if (c.enter()) return c.st;
   pg::Options opt;
-  DeviceBackend be(c, opt, F, P);
-  be.dlt = true;
+  Backend be(c, kLimitEnv, opt, F, P);
   const std::vector<double> zeros(3 * (size_t)F + 4 * (size_t)P, 0.0);
-  be.setup(first, second, R_21, t_21, zeros.data(), zeros.data(), zeros.data(), 0);
+  setup(be, first, second, R_21, t_21, zeros.data(), zeros.data(), zeros.data(), 0, true);
   be.linearise(1.0, true);
   int inf = 0;
   const bool ok = be.solve(1.0, &inf);
@@ -177,12 +92,12 @@ extern "C" pvlm_status pvlm_transavg_solve(pvlm_ctx* ctx, int n_cameras, int n_p
   if (c.enter()) return c.st;
   pg::Options opt;
   opt.loss_a = params->loss_a; opt.max_num_iterations = params->max_num_iterations;
-  DeviceBackend be(c, opt, F, P);
-  be.setup(first, second, R_21, d.data(), bnd.data(), translations, scales, origin_idx);
+  Backend be(c, kLimitEnv, opt, F, P);
+  setup(be, first, second, R_21, d.data(), bnd.data(), translations, scales, origin_idx, false);
   pg::lm_solve(be, opt, &s);
   std::vector<double> t_out(3 * (size_t)F), s_out((size_t)P);
-  c.d2h(t_out.data(), be.d_t[be.cur], t_out.size() * sizeof(double));
-  c.d2h(s_out.data(), be.d_s[be.cur], s_out.size() * sizeof(double));
+  c.d2h(t_out.data(), be.x(), t_out.size() * sizeof(double));
+  c.d2h(s_out.data(), be.s(), s_out.size() * sizeof(double));
   if (c.sync()) return c.st;
   std::memcpy(translations, t_out.data(), t_out.size() * sizeof(double));
   std::memcpy(scales, s_out.data(), s_out.size() * sizeof(double));

@@ -33,7 +33,6 @@ namespace pg = pvlm_pairgraph;
 
 // per-pair record, component-major (component k of pair p at [k * P + p]): side 0 (first) and side 1 (second) as pg::kCam numbers each, then
 enum { kPiv = 30, kGs = 31, kCi = 32, kCj = 35, kRw = 38, kRes = 39, kF = 42, kJf = 43, kPairSlots = 44 };
-enum { kTermStep2 = 2, kTermX2 = 3, kPairTerms = 4 };      // per-pair terms after pg::kTermCost and pg::kTermModel
 
 // d = t_21 / |t_21| (Eigen's normalize); false: zero length or not finite
 PVLM_TA_HD bool direction(const double* t, double* d) {
@@ -120,9 +119,41 @@ PVLM_TA_HD void step_pair(const double* R, const double* d, const double* bnd, c
   *s_cand = sc;
   terms[pg::kTermCost * tstride] = pair_cost(R, d, bnd, cti, ctj, sc, a);
   terms[pg::kTermModel * tstride] = -(rw * ru + 0.5 * rw * uu) - (f * v + 0.5 * v * v);
-  terms[kTermStep2 * tstride] = ds * ds;
-  terms[kTermX2 * tstride] = s * s;
+  terms[pg::kTermStep2 * tstride] = ds * ds;
+  terms[pg::kTermX2 * tstride] = s * s;
 }
+
+// The pair model of both entry points (pvlm_pairgraph_core.h, at lm_solve).  R: R_21 (9 per pair), d: the direction, or t_21 itself with dlt (3), bnd: bounds() (4).
+struct Model {
+  static constexpr int kSlots = kPairSlots, kTerms = 4, kGs = pvlm_transavg::kGs;
+  static constexpr bool kScale = true;
+  const double *R, *d, *bnd;
+  bool dlt;
+
+  // the pair's inputs into the lane's registers
+  PVLM_TA_HD void load(long long p, double* Rp, double* dp, double* bp) const {
+    for (int k = 0; k < 9; ++k) Rp[k] = R[9 * p + k];
+    for (int k = 0; k < 3; ++k) dp[k] = d[3 * p + k];
+    for (int k = 0; k < 4; ++k) bp[k] = bnd[4 * p + k];
+  }
+  PVLM_TA_HD double cost(long long p, const double* ti, const double* tj, double s, double a) const {
+    double Rp[9], dp[3], bp[4];
+    load(p, Rp, dp, bp);
+    return pair_cost(Rp, dp, bp, ti, tj, s, a);
+  }
+  PVLM_TA_HD void linearise(long long p, const double* ti, const double* tj, double s, double a, double radius, double min_diag, double max_diag, bool first_time,
+                            double* sigma, double* rec, long long P, double* off) const {
+    double Rp[9], dp[3], bp[4];
+    load(p, Rp, dp, bp);
+    linearise_pair(Rp, dp, bp, ti, tj, s, a, radius, min_diag, max_diag, first_time, dlt, sigma, rec, P, off);
+  }
+  PVLM_TA_HD void step(long long p, const double* rec, long long P, const double* dti, const double* dtj, const double* cti, const double* ctj, double s, double a,
+                       double* s_cand, double* terms, long long tstride) const {
+    double Rp[9], dp[3], bp[4];
+    load(p, Rp, dp, bp);
+    step_pair(Rp, dp, bp, rec, P, dti, dtj, cti, ctj, s, a, s_cand, terms, tstride);
+  }
+};
 
 PVLM_TA_HD double final_weight(const double* R, const double* t21, const double* ti, const double* tj, double s) {
   double r[3];

@@ -4,12 +4,12 @@
 // pvlm_pairgraph_core.h, with its camera system, gather and fixed reduction tree) over a backend that evaluates, gathers, solves and steps.
 //
 // Unknowns: one CENTRE c per camera (upstream's t_wc; the camera origin_idx is constant and zero).  Pair p carries a unit direction dir_p in the world frame.
-//   kChordal: u = c[first] - c[second], n = |u|, r = u / n - dir (three residuals, weight 1) under HuberLoss(a) on |r|^2; rho'' <= 0, so the corrector scales r and J
+//   Chordal:  u = c[first] - c[second], n = |u|, r = u / n - dir (three residuals, weight 1) under HuberLoss(a) on |r|^2; rho'' <= 0, so the corrector scales r and J
 //             by sqrt(rho').  dr/dc_first = A = (I - uu^T / n^2) / n, dr/dc_second = -A; A^T A = (I - uu^T / n^2) / n^2 is taken in that closed form.  No scale: the
-//             reduced block and gradient of the layer's record equal the unreduced ones, the pivot slot holds 1.  n == 0 makes the cost NaN: at the start that is
+//             reduced block and gradient of the layer's record equal the unreduced ones.  n == 0 makes the cost NaN: at the start that is
 //             termination 5, at a candidate a rejected step (lm_solve).  The cost is invariant under c -> lambda c: the overall scale is a gauge that only the LM
 //             damping holds, so the result keeps roughly the scale of its start.
-//   kLud:     one private scale s_p per pair; e = c[first] - c[second] - s_p dir_p, ONE residual f = w_p |e|^(1/2), no loss.  w_p is an input and is applied (the
+//   Lud:      one private scale s_p per pair; e = c[first] - c[second] - s_p dir_p, ONE residual f = w_p |e|^(1/2), no loss.  w_p is an input and is applied (the
 //             LUD functor reads its weight, unlike K42's).  q = w_p / 2 |e|^(-3/2) e: df/dc_first = q^T, df/dc_second = -q^T, df/ds = -q . dir.
 //             STATED DIVERGENCE: where |e| == 0 at a linearisation point the pair contributes q = 0, a zero row; upstream's Jet gives a non-finite derivative there
 //             and Ceres fails the solve.
@@ -20,7 +20,7 @@
 // CLAMPS the candidate scales onto their parameter bounds and takes the step quality against the model at the clamped step: K42's stand-in for Ceres' projection
 // plus line search, the same divergence.
 // Sums: every scalar is the root of the fixed tree over its per-pair or per-camera terms.
-// Write-back of kLud (:615-626): weight[p] = (|e_p| + 1e-2)^(-1/2) and sum_e = the tree's sum of |e_p|, both on dir_p.  Upstream normalises R_w2 t_21 in the functor
+// Write-back of Lud (:615-626): weight[p] = (|e_p| + 1e-2)^(-1/2) and sum_e = the tree's sum of |e_p|, both on dir_p.  Upstream normalises R_w2 t_21 in the functor
 // and rotates the normalised t_21 in the weight: the two differ by rounding only, one dir_p serves both.
 #pragma once
 #include <cmath>
@@ -40,24 +40,18 @@ namespace pvlm_transdir {
 namespace pg = pvlm_pairgraph;
 namespace ta = pvlm_transavg;
 
-enum { kChordal = 0, kLud = 1 };
-// per-pair record, component-major (component k of pair p at [k * P + p]): side 0 (first) and side 1 (second) as pg::kCam numbers each, then the scale's pivot and
-// gradient and, by model, kLud: q (3), df/ds, f, the ScaleFactor's residual and derivative; kChordal: u / n (3), n, rho', r (3)
-enum { kPiv = 30, kGs = 31, kQ = 32, kJs = 35, kF = 36, kF2 = 37, kJf = 38, kUnit = kQ, kNorm = kJs, kRw = kF, kRes = 37, kPairSlots = 40 };
-enum { kTermStep2 = 2, kTermX2 = 3, kPairTerms = 4 };      // per-pair terms after pg::kTermCost and pg::kTermModel
-
-// bnd[4] = ScaleFactor upper, lower, parameter lower, parameter upper of a kLud pair that comes in at s0
+// bnd[4] = ScaleFactor upper, lower, parameter lower, parameter upper of a Lud pair that comes in at s0
 PVLM_TD_HD void lud_bounds(double s0, double upper_ratio, double lower_ratio, double* bnd) {
   if (s0 != 1) { bnd[0] = s0 * upper_ratio; bnd[1] = s0 * lower_ratio; bnd[2] = s0 * 0.5; bnd[3] = s0 * 3.0; }
   else { bnd[0] = 2.0; bnd[1] = 1.0; bnd[2] = 1.0; bnd[3] = 1.7976931348623157e308; }
 }
 
-// kLud: e = ci - cj - s dir and its length
+// Lud: e = ci - cj - s dir and its length
 PVLM_TD_HD double lud_error(const double* dir, const double* ci, const double* cj, double s, double* e) {
   for (int k = 0; k < 3; ++k) e[k] = ci[k] - cj[k] - s * dir[k];
   return sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
 }
-// kChordal: u / n, r = u / n - dir; returns n (0: the outputs are NaN)
+// Chordal: u / n, r = u / n - dir; returns n (0: the outputs are NaN)
 PVLM_TD_HD double chordal_residual(const double* dir, const double* ci, const double* cj, double* unit, double* r) {
   const double u[3] = {ci[0] - cj[0], ci[1] - cj[1], ci[2] - cj[2]};
   const double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
@@ -65,31 +59,97 @@ PVLM_TD_HD double chordal_residual(const double* dir, const double* ci, const do
   return n;
 }
 
-// the pair's cost term.  kLud: 0.5 w^2 |e| + 0.5 f2^2 (bnd, w and s are read); kChordal: 0.5 rho(|r|^2) (a is read), NaN when the two centres coincide
-PVLM_TD_HD double pair_cost(int model, const double* dir, const double* bnd, double w, const double* ci, const double* cj, double s, double a) {
-  if (model == kLud) {
+// The pair model of TranslationAveragingL2Chordal (pvlm_pairgraph_core.h, at lm_solve): no scale, so the reduced block and gradient of the layer's record equal the
+// unreduced ones.  dir: the unit directions (3 per pair).
+struct Chordal {
+  // the record after the two sides: u / n (3), n, rho', r (3)
+  enum { kUnit = 30, kNorm = 33, kRw = 34, kRes = 35 };
+  static constexpr int kSlots = 38, kTerms = 2;
+  static constexpr bool kScale = false;
+  const double* dir;
+
+  // 0.5 rho(|r|^2), NaN when the two centres coincide
+  PVLM_TD_HD double cost(long long p, const double* ci, const double* cj, double, double a) const {
+    const double d[3] = {dir[3 * p], dir[3 * p + 1], dir[3 * p + 2]};
+    double unit[3], r[3], rho, rho1;
+    chordal_residual(d, ci, cj, unit, r);
+    pg::huber(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rho1);
+    return 0.5 * rho;
+  }
+  PVLM_TD_HD void linearise(long long p, const double* ci, const double* cj, double, double a, double, double, double, bool, double*, double* rec, long long P,
+                            double* off) const {
+    const double d[3] = {dir[3 * p], dir[3 * p + 1], dir[3 * p + 2]};
+    double* si = rec; double* sj = rec + (long long)pg::kCam * P;
+    double unit[3], r[3], rho, rw;
+    const double n = chordal_residual(d, ci, cj, unit, r);
+    pg::huber(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rw);
+    const double ur = unit[0] * r[0] + unit[1] * r[1] + unit[2] * r[2];
+    int t = 0;
+    for (int x = 0; x < 3; ++x)
+      for (int y = x; y < 3; ++y, ++t) {
+        const double h = rw * (((x == y ? 1.0 : 0.0) - unit[x] * unit[y]) / (n * n));
+        si[t * P] = h; sj[t * P] = h;
+        if (x == y) { si[(6 + x) * P] = h; sj[(6 + x) * P] = h; }
+      }
+    for (int k = 0; k < 3; ++k) {
+      const double gi = rw * ((r[k] - unit[k] * ur) / n);
+      si[(9 + k) * P] = gi; sj[(9 + k) * P] = -gi; si[(12 + k) * P] = gi; sj[(12 + k) * P] = -gi;
+      rec[(kUnit + k) * P] = unit[k]; rec[(kRes + k) * P] = r[k];
+      for (int y = 0; y < 3; ++y) off[6 * k + y] = -(rw * (((k == y ? 1.0 : 0.0) - unit[k] * unit[y]) / (n * n)));
+    }
+    rec[kNorm * P] = n; rec[kRw * P] = rw;
+  }
+  // dti / dtj: the steps of the pair's two cameras, cti / ctj: their candidates
+  PVLM_TD_HD void step(long long p, const double* rec, long long P, const double* dti, const double* dtj, const double* cti, const double* ctj, double, double a, double*,
+                       double* terms, long long tstride) const {
+    const double d[3] = {dti[0] - dtj[0], dti[1] - dtj[1], dti[2] - dtj[2]};
+    const double n = rec[kNorm * P], rw = rec[kRw * P];
+    const double ud = rec[kUnit * P] * d[0] + rec[(kUnit + 1) * P] * d[1] + rec[(kUnit + 2) * P] * d[2];
+    double rv = 0, vv = 0;
+    for (int k = 0; k < 3; ++k) { const double v = (d[k] - rec[(kUnit + k) * P] * ud) / n; rv += rec[(kRes + k) * P] * v; vv += v * v; }
+    terms[pg::kTermCost * tstride] = cost(p, cti, ctj, 0.0, a);
+    terms[pg::kTermModel * tstride] = -(rw * rv + 0.5 * rw * vv);
+  }
+};
+
+// The pair model of one LUD solve: the scale of every pair is eliminated by its 1 x 1 pivot.  dir: the unit directions (3 per pair), bnd: lud_bounds() (4), w: the
+// weights (1).  The loss parameter a is not read.
+struct Lud {
+  // the record after the two sides: the scale's pivot and gradient, q (3), df/ds, f, the ScaleFactor's residual and derivative
+  enum { kPiv = 30, kQ = 32, kJs = 35, kF = 36, kF2 = 37, kJf = 38 };
+  static constexpr int kSlots = 39, kTerms = 4, kGs = 31;
+  static constexpr bool kScale = true;
+  const double *dir, *bnd, *w;
+
+  // the pair's inputs into the lane's registers
+  PVLM_TD_HD void load(long long p, double* dp, double* bp) const {
+    for (int k = 0; k < 3; ++k) dp[k] = dir[3 * p + k];
+    for (int k = 0; k < 4; ++k) bp[k] = bnd[4 * p + k];
+  }
+  // 0.5 w^2 |e| + 0.5 f2^2
+  PVLM_TD_HD static double cost_of(const double* dp, const double* bp, double wp, const double* ci, const double* cj, double s) {
     double e[3], f2, jf;
-    const double f = w * sqrt(lud_error(dir, ci, cj, s, e));
-    ta::scale_factor(s, bnd, &f2, &jf);
+    const double f = wp * sqrt(lud_error(dp, ci, cj, s, e));
+    ta::scale_factor(s, bp, &f2, &jf);
     return 0.5 * f * f + 0.5 * f2 * f2;
   }
-  double unit[3], r[3], rho, rho1;
-  chordal_residual(dir, ci, cj, unit, r);
-  pg::huber(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rho1);
-  return 0.5 * rho;
-}
-
-// Kernel a for one pair: the linearisation at (ci, cj, s), with the scale eliminated for kLud.  rec: the pair's record (stride P), off: the 3 x 3 block between first
-// (rows) and second (columns), written into a 6 x 6 row-major block.  first_time: the Jacobi scale of s is taken here (*sigma), else read (kLud only).
-PVLM_TD_HD void linearise_pair(int model, const double* dir, const double* bnd, double w, const double* ci, const double* cj, double s, double a, double radius,
-                               double min_diag, double max_diag, bool first_time, double* sigma, double* rec, long long P, double* off) {
-  double* si = rec; double* sj = rec + (long long)pg::kCam * P;
-  if (model == kLud) {
+  PVLM_TD_HD double cost(long long p, const double* ci, const double* cj, double s, double) const {
+    double dp[3], bp[4];
+    load(p, dp, bp);
+    return cost_of(dp, bp, w[p], ci, cj, s);
+  }
+  // first_time: the Jacobi scale of s is taken here (*sigma), else read
+  PVLM_TD_HD void linearise(long long p, const double* ci, const double* cj, double s, double, double radius, double min_diag, double max_diag, bool first_time,
+                            double* sigma, double* rec, long long P, double* off) const {
+    double dp[3], bp[4];
+    load(p, dp, bp);
+    const double wp = w[p];
+    double* si = rec; double* sj = rec + (long long)pg::kCam * P;
     double e[3], q[3], f2, jf;
-    const double m = lud_error(dir, ci, cj, s, e), f = w * sqrt(m), g = m > 0.0 ? w * 0.5 / (m * sqrt(m)) : 0.0;
+    const double m = lud_error(dp, ci, cj, s, e), f = wp * sqrt(m), g = m > 0.0 ? wp * 0.5 / (m * sqrt(m)) : 0.0;
     for (int k = 0; k < 3; ++k) q[k] = g * e[k];
-    const double js = -(q[0] * dir[0] + q[1] * dir[1] + q[2] * dir[2]);
-    ta::scale_factor(s, bnd, &f2, &jf);
+    const double js = -(q[0] * dp[0] + q[1] * dp[1] + q[2] * dp[2]);
+    ta::scale_factor(s, bp, &f2, &jf);
     const double hss = js * js + jf * jf;
     if (first_time) *sigma = 1.0 / (1.0 + sqrt(hss));
     const double sg = *sigma;
@@ -110,57 +170,26 @@ PVLM_TD_HD void linearise_pair(int model, const double* dir, const double* bnd, 
       for (int y = 0; y < 3; ++y) off[6 * k + y] = -q[k] * q[y] + c * (q[y] * js) / piv;
     }
     rec[kPiv * P] = piv; rec[kGs * P] = gs; rec[kJs * P] = js; rec[kF * P] = f; rec[kF2 * P] = f2; rec[kJf * P] = jf;
-    return;
   }
-  double unit[3], r[3], rho, rw;
-  const double n = chordal_residual(dir, ci, cj, unit, r);
-  pg::huber(a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], &rho, &rw);
-  const double ur = unit[0] * r[0] + unit[1] * r[1] + unit[2] * r[2];
-  int t = 0;
-  for (int x = 0; x < 3; ++x)
-    for (int y = x; y < 3; ++y, ++t) {
-      const double h = rw * (((x == y ? 1.0 : 0.0) - unit[x] * unit[y]) / (n * n));
-      si[t * P] = h; sj[t * P] = h;
-      if (x == y) { si[(6 + x) * P] = h; sj[(6 + x) * P] = h; }
-    }
-  for (int k = 0; k < 3; ++k) {
-    const double gi = rw * ((r[k] - unit[k] * ur) / n);
-    si[(9 + k) * P] = gi; sj[(9 + k) * P] = -gi; si[(12 + k) * P] = gi; sj[(12 + k) * P] = -gi;
-    rec[(kUnit + k) * P] = unit[k]; rec[(kRes + k) * P] = r[k];
-    for (int y = 0; y < 3; ++y) off[6 * k + y] = -(rw * (((k == y ? 1.0 : 0.0) - unit[k] * unit[y]) / (n * n)));
-  }
-  rec[kPiv * P] = 1.0; rec[kGs * P] = 0.0; rec[kNorm * P] = n; rec[kRw * P] = rw;
-}
-
-// Kernel d for one pair: for kLud the scale step from the camera steps, the clamp and the candidate scale; the pair's terms.  dti / dtj: the steps of its two
-// cameras, cti / ctj: their candidates.
-PVLM_TD_HD void step_pair(int model, const double* dir, const double* bnd, double w, const double* rec, long long P, const double* dti, const double* dtj,
-                          const double* cti, const double* ctj, double s, double a, double* s_cand, double* terms, long long tstride) {
-  const double d[3] = {dti[0] - dtj[0], dti[1] - dtj[1], dti[2] - dtj[2]};
-  if (model == kLud) {
+  // the scale step from the camera steps (dti / dtj), the clamp, the candidate scale and the pair's terms at the candidates cti / ctj
+  PVLM_TD_HD void step(long long p, const double* rec, long long P, const double* dti, const double* dtj, const double* cti, const double* ctj, double s, double,
+                       double* s_cand, double* terms, long long tstride) const {
+    double dp[3], bp[4];
+    load(p, dp, bp);
+    const double d[3] = {dti[0] - dtj[0], dti[1] - dtj[1], dti[2] - dtj[2]};
     const double piv = rec[kPiv * P], gs = rec[kGs * P], js = rec[kJs * P], f = rec[kF * P], f2 = rec[kF2 * P], jf = rec[kJf * P];
     const double qd = rec[kQ * P] * d[0] + rec[(kQ + 1) * P] * d[1] + rec[(kQ + 2) * P] * d[2];
-    const double sc = ta::clamp_scale(s + (-gs - js * qd) / piv, bnd), ds = sc - s;
+    const double sc = ta::clamp_scale(s + (-gs - js * qd) / piv, bp), ds = sc - s;
     const double v = qd + js * ds, v2 = jf * ds;
     *s_cand = sc;
-    terms[pg::kTermCost * tstride] = pair_cost(kLud, dir, bnd, w, cti, ctj, sc, a);
+    terms[pg::kTermCost * tstride] = cost_of(dp, bp, w[p], cti, ctj, sc);
     terms[pg::kTermModel * tstride] = -(f * v + 0.5 * v * v) - (f2 * v2 + 0.5 * v2 * v2);
-    terms[kTermStep2 * tstride] = ds * ds;
-    terms[kTermX2 * tstride] = s * s;
-    return;
+    terms[pg::kTermStep2 * tstride] = ds * ds;
+    terms[pg::kTermX2 * tstride] = s * s;
   }
-  const double n = rec[kNorm * P], rw = rec[kRw * P];
-  const double ud = rec[kUnit * P] * d[0] + rec[(kUnit + 1) * P] * d[1] + rec[(kUnit + 2) * P] * d[2];
-  double rv = 0, vv = 0;
-  for (int k = 0; k < 3; ++k) { const double v = (d[k] - rec[(kUnit + k) * P] * ud) / n; rv += rec[(kRes + k) * P] * v; vv += v * v; }
-  *s_cand = s;
-  terms[pg::kTermCost * tstride] = pair_cost(kChordal, dir, bnd, w, cti, ctj, s, a);
-  terms[pg::kTermModel * tstride] = -(rw * rv + 0.5 * rw * vv);
-  terms[kTermStep2 * tstride] = 0.0;
-  terms[kTermX2 * tstride] = 0.0;
-}
+};
 
-// kLud's write-back: the next weight of the pair, its |e| in *m
+// Lud's write-back: the next weight of the pair, its |e| in *m
 PVLM_TD_HD double final_weight(const double* dir, const double* ci, const double* cj, double s, double* m) {
   double e[3];
   *m = lud_error(dir, ci, cj, s, e);

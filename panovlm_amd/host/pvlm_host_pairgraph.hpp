@@ -1,6 +1,7 @@
 // The pair-graph layer of csrc/pvlm_pairgraph_core.h on the host: what csrc/pvlm_pairgraph.h does on the device, done by loops — the gather over kGroup lanes and
-// their butterfly, the camera step — with a dense host Cholesky of the camera system in place of the library's solver.  Under the host twins of K40
-// (pvlm_host_rotavg.hpp), K42 (pvlm_host_transavg.hpp) and K44 (pvlm_host_bata.hpp); no device, no dependency on the rest of the host mirror.
+// their butterfly, the camera step, the LM backend of a pair model — with a dense host Cholesky of the camera system in place of the library's solver.  Under the
+// host twins of K40 (pvlm_host_rotavg.hpp), K42 (pvlm_host_transavg.hpp), K44 (pvlm_host_bata.hpp), K45 (pvlm_host_rotstart.hpp), K46 (pvlm_host_transdir.hpp) and
+// K47 (pvlm_host_translp.hpp); no device, no dependency on the rest of the host mirror.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -63,18 +64,18 @@ template <int LANES, int N> inline void butterfly(double (*part)[N]) {
   }
 }
 
-// What an LM backend (pg::lm_solve) keeps besides its own state vectors, per-pair work and records: the pair list and its CSR, the camera system and its block list
-// ([F diagonal | P off-diagonal]), the gather, the step.  finite_pivot: see dense_spd_solve.
+// What an LM backend (pg::lm_solve) keeps whatever its pair model: the pair list and its CSR, the camera system and its block list ([F diagonal | P off-diagonal]),
+// the gather, the step.  finite_pivot: see dense_spd_solve.
 struct LmHost {
   pg::Options opt; int F, P; bool finite_pivot;
-  const int *first, *second; const double* R21;
+  const int *first, *second;
   std::vector<double> blocks, cam, step, cterms;
   std::vector<int> off, ent;
   pg::CameraSystem sys;
   int info = 0;                // of the last factorisation
 
-  LmHost(const pg::Options& o, int F_, int P_, const int* fi, const int* se, const double* R21_, int origin, bool finite_pivot_)
-      : opt(o), F(F_), P(P_), finite_pivot(finite_pivot_), first(fi), second(se), R21(R21_) {
+  LmHost(const pg::Options& o, int F_, int P_, const int* fi, const int* se, int origin, bool finite_pivot_)
+      : opt(o), F(F_), P(P_), finite_pivot(finite_pivot_), first(fi), second(se) {
     pg::build_csr(F, P, first, second, &off, &ent);
     sys.init(F, P, first, second, origin);
     blocks.assign(36 * ((size_t)F + P), 0.0); cam.assign((size_t)pg::kCam * F, 0.0); cterms.assign(2 * (size_t)F, 0.0);
@@ -91,7 +92,7 @@ struct LmHost {
       pg::diagonal_block(part[0], &blocks[36 * (size_t)c]);
     }
   }
-  bool solve(double radius, bool damped = true) {
+  bool solve(double radius, bool damped) {
     sys.prepare(cam.data(), damped, radius, opt);
     info = solve_camera_system(&sys, blocks, finite_pivot);
     if (info != 0) return false;
@@ -107,6 +108,54 @@ struct LmHost {
     }
   }
   double camera_term(int k) const { return pg::tree_reduce_host<false>(&cterms[(size_t)k * F], F); }
+};
+
+// The LM backend of a pair model M (csrc/pvlm_pairgraph_core.h, at lm_solve): LmPairDevice of csrc/pvlm_pairgraph.h with a loop over the pairs for every launch.
+// The model's pointers are host memory that outlives the backend.  x0: 3 F; s0: P where M::kScale, else unread.  damped = false: see LmPairDevice.
+template <class M> struct LmPairHost : LmHost {
+  M model;
+  bool damped = true;
+  std::vector<double> x[2], s[2], sigma, gs, rec, terms;
+  int cur = 0;
+
+  LmPairHost(const M& m, const pg::Options& o, int F_, int P_, const int* fi, const int* se, const double* x0, const double* s0, int origin, bool finite_pivot_)
+      : LmHost(o, F_, P_, fi, se, origin, finite_pivot_), model(m) {
+    x[0].assign(x0, x0 + 3 * (size_t)F); x[1] = x[0];
+    if (M::kScale) { s[0].assign(s0, s0 + (size_t)P); s[1] = s[0]; sigma.assign((size_t)P, 0.0); gs.assign((size_t)P, 0.0); }
+    rec.assign((size_t)M::kSlots * P, 0.0); terms.assign((size_t)M::kTerms * P, 0.0);
+  }
+  double initial_cost() {
+    for (int p = 0; p < P; ++p)
+      terms[(size_t)p] = model.cost(p, &x[cur][3 * (size_t)first[p]], &x[cur][3 * (size_t)second[p]], pg::pair_scale<M>(s[cur].data(), p), opt.loss_a);
+    return pg::tree_reduce_host<false>(terms.data(), P);
+  }
+  double linearise(double radius, bool first_time) {
+    for (int p = 0; p < P; ++p) {
+      model.linearise(p, &x[cur][3 * (size_t)first[p]], &x[cur][3 * (size_t)second[p]], pg::pair_scale<M>(s[cur].data(), p), opt.loss_a, radius, opt.min_lm_diagonal,
+                      opt.max_lm_diagonal, first_time, pg::pair_slot<M>(sigma.data(), p), &rec[(size_t)p], P, off_block(p));
+      if constexpr (M::kScale) gs[(size_t)p] = std::fabs(rec[(size_t)M::kGs * P + p]);
+    }
+    gather(rec);
+    if (first_time && damped) sys.set_sigma(cam.data());
+    const double g_max = sys.gradient_max(cam.data());
+    if constexpr (M::kScale) return std::fmax(pg::tree_reduce_host<true>(gs.data(), P), g_max);
+    else return g_max;
+  }
+  bool solve(double radius) { return LmHost::solve(radius, damped); }
+  pg::Scalars candidate() {
+    std::vector<double>& xc = x[cur ^ 1];
+    step_cameras(x[cur], xc);
+    for (int p = 0; p < P; ++p) {
+      const size_t i = (size_t)first[p], j = (size_t)second[p];
+      model.step(p, &rec[(size_t)p], P, &step[3 * i], &step[3 * j], &xc[3 * i], &xc[3 * j], pg::pair_scale<M>(s[cur].data(), p), opt.loss_a,
+                 pg::pair_slot<M>(s[cur ^ 1].data(), p), &terms[(size_t)p], P);
+    }
+    double pt[4] = {0, 0, 0, 0};
+    for (int k = 0; k < M::kTerms; ++k) pt[k] = pg::tree_reduce_host<false>(&terms[(size_t)k * P], P);
+    if constexpr (M::kScale) return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], pt[pg::kTermStep2] + camera_term(0), pt[pg::kTermX2] + camera_term(1)};
+    else return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], camera_term(0), camera_term(1)};
+  }
+  void accept() { cur ^= 1; }
 };
 
 }  // namespace pairgraph_detail

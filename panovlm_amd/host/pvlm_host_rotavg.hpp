@@ -125,39 +125,6 @@ inline int L1Host(int F, int P, const int* first, const int* second, const doubl
   return 0;
 }
 
-// the LM backend of the L2 stage on the host's layer; finite_pivot = true, as the Cholesky of this twin has always tested (pair-graph layer)
-struct L2HostBackend : pairgraph_detail::LmHost {
-  std::vector<double> rec, terms;
-  std::vector<double> aa[2];
-  int cur = 0;
-
-  L2HostBackend(const pg::Options& o, int F_, int P_, const int* fi, const int* se, const double* R21_, const double* aa0) : LmHost(o, F_, P_, fi, se, R21_, -1, true) {
-    rec.assign((size_t)ra::kL2Slots * P, 0.0); terms.assign(2 * (size_t)P, 0.0);
-    aa[0].assign(aa0, aa0 + 3 * (size_t)F); aa[1] = aa[0];
-  }
-  double initial_cost() {
-    for (int p = 0; p < P; ++p) terms[(size_t)p] = ra::l2_pair_cost(&aa[cur][3 * (size_t)first[p]], &aa[cur][3 * (size_t)second[p]], R21 + 9 * (size_t)p, opt.loss_a);
-    return pg::tree_reduce_host<false>(terms.data(), P);
-  }
-  double linearise(double, bool first_time) {
-    for (int p = 0; p < P; ++p)
-      ra::l2_linearise_pair(&aa[cur][3 * (size_t)first[p]], &aa[cur][3 * (size_t)second[p]], R21 + 9 * (size_t)p, opt.loss_a, &rec[(size_t)p], P, off_block(p));
-    gather(rec);
-    if (first_time) sys.set_sigma(cam.data());
-    return sys.gradient_max(cam.data());
-  }
-  pg::Scalars candidate() {
-    std::vector<double>& ac = aa[cur ^ 1];
-    step_cameras(aa[cur], ac);
-    for (int p = 0; p < P; ++p) {
-      const size_t i = (size_t)first[p], j = (size_t)second[p];
-      ra::l2_step_pair(R21 + 9 * (size_t)p, &rec[(size_t)p], P, &step[3 * i], &step[3 * j], &ac[3 * i], &ac[3 * j], opt.loss_a, &terms[(size_t)p], P);
-    }
-    return pg::Scalars{pg::tree_reduce_host<false>(&terms[0], P), pg::tree_reduce_host<false>(&terms[(size_t)P], P), camera_term(0), camera_term(1)};
-  }
-  void accept() { cur ^= 1; }
-};
-
 // pvlm_rotavg_l2 on the host.  Returns 0, or -1 (PVLM_ERR_ARG) with nothing written.
 inline int L2Host(int F, int P, const int* first, const int* second, const double* R21, double* rotations, double loss_a, int max_num_iterations, pg::Summary* summary) {
   if (!summary || max_num_iterations < 0 || !std::isfinite(loss_a) || ra::check_args(F, P, first, second, R21, rotations, -1, false)) return -1;
@@ -167,9 +134,10 @@ inline int L2Host(int F, int P, const int* first, const int* second, const doubl
     for (int c = 0; c < F; ++c) ra::log_rotation(rotations + 9 * (size_t)c, &aa[3 * (size_t)c]);
     pg::Options opt;
     opt.loss_a = loss_a; opt.max_num_iterations = max_num_iterations;
-    L2HostBackend be(opt, F, P, first, second, R21, aa.data());
+    // the host's LM backend over the device's pair model; finite_pivot = true, as the Cholesky of this twin has always tested (pair-graph layer)
+    pairgraph_detail::LmPairHost<ra::L2Model> be(ra::L2Model{R21}, opt, F, P, first, second, aa.data(), nullptr, -1, true);
     pg::lm_solve(be, opt, &s);
-    if (pg::finite_all(be.aa[be.cur].data(), 3 * (size_t)F)) for (int c = 0; c < F; ++c) ra::exp_rotation(&be.aa[be.cur][3 * (size_t)c], rotations + 9 * (size_t)c);
+    if (pg::finite_all(be.x[be.cur].data(), 3 * (size_t)F)) for (int c = 0; c < F; ++c) ra::exp_rotation(&be.x[be.cur][3 * (size_t)c], rotations + 9 * (size_t)c);
   }
   *summary = s;
   return 0;

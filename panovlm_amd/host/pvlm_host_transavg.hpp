@@ -17,48 +17,9 @@ namespace transavg_detail {
 namespace ta = pvlm_transavg;
 namespace pg = pvlm_pairgraph;
 
-// the LM backend on the host's layer; finite_pivot = false: the pivot test of the library's factorisation (d > 0 alone), which this twin exists to equal
-struct HostBackend : pairgraph_detail::LmHost {
-  bool dlt = false;
-  std::vector<double> d, bnd, sigma, rec, terms, gs;
-  std::vector<double> t[2], s[2];
-  int cur = 0;
-
-  HostBackend(const pg::Options& o, int F_, int P_, const int* fi, const int* se, const double* R_, const double* d_, const double* bnd_, const double* t0, const double* s0,
-              int origin) : LmHost(o, F_, P_, fi, se, R_, origin, false), d(d_, d_ + 3 * (size_t)P_), bnd(bnd_, bnd_ + 4 * (size_t)P_) {
-    sigma.assign((size_t)P, 0.0); rec.assign((size_t)ta::kPairSlots * P, 0.0); terms.assign((size_t)ta::kPairTerms * P, 0.0); gs.assign((size_t)P, 0.0);
-    t[0].assign(t0, t0 + 3 * (size_t)F); t[1] = t[0]; s[0].assign(s0, s0 + (size_t)P); s[1] = s[0];
-  }
-  double initial_cost() {
-    for (int p = 0; p < P; ++p)
-      terms[(size_t)p] = ta::pair_cost(R21 + 9 * (size_t)p, &d[3 * (size_t)p], &bnd[4 * (size_t)p], &t[cur][3 * (size_t)first[p]], &t[cur][3 * (size_t)second[p]], s[cur][(size_t)p], opt.loss_a);
-    return pg::tree_reduce_host<false>(terms.data(), P);
-  }
-  double linearise(double radius, bool first_time) {
-    for (int p = 0; p < P; ++p) {
-      ta::linearise_pair(R21 + 9 * (size_t)p, &d[3 * (size_t)p], &bnd[4 * (size_t)p], &t[cur][3 * (size_t)first[p]], &t[cur][3 * (size_t)second[p]], s[cur][(size_t)p], opt.loss_a,
-                         radius, opt.min_lm_diagonal, opt.max_lm_diagonal, first_time, dlt, &sigma[(size_t)p], &rec[(size_t)p], P, off_block(p));
-      gs[(size_t)p] = std::fabs(rec[(size_t)ta::kGs * P + p]);
-    }
-    gather(rec);
-    if (first_time && !dlt) sys.set_sigma(cam.data());
-    return std::fmax(pg::tree_reduce_host<true>(gs.data(), P), sys.gradient_max(cam.data()));
-  }
-  bool solve(double radius) { return LmHost::solve(radius, !dlt); }
-  pg::Scalars candidate() {
-    std::vector<double>& tc = t[cur ^ 1];
-    step_cameras(t[cur], tc);
-    for (int p = 0; p < P; ++p) {
-      const size_t i = (size_t)first[p], j = (size_t)second[p];
-      ta::step_pair(R21 + 9 * (size_t)p, &d[3 * (size_t)p], &bnd[4 * (size_t)p], &rec[(size_t)p], P, &step[3 * i], &step[3 * j], &tc[3 * i], &tc[3 * j], s[cur][(size_t)p], opt.loss_a,
-                    &s[cur ^ 1][(size_t)p], &terms[(size_t)p], P);
-    }
-    double pt[ta::kPairTerms];
-    for (int k = 0; k < ta::kPairTerms; ++k) pt[k] = pg::tree_reduce_host<false>(&terms[(size_t)k * P], P);
-    return pg::Scalars{pt[pg::kTermCost], pt[pg::kTermModel], pt[ta::kTermStep2] + camera_term(0), pt[ta::kTermX2] + camera_term(1)};
-  }
-  void accept() { cur ^= 1; }
-};
+// the LM backend on the host's layer over the device's pair model; finite_pivot = false: the pivot test of the library's factorisation (d > 0 alone), which this
+// twin exists to equal
+using Backend = pairgraph_detail::LmPairHost<ta::Model>;
 
 // pvlm_transavg_dlt on the host.  Returns 0, or -1 (PVLM_ERR_ARG) with nothing written.  info: 0, or k > 0 when the system is not positive definite (out untouched).
 inline int DltHost(int F, int P, const int* first, const int* second, const double* R, const double* t21, double* out, int* info) {
@@ -66,8 +27,8 @@ inline int DltHost(int F, int P, const int* first, const int* second, const doub
   if (P == 0) { *info = F <= 1 ? 0 : 1; if (F == 1) out[0] = out[1] = out[2] = 0.0; return 0; }
   const std::vector<double> zeros(3 * (size_t)F + 4 * (size_t)P, 0.0);
   pg::Options opt;
-  HostBackend be(opt, F, P, first, second, R, t21, zeros.data(), zeros.data(), zeros.data(), 0);
-  be.dlt = true;
+  Backend be(ta::Model{R, t21, zeros.data(), true}, opt, F, P, first, second, zeros.data(), zeros.data(), 0, false);
+  be.damped = false;
   be.linearise(1.0, true);
   const bool ok = be.solve(1.0);
   *info = be.info;
@@ -88,9 +49,9 @@ inline int SolveHost(int F, int P, const int* first, const int* second, const do
     for (int p = 0; p < P; ++p) { ta::direction(t21 + 3 * (size_t)p, &d[3 * (size_t)p]); ta::bounds(scales[p], upper_ratio, lower_ratio, &bnd[4 * (size_t)p]); }
     pg::Options opt;
     opt.loss_a = loss_a; opt.max_num_iterations = max_num_iterations;
-    HostBackend be(opt, F, P, first, second, R, d.data(), bnd.data(), translations, scales, origin);
+    Backend be(ta::Model{R, d.data(), bnd.data(), false}, opt, F, P, first, second, translations, scales, origin, false);
     pg::lm_solve(be, opt, &s);
-    std::memcpy(translations, be.t[be.cur].data(), 3 * (size_t)F * sizeof(double));
+    std::memcpy(translations, be.x[be.cur].data(), 3 * (size_t)F * sizeof(double));
     std::memcpy(scales, be.s[be.cur].data(), (size_t)P * sizeof(double));
     for (int p = 0; p < P; ++p)
       weight[p] = ta::final_weight(R + 9 * (size_t)p, t21 + 3 * (size_t)p, &translations[3 * (size_t)first[p]], &translations[3 * (size_t)second[p]], scales[p]);

@@ -82,6 +82,24 @@ def test_past_a_grid_stride_trip(ctx):
     assert (held2["initial_cost"], held2["final_cost"]) == (free2["initial_cost"], free2["final_cost"])
 
 
+def test_l2_pairs_past_a_grid_stride_trip(ctx):
+    """The scenes above have at most 189 pairs, so the L2 stage's per-pair kernels (the pair-graph layer's, shared with K42 and K46) never take a second trip of
+    their stride loop there.  90 cameras, each paired with its next three: 264 pairs, two trips of 256 when the kernels are held to ONE workgroup.  Five LM
+    iterations from the spanning-tree start, free and held: the same bits in the rotations, both costs, both step counts and the termination."""
+    sc = rr.scene(490, rr.chain_pairs(90, 3), 90)
+    assert sc["P"] == 264
+    free = _l2(ctx, sc, sc["R0"], max_num_iterations=5)
+    os.environ["PVLM_ROTAVG_MAX_BLOCKS"] = "1"
+    try:
+        held = _l2(ctx, sc, sc["R0"], max_num_iterations=5)
+    finally:
+        del os.environ["PVLM_ROTAVG_MAX_BLOCKS"]
+    print("free", rr.counts_l2(free), free["initial_cost"], free["final_cost"], "held", rr.counts_l2(held), held["initial_cost"], held["final_cost"])
+    assert free["rc"] == 0 and held["rc"] == 0 and free["successful"] + free["unsuccessful"] > 0
+    assert np.array_equal(_bits(held["rotations"]), _bits(free["rotations"])) and rr.counts_l2(held) == rr.counts_l2(free)
+    assert (held["initial_cost"], held["final_cost"]) == (free["initial_cost"], free["final_cost"])
+
+
 @pytest.mark.parametrize("name", ["hub17", "F66"])
 def test_two_runs_same_bits(ctx, name):
     sc = rr.scenes()[name]
