@@ -677,6 +677,34 @@ pvlm_status pvlm_transavg_l1(pvlm_ctx* ctx, int n_cameras, int n_pairs, const in
                              const pvlm_translp_params* params, pvlm_translp_summary* summary);
 int pvlm_translp_group_size(void);
 
+/* ---- K48: the triplets of the pair graph (PoseGraph::FindTriplet, sfm/PoseGraph.cpp:195-226) and SfM::FilterByTriplet's test (sfm/SfM.cpp:705-778) ---- *
+ * The definition (csrc/pvlm_triplet_core.h).  n_pairs pairs (first, second) with first < second < n_cameras, no pair named twice, in any list order.  The rank of a
+ * pair is its position in ascending order of first * n_cameras + second.  The triplets are all (i, j, k), i < j < k, whose three pairs are in the list, in
+ * lexicographic order: under these conditions exactly the order of upstream's walk over its std::set of edges.
+ * pvlm_triplets_find: `triplets` receives i, j, k per triplet and `triplet_pairs` the caller's list indices of (i,j), (j,k), (i,k) — the layout pvlm_transavg_l1
+ *   takes; either may be NULL (not wanted).  *needed = the number of triplets, always set (64-bit: an exhaustive graph of 454 cameras has 15.5 M).  When an output is
+ *   wanted and *needed exceeds capacity (in triplets) the call returns PVLM_ERR_CAPACITY with *needed and pair_counts set and no triplet at or past capacity written
+ *   (the convention of pvlm_match_pairs); with neither output wanted capacity is not looked at.  pair_counts, when given, receives per pair of the caller's list the
+ *   number of triplets whose smallest pair (i, j) it is; their sum is *needed and, taken in rank order, their running sum is a triplet's position.
+ * pvlm_triplets_filter: the loop measure of a triplet is upstream's as written, c = trace((R_31^T R_32) R_21) / 3 clamped by min(1.0, max(c, -1.0)); a triplet is
+ *   kept when acos(c) * 180 / M_PI < angle_threshold_deg, and keep[p] = 1 when pair p lies in at least one kept triplet, else 0.  The device decides clamp(c) > cut with
+ *   cut = cos(angle_threshold_deg * pi / 180) wherever |clamp(c) - cut| > 1e-12; the triplets inside that band (n_uncertain of them) are decided on the host by the
+ *   literal acos chain, so keep is the literal test's result.  A c that is not finite goes where the written clamp sends it (NaN to 1.0: kept, as upstream keeps it);
+ *   R_21 is therefore not required to be finite.  A threshold <= 0 keeps nothing, one above 180 everything.
+ * PVLM_ERR_ARG, with no output touched: a NULL (the outputs marked optional apart; with n_pairs == 0 only needed / stats are required), a negative size or capacity, a
+ * camera index out of range, first >= second, a pair named twice, a threshold that is not finite.  n_pairs == 0 is PVLM_OK with zero triplets.
+ * Rank and rows are made on the host in the call's set-up (one sort of n_pairs keys).  The environment variable PVLM_TRIPLET_MAX_BLOCKS (read at every call) lowers
+ * the grids of the kernels and PVLM_TRIPLET_UNCERTAIN_CAP the first capacity of the uncertain list (4096; an overflow runs the pass once more with the reported
+ * count); neither changes a result, the tests use them.  With PVLM_TRIPLET_PROFILE set, a call prints one line on stderr: its wall clock split into rank / rows,
+ * upload, count, scan, emit and copy-out (find) or filter pass and copy-out (filter), each stage then ending in a wait.  Synchronous; PVLM_ERR_STATE inside a capture. */
+typedef struct pvlm_triplet_stats { long long n_triplets, n_kept_triplets, n_uncertain, n_kept_pairs; } pvlm_triplet_stats;
+pvlm_status pvlm_triplets_find(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, int* triplets /* 3 per triplet, NULL: not wanted */,
+                               int* triplet_pairs /* 3 per triplet, NULL: not wanted */, long long capacity, long long* needed,
+                               long long* pair_counts /* n_pairs, optional: triplets whose smallest pair this is */);
+pvlm_status pvlm_triplets_filter(pvlm_ctx* ctx, int n_cameras, int n_pairs, const int* first, const int* second, const double* R_21 /* n_pairs * 9, row-major */,
+                                 double angle_threshold_deg, unsigned char* keep /* n_pairs */, pvlm_triplet_stats* stats);
+int pvlm_triplet_group_size(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

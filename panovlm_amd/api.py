@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "pvlm_rotavg_l1", "pvlm_rotavg_l2", "pvlm_rotavg_group_size", "pvlm_rotavg_least_square",
     "pvlm_transavg_chordal", "pvlm_transavg_lud", "pvlm_transdir_group_size",
     "pvlm_transavg_l1", "pvlm_translp_group_size",
+    "pvlm_triplets_find", "pvlm_triplets_filter", "pvlm_triplet_group_size",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1893,6 +1894,68 @@ def transavg_l1(ctx, first, second, R_21, t_21, triplet_pairs, origin_idx, trans
     out = dict(translations=t[:F], duals=None if duals is None else duals[:T], guard_intact=intact, rc=int(rc))
     for name, _ in TranslpSummary._fields_:
         out[name] = getattr(sm, name)
+    return out
+
+
+class TripletStats(C.Structure):
+    _fields_ = [("n_triplets", C.c_longlong), ("n_kept_triplets", C.c_longlong), ("n_uncertain", C.c_longlong), ("n_kept_pairs", C.c_longlong)]
+
+
+TRIPLET_GUARD = 8     # sentinel records the wrapper keeps behind every output
+
+
+def triplet_group_size():
+    """pvlm_triplet_group_size (K48): the lanes that share one pair's candidates."""
+    return int(load_library().pvlm_triplet_group_size())
+
+
+def triplets_find(ctx, n_cameras, first, second, want_triplets=True, want_pairs=True, capacity=None, check=True):
+    """pvlm_triplets_find (K48): the triplets (i < j < k) of the pair graph in lexicographic order and, per triplet, the caller's list indices of its pairs (i,j),
+    (j,k), (i,k).  capacity None sizes ONE call by 8 triplets per pair and repeats it once with the reported count on PVLM_ERR_CAPACITY (calls == 2), as sift_extract
+    does; a given capacity is used as it is.  Returns a dict: triplets and triplet_pairs (n x 3 int32, or None), needed, pair_counts (int64 per pair), overflow,
+    calls, guard_intact (the TRIPLET_GUARD sentinel records behind the outputs were not written), rc.  An argument the library refuses raises PvlmError; with
+    check=False the dict comes back with its rc (needed and pair_counts then hold -7)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRIPLET_GUARD
+    want = want_triplets or want_pairs
+
+    def call(cap):
+        t = np.full((cap + G, 3), -7, np.int32) if want_triplets else None
+        tp = np.full((cap + G, 3), -7, np.int32) if want_pairs else None
+        pc = np.full(P + G, -7, np.int64); needed = C.c_longlong(-7)
+        rc = ctx.lib.pvlm_triplets_find(ctx._h, C.c_int(n_cameras), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(t, C.c_int), _p(tp, C.c_int),
+                                        C.c_longlong(cap), C.byref(needed), _p(pc, C.c_longlong))
+        return rc, t, tp, pc, needed.value
+
+    cap = int(capacity) if capacity is not None else (8 * P if want else 0)
+    rc, t, tp, pc, needed = call(cap)
+    calls = 1
+    if capacity is None and rc == ERR_CAPACITY:
+        cap = needed
+        rc, t, tp, pc, needed = call(cap)
+        calls = 2
+    if check and rc != ERR_CAPACITY:
+        ctx._check(rc, "pvlm_triplets_find")
+    n = max(0, min(needed, cap))
+    intact = bool((t is None or np.all(t[cap:] == -7)) and (tp is None or np.all(tp[cap:] == -7)) and np.all(pc[P:] == -7))
+    return dict(triplets=None if t is None else t[:n], triplet_pairs=None if tp is None else tp[:n], needed=needed, pair_counts=pc[:P], overflow=rc == ERR_CAPACITY,
+                calls=calls, guard_intact=intact, rc=int(rc))
+
+
+def triplets_filter(ctx, n_cameras, first, second, R_21, angle_threshold_deg, check=True):
+    """pvlm_triplets_filter (K48): SfM::FilterByTriplet's test.  keep[p] = 1 when pair p lies in a triplet whose loop measure acos(trace(R_13 R_32 R_21) / 3) in
+    degrees is below the threshold.  Returns a dict: keep (uint8 per pair), n_triplets, n_kept_triplets, n_uncertain (decided on the host by the literal chain),
+    n_kept_pairs, guard_intact, rc.  An argument the library refuses raises PvlmError; with check=False the dict comes back with its rc (keep then holds 7s)."""
+    first = _i32(first); second = _i32(second); P = len(first); G = TRIPLET_GUARD
+    R = _f64(np.asarray(R_21, np.float64).reshape(-1, 9))
+    keep = np.full(P + G, 7, np.uint8)
+    st = TripletStats(-7, -7, -7, -7)
+    rc = ctx.lib.pvlm_triplets_filter(ctx._h, C.c_int(n_cameras), C.c_int(P), _p(first, C.c_int), _p(second, C.c_int), _p(R, C.c_double), C.c_double(angle_threshold_deg),
+                                      _p(keep, C.c_ubyte), C.byref(st))
+    if check:
+        ctx._check(rc, "pvlm_triplets_filter")
+    out = dict(keep=keep[:P], guard_intact=bool(np.all(keep[P:] == 7)), rc=int(rc))
+    for name, _ in TripletStats._fields_:
+        out[name] = int(getattr(st, name))
     return out
 
 

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip", "pvlm_rotavg.hip", "pvlm_bata.hip", "pvlm_rotstart.hip", "pvlm_transdir.hip", "pvlm_translp.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip", "pvlm_rotavg.hip", "pvlm_bata.hip", "pvlm_rotstart.hip", "pvlm_transdir.hip", "pvlm_translp.hip", "pvlm_triplet.hip")
 
 
 def _hipcc():
@@ -130,6 +130,7 @@ BATA_DRIVER = os.path.join(HERE, "build", "pvlm_bata_driver")
 ROTSTART_DRIVER = os.path.join(HERE, "build", "pvlm_rotstart_driver")
 TRANSDIR_DRIVER = os.path.join(HERE, "build", "pvlm_transdir_driver")
 TRANSLP_DRIVER = os.path.join(HERE, "build", "pvlm_translp_driver")
+TRIPLET_DRIVER = os.path.join(HERE, "build", "pvlm_triplet_driver")
 
 
 def build_host(force=False):
@@ -289,6 +290,14 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", ldrv, "-o", TRANSLP_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     build_translp_check()
+    # the triplet driver (FindTripletDevice, FilterByTripletDevice, EstimateGlobalRotation and TranslationAveragingL1 with device_triplets, on the host compile or
+    # through the device: K48) and the host compile of the K48 core for the tests
+    pdrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_triplet_driver.cpp")
+    if os.path.exists(pdrv) and (force or not os.path.exists(TRIPLET_DRIVER) or
+                                 os.path.getmtime(TRIPLET_DRIVER) < max(os.path.getmtime(pdrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", pdrv, "-o", TRIPLET_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    build_triplet_check()
     return HOST_LIB
 
 
@@ -305,7 +314,7 @@ def _include_closure(src):
 
 
 def build_core_check(kind, main=False, sanitize=False):
-    """The host compile of a pair-graph stage's core (kind "transavg": K42, "rotavg": K40, "bata": K44, "rotstart": K45, "transdir": K46, "translp": K47; csrc/pvlm_<kind>_core.h behind tests/cpp/<kind>_core_check.cpp; no device,
+    """The host compile of a pair-graph stage's core (kind "transavg": K42, "rotavg": K40, "bata": K44, "rotstart": K45, "transdir": K46, "translp": K47, "triplet": K48; csrc/pvlm_<kind>_core.h behind tests/cpp/<kind>_core_check.cpp; no device,
     -ffp-contract=off as the device build of pvlm_<kind>.hip): build/lib<kind>_check.so for the tests, or with main=True the stand-alone program of the same file
     (sanitize: the host sanitizers).  Rebuilt when the source or any header it includes, directly or not, is newer."""
     chk = os.path.join(HERE, "..", "tests", "cpp", kind + "_core_check.cpp")
@@ -341,6 +350,10 @@ def build_transdir_check(main=False, sanitize=False):
 
 def build_translp_check(main=False, sanitize=False):
     return build_core_check("translp", main, sanitize)
+
+
+def build_triplet_check(main=False, sanitize=False):
+    return build_core_check("triplet", main, sanitize)
 
 
 if __name__ == "__main__":

@@ -830,6 +830,9 @@ struct TranslationOptions {
   bool enable_chordal = false, enable_lud = false;
   // Method 2 (L1, K47) runs only when this is set: the same test pins it under default options, for the same reason.
   bool enable_l1 = false;
+  // Method 2 takes its triplets from FindTripletDevice (K48, pvlm_host_triplet.hpp) instead of FindTriplet and the std::map lookups when this is set.  Opt-in, as
+  // the flags above: without it the call runs the code it always ran.
+  bool device_triplets = false;
 };
 // TranslationAveragingDLT (:31-84) through pvlm_transavg_dlt: the normal equations with camera 0 fixed at zero.  Upstream's SparseQR returns SOME basic solution of a
 // system that is rank-deficient by the gauge t_i = R_i c; every caller runs SetToOrigin afterwards, which cancels the difference.  false: a pair names a camera
@@ -876,8 +879,10 @@ bool TranslationAveragingLUD(std::vector<RelativePair>& image_pairs, const std::
 // taken.  The call starts from t = 0.  summary: the call's, when given.  false: global_translations[origin_idx] not zero (upstream asserts), a pair with
 // first >= second or a camera past global_translations (upstream reads another pair's data or writes out of range), or a solve that did not converge ("Solve linear
 // program failed").  A pair list without a triplet leaves every translation zero and returns true.
+// device_triplets: the triplets and their pair indices come from FindTripletDevice (K48: pvlm_triplets_find; with host, the host compile of its core) instead of
+// FindTriplet and three std::map lookups per triplet; the same triplet_pairs either way.
 bool TranslationAveragingL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const bool host = false,
-                            pvlm_translp_summary* summary = nullptr);
+                            pvlm_translp_summary* summary = nullptr, const bool device_triplets = false);
 // SfM::ReIndex (sfm/SfM.cpp:908-934): the frame ids of a pair list onto 0 .. n - 1 in ascending order
 void ReIndex(const std::vector<RelativePair>& pairs, std::map<size_t, size_t>& forward, std::map<size_t, size_t>& backward);
 // SfM::SetToOrigin (:1385-1421) without the structure: every valid pose into the frame of frames[frame_idx] (the first valid frame when that one has no pose).
@@ -904,6 +909,8 @@ struct RotationOptions {
   // test_estimate_global_rotation_host and tests/test_rotavg_gpu.py pin method 2 under default options to its refusal and existing tests do not change; a later
   // change that may edit those tests removes it.
   bool enable_l2_start = false;
+  // FilterByTriplet(pairs, 0.1) runs as FilterByTripletDevice (K48, pvlm_host_triplet.hpp) when this is set.  Opt-in: without it the call runs the code it always ran.
+  bool device_triplets = false;
 };
 struct Triplet { uint32_t i, j, k; };
 // PoseGraph::FindTriplet (sfm/PoseGraph.cpp:195-226): per edge in the set's order, the nodes adjacent to both its ends, then the edge leaves the adjacency
@@ -1107,3 +1114,5 @@ class CameraLidarOptimizer {
 };
 
 }  // namespace pvlm
+
+#include "pvlm_host_triplet.hpp"

@@ -24,6 +24,7 @@
 #include "pvlm_host_rotstart.hpp"
 #include "pvlm_host_transdir.hpp"
 #include "pvlm_host_translp.hpp"
+#include "../csrc/pvlm_triplet_core.h"
 
 namespace pvlm {
 
@@ -1078,7 +1079,7 @@ bool TranslationAveragingL2Chordal(const std::vector<RelativePair>& image_pairs,
 
 // K47: TranslationAveragingL1 (sfm/TranslationAveraging.cpp:277-417)
 bool TranslationAveragingL1(const std::vector<RelativePair>& image_pairs, std::vector<Vector3d>& global_translations, const size_t origin_idx, const bool host,
-                            pvlm_translp_summary* summary_out) {
+                            pvlm_translp_summary* summary_out, const bool device_triplets) {
   const size_t F = global_translations.size();
   if (origin_idx >= F || global_translations[origin_idx] != Vector3d{0, 0, 0}) return false;             // upstream asserts (:281)
   std::map<std::pair<size_t, size_t>, size_t> image_pair_to_idx;                                         // :285-291: a repeated pair resolves to its last index
@@ -1099,7 +1100,9 @@ bool TranslationAveragingL1(const std::vector<RelativePair>& image_pairs, std::v
     R21.insert(R21.end(), p.R_21.begin(), p.R_21.end()); t21.insert(t21.end(), p.t_21.begin(), p.t_21.end());
     edges.insert(kv.first);
   }
-  for (const Triplet& tr : FindTriplet(edges)) { trip_pairs.push_back(place[{tr.i, tr.j}]); trip_pairs.push_back(place[{tr.j, tr.k}]); trip_pairs.push_back(place[{tr.i, tr.k}]); }
+  if (device_triplets) FindTripletDevice(edges, &trip_pairs, host);            // K48: `place` is the position in the set's order, which is what it indexes by
+  else for (const Triplet& tr : FindTriplet(edges)) { trip_pairs.push_back(place[{tr.i, tr.j}]); trip_pairs.push_back(place[{tr.j, tr.k}]); trip_pairs.push_back(place[{tr.i, tr.k}]); }
+  if (trip_pairs.size() / 3 > (size_t)INT_MAX) return false;
   const int P = (int)first.size(), T = (int)trip_pairs.size() / 3;
   first.push_back(0); second.push_back(0); R21.resize(R21.size() + 9); t21.resize(t21.size() + 3); trip_pairs.push_back(0);      // never empty
   pvlm_translp_summary sum{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1275,7 +1278,7 @@ bool EstimateGlobalTranslation(std::vector<Frame>& frames, std::vector<RelativeP
   else if (method == TRANSLATION_AVERAGING_LUD && o.enable_lud)        // :1295-1305; behind the flag
     success = TranslationAveragingLUD(image_pairs, frames, global_translations, new_to_old_global, origin_idx, o.num_iteration_L2IRLS, o.upper_scale_ratio, o.lower_scale_ratio, o.host);
   else if (method == TRANSLATION_AVERAGING_L1 && o.enable_l1)          // :1264-1273; behind the flag
-    success = TranslationAveragingL1(image_pairs, global_translations, origin_idx, o.host);
+    success = TranslationAveragingL1(image_pairs, global_translations, origin_idx, o.host, nullptr, o.device_triplets);
   else return Say(o, "Translaton average method not supported");       // L1, BATA, chordal and LUD only behind their flags; the text is upstream's (:1308)
   if (!success)
     return Say(o, method == TRANSLATION_AVERAGING_SOFTL1 ? "Translation average Soft L1 failed" : method == TRANSLATION_AVERAGING_BATA ? "Translation average BATA failed" :
@@ -1351,6 +1354,83 @@ std::vector<RelativePair> FilterByTriplet(const std::vector<RelativePair>& init_
   }
   std::vector<RelativePair> pairs_after_triplet_filter;
   for (const RelativePair& m : init_pairs) if (pairs.count(m.image_pair) > 0) pairs_after_triplet_filter.push_back(m);
+  return LargestBiconnectedGraph(pairs_after_triplet_filter, covered_frames);
+}
+
+// K48: the two functions above through pvlm_triplets_find / pvlm_triplets_filter (host: the host compile of csrc/pvlm_triplet_core.h)
+std::vector<Triplet> FindTripletDevice(const std::set<std::pair<size_t, size_t>>& edges, std::vector<int>* triplet_pairs, const bool host) {
+  if (triplet_pairs) triplet_pairs->clear();
+  std::vector<int> first, second;
+  first.reserve(edges.size()); second.reserve(edges.size());
+  size_t n_cameras = 0;
+  for (const std::pair<size_t, size_t>& e : edges) {
+    if (!(e.first < e.second) || e.second >= (size_t)INT_MAX) return {};
+    first.push_back((int)e.first); second.push_back((int)e.second);
+    n_cameras = std::max(n_cameras, e.second + 1);
+  }
+  const int F = (int)n_cameras, P = (int)first.size();
+  first.push_back(0); second.push_back(0);                                    // never empty
+  std::vector<int> trip, pairs3;
+  long long needed = 0, capacity = 0;
+  // a sizing call (no output wanted: the count alone), then the call that writes
+  for (int round = 0; round < 2; ++round) {
+    trip.assign(3 * (size_t)capacity + 1, 0);
+    if (triplet_pairs) pairs3.assign(3 * (size_t)capacity + 1, 0);
+    int* want_trip = round ? trip.data() : nullptr;
+    int* want_pairs = round && triplet_pairs ? pairs3.data() : nullptr;
+    if (host) {
+      if (pvlm_triplet::find_host(F, P, first.data(), second.data(), want_trip, want_pairs, capacity, &needed, nullptr)) throw std::runtime_error("FindTripletDevice: refused");
+    } else {
+      Engine& e = Engine::Default();
+      e.Check(pvlm_triplets_find(e.ctx(), F, P, first.data(), second.data(), want_trip, want_pairs, capacity, &needed, nullptr), "pvlm_triplets_find");
+    }
+    capacity = needed;
+  }
+  std::vector<Triplet> triplets((size_t)needed);
+  for (size_t t = 0; t < triplets.size(); ++t) triplets[t] = Triplet{(uint32_t)trip[3 * t], (uint32_t)trip[3 * t + 1], (uint32_t)trip[3 * t + 2]};
+  if (triplet_pairs) { pairs3.resize(3 * (size_t)needed); triplet_pairs->swap(pairs3); }
+  return triplets;
+}
+
+std::vector<RelativePair> FilterByTripletDevice(const std::vector<RelativePair>& init_pairs, const double angle_threshold, std::set<size_t>& covered_frames, const bool host,
+                                                pvlm_triplet_stats* stats_out) {
+  covered_frames.clear();
+  std::map<std::pair<size_t, size_t>, size_t> last;                            // a pair named twice: its last entry's rotation, as the map assignment of FilterByTriplet
+  size_t n_cameras = 0;
+  for (size_t i = 0; i < init_pairs.size(); ++i) {
+    const std::pair<size_t, size_t>& p = init_pairs[i].image_pair;
+    if (!(p.first < p.second) || p.second >= (size_t)INT_MAX) return {};      // upstream asserts
+    last[p] = i;
+    n_cameras = std::max(n_cameras, p.second + 1);
+  }
+  std::vector<int> first, second;
+  std::vector<double> R;
+  first.reserve(last.size()); second.reserve(last.size()); R.reserve(9 * last.size() + 9);
+  for (const auto& kv : last) {
+    first.push_back((int)kv.first.first); second.push_back((int)kv.first.second);
+    const Matrix3d& m = init_pairs[kv.second].R_21;
+    R.insert(R.end(), m.begin(), m.end());
+  }
+  const int F = (int)n_cameras, P = (int)first.size();
+  first.push_back(0); second.push_back(0); R.resize(R.size() + 9);            // never empty
+  std::vector<unsigned char> keep((size_t)P + 1, 0);
+  pvlm_triplet_stats st{0, 0, 0, 0};
+  // the library wants a finite threshold; `angle_error < angle_threshold` as written keeps nothing at or below 0 (NaN included) and everything above 180
+  const double threshold = std::isnan(angle_threshold) ? 0.0 : std::min(std::max(angle_threshold, 0.0), 181.0);
+  if (host) {
+    pvlm_triplet::Stats hs{0, 0, 0, 0};
+    if (pvlm_triplet::filter_host(F, P, first.data(), second.data(), R.data(), threshold, keep.data(), &hs)) throw std::runtime_error("FilterByTripletDevice: refused");
+    st = {hs.n_triplets, hs.n_kept_triplets, hs.n_uncertain, hs.n_kept_pairs};
+  } else {
+    Engine& e = Engine::Default();
+    e.Check(pvlm_triplets_filter(e.ctx(), F, P, first.data(), second.data(), R.data(), threshold, keep.data(), &st), "pvlm_triplets_filter");
+  }
+  if (stats_out) *stats_out = st;
+  std::set<std::pair<size_t, size_t>> kept;
+  size_t at = 0;
+  for (const auto& kv : last) if (keep[at++]) kept.insert(kept.end(), kv.first);
+  std::vector<RelativePair> pairs_after_triplet_filter;
+  for (const RelativePair& m : init_pairs) if (kept.count(m.image_pair) > 0) pairs_after_triplet_filter.push_back(m);
   return LargestBiconnectedGraph(pairs_after_triplet_filter, covered_frames);
 }
 
@@ -1532,7 +1612,7 @@ bool EstimateGlobalRotation(std::vector<Frame>& frames, std::vector<RelativePair
   }
   std::set<size_t> covered_frames;
   image_pairs = LargestBiconnectedGraph(image_pairs, covered_frames);
-  image_pairs = FilterByTriplet(image_pairs, 0.1, covered_frames);
+  image_pairs = o.device_triplets ? FilterByTripletDevice(image_pairs, 0.1, covered_frames, o.host) : FilterByTriplet(image_pairs, 0.1, covered_frames);
   if (image_pairs.empty()) return Say(o, "no pair is left after the graph and triplet filters");
   std::map<size_t, size_t> old_to_new, new_to_old;
   ReIndex(image_pairs, old_to_new, new_to_old);
