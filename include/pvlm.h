@@ -705,6 +705,34 @@ pvlm_status pvlm_triplets_filter(pvlm_ctx* ctx, int n_cameras, int n_pairs, cons
                                  double angle_threshold_deg, unsigned char* keep /* n_pairs */, pvlm_triplet_stats* stats);
 int pvlm_triplet_group_size(void);
 
+/* ---- K49: MVS::SelectNeighborSFM (mvs/MVS.cpp:248-332): the neighbour views of every reference view from the tracks the views share ---- *
+ * The definition (csrc/pvlm_neighbor_sfm_core.h).  F views with poses T_wc (3 x 4, row-major, the camera centre in the fourth column), T tracks in CSR form
+ * (track_offsets[T + 1] from 0, view_ids ascending inside a track — a view may occur twice —, points 3 per track).  For every track in order and every i < j of its
+ * views, in double: V = X - C, depth = |V|, angle = VectorAngle3D(V1, V2) * 180 / M_PI, a = min(powf(float(angle / 10.0), 1.5f), 1.f) (a float), s12 = f(depth1 /
+ * depth2), s21 = f(depth2 / depth1) with f(s) = 1.6 * 1.6 / s / s above 1.6, 1 from 1 on, s * s below; score(id1, id2) += s12 * a and score(id2, id1) += s21 * a into
+ * a FLOAT matrix, every += being float(double(cell) + product), the additions of a cell in track order.  Per row the columns with score > 0 are walked by
+ * std::greater<pair<float, size_t>> (score descending, equal scores by column DESCENDING) until neighbor_size are accepted; a candidate is accepted when
+ * ||t_nr|| > sq_distance_threshold, T_nr = T_wn^-1 T_wr.  Upstream compares the norm, not its square, with the squared threshold (:322): kept literally.  T_nr is
+ * the rigid inverse in double, stored as float (as SelectNeighborKNN of the host mirror).  A view may be its own neighbour when a track names it twice, as upstream.
+ * Outputs: n_neighbors[F]; ids / scores [F * neighbor_size], R_nr [.. * 9, row-major], t_nr [.. * 3]; the slots a row does not fill hold id -1 and zeros.
+ * The score matrix stays on the device.  The device's acos / powf need not equal the host library's to the bit; a score differs from the literal host loop's by at
+ * most (n + 2) * 2^-23 * score, n the cell's contribution count.  A row in which two candidates adjacent in the walk (the first one behind the walk included) are
+ * closer than the sum of their bounds, or a tested ||t_nr|| lies within 1e-12 (relative) of the threshold, is recomputed on the host by the literal loop for that row:
+ * stats->n_uncertain counts them.  n_candidates: cells with score > 0; n_contributions: additions (two per (i, j)); n_repeat_tracks: tracks naming a view twice.
+ * Deliberate divergence: a track naming a view >= F or one with pose_valid == 0 is refused (upstream would read a sentinel pose and produce NaNs).
+ * PVLM_ERR_ARG, with no output touched: a NULL, a negative size, offsets that do not start at 0 or ascend, views of a track that do not ascend, such a track, a NaN
+ * threshold.  PVLM_NEIGHBOR_TILE (read at every call) lowers the column tile of the accumulation (pvlm_neighbor_sfm_tile_cols()); it changes no result, the tests use
+ * it.  With PVLM_NEIGHBOR_PROFILE set a call prints its wall clock split into index, upload, accumulation, selection, copy-out and host rows on stderr, each stage
+ * then ending in a wait.  Synchronous; PVLM_ERR_STATE inside a capture.
+ * pvlm_mvs_neighbor_sfm_score_row: one row of the device's score matrix (and the contribution counts, optional) for the tests. */
+typedef struct pvlm_neighbor_sfm_stats { long long n_candidates, n_contributions, n_repeat_tracks, n_uncertain; } pvlm_neighbor_sfm_stats;
+pvlm_status pvlm_mvs_select_neighbors_sfm(pvlm_ctx* ctx, int n_views, const double* T_wc_3x4, const unsigned char* pose_valid, int n_tracks, const int64_t* track_offsets,
+                                          const int* view_ids, const double* points /* n_tracks x 3 */, int neighbor_size, double sq_distance_threshold,
+                                          int* n_neighbors /* n_views */, int* ids, float* R_nr, float* t_nr, float* scores, pvlm_neighbor_sfm_stats* stats);
+pvlm_status pvlm_mvs_neighbor_sfm_score_row(pvlm_ctx* ctx, int n_views, const double* T_wc_3x4, const unsigned char* pose_valid, int n_tracks, const int64_t* track_offsets,
+                                            const int* view_ids, const double* points, int row, float* scores /* n_views */, int* counts /* n_views, optional */);
+int pvlm_neighbor_sfm_tile_cols(void);
+
 /* ---- dense SPD solve for an LM driver (not hot path) ------------------------------------------------------------ *
  * Blocked fp64 Cholesky + triangular solves on the GPU (hand-written: 32-wide block columns, 64 x 64 register-tiled
  * trailing updates).  Solves A X = B for a symmetric positive definite n x n matrix (dense, host, full symmetric storage)

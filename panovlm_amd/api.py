@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "pvlm_transavg_chordal", "pvlm_transavg_lud", "pvlm_transdir_group_size",
     "pvlm_transavg_l1", "pvlm_translp_group_size",
     "pvlm_triplets_find", "pvlm_triplets_filter", "pvlm_triplet_group_size",
+    "pvlm_mvs_select_neighbors_sfm", "pvlm_mvs_neighbor_sfm_score_row", "pvlm_neighbor_sfm_tile_cols",
     "pvlm_depth_completion", "pvlm_compute_depth_images",
     "pvlm_depthset_compute", "pvlm_depthset_create", "pvlm_depthset_upload", "pvlm_depthset_info", "pvlm_depthset_read", "pvlm_depthset_destroy",
     "pvlm_set_translation_scales", "pvlm_scale_workgroup_size",
@@ -1957,6 +1958,65 @@ def triplets_filter(ctx, n_cameras, first, second, R_21, angle_threshold_deg, ch
     for name, _ in TripletStats._fields_:
         out[name] = int(getattr(st, name))
     return out
+
+
+class NeighborSfmStats(C.Structure):
+    _fields_ = [("n_candidates", C.c_longlong), ("n_contributions", C.c_longlong), ("n_repeat_tracks", C.c_longlong), ("n_uncertain", C.c_longlong)]
+
+
+NEIGHBOR_GUARD = 4     # sentinel slots the wrapper keeps behind every output
+
+
+def neighbor_sfm_tile_cols():
+    """pvlm_neighbor_sfm_tile_cols (K49): the columns of a score row the accumulation holds in LDS at once (PVLM_NEIGHBOR_TILE lowers it)."""
+    return int(load_library().pvlm_neighbor_sfm_tile_cols())
+
+
+def _neighbor_inputs(T_wc, pose_valid, track_offsets, view_ids, points):
+    T_wc = _f64(np.asarray(T_wc, np.float64).reshape(-1, 12)); F = len(T_wc)
+    valid = np.ascontiguousarray(pose_valid, np.uint8)
+    off = _i64(track_offsets); T = len(off) - 1
+    views = _i32(np.concatenate([np.asarray(view_ids, np.int64).reshape(-1), [0]]))      # never empty
+    pts = _f64(np.asarray(points, np.float64).reshape(-1, 3))
+    if len(valid) != F or len(pts) != T:
+        raise ValueError("pose_valid needs one entry per view and points one row per track")
+    return F, T, T_wc, valid, off, views, pts
+
+
+def mvs_select_neighbors_sfm(ctx, T_wc, pose_valid, track_offsets, view_ids, points, neighbor_size, sq_distance_threshold, check=True):
+    """pvlm_mvs_select_neighbors_sfm (K49): MVS::SelectNeighborSFM.  T_wc: F x 3 x 4 poses; the tracks in CSR form (track_offsets T + 1, view_ids ascending inside a
+    track, points T x 3).  Returns a dict: n_neighbors (F), ids (F x neighbor_size, -1 in the unused slots), R_nr (F x neighbor_size x 3 x 3 float32), t_nr
+    (.. x 3), scores (F x neighbor_size), n_candidates, n_contributions, n_repeat_tracks, n_uncertain (rows redone on the host by the literal loop), guard_intact, rc.
+    The norm of t_nr is compared with sq_distance_threshold as it is (upstream's test).  An argument the library refuses raises PvlmError; with check=False the dict
+    comes back with its rc (the outputs then hold -7)."""
+    F, T, T_wc, valid, off, views, pts = _neighbor_inputs(T_wc, pose_valid, track_offsets, view_ids, points)
+    K = int(neighbor_size); n = F * max(K, 0); G = NEIGHBOR_GUARD
+    nn = np.full(F + G, -7, np.int32); ids = np.full(n + G, -7, np.int32); R = np.full(9 * (n + G), -7, np.float32); t = np.full(3 * (n + G), -7, np.float32)
+    sc = np.full(n + G, -7, np.float32)
+    st = NeighborSfmStats(-7, -7, -7, -7)
+    rc = ctx.lib.pvlm_mvs_select_neighbors_sfm(ctx._h, C.c_int(F), _p(T_wc, C.c_double), _p(valid, C.c_ubyte), C.c_int(T), _p(off, C.c_int64), _p(views, C.c_int),
+                                               _p(pts, C.c_double), C.c_int(K), C.c_double(sq_distance_threshold), _p(nn, C.c_int), _p(ids, C.c_int), _p(R, C.c_float),
+                                               _p(t, C.c_float), _p(sc, C.c_float), C.byref(st))
+    if check:
+        ctx._check(rc, "pvlm_mvs_select_neighbors_sfm")
+    intact = bool(np.all(nn[F:] == -7) and np.all(ids[n:] == -7) and np.all(R[9 * n:] == -7) and np.all(t[3 * n:] == -7) and np.all(sc[n:] == -7))
+    out = dict(n_neighbors=nn[:F], ids=ids[:n].reshape(F, max(K, 0)), R_nr=R[:9 * n].reshape(F, max(K, 0), 3, 3), t_nr=t[:3 * n].reshape(F, max(K, 0), 3),
+               scores=sc[:n].reshape(F, max(K, 0)), guard_intact=intact, rc=int(rc))
+    for name, _ in NeighborSfmStats._fields_:
+        out[name] = int(getattr(st, name))
+    return out
+
+
+def mvs_neighbor_sfm_score_row(ctx, T_wc, pose_valid, track_offsets, view_ids, points, row):
+    """pvlm_mvs_neighbor_sfm_score_row (K49): one row of the device's score matrix and the contribution counts of its cells (float32 F, int32 F); for the tests."""
+    F, T, T_wc, valid, off, views, pts = _neighbor_inputs(T_wc, pose_valid, track_offsets, view_ids, points)
+    s = np.full(F + NEIGHBOR_GUARD, -7, np.float32); n = np.full(F + NEIGHBOR_GUARD, -7, np.int32)
+    rc = ctx.lib.pvlm_mvs_neighbor_sfm_score_row(ctx._h, C.c_int(F), _p(T_wc, C.c_double), _p(valid, C.c_ubyte), C.c_int(T), _p(off, C.c_int64), _p(views, C.c_int),
+                                                 _p(pts, C.c_double), C.c_int(row), _p(s, C.c_float), _p(n, C.c_int))
+    ctx._check(rc, "pvlm_mvs_neighbor_sfm_score_row")
+    if not (np.all(s[F:] == -7) and np.all(n[F:] == -7)):
+        raise PvlmError("pvlm_mvs_neighbor_sfm_score_row wrote past its outputs")
+    return s[:F], n[:F]
 
 
 class BataParams(C.Structure):

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libpvlm.so")
 ARCH = "gfx950"
 # sources whose float / double decisions must equal a non-FMA x86-64 build of the reference bit for bit
 NO_CONTRACT = ("pvlm_assoc.hip", "pvlm_lines.hip", "pvlm_linegrow.hip", "pvlm_mvs.hip", "pvlm_ring.hip", "pvlm_undistort.hip", "pvlm_fuse.hip", "pvlm_texture.hip",
-               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip", "pvlm_rotavg.hip", "pvlm_bata.hip", "pvlm_rotstart.hip", "pvlm_transdir.hip", "pvlm_translp.hip", "pvlm_triplet.hip")
+               "pvlm_sfm_filter.hip", "pvlm_triangulate.hip", "pvlm_match.hip", "pvlm_essential.hip", "pvlm_vlad.hip", "pvlm_depthfill.hip", "pvlm_scale.hip", "pvlm_sift.hip", "pvlm_transavg.hip", "pvlm_rotavg.hip", "pvlm_bata.hip", "pvlm_rotstart.hip", "pvlm_transdir.hip", "pvlm_translp.hip", "pvlm_triplet.hip", "pvlm_neighbor_sfm.hip")
 
 
 def _hipcc():
@@ -131,6 +131,7 @@ ROTSTART_DRIVER = os.path.join(HERE, "build", "pvlm_rotstart_driver")
 TRANSDIR_DRIVER = os.path.join(HERE, "build", "pvlm_transdir_driver")
 TRANSLP_DRIVER = os.path.join(HERE, "build", "pvlm_translp_driver")
 TRIPLET_DRIVER = os.path.join(HERE, "build", "pvlm_triplet_driver")
+NEIGHBOR_DRIVER = os.path.join(HERE, "build", "pvlm_neighbor_driver")
 
 
 def build_host(force=False):
@@ -298,6 +299,14 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", pdrv, "-o", TRIPLET_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
                                "-Wl,-rpath," + HERE])
     build_triplet_check()
+    # the neighbour-selection driver (SelectNeighborSFM and SelectNeighborViews on the literal host loop or through the device: K49) and the host compile of the K49
+    # core for the tests
+    ndrv = os.path.join(HERE, "..", "tests", "cpp", "pvlm_neighbor_driver.cpp")
+    if os.path.exists(ndrv) and (force or not os.path.exists(NEIGHBOR_DRIVER) or
+                                 os.path.getmtime(NEIGHBOR_DRIVER) < max(os.path.getmtime(ndrv), os.path.getmtime(HOST_LIB))):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread", ndrv, "-o", NEIGHBOR_DRIVER, "-L" + HERE, "-lpvlm_host", "-lpvlm",
+                               "-Wl,-rpath," + HERE])
+    build_neighbor_sfm_check()
     return HOST_LIB
 
 
@@ -314,7 +323,7 @@ def _include_closure(src):
 
 
 def build_core_check(kind, main=False, sanitize=False):
-    """The host compile of a pair-graph stage's core (kind "transavg": K42, "rotavg": K40, "bata": K44, "rotstart": K45, "transdir": K46, "translp": K47, "triplet": K48; csrc/pvlm_<kind>_core.h behind tests/cpp/<kind>_core_check.cpp; no device,
+    """The host compile of a pair-graph stage's core (kind "transavg": K42, "rotavg": K40, "bata": K44, "rotstart": K45, "transdir": K46, "translp": K47, "triplet": K48, "neighbor_sfm": K49; csrc/pvlm_<kind>_core.h behind tests/cpp/<kind>_core_check.cpp; no device,
     -ffp-contract=off as the device build of pvlm_<kind>.hip): build/lib<kind>_check.so for the tests, or with main=True the stand-alone program of the same file
     (sanitize: the host sanitizers).  Rebuilt when the source or any header it includes, directly or not, is newer."""
     chk = os.path.join(HERE, "..", "tests", "cpp", kind + "_core_check.cpp")
@@ -354,6 +363,10 @@ def build_translp_check(main=False, sanitize=False):
 
 def build_triplet_check(main=False, sanitize=False):
     return build_core_check("triplet", main, sanitize)
+
+
+def build_neighbor_sfm_check(main=False, sanitize=False):
+    return build_core_check("neighbor_sfm", main, sanitize)
 
 
 if __name__ == "__main__":

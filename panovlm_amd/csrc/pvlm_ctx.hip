@@ -422,6 +422,7 @@ pvlm_status pvlm_preload(pvlm_ctx* ctx) {
   pvlm_i_preload_transdir(ctx->stream);
   pvlm_i_preload_translp(ctx->stream);
   pvlm_i_preload_triplet(ctx->stream);
+  pvlm_i_preload_neighbor_sfm(ctx->stream);
   pvlm_i_preload_depthfill(ctx->stream);
   pvlm_i_preload_scale(ctx->stream);
   pvlm_i_preload_sift(ctx->stream);

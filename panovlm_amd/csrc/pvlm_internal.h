@@ -355,6 +355,7 @@ void pvlm_i_preload_rotstart(hipStream_t s);
 void pvlm_i_preload_transdir(hipStream_t s);
 void pvlm_i_preload_translp(hipStream_t s);
 void pvlm_i_preload_triplet(hipStream_t s);
+void pvlm_i_preload_neighbor_sfm(hipStream_t s);
 void pvlm_i_preload_depthfill(hipStream_t s);
 void pvlm_i_preload_scale(hipStream_t s);
 void pvlm_i_preload_sift(hipStream_t s);

@@ -998,6 +998,7 @@ struct NeighborInfo {
   std::array<float, 3> t_nr{};
 };
 std::vector<std::vector<NeighborInfo>> SelectNeighborKNN(const std::vector<Frame>& frames, int neighbor_size, float sq_distance_threshold);
+// SelectNeighborSFM (mvs/MVS.cpp:248-332, K49) and the dispatch SelectNeighborViews (:66-79): pvlm_host_neighbor.hpp
 
 // ---- mvs/MVS.cpp:2168-2334 — MVS::FuseDepthImages(use_filtered_depth = true), the second half of MVS::FuseDepthMaps (:224-231; the first
 // half, MergeDepthImages, is a loop over pvlm_mvs_depth_to_cloud).  The greedy confidence-weighted fusion walks frames by decreasing
@@ -1116,3 +1117,4 @@ class CameraLidarOptimizer {
 }  // namespace pvlm
 
 #include "pvlm_host_triplet.hpp"
+#include "pvlm_host_neighbor.hpp"
